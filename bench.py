@@ -13,10 +13,14 @@ envs per GPU, PPO MLP[256,256] bf16.  The model is the labelled SYNTHETIC MyoHan
 blob; the integrator is the model's own option (Euler, as in the only decodable MyoSuite
 model); --integrator rk4 runs the RK4 variant north_star mentions.
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both sides
-and taken as the max over ranks; blocks repeat until --min-seconds (default 2 s) of timed wall have passed, so
-that the GPU is busy long enough for outside telemetry; `ms_per_step` / `value` are the MEDIAN block
-(`blocks`, `timed_seconds`, `ms_per_step_min/max` say what was seen).  `variants` (rank 0, N = 1) carries the
+Timing: W warm-up steps, then ONE block of exactly K timed steps, bracketed by barrier + synchronize on both sides and
+taken as the max over ranks; `ms_per_step` is that block's wall time / K and `value` the env-steps/s it gives.
+--min-seconds S > 0 repeats the K-step block until S seconds of timed wall have passed (for outside telemetry); then
+`ms_per_step` / `value` are the MEDIAN block (`blocks`, `timed_steps`, `timed_seconds`, `ms_per_step_min/max` say what was seen).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path computed in its last step as DIR/<name>.npy
+(float32 / float64; see dump_outputs()).  Inputs are seeded (env seed, policy init, sampling stream), so two builds
+run with the same arguments can be compared output for output.  `variants` (rank 0, N = 1) carries the
 same measurement for the mixed-precision stepper and for the RK4 integrator, `config_C_p2_8192` (BASELINE config C: phase 2, 8192 envs) and
 `reorient_p2_mlp` (the die env with the MLP policy) on the fp64 stepper, plus `config_E_lstm256`: BASELINE config E (die reorient,
 4096 envs, the reference's recurrent LSTM-256 policy class, rollout + update; myochallenge_amd/rl/bench_reorient_lstm.py).  Since round 4 the headline is the all-fp64 stepper
@@ -168,6 +172,36 @@ def trajectory_parity():
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, per_env, shared, n_envs, seed=0):
+    """Writes DIR/<name>.npy for every array: float64 stays float64, everything else becomes float32.  `per_env` arrays have
+    one row per env; if all of them together exceed DUMP_BUDGET_BYTES (minus the `shared` arrays), the same fixed, seeded
+    sample of env rows (sorted) is written for each.  `env_index.npy` names the env rows written.  Returns {name: shape}."""
+    import numpy as np
+
+    def host(x):
+        if hasattr(x, "detach"):       # a torch tensor (bfloat16 has no numpy type: convert on the torch side)
+            import torch
+            return x.detach().to(torch.float64 if x.dtype == torch.float64 else torch.float32).cpu().numpy()
+        a = np.asarray(x)
+        return a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    per_env = {k: host(v) for k, v in per_env.items()}
+    shared = {k: host(v) for k, v in shared.items()}
+    row_bytes = sum(a.nbytes // max(1, n_envs) for a in per_env.values()) + 8
+    room = DUMP_BUDGET_BYTES - sum(a.nbytes for a in shared.values())
+    keep = max(1, min(n_envs, room // max(1, row_bytes)))
+    rows = np.arange(n_envs) if keep == n_envs else np.sort(np.random.RandomState(seed).choice(n_envs, keep, replace=False))
+    arrays = dict(shared)
+    arrays.update({k: a[rows] for k, a in per_env.items()})
+    arrays["env_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, torchrun with the
     rendezvous on 127.0.0.1) as a CHILD process and relay its output and exit code.  Called before torch is imported, so
@@ -194,7 +228,8 @@ def main():
     ap.add_argument("--dtype", default="f64", choices=["mixed", "f64", "f32"],
                     help="stepper arithmetic: f64 = everything fp64, the reference's own arithmetic (MuJoCo), the headline since round 4; "
                          "mixed = fp64 state / kinematic chain / contact distances / tendon lengths, fp32 dynamics (f32 is round 1's name for it)")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the K-step block until this much timed wall has passed")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the K-step block until this much timed wall has passed "
+                    "(default 0: exactly one block, i.e. --steps timed steps)")
     ap.add_argument("--no-variants", action="store_true", help="skip the f64 / RK4 variant measurements (rank 0, N = 1 only)")
     ap.add_argument("--integrator", default="model", choices=["model", "euler", "rk4"])
     ap.add_argument("--n-steps", type=int, default=64, help="rollout length between PPO updates")
@@ -210,6 +245,8 @@ def main():
                          "graphs; the reference's single VecNormalize over all envs, exactly), once per rollout, or not at all")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (rank 0, at most 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -249,8 +286,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def measure(dtype, integrator, min_seconds, steps, warmup, env_name=None, envs=None):
-        """One configuration: set-up, W warm-up steps, then blocks of exactly `steps` steps until `min_seconds`."""
+    def measure(dtype, integrator, min_seconds, steps, warmup, env_name=None, envs=None, dump_dir=None):
+        """One configuration: set-up, W warm-up steps, then blocks of exactly `steps` steps until `min_seconds` (one block at 0);
+        with `dump_dir`, rank 0 then writes what the last timed step computed (dump_outputs())."""
         env_name, envs = env_name or args.env_name, envs or args.envs
         from myochallenge_amd.envs.environment_factory import EnvironmentFactory
         from myochallenge_amd.rl.policy import ActorCriticPolicy
@@ -276,10 +314,11 @@ def main():
         algo = PPO(venv, policy, cfg, seed=rank)
         # one "step" of the bench = one rollout step (PPO.rollout_step: hipGraph(policy) -> myo_batch_step
         # -> hipGraph(normaliser, bootstrap, buffer write)); the PPO update fires every n_steps steps
-        state = {"t": 0}
+        state = {"t": 0, "row": 0}
 
         def one_step():
             algo.rollout_step()
+            state["row"] = state["t"]        # the rollout-buffer row this step wrote
             state["t"] += 1
             if state["t"] == cfg.n_steps:
                 state["t"] = 0
@@ -326,10 +365,25 @@ def main():
             dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
             replicas_identical = bool(float(lo[0]) == float(hi[0]))
             replica_spread = float(hi[0]) - float(lo[0])
+        dumped = None
+        if dump_dir and rank == 0:
+            # what a caller of the timed step receives: the rollout-buffer row of the last step (policy input, sampled actions,
+            # value, log-prob, normalised reward), the normalised next observation and episode starts, the env's raw outputs and
+            # physics state, and the policy / normaliser the PPO updates inside the timed region left behind
+            r = state["row"]
+            qpos, qvel, act, tm = env.get_state()
+            per_env = {"policy_obs": algo.obs_buf[r], "actions": algo.act_buf[r], "values": algo.val_buf[r],
+                       "log_probs": algo.logp_buf[r], "rewards": algo.rew_buf[r], "next_obs": algo._obs_s,
+                       "episode_starts": algo._starts_s, "raw_obs": env._obs, "raw_rewards": env._rew, "dones": env._done,
+                       "truncated": env._trunc, "reward_components": env._comps, "qpos": qpos, "qvel": qvel, "act": act, "time": tm}
+            shared = {"policy_params": torch.cat([p.detach().float().reshape(-1) for p in policy.parameters()]),
+                      "obs_rms_mean": venv.obs_rms.mean, "obs_rms_var": venv.obs_rms.var}
+            dumped = dump_outputs(dump_dir, per_env, shared, envs)
         blocks.sort()
         med = blocks[len(blocks) // 2] if len(blocks) % 2 else 0.5 * (blocks[len(blocks) // 2 - 1] + blocks[len(blocks) // 2])
         res = {"dtype": dtype, "integrator": integ_name, "value": envs * world * steps / med, "ms_per_step": 1e3 * med / steps,
                "ms_per_step_min": 1e3 * blocks[0] / steps, "ms_per_step_max": 1e3 * blocks[-1] / steps, "blocks": len(blocks),
+               "timed_steps": len(blocks) * steps, "dumped": dumped,
                "timed_seconds": total, "env_kernel_ms": kernel_ms, "optimizer_steps_per_sec": (algo.n_updates - upd0) / total,
                "n_steps": cfg.n_steps, "batch_size": cfg.batch_size, "n_epochs": cfg.n_epochs, "lds_bytes": env.batch.lds_bytes, "health": health,
                "replicas_identical": replicas_identical, "replica_checksum_spread": replica_spread, "normalizer_sync": args.normalizer_sync if world > 1 else None,
@@ -346,7 +400,7 @@ def main():
         return res
 
     dtype = "mixed" if args.dtype == "f32" else args.dtype
-    main_res = measure(dtype, args.integrator, args.min_seconds, args.steps, args.warmup)
+    main_res = measure(dtype, args.integrator, args.min_seconds, args.steps, args.warmup, dump_dir=args.dump_outputs)
     variants = {}
     if rank == 0 and world == 1 and not args.no_variants and not args.no_ppo and not args.lstm_hidden:
         # the other steppers of the same workload, so that the driver's run records them too (short blocks: ~1 s each)
@@ -446,7 +500,7 @@ def main():
                        "ppo": "rollout-only" if args.no_ppo else
                        f"n_steps={main_res['n_steps']}, batch={main_res['batch_size']}, epochs={main_res['n_epochs']}, update inside timed region",
                        "parallelism": f"env-sharded x{world}, 1 RCCL grad all-reduce per optimizer step"},
-            "blocks": main_res["blocks"], "timed_seconds": main_res["timed_seconds"],
+            "blocks": main_res["blocks"], "timed_steps": main_res["timed_steps"], "timed_seconds": main_res["timed_seconds"],
             "ms_per_step_min": main_res["ms_per_step_min"], "ms_per_step_max": main_res["ms_per_step_max"],
             "trajectory_parity": trajectory_parity(),
             "ppo_optimizer_steps_per_sec": main_res["optimizer_steps_per_sec"],
@@ -492,6 +546,8 @@ def main():
             print("bench.py: variants with non-zero batch health counters: %r" % (flagged,), file=sys.stderr)
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if args.dump_outputs:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": main_res["dumped"]}
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

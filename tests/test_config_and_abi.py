@@ -200,3 +200,36 @@ def test_bench_gpus_n_spawns_a_launcher_before_torch(monkeypatch):
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node=4" in cmd and "127.0.0.1" in cmd
     assert cmd[-6:] == ["--gpus", "4", "--steps", "3", "--warmup", "1"] and cmd[-7].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_bench_dump_outputs_types_budget_and_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs (bench.py --dump-outputs): float64 stays float64, every other dtype is written as float32; under the
+    budget every env row is written, over it the same seeded, sorted sample of rows for every per-env array, named by env_index."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 1000
+    per_env = {"qpos": torch.arange(n * 3, dtype=torch.float64).view(n, 3), "dones": (torch.arange(n) % 2).to(torch.uint8),
+               "actions": torch.arange(n * 4, dtype=torch.bfloat16).view(n, 4) * 0 + 1}
+    shared = {"policy_params": torch.linspace(0, 1, 17)}
+    shapes = bench.dump_outputs(str(tmp_path / "all"), per_env, shared, n)
+    assert shapes == {"qpos": [n, 3], "dones": [n], "actions": [n, 4], "policy_params": [17], "env_index": [n]}
+    q = np.load(tmp_path / "all" / "qpos.npy")
+    assert q.dtype == np.float64 and np.array_equal(q, per_env["qpos"].numpy())
+    d, a = np.load(tmp_path / "all" / "dones.npy"), np.load(tmp_path / "all" / "actions.npy")
+    assert d.dtype == np.float32 and a.dtype == np.float32 and np.array_equal(d, per_env["dones"].numpy().astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "all" / "env_index.npy"), np.arange(n, dtype=np.float64))
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 17 * 4 + 100 * (3 * 8 + 4 + 4 * 4 + 8))      # room for exactly 100 env rows
+    bench.dump_outputs(str(tmp_path / "s1"), per_env, shared, n)
+    bench.dump_outputs(str(tmp_path / "s2"), per_env, shared, n)
+    idx = np.load(tmp_path / "s1" / "env_index.npy")
+    assert idx.shape == (100,) and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "s2" / "env_index.npy"))
+    rows = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "s1" / "qpos.npy"), per_env["qpos"].numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "dones.npy"), per_env["dones"].numpy()[rows].astype(np.float32))
+    assert np.load(tmp_path / "s1" / "policy_params.npy").shape == (17,)
+    total = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert total <= bench.DUMP_BUDGET_BYTES + 128 * len(os.listdir(tmp_path / "s1"))      # (+ the .npy headers)

@@ -791,11 +791,42 @@ def test_bench_spawns_its_own_ranks(hip_lib):
     assert rec["config"]["normalizer_sync"] == "step" and len(rec["rank_block_seconds_min_max"]) == 2
 
 
-def test_bench_at_config_d_shape_with_eight_ranks(hip_lib):
-    """BASELINE config D's shape before the first RCCL run: `bench.py --gpus 8 --envs 4096 --env-name
-    CustomMyoBaodingBallsP2` — eight ranks x 4096 phase-2 envs = 32768 envs, here sharing this box's one GPU over gloo.  The line
-    must carry 8 ranks / 32768 envs, the replicas must hold identical parameters after the timed updates (rollout of 8 steps, two
-    epochs x two minibatches per update, two updates), with the per-rollout normaliser exchange as well as the per-step one."""
+def test_bench_times_exactly_its_steps_and_dumps_the_last_one(hip_lib, tmp_path):
+    """`bench.py --steps K` times exactly K steps (one block: ms_per_step = its wall / K), and --dump-outputs DIR writes what the
+    last timed step computed — rollout row, next observation, raw env outputs, fp64 physics state, policy and normaliser — as
+    float32 / float64 .npy files whose shapes the result line lists."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--envs", "256",
+                        "--no-variants", "--no-cpu-baseline", "--dump-outputs", out], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 6 and rec["timed_steps"] == 6 and rec["blocks"] == 1 and rec["warmup"] == 2
+    assert abs(rec["value"] - 256 / (rec["ms_per_step"] * 1e-3)) <= 1e-3 * rec["value"]
+    shapes = rec["dump_outputs"]["arrays"]
+    assert sorted(shapes) == sorted(f[:-4] for f in os.listdir(out))
+    for name, shape in shapes.items():
+        a = np.load(os.path.join(out, name + ".npy"))
+        assert list(a.shape) == shape and a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+    a = {k: np.load(os.path.join(out, k + ".npy")) for k in ("qpos", "qvel", "actions", "policy_obs", "next_obs", "raw_obs", "env_index")}
+    assert a["qpos"].dtype == np.float64 and a["qpos"].shape[0] == 256 and a["qvel"].dtype == np.float64
+    assert a["actions"].shape == (256, 39) and a["policy_obs"].shape == a["next_obs"].shape == a["raw_obs"].shape == (256, 86)
+    assert np.array_equal(a["env_index"], np.arange(256))
+    assert not np.array_equal(a["policy_obs"], a["next_obs"])
+
+
+def test_bench_at_config_d_scale_with_four_ranks(hip_lib):
+    """BASELINE config D's node total before the first RCCL run: `bench.py --gpus 4 --envs 8192 --env-name
+    CustomMyoBaodingBallsP2` — four ranks x 8192 phase-2 envs = 32768 envs, here sharing this box's one GPU over gloo.  Four ranks,
+    not config D's eight: with this pytest process the test holds five processes on the GPU, within the six a shared GPU box allows
+    at once.  The line must carry 4 ranks / 32768 envs, the replicas must hold identical parameters after the timed updates (rollout
+    of 8 steps, two epochs x four minibatches per update), with the per-rollout normaliser exchange as well as the per-step one."""
     import json
     import os
     import subprocess
@@ -805,7 +836,7 @@ def test_bench_at_config_d_shape_with_eight_ranks(hip_lib):
     env["MYO_DIST_BACKEND"] = "gloo"
     env["OMP_NUM_THREADS"] = "2"
     for sync in ("step", "rollout"):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "8", "--warmup", "0", "--envs", "4096",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "8", "--warmup", "0", "--envs", "8192",
                             "--env-name", "CustomMyoBaodingBallsP2", "--n-epochs", "2", "--min-seconds", "0", "--no-variants",
                             "--no-cpu-baseline", "--dtype", "f64", "--normalizer-sync", sync],
                            env=env, capture_output=True, text=True, timeout=1500)
@@ -813,7 +844,7 @@ def test_bench_at_config_d_shape_with_eight_ranks(hip_lib):
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         assert len(lines) == 1, r.stdout[-2000:]
         rec = json.loads(lines[0])
-        assert rec["n_gpus"] == 8 and rec["rccl_ranks"] == 8 and rec["config"]["global_envs"] == 32768
+        assert rec["n_gpus"] == 4 and rec["rccl_ranks"] == 4 and rec["config"]["global_envs"] == 32768
         assert rec["replicas_identical"] is True and rec["config"]["normalizer_sync"] == sync
         assert rec["health"]["protocol_errors"] == 0
         assert abs(rec["value"] - 32768 / (rec["ms_per_step"] * 1e-3)) <= 1e-3 * rec["value"]

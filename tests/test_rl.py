@@ -800,7 +800,7 @@ def test_lstm_seq_layouts_follow_the_header(H, rs):
     assert lstm_seq_row_split(128, 2, 4096) == 1 and lstm_seq_row_split(256, 2, 1024) == 2
 
 
-def test_callbacks_of_a_resumed_run_count_from_their_first_rollout():
+def test_callbacks_of_a_resumed_run_count_from_their_first_rollout(tmp_path):
     """a callback object created for a run that resumes from a checkpoint (num_timesteps far above 0) must not fire on the
     first rollout — SB3's n_calls restarts with the callback object — and the checkpoint it writes later is named after the run's
     ABSOLUTE timesteps."""
@@ -809,7 +809,7 @@ def test_callbacks_of_a_resumed_run_count_from_their_first_rollout():
     saved = []
     algo = SimpleNamespace(env=SimpleNamespace(num_envs=4), world=1, cfg=SimpleNamespace(n_steps=8), num_timesteps=0, n_calls=0, policy=None,
                            save=lambda path: saved.append(path))
-    ck = CheckpointCallback(save_freq=20, save_path="/tmp/_myo_ck_test", name_prefix="m")
+    ck = CheckpointCallback(save_freq=20, save_path=str(tmp_path / "ck"), name_prefix="m")
     ev = EvalCallback(eval_env=None, eval_freq=20, verbose=0)
     ls = EvaluateLSTM(eval_freq=1000, eval_env=None, name="x")
     fired = {"ev": 0, "ls": 0}
@@ -824,7 +824,7 @@ def test_callbacks_of_a_resumed_run_count_from_their_first_rollout():
             assert "last" not in fired and not saved, (cb, saved)            # nothing fires: 8 steps < every frequency
         algo.n_calls, algo.num_timesteps = 1000 + 24, (1000 + 24) * 4         # 24 steps since the resume: the 20-step callbacks fire once
         ck(algo)
-        assert saved == ["/tmp/_myo_ck_test/m_%d_steps.zip" % ((1000 + 20) * 4)], saved
+        assert saved == [os.path.join(str(tmp_path / "ck"), "m_%d_steps.zip" % ((1000 + 20) * 4))], saved
         fired.pop("last", None); ev(algo); assert fired.get("last") == 1
         fired.pop("last", None); ls(algo); assert "last" not in fired        # (4096 timesteps: no multiple of 1000 since 4032)
         algo.n_calls, algo.num_timesteps = 1251, 5004

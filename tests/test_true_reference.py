@@ -123,9 +123,21 @@ def test_oracle_against_true_mujoco_trajectories(path, models):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("path", TRUE_FILES or [None])
-def test_hip_stepper_against_true_mujoco_trajectories(path, models, hip_lib):
+def test_hip_stepper_against_true_mujoco_trajectories(path, models, hip_lib, tmp_path):
+    """PINS THE HIP STEPPER to every true MuJoCo trajectory in tests/golden.  While none ships (`path` None), the same file route runs
+    on the device with the oracle as the stand-in producer on the reference's finger model — what test_trajectory_file_format_roundtrip
+    does on the emulation build: a written trajectory loads and replays through the HIP steppers, fp64 at the precision of
+    test_gpu_parity.py::test_trajectory_small_models over the first 100 substeps and within north_star's 1e-4 over all 300."""
     if path is None:
-        pytest.skip("no tests/golden/mujoco_traj_*.npz")
+        out = str(tmp_path / "traj_finger_oracle.npz")
+        meta = dmt.dump("oracle", os.path.join(GOLDEN, "myo_finger_v0.mjb"), out, substeps=300, seed=1, hold=10)
+        m2, z = load_traj(out)
+        assert m2 == meta and meta["is_true_reference"] is False and z["ctrl"].shape == (300, meta["nu"])
+        mj = model_for(meta, models)
+        err = replay_stepper(hip_lib, native.MYO_F64, meta, z, mj)
+        assert err[:100].max() < 1e-8 and err.max() < 1e-4, (err[:100].max(), err.max())
+        assert replay_stepper(hip_lib, native.MYO_MIXED, meta, z, mj)[:100].max() < 1e-4
+        return
     meta, z = load_traj(path)
     if not meta["is_true_reference"]:
         pytest.skip("stand-in producer")
