@@ -39,13 +39,16 @@ typedef struct myo_batch myo_batch;
  * kinematic chain, contact / joint-limit distances, the tendon-wrap predicates, the Newton cost, the observation —
  * and fp32 for the rest of the dynamics.  MYO_F32 is round 1's name for value 1. */
 enum { MYO_F64 = 0, MYO_MIXED = 1, MYO_F32 = 1 };
-enum { MYO_TASK_NONE = 0, MYO_TASK_BAODING_P1 = 1, MYO_TASK_BAODING_P2 = 2, MYO_TASK_REORIENT = 3 };
+enum { MYO_TASK_NONE = 0, MYO_TASK_BAODING_P1 = 1, MYO_TASK_BAODING_P2 = 2, MYO_TASK_REORIENT = 3, MYO_TASK_POSE = 4 };
+enum { MYO_POSE_RESET_INIT = 0, MYO_POSE_RESET_RANDOM = 1, MYO_POSE_RESET_SDS = 2 };      /* CustomPoseEnv reset_type ("none" is refused) */
+enum { MYO_POSE_TARGET_GENERATE = 0, MYO_POSE_TARGET_FIXED = 1 };                       /* CustomPoseEnv target_type */
 enum { MYO_WHICH_HOLD = 0, MYO_WHICH_CW = 1, MYO_WHICH_CCW = 2 }; /* MyoSuite Task enum */
 enum { MYO_CHOICE_FIXED = 0, MYO_CHOICE_CW = 1, MYO_CHOICE_CCW = 2, MYO_CHOICE_RANDOM = 3 };
 
 #define MYO_N_RWD 8 /* Baoding: pos_dist_1,pos_dist_2,act_reg,alive,sparse,solved,done,dense; die reorient: pos_dist,rot_dist,... */
 #define MYO_ROT_CHOICE_MAX 4 /* entries of a goal_rot_x/y/z range list */
 #define MYO_OBJG_MAX 20      /* geoms of the per-env object group (the die) */
+#define MYO_POSE_NQ_MAX 38   /* joints of a MYO_TASK_POSE model (the stepper's qpos capacity) */
 
 /* Task configuration = the kwargs of CustomBaodingEnv._setup / CustomBaodingP2Env._setup
  * (/root/reference/src/envs/baoding.py:210-227,300-324) lowered to plain numbers, plus the
@@ -81,6 +84,16 @@ typedef struct myo_task_cfg {
   double ro_obj_size_change, ro_pos_th, ro_rot_th;
   double ro_goal_init_pos[3], ro_goal_obj_offset[3];   /* site_xpos[target_o] and site_xpos[target_o] - site_xpos[object_o] at setup */
   double ro_rsi_distance_pos, ro_rsi_distance_rot;
+  /* -- kind MYO_TASK_POSE: the kwargs of CustomPoseEnv._setup (/root/reference/src/envs/pose.py:7-51) for a model of hinge joints only
+   * (nq = nv = n_hand; the hand with no object).  frame_skip, max_episode_steps as above; every other field above is unused.
+   * Arrays are indexed by joint = qpos index; pose_init_qpos is the env's init_qpos (the model's qpos0). */
+  double pose_weights[7];    /* weighted_reward_keys: pose, bonus, penalty, act_reg, sparse, solved, done */
+  double pose_thd, pose_far_th, pose_sds_distance, pose_target_distance;
+  int32_t pose_reset_type, pose_target_type;                /* MYO_POSE_RESET_*, MYO_POSE_TARGET_* */
+  double pose_init_qpos[MYO_POSE_NQ_MAX];
+  double pose_target_value[MYO_POSE_NQ_MAX];               /* target_type fixed: target_jnt_value */
+  double pose_target_range[MYO_POSE_NQ_MAX][2];            /* target_type generate: target_jnt_range (low, high) per joint */
+  double pose_reset_range[MYO_POSE_NQ_MAX][2];             /* reset_type random: the model's jnt_range */
 } myo_task_cfg;
 
 /* -- model ------------------------------------------------------------------------------
@@ -187,7 +200,11 @@ int myo_batch_warmstart(myo_batch* b, double* get_qacc_warmstart, const double* 
  *                           target1_x, target1_y, target2_x, target2_y (palm-frame site xy)
  * ball_d  dev double[N,10]= mass1, mass2, friction1[3], friction2[3], size1, size2
  * MYO_TASK_REORIENT batches: task_i = 0, episode step counter; task_d = goal_pos[3], goal_quat[4], pos_dist, rot_dist
- * (the shaping state of reorient.py:207-210); ball_d[8] = the die's size delta, the rest unused. */
+ * (the shaping state of reorient.py:207-210); ball_d[8] = the die's size delta, the rest unused.
+ * MYO_TASK_POSE batches: task_i = 0, episode step counter; task_d = dev double[N, 2 nq] = target_qpos[nq] (the episode's target after
+ * the target_distance blend), init_qpos[nq] (the state the episode started from: the reset_type's draw); ball_d unused (may be NULL).
+ * Both come from the env's Philox stream keyed by (seed, env, episode): draw j < nq = target joint j (generate), draw nq + j = reset
+ * joint j (random), each lo + (hi - lo) u. */
 int myo_batch_set_task(myo_batch* b, const int32_t* task_i, const double* task_d,
                        const double* ball_d, void* stream);
 int myo_batch_get_task(myo_batch* b, int32_t* task_i, double* task_d, double* ball_d, void* stream);

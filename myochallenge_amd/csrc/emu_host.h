@@ -79,7 +79,9 @@ extern "C" int myo_batch_set_task(myo_batch* b, const int32_t* task_i, const dou
   if (!b) return fail(MYO_E_ARG, "null batch");
   be_stream st = (be_stream)stream;
   xfer_i(b, b->L.off_misc, 2, (int*)task_i, 0, st);
-  xfer(b, b->L.off_taskd, MYO_TASKD_N, (double*)task_d, 0, st); xfer(b, b->L.off_balld, MYO_BALLD_N, (double*)ball_d, 0, st);
+  if (b->K.kind == MYO_TASK_POSE) xfer(b, b->L.off_pose, 2 * b->nq, (double*)task_d, 0, st);     // target_qpos | init_qpos
+  else xfer(b, b->L.off_taskd, MYO_TASKD_N, (double*)task_d, 0, st);
+  xfer(b, b->L.off_balld, MYO_BALLD_N, (double*)ball_d, 0, st);
   return MYO_OK;
 }
 extern "C" int myo_batch_set_object_group(myo_batch* b, int gid0, int gidn) {
@@ -118,7 +120,9 @@ extern "C" int myo_batch_get_task(myo_batch* b, int32_t* task_i, double* task_d,
   if (!b) return fail(MYO_E_ARG, "null batch");
   be_stream st = (be_stream)stream;
   xfer_i(b, b->L.off_misc, 2, (int*)task_i, 1, st);
-  xfer(b, b->L.off_taskd, MYO_TASKD_N, task_d, 1, st); xfer(b, b->L.off_balld, MYO_BALLD_N, ball_d, 1, st);
+  if (b->K.kind == MYO_TASK_POSE) xfer(b, b->L.off_pose, 2 * b->nq, task_d, 1, st);
+  else xfer(b, b->L.off_taskd, MYO_TASKD_N, task_d, 1, st);
+  xfer(b, b->L.off_balld, MYO_BALLD_N, ball_d, 1, st);
   return MYO_OK;
 }
 

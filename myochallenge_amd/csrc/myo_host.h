@@ -945,9 +945,17 @@ static void make_taskdev(const myo_task_cfg* c, uint64_t seed, TaskDev& K) {
     K.ro_obj_size_change = c->ro_obj_size_change; K.ro_pos_th = c->ro_pos_th; K.ro_rot_th = c->ro_rot_th;
     memcpy(K.ro_goal_init_pos, c->ro_goal_init_pos, 24); memcpy(K.ro_goal_obj_offset, c->ro_goal_obj_offset, 24);
   }
+  if (c->kind == MYO_TASK_POSE) {
+    memcpy(K.pose_weights, c->pose_weights, sizeof K.pose_weights);
+    K.pose_thd = c->pose_thd; K.pose_far_th = c->pose_far_th; K.pose_sds_distance = c->pose_sds_distance;
+    K.pose_target_distance = c->pose_target_distance; K.pose_reset_type = c->pose_reset_type; K.pose_target_type = c->pose_target_type;
+    memcpy(K.pose_init_qpos, c->pose_init_qpos, sizeof K.pose_init_qpos); memcpy(K.pose_target_value, c->pose_target_value, sizeof K.pose_target_value);
+    memcpy(K.pose_target_range, c->pose_target_range, sizeof K.pose_target_range); memcpy(K.pose_reset_range, c->pose_reset_range, sizeof K.pose_reset_range);
+  }
 }
-static_assert(MYO_TASK_REORIENT == MYO_TASK_REORIENT_K, "task kind ids");
+static_assert(MYO_TASK_REORIENT == MYO_TASK_REORIENT_K && MYO_TASK_POSE == MYO_TASK_POSE_K, "task kind ids");
 static int task_nobs_host(const myo_task_cfg* c, int na) {
+  if (c->kind == MYO_TASK_POSE) return 3 * c->n_hand;
   return c->kind == MYO_TASK_REORIENT ? 2 * c->n_hand + 18 + na : c->n_hand + 24 + na;
 }
 
@@ -956,9 +964,14 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
   if (!m || !out || n_envs <= 0) return fail(MYO_E_ARG, "bad arguments to myo_batch_create");
   if (dtype != MYO_F64 && dtype != MYO_F32) return fail(MYO_E_ARG, "dtype must be MYO_F64 or MYO_F32");
   if (cfg && cfg->kind != MYO_TASK_NONE) {
-    if (cfg->kind != MYO_TASK_BAODING_P1 && cfg->kind != MYO_TASK_BAODING_P2 && cfg->kind != MYO_TASK_REORIENT)
+    if (cfg->kind != MYO_TASK_BAODING_P1 && cfg->kind != MYO_TASK_BAODING_P2 && cfg->kind != MYO_TASK_REORIENT && cfg->kind != MYO_TASK_POSE)
       return fail(MYO_E_ARG, "unknown task kind");
-    if (cfg->kind == MYO_TASK_REORIENT) {
+    if (cfg->kind == MYO_TASK_POSE) {
+      if (cfg->n_hand != m->nq || m->nv != m->nq || m->nq > MYO_POSE_NQ_MAX || task_nobs_host(cfg, m->na) > MYO_OBS_MAX)
+        return fail(MYO_E_UNSUPPORTED, "joint-pose task needs a model of hinge / slide joints only (nq = nv = n_hand <= %d)", MYO_POSE_NQ_MAX);
+      if (cfg->pose_reset_type < MYO_POSE_RESET_INIT || cfg->pose_reset_type > MYO_POSE_RESET_SDS) return fail(MYO_E_ARG, "pose_reset_type");
+      if (cfg->pose_target_type != MYO_POSE_TARGET_GENERATE && cfg->pose_target_type != MYO_POSE_TARGET_FIXED) return fail(MYO_E_ARG, "pose_target_type");
+    } else if (cfg->kind == MYO_TASK_REORIENT) {
       if (cfg->obj1_sid < 0 || cfg->obj1_sid >= m->nsite || cfg->target1_sid < 0 || cfg->target1_sid >= m->nsite ||
           cfg->obj1_bid <= 0 || cfg->obj1_bid >= m->nbody || cfg->obj1_gid < 0 || cfg->obj2_gid <= cfg->obj1_gid || cfg->obj2_gid > m->ngeom)
         return fail(MYO_E_ARG, "task ids out of range");
@@ -1001,6 +1014,7 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
   L.off_qpos = o; o += m->nq; L.off_qvel = o; o += m->nv; L.off_act = o; o += m->na; L.off_warm = o; o += m->nv;
   L.off_time = o; o += 1; L.off_taskd = o; o += MYO_TASKD_N; L.off_balld = o; o += MYO_BALLD_N; L.off_misc = o; o += MYO_MISC_N;
   L.off_objfric = o; o += 3 * MYO_OBJG_MAX;
+  L.off_pose = o; if (b->K.kind == MYO_TASK_POSE) o += 2 * m->nq;     // (the other kinds' records keep their size)
   // (store_env writes qpos | qvel | act | warm | time as one run: the order above is part of the kernels' contract)
   if (L.off_qvel != L.off_qpos + m->nq || L.off_act != L.off_qvel + m->nv || L.off_warm != L.off_act + m->na || L.off_time != L.off_warm + m->nv) { delete b; return fail(MYO_E_STATE, "record layout"); }
   L.stride = (o + 15) / 16 * 16;      // whole 128-byte lines per env: no line is shared by two workgroups
@@ -1026,6 +1040,15 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
       for (int k = 0; k < 3; ++k) td[k] = b->K.ro_goal_init_pos[k];
       td[3] = 1.0;
       for (int j = 0; j < 3 * (b->K.objg_gidn - b->K.objg_gid0); ++j) r[L.off_objfric + j] = m->geom_friction[3 * b->K.objg_gid0 + j];
+    } else if (b->K.kind == MYO_TASK_POSE) {
+      // the init pose and the pseudo target of CustomPoseEnv._setup (pose.py:38-43: the mean of each target range); reset() draws the episode's
+      memset(td, 0, sizeof(double) * MYO_TASKD_N); mi[0] = 0;
+      for (int i = 0; i < m->nq; ++i) {
+        const double tv = b->K.pose_target_type == MYO_POSE_TARGET_FIXED ? b->K.pose_target_value[i]
+                                                                          : 0.5 * (b->K.pose_target_range[i][0] + b->K.pose_target_range[i][1]);
+        r[L.off_qpos + i] = b->K.pose_init_qpos[i];
+        r[L.off_pose + i] = tv; r[L.off_pose + m->nq + i] = b->K.pose_init_qpos[i];
+      }
     } else if (b->K.kind) {
       td[2] = 0.5 * (b->K.goal_xrange[0] + b->K.goal_xrange[1]); td[3] = 0.5 * (b->K.goal_yrange[0] + b->K.goal_yrange[1]);
       td[4] = 0.5 * (b->K.goal_time_period[0] + b->K.goal_time_period[1]);

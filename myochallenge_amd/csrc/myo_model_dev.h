@@ -46,6 +46,10 @@
 #ifndef MYO_ROT_CHOICE_MAX
 #define MYO_ROT_CHOICE_MAX 4
 #endif
+#ifndef MYO_POSE_NQ_MAX
+#define MYO_POSE_NQ_MAX 38  // joints of a joint-pose model (include/myobatch.h)
+#endif
+static_assert(MYO_POSE_NQ_MAX == MYO_NQ_MAX, "a pose model may use every qpos slot of the stepper");
 
 // X-macro lists: (type, name).  I = int32, U = uint64, R = real (T)
 #define MYO_MODEL_INT_ARRAYS(X)                                                                  \
@@ -128,6 +132,7 @@ struct DevModel {
 struct EnvRecordLayout {
   int nq, nv, na;
   int off_qpos, off_qvel, off_act, off_warm, off_time, off_taskd, off_balld, off_misc, off_objfric;
+  int off_pose;  // kind MYO_TASK_POSE: target_qpos[nq], init_qpos[nq] of the episode (2 nq doubles; other kinds: none, = stride)
   int stride;  // doubles per env
 };
 // taskd: start_angle[2], x_radius, y_radius, time_period, target_xy[4]  (9); die reorient: goal_pos[3], goal_quat[4], pos_dist, rot_dist

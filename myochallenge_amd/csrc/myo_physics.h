@@ -85,6 +85,7 @@ __device__ __forceinline__ constexpr int myo_hrow(int i) { const int q = i >> 2;
 #define MYO_WS_WARM (MYO_WS_RWD + 8)            /* the solver's warm start while a workgroup holds the env (load_env .. store_env) */
 #define MYO_ENVWS_N ((MYO_WS_WARM + MYO_NV_MAX + 15) / 16 * 16)
 #define MYO_TASK_REORIENT_K 3   // == MYO_TASK_REORIENT of include/myobatch.h (checked in myobatch.hip)
+#define MYO_TASK_POSE_K 4       // == MYO_TASK_POSE
 struct TaskDev {  // device copy of myo_task_cfg (ids = -1 when there is no task layer)
   int kind, frame_skip, max_episode_steps, n_hand;
   int obj1_sid, obj2_sid, target1_sid, target2_sid, obj1_bid, obj2_bid, obj1_gid, obj2_gid;
@@ -100,6 +101,10 @@ struct TaskDev {  // device copy of myo_task_cfg (ids = -1 when there is no task
   double ro_weights[9], ro_goal_pos[2], ro_goal_rot[2], ro_rot_choice[3][MYO_ROT_CHOICE_MAX][2];
   double ro_obj_size_change, ro_pos_th, ro_rot_th, ro_goal_init_pos[3], ro_goal_obj_offset[3];
   int ro_n_rot_choice[3], ro_obj_bid;
+  // joint pose (kind 4; include/myobatch.h pose_*)
+  double pose_weights[7], pose_thd, pose_far_th, pose_sds_distance, pose_target_distance;
+  int pose_reset_type, pose_target_type;
+  double pose_init_qpos[MYO_POSE_NQ_MAX], pose_target_value[MYO_POSE_NQ_MAX], pose_target_range[MYO_POSE_NQ_MAX][2], pose_reset_range[MYO_POSE_NQ_MAX][2];
   void* rk_ws;                // RkScratch<T>[n_envs] in global memory (RK4 models), else null
   int objf_off;               // env record: doubles from the warm start to the object group's friction triples (Scratch::SPILL reads them in place)
   int* slot_map;              // int[MYO_WS_SLOTS]: owner flags of the workspace blocks (myo_ws_acquire / myo_ws_release, wave.h); emulation: null

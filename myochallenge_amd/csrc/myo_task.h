@@ -14,6 +14,9 @@
 //   CustomReorientEnv.reset / set_orientation  /root/reference/src/envs/reorient.py:124-205
 //   CustomReorientEnv.step (shaping state)     /root/reference/src/envs/reorient.py:207-212
 //   ReorientEnvV0.get_obs_dict, euler2quat / mat2euler  [MyoSuite 1.2.3, 3P-RECALL]
+// Joint pose (kind MYO_TASK_POSE), same structure:
+//   CustomPoseEnv.reset / get_target_pose      /root/reference/src/envs/pose.py:55-117
+//   PoseEnvV0.get_obs_dict / get_reward_dict   [MyoSuite 1.x, 3P-RECALL: the table at the top of envs/pose.py]
 // Random numbers: the reference mixes gym's np_random, the global np.random and random.choice
 // (SURVEY §7.4-6); seed-for-seed parity is not meaningful, so the device draws from
 // Philox4x32-10 keyed by (seed, env, episode) in the reference's draw ORDER.
@@ -198,20 +201,56 @@ DEVFN void reorient_obs_reward(const DevModel<T>& M_in, const TaskDev& K_in, Scr
   SYNC_G();      // (Scratch::SPILL keeps the reward terms in global memory: every lane reads them)
 }
 
+// ---- joint pose: observation = qpos, qvel * dt, pose_err = target - qpos (nq + nv + nq; a model of hinge / slide joints); the reward
+// dictionary of PoseEnvV0.get_reward_dict with pose_dist = |pose_err|, act_mag = |act| / na.  comps = pose, bonus, penalty, act_reg,
+// sparse, solved, done, dense (`done` in slot 6 and `dense` in slot 7, where env_step reads them for every kind).
+// P: the env's pose block in its HBM record (target_qpos[nq], init_qpos[nq]), written by pose_reset only.
 template <typename T, int NC>
-DEV void task_obs_reward(const DevModel<T>& M, const TaskDev& K, Scratch<T, NC>& s) {
-  if (K.kind == MYO_TASK_REORIENT_K) reorient_obs_reward(M, K, s); else baoding_obs_reward(M, K, s);
+DEVFN void pose_obs_reward(const DevModel<T>& M_in, const TaskDev& K_in, Scratch<T, NC>& s_in, const double* P) {
+  MYO_BIND_M(T) MYO_BIND_K MYO_BIND_S(T)
+  WAVE_FN
+  const int nq = M.nq, nv = M.nv;
+  const HP dt = (HP)K.frame_skip * M.h_timestep;
+  T* o = S_OBS(s);
+  PHASE {
+    for (int i = lane; i < nq; i += 64) { o[i] = (T)s.qpos[i]; o[nq + nv + i] = (T)(P[i] - s.qpos[i]); }
+    for (int i = lane; i < nv; i += 64) o[nq + i] = (T)(s.qvel[i] * dt);
+  }
+  SYNC();
+  WAVE_SUM_N(HP, esq, nq, i, ((P[i] - s.qpos[i]) * (P[i] - s.qpos[i])));
+  WAVE_SUM_N(HP, asq, M.na, i, ((HP)S_ACT(M, s)[i] * (HP)S_ACT(M, s)[i]));
+  PHASE {
+    if (lane == 0) {
+      const HP d = sqrt(esq), am = M.na ? sqrt(asq) / (HP)M.na : (HP)0;
+      const int far = d > K.pose_far_th, near = d < K.pose_thd;
+      HP c[7];
+      c[0] = -d; c[1] = (HP)near + (HP)(d < 1.5 * K.pose_thd); c[2] = far ? -1 : 0; c[3] = -am; c[4] = -d; c[5] = near; c[6] = far;
+      HP dense = 0;
+      for (int k = 0; k < 7; ++k) { dense += K.pose_weights[k] * c[k]; S_RWD(s)[k] = (T)c[k]; }
+      S_RWD(s)[7] = (T)dense;
+    }
+  }
+  SYNC_G();      // (Scratch::SPILL keeps the reward terms in global memory: every lane reads them)
 }
-DEV int task_nobs(const TaskDev& K, int na) { return K.kind == MYO_TASK_REORIENT_K ? 2 * K.n_hand + 18 + na : K.n_hand + 24 + na; }
+
+template <typename T, int NC>
+DEV void task_obs_reward(const DevModel<T>& M, const TaskDev& K, Scratch<T, NC>& s, const double* pose) {
+  if (K.kind == MYO_TASK_POSE_K) pose_obs_reward(M, K, s, pose);
+  else if (K.kind == MYO_TASK_REORIENT_K) reorient_obs_reward(M, K, s); else baoding_obs_reward(M, K, s);
+}
+DEV int task_nobs(const TaskDev& K, int na) {
+  if (K.kind == MYO_TASK_POSE_K) return 3 * K.n_hand;
+  return K.kind == MYO_TASK_REORIENT_K ? 2 * K.n_hand + 18 + na : K.n_hand + 24 + na;
+}
 
 // ---- env.step(a) without the VecEnv bookkeeping
 // An env step may be run in parts by several workgroups (the launch's makespan, see k_step): substeps [k_lo, k_hi) of the
 // frame_skip; the part that starts at 0 also moves the targets, every part recomputes ctrl (a pure function of the action), the
 // part that ends at frame_skip also makes observation and reward (k_hi < 0 = frame_skip).  Everything a substep hands to the
-// next one is in the env record (load_env / store_env), so the split is bit-exact.
+// next one is in the env record (load_env / store_env), so the split is bit-exact.  pose: the env's pose block (MYO_TASK_POSE only).
 template <typename T, int RKM = -1, int NC>
 DEV void task_step_core(const DevModel<T>& M_in, const TaskDev& K_in, Scratch<T, NC>& s_in, const float* action /* may be null = zeros */,
-                        int k_lo = 0, int k_hi = -1) {
+                        int k_lo = 0, int k_hi = -1, const double* pose = nullptr) {
   MYO_BIND_M(T) MYO_BIND_K MYO_BIND_S(T)
   WAVE_FN_K
   PHASE {
@@ -244,8 +283,8 @@ DEV void task_step_core(const DevModel<T>& M_in, const TaskDev& K_in, Scratch<T,
   for (int k = k_lo; k < k_end; ++k) mj_step<T, RKM>(M, K, s);
   if (k_end < K.frame_skip) return;
   check_state(M, s, 0);            // a non-finite value produced by the LAST advance must not leave through obs / reward
-  kinematics(M, s);
-  task_obs_reward(M, K, s);
+  if (K.kind != MYO_TASK_POSE_K) kinematics(M, s);     // (the pose observation is joint space only)
+  task_obs_reward(M, K, s, pose);
 }
 
 template <typename T, int NC>
@@ -454,9 +493,45 @@ DEVFN void reorient_reset(const DevModel<T>& M_in, const TaskDev& K_in, Scratch<
   reorient_obs_reward(M, K, s);      // leaves pos_dist / rot_dist of the reset state (reorient.py:178-179)
 }
 
+// ---- joint pose reset (pose.py:55-97 with get_target_pose, :109-113): the target first (fixed value or U(target_jnt_range) per joint,
+// then init_qpos + target_distance (target - init_qpos)), then the state by reset_type — init: init_qpos; random: U(jnt_range) per joint;
+// sds: (1 - sds_distance) target + sds_distance init_qpos — with zero velocity, activations and warm start (robot.reset).  Draws from
+// the env's Philox stream of the episode: lane j takes draw j (target joint j) and draw nq + j (reset joint j), the reference's order.
 template <typename T, int NC>
-DEV void task_reset(const DevModel<T>& M, const TaskDev& K, Scratch<T, NC>& s, int env) {
-  if (K.kind == MYO_TASK_REORIENT_K) reorient_reset(M, K, s, env); else baoding_reset(M, K, s, env);
+DEVFN void pose_reset(const DevModel<T>& M_in, const TaskDev& K_in, Scratch<T, NC>& s_in, int env, double* P) {
+  MYO_BIND_M(T) MYO_BIND_K MYO_BIND_S(T)
+  WAVE_FN
+  Philox g;
+  g.key0 = (unsigned int)K.seed; g.key1 = (unsigned int)(K.seed >> 32);
+  g.c0 = (unsigned int)env; g.c1 = (unsigned int)s.episode; g.c2 = 0x504f5345u; g.idx = 0;
+  const int nq = M.nq;
+  PHASE {
+    for (int i = lane; i < nq; i += 64) {
+      Philox h = g;
+      h.idx = (unsigned int)i;
+      const double q0 = K.pose_init_qpos[i];
+      const double full = K.pose_target_type == MYO_POSE_TARGET_FIXED ? K.pose_target_value[i]
+                                                                       : rng_range(h, K.pose_target_range[i][0], K.pose_target_range[i][1]);
+      const double tv = q0 + K.pose_target_distance * (full - q0);
+      double qs = q0;
+      if (K.pose_reset_type == MYO_POSE_RESET_RANDOM) { h.idx = (unsigned int)(nq + i); qs = rng_range(h, K.pose_reset_range[i][0], K.pose_reset_range[i][1]); }
+      else if (K.pose_reset_type == MYO_POSE_RESET_SDS) qs = (1.0 - K.pose_sds_distance) * tv + K.pose_sds_distance * q0;
+      P[i] = tv; P[nq + i] = qs;
+      s.qpos[i] = qs;
+    }
+    for (int i = lane; i < M.nv; i += 64) { s.qvel[i] = 0; warm_set(s, i, (T)0); }
+    for (int i = lane; i < M.na; i += 64) act_set(M, s, i, (HP)0);
+    for (int i = lane; i < M.nu; i += 64) ctrl_set(s, i, (T)0);
+    if (lane == 0) { s.time = 0; s.bad = 0; s.which_task = 0; s.counter = 0; s.elapsed = 0; s.ep_ret = 0; s.ep_len = 0; }
+  }
+  SYNC_G();      // (every lane reads the pose block back)
+  pose_obs_reward(M, K, s, P);
+}
+
+template <typename T, int NC>
+DEV void task_reset(const DevModel<T>& M, const TaskDev& K, Scratch<T, NC>& s, int env, double* pose) {
+  if (K.kind == MYO_TASK_POSE_K) pose_reset(M, K, s, env, pose);
+  else if (K.kind == MYO_TASK_REORIENT_K) reorient_reset(M, K, s, env); else baoding_reset(M, K, s, env);
 }
 
 // ---- HBM record <-> scratch
@@ -585,7 +660,7 @@ DEV void env_step(const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout&
   WAVE_FN_K
   const int nobs = task_nobs(K, M.na);
   load_env(M, K, L, rec, s, env, pub);
-  task_step_core<T, RKM>(M, K, s, act + (size_t)env * M.nu, k_lo, k_hi);
+  task_step_core<T, RKM>(M, K, s, act + (size_t)env * M.nu, k_lo, k_hi, rec + L.off_pose);
   if (k_hi >= 0 && k_hi < K.frame_skip) { store_env(M, K, L, rec, s, (s.pub ? 3 : 1) | (k_lo > 0 ? 4 : 0)); ws_release(K, s); return; }
   // A numerically blown-up env (mj_checkPos / mj_checkVel / mj_checkAcc: MuJoCo warns and resets the data) is not
   // an error of the batch: the env ends its episode with done = 1, reward 0, zero reward components except `done`,
@@ -614,7 +689,7 @@ DEV void env_step(const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout&
   if (is_done) {
     PHASE { if (lane == 0) s.episode++; }
     SYNC();
-    task_reset(M, K, s, env);
+    task_reset(M, K, s, env, rec + L.off_pose);
   }
   PHASE {
     for (int i = lane; i < nobs; i += 64) {
@@ -639,12 +714,12 @@ DEV void env_step_inner(const DevModel<T>& M, const TaskDev& K, const EnvRecordL
   const int nobs = task_nobs(K, M.na);
   const int io = row < 0 ? env : row;
   load_env(M, K, L, rec, s, env);
-  task_step_core<T, RKM>(M, K, s, act + (size_t)io * M.nu);
+  task_step_core<T, RKM>(M, K, s, act + (size_t)io * M.nu, 0, -1, rec + L.off_pose);
   const int bad = s.bad, fall = S_RWD(s)[6] != 0 || bad;
   if (bad) {                        // blown-up env: back to a finite reset state (see env_step)
     PHASE { if (lane == 0) s.episode++; }
     SYNC();
-    task_reset(M, K, s, env);
+    task_reset(M, K, s, env, rec + L.off_pose);
   }
   PHASE {
     if (lane == 0 && done_out) done_out[io] = (unsigned char)fall;
@@ -664,7 +739,7 @@ DEV void env_reset(const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout
   load_env(M, K, L, rec, s, env);
   PHASE { if (lane == 0) s.episode++; }
   SYNC();
-  task_reset(M, K, s, env);
+  task_reset(M, K, s, env, rec + L.off_pose);
   if (obs) { PHASE { for (int i = lane; i < nobs; i += 64) obs[(size_t)env * nobs + i] = (float)S_OBS(s)[i]; } SYNC(); }
   store_env(M, K, L, rec, s);
   ws_release(K, s);

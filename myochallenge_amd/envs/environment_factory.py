@@ -35,15 +35,18 @@ class EnvironmentFactory:
         if env_name in ("CustomMyoReorientP1", "CustomMyoReorientP2"):          # src/envs/reorient.py
             from .reorient import ReorientVecEnv
             return ReorientVecEnv(env_name, num_envs, kwargs, **batch_kw)
+        from .pose import REGISTRATION as POSE_REGISTRATION
+        if env_name in POSE_REGISTRATION:                                         # src/envs/pose.py
+            from .pose import PoseVecEnv
+            return PoseVecEnv(env_name, num_envs, kwargs, **batch_kw)
         known_elsewhere = ("MyoFingerPoseFixed", "MyoFingerPoseRandom", "MyoFingerReachFixed",
                            "MyoFingerReachRandom", "MyoHandKeyTurnFixed", "MyoHandKeyTurnRandom",
                            "MyoBaodingBallsP1",
                            "MyoBaodingBallsP2", "CustomMyoElbowPoseFixed",
                            "CustomMyoElbowPoseRandom", "CustomMyoFingerPoseFixed",
-                           "CustomMyoFingerPoseRandom", "CustomMyoHandPoseFixed",
-                           "CustomMyoHandPoseRandom", "CustomMyoPenTwirlRandom")
+                           "CustomMyoFingerPoseRandom", "CustomMyoPenTwirlRandom")
         if env_name in known_elsewhere:
             raise NotImplementedError(
                 f"{env_name}: named by the reference but outside this build's hot-path scope "
-                "(SURVEY.md §8: the Baoding P1 / P2 / MixtureModel and die-reorient P1 / P2 envs are implemented so far)")
+                "(SURVEY.md §8: the Baoding P1 / P2 / MixtureModel, die-reorient P1 / P2 and MyoHand joint-pose envs are implemented so far)")
         raise ValueError("Environment name not recognized:", env_name)

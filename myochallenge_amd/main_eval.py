@@ -32,7 +32,9 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
     from .metrics.evaluation import evaluate_policy, summarize
     from .rl.sb3_zip import load_policy
     from .rl.vec_normalize import VecNormalize
-    config = dict(DEFAULT_CONFIG if config is None else config)
+    if config is None:             # the reference script's Baoding config; other envs: their registration defaults
+        config = DEFAULT_CONFIG if env_name.startswith("CustomMyoBaoding") or env_name == "MixtureModelBaodingEnv" else {}
+    config = dict(config)
     env = EnvironmentFactory.create(env_name, num_envs=min(num_envs, num_episodes), seed=seed, **config)
     venv = VecNormalize.load(env_path, env)
     venv.training = False          # src/main_eval.py:66-67

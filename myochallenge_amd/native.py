@@ -18,13 +18,15 @@ LIB_PATH = os.path.join(_HERE, "libmyobatch.so")
 
 MYO_F64, MYO_MIXED = 0, 1     # stepper arithmetic: all fp64 | mixed (fp64 state, kinematic chain, contact distances; fp32 dynamics)
 MYO_F32 = MYO_MIXED             # the name of round 1, when dtype 1 was a pure fp32 stepper
-TASK_NONE, TASK_BAODING_P1, TASK_BAODING_P2, TASK_REORIENT = 0, 1, 2, 3
+TASK_NONE, TASK_BAODING_P1, TASK_BAODING_P2, TASK_REORIENT, TASK_POSE = 0, 1, 2, 3, 4
+POSE_RESET_INIT, POSE_RESET_RANDOM, POSE_RESET_SDS = 0, 1, 2
+POSE_TARGET_GENERATE, POSE_TARGET_FIXED = 0, 1
 CHOICE_FIXED, CHOICE_CW, CHOICE_CCW, CHOICE_RANDOM = 0, 1, 2, 3
 N_RWD = 8
 RWD_KEYS = ("pos_dist_1", "pos_dist_2", "act_reg", "alive", "sparse", "solved", "done", "dense")
 
 
-ROT_CHOICE_MAX, OBJG_MAX = 4, 20      # include/myobatch.h
+ROT_CHOICE_MAX, OBJG_MAX, POSE_NQ_MAX = 4, 20, 38      # include/myobatch.h
 
 
 class TaskCfg(C.Structure):
@@ -54,6 +56,13 @@ class TaskCfg(C.Structure):
         ("ro_obj_size_change", C.c_double), ("ro_pos_th", C.c_double), ("ro_rot_th", C.c_double),
         ("ro_goal_init_pos", C.c_double * 3), ("ro_goal_obj_offset", C.c_double * 3),
         ("ro_rsi_distance_pos", C.c_double), ("ro_rsi_distance_rot", C.c_double),
+        # joint pose (kind TASK_POSE)
+        ("pose_weights", C.c_double * 7),
+        ("pose_thd", C.c_double), ("pose_far_th", C.c_double), ("pose_sds_distance", C.c_double),
+        ("pose_target_distance", C.c_double),
+        ("pose_reset_type", C.c_int32), ("pose_target_type", C.c_int32),
+        ("pose_init_qpos", C.c_double * POSE_NQ_MAX), ("pose_target_value", C.c_double * POSE_NQ_MAX),
+        ("pose_target_range", C.c_double * 2 * POSE_NQ_MAX), ("pose_reset_range", C.c_double * 2 * POSE_NQ_MAX),
     ]
 
 

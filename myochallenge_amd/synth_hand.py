@@ -30,6 +30,8 @@ contacts), not its biomechanics.
 """
 from __future__ import annotations
 
+import copy
+import functools
 import os
 
 import numpy as np
@@ -40,6 +42,11 @@ from .setconst import set_const
 
 ASSET = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "synth_myohand_baoding.npz")
 ASSET_DIE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "synth_myohand_die.npz")
+# joint names and order of myo_hand_pose.mjb: jnt_namesHand, /root/reference/src/envs/__init__.py:191
+JNT_NAMES_HAND = ("pro_sup", "deviation", "flexion", "cmc_abduction", "cmc_flexion", "mp_flexion", "ip_flexion",
+                  "mcp2_flexion", "mcp2_abduction", "pm2_flexion", "md2_flexion", "mcp3_flexion", "mcp3_abduction",
+                  "pm3_flexion", "md3_flexion", "mcp4_flexion", "mcp4_abduction", "pm4_flexion", "md4_flexion",
+                  "mcp5_flexion", "mcp5_abduction", "pm5_flexion", "md5_flexion")
 DIE_H = 0.014        # half extent of the die's outer envelope
 DIE_R = 0.004        # radius of its corner spheres / edge capsules
 DIE_MASS = 0.05
@@ -266,14 +273,21 @@ def _palm_frame(t1, t2, b1, b2):
     return R, O
 
 
-def build_synthetic_hand(golden_obs=None, lengthrange_samples=384, objects="balls") -> MjbModel:
+def build_synthetic_hand(golden_obs=None, lengthrange_samples=384, objects="balls", targets=None) -> MjbModel:
     """objects = "balls": the Baoding model (two free spheres).  objects = "die": the same hand with ONE free
     die for the reorient task (src/envs/reorient.py): body ``Object`` = 12 edge capsules + 3 box slabs (a rounded
     cube whose last three geoms are boxes, as reorient.py:143-145 indexes them), site ``object_o``; static body ``target`` with site ``target_o``, ``target_ball`` and the
-    non-colliding geom ``target_dice`` (reorient.py:76-101)."""
+    non-colliding geom ``target_dice`` (reorient.py:76-101).  objects = "none": the hand alone, the stand-in for ``myo_hand_pose.mjb`` of
+    the joint-pose tasks (src/envs/__init__.py:171-228): 23 hinges in the order of ``jnt_namesHand``; its geoms have contype 1 and
+    conaffinity 0, so no two of them collide (as in the Baoding model, whose hand only touches the balls).
+    targets = (target1, target2): the world positions of the two target sites at the init pose, in place of golden_obs[35:41]."""
+    if objects not in ("balls", "die", "none"):
+        raise ValueError(f"objects must be 'balls', 'die' or 'none', not {objects!r}")
     t1, t2 = TARGET1.copy(), TARGET2.copy()
     if golden_obs is not None:
         t1, t2 = np.array(golden_obs[35:38], float), np.array(golden_obs[38:41], float)
+    if targets is not None:
+        t1, t2 = np.array(targets[0], float), np.array(targets[1], float)
     R, O = _palm_frame(t1, t2, BALL1, BALL2)
     b1l, b2l = R.T @ (BALL1 - O), R.T @ (BALL2 - O)
     B = _Builder()
@@ -385,7 +399,7 @@ def build_synthetic_hand(golden_obs=None, lengthrange_samples=384, objects="ball
         B.add_geom("ball2", ball2, 2, (BALL_R,), collide=2)
         B.add_site("ball1_site", ball1, (0, 0, 0))
         B.add_site("ball2_site", ball2, (0, 0, 0))
-    else:
+    elif objects == "die":
         # ---- die: rests on the palm surface between the two ball positions, axes along the palm frame
         n_w = R @ nb_                                         # palm-surface normal in world coordinates
         die0 = 0.5 * (BALL1 + BALL2) + (DIE_H - BALL_R) * n_w
@@ -542,6 +556,28 @@ def load_asset(path=ASSET) -> MjbModel:
 def synthetic_hand() -> MjbModel:
     """The committed synthetic stand-in (rebuild with ``python -m myochallenge_amd.synth_hand``)."""
     return load_asset()
+
+
+@functools.lru_cache(maxsize=1)
+def _pose_model() -> MjbModel:
+    # the hand of the committed Baoding stand-in, built again without its balls: the builder's palm frame comes from the world
+    # positions of the two target sites at the init pose qpos = [-1.57, 0, ...] (baoding.py:283), read off that model
+    from .setconst import kinematics
+    hand = synthetic_hand()
+    q = np.array(hand.qpos0, float)
+    q[0] = -1.57
+    xpos, _, xmat, _, _ = kinematics(hand, q)
+    site_pos, site_body = np.asarray(hand.site_pos, float).reshape(-1, 3), np.asarray(hand.site_bodyid)
+    t = [xpos[site_body[s]] + xmat[site_body[s]] @ site_pos[s] for s in (hand.name2id("site", "target1_site"), hand.name2id("site", "target2_site"))]
+    m = build_synthetic_hand(objects="none", targets=t)
+    assert tuple(m.names["jnt"]) == JNT_NAMES_HAND, "joint order of the pose model must be jnt_namesHand"
+    return m
+
+
+def synthetic_hand_pose() -> MjbModel:
+    """The synthetic hand of the joint-pose tasks (no object): labelled stand-in for ``myo_hand_pose.mjb``.  Built from source on
+    first use in a process (a few seconds: set_const's length-range sampling), then copied from the cache."""
+    return copy.deepcopy(_pose_model())
 
 
 def synthetic_hand_die() -> MjbModel:
