@@ -20,8 +20,12 @@ taken as the max over ranks; `ms_per_step` is that block's wall time / K and `va
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the timed path computed in its last step as DIR/<name>.npy
 (float32 / float64; see dump_outputs()).  Inputs are seeded (env seed, policy init, sampling stream), so two builds
-run with the same arguments can be compared output for output.  `variants` (rank 0, N = 1) carries the
-same measurement for the mixed-precision stepper and for the RK4 integrator, `config_C_p2_8192` (BASELINE config C: phase 2, 8192 envs) and
+run with the same arguments can be compared output for output.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump, the result line (whose `roofline`
+prices this run's kernel time with the committed flop and PMC records).  --full adds what it does not need: the pointer to the
+committed trajectory-parity records, the CPU baseline with its flop count (N = 1, run before the GPU is opened), and `variants`
+(rank 0, N = 1), which carries the same measurement for the mixed-precision stepper and for the RK4 integrator, `config_C_p2_8192` (BASELINE config C: phase 2, 8192 envs) and
 `reorient_p2_mlp` (the die env with the MLP policy) on the fp64 stepper, plus `config_E_lstm256`: BASELINE config E (die reorient,
 4096 envs, the reference's recurrent LSTM-256 policy class, rollout + update; myochallenge_amd/rl/bench_reorient_lstm.py).  Since round 4 the headline is the all-fp64 stepper
 (`--dtype f64`, the reference's own arithmetic); `--dtype mixed` is the faster variant whose per-step error is bounded in
@@ -87,7 +91,7 @@ def cpu_baseline(seconds: float, all_cores: bool):
     out["flops"] = count_flops()
     if all_cores:
         import multiprocessing as mp
-        nc = os.cpu_count() or 1
+        nc = len(os.sched_getaffinity(0))      # the CPUs this process may run on (os.cpu_count() on an unrestricted host)
         ctx = mp.get_context("fork")
         q = ctx.Queue()
         ps = [ctx.Process(target=worker, args=(seconds, 100 + i, q)) for i in range(nc)]
@@ -230,7 +234,9 @@ def main():
                          "mixed = fp64 state / kinematic chain / contact distances / tendon lengths, fp32 dynamics (f32 is round 1's name for it)")
     ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the K-step block until this much timed wall has passed "
                     "(default 0: exactly one block, i.e. --steps timed steps)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the f64 / RK4 variant measurements (rank 0, N = 1 only)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the CPU baseline, the "
+                    "variants (other steppers, integrators and configs) and the trajectory-parity pointer (default: off)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the variant measurements (rank 0, N = 1 only)")
     ap.add_argument("--integrator", default="model", choices=["model", "euler", "rk4"])
     ap.add_argument("--n-steps", type=int, default=64, help="rollout length between PPO updates")
     ap.add_argument("--n-epochs", type=int, default=10)
@@ -244,13 +250,18 @@ def main():
                     help="N > 1 ranks: VecNormalize statistics exchanged at every env step (one small all-reduce between the two rollout "
                          "graphs; the reference's single VecNormalize over all envs, exactly), once per rollout, or not at all")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the arrays the last timed step computed as DIR/<name>.npy (rank 0, at most 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
+
+    # host-only work, done before this process opens the GPU so that the forked workers hold no handle on it
+    cpu = None
+    if args.full and not args.no_cpu_baseline and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+        cpu = cpu_baseline(args.cpu_seconds, all_cores=True)
 
     import torch
     import torch.distributed as dist
@@ -402,8 +413,8 @@ def main():
     dtype = "mixed" if args.dtype == "f32" else args.dtype
     main_res = measure(dtype, args.integrator, args.min_seconds, args.steps, args.warmup, dump_dir=args.dump_outputs)
     variants = {}
-    if rank == 0 and world == 1 and not args.no_variants and not args.no_ppo and not args.lstm_hidden:
-        # the other steppers of the same workload, so that the driver's run records them too (short blocks: ~1 s each)
+    if args.full and rank == 0 and world == 1 and not args.no_variants and not args.no_ppo and not args.lstm_hidden:
+        # the other steppers of the same workload, so that a --full run records them too (short blocks: ~1 s each)
         other = "mixed" if dtype == "f64" else "f64"
         for name, (dt, integ) in {other: (other, args.integrator), "rk4": (dtype, "rk4"), "rk4_" + other: (other, "rk4")}.items():
             if (dt, integ) == (dtype, args.integrator):
@@ -441,9 +452,6 @@ def main():
         kernel_ms, integ_name = main_res["env_kernel_ms"], main_res["integrator"]
         alg_bytes = ALG_BYTES_F64_STATE * args.envs
         achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else None
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            cpu = cpu_baseline(args.cpu_seconds, all_cores=True)
         flops = (cpu or {}).get("flops")
         if flops is None:
             try:
@@ -502,7 +510,6 @@ def main():
                        "parallelism": f"env-sharded x{world}, 1 RCCL grad all-reduce per optimizer step"},
             "blocks": main_res["blocks"], "timed_steps": main_res["timed_steps"], "timed_seconds": main_res["timed_seconds"],
             "ms_per_step_min": main_res["ms_per_step_min"], "ms_per_step_max": main_res["ms_per_step_max"],
-            "trajectory_parity": trajectory_parity(),
             "ppo_optimizer_steps_per_sec": main_res["optimizer_steps_per_sec"],
             "env_kernel_ms": kernel_ms,
             "env_kernel_only_steps_per_sec_per_gpu": args.envs / (kernel_ms * 1e-3) if kernel_ms > 0 else None,
@@ -525,7 +532,6 @@ def main():
                          "note": "one env per wavefront; the launch is a long dependent chain of small vector ops, so the bound is "
                                  "vector-ALU issue + LDS / instruction latency, not HBM (algorithmic bytes = 2508 B/env-step x envs "
                                  "per launch) and not MFMA; kernel_ms is measured live with HIP events on the launch stream"},
-            "variants": variants,
             "health": main_res["health"],
             "library_build": lib_build,
         }
@@ -538,6 +544,9 @@ def main():
             out["normalizer_allreduce_ms_per_step"] = main_res["normalizer_allreduce_ms_per_step"]      # host wall per env step, rank 0 (whole run incl. warm-up)
         if main_res.get("rank_block_seconds_min_max"):
             out["rank_block_seconds_min_max"] = main_res["rank_block_seconds_min_max"]
+        if args.full:
+            out["trajectory_parity"] = trajectory_parity()
+            out["variants"] = variants
         if any(main_res["health"].values()):
             print("bench.py: batch health counters are non-zero: %r" % (main_res["health"],), file=sys.stderr)
         flagged = {k: v["health"] for k, v in (out.get("variants") or {}).items() if isinstance(v, dict) and isinstance(v.get("health"), dict) and any(v["health"].values())}

@@ -1,5 +1,5 @@
 """BASELINE config E (die-reorient, 4096 envs on one MI355X, recurrent LSTM policy): env-steps/s of rollout + PPO update.
-Not the headline bench; `bench.py` records it as `variants.config_E_lstm256`, `tools/bench_reorient.py` prints it.  The env step is
+Not the headline bench; `bench.py --full` records it as `variants.config_E_lstm256`, `tools/bench_reorient.py` prints it.  The env step is
 the step kernel's MYO_TASK_REORIENT task (csrc/myo_task.h); the LSTM policy (/root/reference/src/main_reorient.py:53-71: LSTM-256
 actor + critic -> [256, 256] ReLU, log_std_init -2) rolls out and trains on the HIP-kernel recurrent path."""
 import time

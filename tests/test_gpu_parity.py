@@ -821,6 +821,35 @@ def test_bench_times_exactly_its_steps_and_dumps_the_last_one(hip_lib, tmp_path)
     assert not np.array_equal(a["policy_obs"], a["next_obs"])
 
 
+def test_bench_plain_run_leaves_the_rest_to_full(hip_lib):
+    """A plain `bench.py` run measures the headline alone; `--full` adds the CPU baseline (its all-cores leg on the CPUs the
+    process may run on: two here), the other steppers as `variants` and the trajectory-parity pointer, on the same line."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    two_cpus = sorted(os.sched_getaffinity(0))[:2]
+    recs = {}
+    for form, extra in (("plain", []), ("full", ["--full", "--cpu-seconds", "0.5"])):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--envs", "256"] + extra,
+                           capture_output=True, text=True, timeout=900, preexec_fn=lambda: os.sched_setaffinity(0, two_cpus))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        recs[form] = rec = json.loads(lines[0])
+        assert rec["steps"] == 4 and rec["timed_steps"] == 4 and rec["warmup"] == 1 and rec["dtype"] == "f64"
+        assert abs(rec["value"] - 256 / (rec["ms_per_step"] * 1e-3)) <= 1e-3 * rec["value"]
+    plain, full = recs["plain"], recs["full"]
+    assert not {"variants", "cpu_baseline", "trajectory_parity"} & set(plain)
+    assert plain["roofline"]["flops"]["per_env_step"] > 0          # priced with the committed flop count
+    assert sorted(full["variants"]) == ["mixed", "rk4", "rk4_mixed"]
+    assert all("error" not in v and v["value"] > 0 and v["health"]["protocol_errors"] == 0 for v in full["variants"].values()), full["variants"]
+    cpu = full["cpu_baseline"]
+    assert cpu["value"] > 0 and cpu["flops"]["per_env_step"] > 0 and cpu["all_cores"]["cores"] == len(two_cpus) and cpu["all_cores"]["value"] > 0
+    assert full["trajectory_parity"]["worst_within1e-4_streams"]
+
+
 def test_bench_at_config_d_scale_with_four_ranks(hip_lib):
     """BASELINE config D's node total before the first RCCL run: `bench.py --gpus 4 --envs 8192 --env-name
     CustomMyoBaodingBallsP2` — four ranks x 8192 phase-2 envs = 32768 envs, here sharing this box's one GPU over gloo.  Four ranks,

@@ -1,6 +1,6 @@
 """BASELINE config E (die-reorient, 4096 envs on one MI355X, recurrent LSTM policy): env-steps/s of rollout +
-PPO update.  Not the headline bench (myochallenge_amd/rl/bench_reorient_lstm.py does the work; bench.py records the same
-measurement as `variants.config_E_lstm256`)."""
+PPO update.  Not the headline bench (myochallenge_amd/rl/bench_reorient_lstm.py does the work; `bench.py --full` records
+the same measurement as `variants.config_E_lstm256`)."""
 import argparse
 import json
 import os

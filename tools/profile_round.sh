@@ -10,7 +10,7 @@ export PYTHONPATH=$ROOT
 python3 -c "from myochallenge_amd import native; print(native.load().build_id)" > $OUT/build_id.txt
 cd /tmp && export TMPDIR=/tmp
 # 1. the bench line itself (with the CPU baseline leg)
-python3 $ROOT/bench.py > $OUT/bench_line.json 2> $OUT/bench.err      # includes the f64 / RK4 variants and the CPU leg
+python3 $ROOT/bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err      # --full: includes the f64 / RK4 variants and the CPU leg
 # 2. per-kernel time of the same command (no CPU leg: it is host-only work)
 rm -rf /tmp/prof_stats
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o b -- python3 $ROOT/bench.py --no-cpu-baseline --no-variants > /tmp/stats.log 2>&1
