@@ -244,6 +244,52 @@ int myo_batch_forward_dump(myo_batch* b, const double* ctrl, double* out, void* 
 int myo_batch_dump_size(const myo_batch* b);
 int myo_batch_dump_offset(const myo_batch* b, const char* name);
 
+/* ---- rendering of env states (MuJoCo's mjr_render / mjr_readPixels seam: CustomPenEnv.render -> self.sim.render,
+ * /root/reference/src/main_eval.py:96-97).  Draws what the stepper holds: every geom at the pose of the env's present state
+ * and with the env's own geometry (Baoding P2 ball radius, die size delta), the Baoding target sites where the task puts
+ * them, the die's `target` body at the episode's goal_pos / goal_quat.  No tendons, no model cameras, no lights or shadows.
+ *
+ * Render items: the ngeom geoms, then the nsite sites (spheres of site_size[0]).  Visibility and colour: MuJoCo's rule when
+ * the model carries geom_rgba (groups 0-2, alpha > 0, mat_rgba where matid >= 0); without visual data (the synthetic models)
+ * they are derived — colliding hand geoms one skin colour, free-joint bodies distinct colours, non-colliding geoms of a body
+ * welded to the world translucent, wrap-only geoms hidden.  Sites other than the task's targets are drawn only with
+ * MYO_RENDER_SITES (MuJoCo would draw every site of groups 0-2). */
+typedef struct myo_render_camera {      /* MuJoCo's free camera (mjvCamera, type mjCAMERA_FREE); angles in degrees */
+  double lookat[3];
+  double distance, azimuth, elevation;
+  double fovy;                          /* vertical field of view (mjVisual.global.fovy) */
+} myo_render_camera;
+#define MYO_RENDER_RGB 1
+#define MYO_RENDER_DEPTH 2
+#define MYO_RENDER_SEG 4
+#define MYO_RENDER_SITES 8              /* draw every site, not only the task's targets */
+#define MYO_RENDER_ITEM_N 24            /* doubles per item of myo_batch_geom_poses */
+#define MYO_RENDER_MAX_PIXELS (1 << 24) /* width * height */
+
+/* the model's default free camera: lookat = stat.center, distance = 1.5 stat.extent (without stat in the model: the bounding
+ * sphere of the drawn geoms at qpos0, centre c and radius r, as lookat = c, extent = 2 r); azimuth 90, elevation -45, fovy 45
+ * (MuJoCo 2.1's mjVisual.global defaults) */
+int myo_model_default_camera(const myo_model* m, myo_render_camera* out);
+
+/* Pose pass: for envs env_idx[0 .. k) (dev int32; an index outside [0, N) gets an all-zero row: nothing drawn), one wave per env loads the env's state and runs the
+ * stepper's kinematics; out (dev double[k, ngeom + nsite, MYO_RENDER_ITEM_N]) receives per item: world position [0..3),
+ * world rotation matrix, row-major [3..12), size [12..15), type (mjtGeom; sites: sphere) [15], rgba [16..20) (alpha 0:
+ * never drawn), bounding radius [20], 1 for a site drawn only with MYO_RENDER_SITES [21], 0 [22..24).  Reads the env
+ * records only: no record, draw counter, warm start or health counter changes. */
+int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream);
+
+/* Pinhole ray casting of the items of envs env_idx[0 .. k): one ray through every pixel centre, row 0 at the top (gym's
+ * rgb_array; mjr_readPixels is bottom-up).  cams: HOST array of ncams cameras, ncams = 1 (all envs) or k (one per env).
+ * flags: MYO_RENDER_* ; each requested output is a dev buffer owned by the caller:
+ *   rgb   uint8 [k, height, width, 3]  headlight Lambert shading rgb * (0.3 + 0.7 |n . d|) over a fixed background; a
+ *                                      translucent item (alpha < 1) nearer than the nearest opaque one is blended over it
+ *   depth float [k, height, width]     distance along the camera axis, +inf for the background
+ *   segid int32 [k, height, width]     geom id, ngeom + site id for sites, -1 for the background
+ * Depth and segmentation are those of the nearest drawn surface, translucent ones included.  Invalid arguments return
+ * MYO_E_ARG before any device call. */
+int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
+                     int flags, uint8_t* rgb, float* depth, int32_t* segid, void* stream);
+
 /* average duration (ms) of the step kernel over the launches since the last call, measured
  * with HIP events on the launch stream; resets the accumulator.  Returns <0 if no launch. */
 double myo_batch_kernel_ms(myo_batch* b);

@@ -260,3 +260,47 @@ extern "C" double myo_batch_kernel_ms(myo_batch* b) {
 }
 
 
+
+// rendering: the pose pass env by env, then the ray cast tile by tile with the kernel's three thread phases one after the other
+static void emu_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out) {
+  for (int r = 0; r < k; ++r) {
+    const int e = env_idx[r];
+    double* o = out + (size_t)r * b->nitem * MYO_RENDER_ITEM_N;
+    if (e < 0 || e >= b->n) { memset(o, 0, sizeof(double) * (size_t)b->nitem * MYO_RENDER_ITEM_N); continue; }
+#define ONE_ENV(TT, NCV, MD) { Scratch<TT, NCV>* s = new Scratch<TT, NCV>(); memset(s, 0, sizeof *s); RkScratch<TT>* rk = new RkScratch<TT>(); s->rk = rk; \
+      env_geom_poses<TT>(MD, b->K, b->L, b->rec + (size_t)e * b->L.stride, *s, e, b->vis, o); delete s; delete rk; }
+    if (b->dtype == MYO_F64) { if (b->ncap > MYO_NCON_MAX) ONE_ENV(double, MYO_NCON_BIG, b->Md) else ONE_ENV(double, MYO_NCON_F64, b->Md) }
+    else { if (b->ncap > MYO_NCON_MAX) ONE_ENV(float, MYO_NCON_BIG, b->Mf) else ONE_ENV(float, MYO_NCON_MAX, b->Mf) }
+#undef ONE_ENV
+  }
+}
+extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
+  int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses");
+  if (rc) return rc;
+  if (!out) return fail(MYO_E_ARG, "myo_batch_geom_poses: null output");
+  (void)stream;
+  emu_geom_poses(b, env_idx, k, out);
+  return MYO_OK;
+}
+extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
+                                int flags, uint8_t* rgb, float* depth, int32_t* segid, void* stream) {
+  std::vector<double> cam_tab;
+  int rc = render_check(b, env_idx, k, cams, ncams, width, height, flags, rgb, depth, segid, cam_tab);
+  if (rc) return rc;
+  (void)stream;
+  std::vector<double> items((size_t)k * b->nitem * MYO_RENDER_ITEM_N);
+  emu_geom_poses(b, env_idx, k, items.data());
+  std::vector<RItem> lds((size_t)b->nitem);
+  const int tiles_x = (width + MYO_RTILE - 1) / MYO_RTILE, tiles_y = (height + MYO_RTILE - 1) / MYO_RTILE, nt = MYO_RTILE * MYO_RTILE;
+  for (int e = 0; e < k; ++e) {
+    const double* cam = &cam_tab[(size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N];
+    for (int ty = 0; ty < tiles_y; ++ty)
+      for (int tx = 0; tx < tiles_x; ++tx) {
+        for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), items.data() + (size_t)e * b->nitem * MYO_RENDER_ITEM_N, b->nitem, cam, flags);
+        for (int t = 0; t < nt; ++t) render_cull(t, lds.data(), b->nitem, cam, width, height, tx * MYO_RTILE, ty * MYO_RTILE);
+        for (int t = 0; t < nt; ++t)
+          render_pixel(lds.data(), b->nitem, cam, width, height, tx * MYO_RTILE + t % MYO_RTILE, ty * MYO_RTILE + t / MYO_RTILE, flags, (size_t)e, rgb, depth, segid);
+      }
+  }
+  return MYO_OK;
+}

@@ -23,6 +23,7 @@
 #include "../../include/myo_model_blob.h"
 #include "myo_mjb.h"
 #include "myo_task.h"
+#include "myo_render.h"
 
 
 // ------------------------------------------------------------------------------------------ backend (defined by the including file)
@@ -68,6 +69,11 @@ struct myo_model {
 #define X(n) std::vector<double> n;
   MYO_MODEL_REAL_ARRAYS(X)
 #undef X
+  // rendering (csrc/myo_render.h): per item (ngeom geoms, then nsite sites) rgba[4], site radius, optional, 0, 0 (render_vis_table);
+  // the free camera's default lookat / distance (myo_model_default_camera)
+  std::vector<float> vis;
+  int has_visual;
+  double cam_lookat[3], cam_distance;
 };
 
 static const myo_blob_field* blob_find(const void* blob, const char* name) {
@@ -229,6 +235,113 @@ static void sol_precompute(double* ref2, double* imp5, double timestep, int disa
   } else { K = -tc / (d1 * d1); B = -dr / d1; }
   ref2[0] = K; ref2[1] = B;
   imp5[0] = d0; imp5[1] = d1; imp5[2] = (d0 == d1 || width <= 1e-15) ? 0.0 : 1.0 / width; imp5[3] = mid; imp5[4] = power;
+}
+
+// Visual table of the render items and the default camera (include/myobatch.h, myo_batch_render).  With geom_rgba in the blob (a real
+// .mjb: both model routes carry geom_rgba / geom_group / geom_matid / mat_rgba / site_rgba / site_size / site_group / stat): MuJoCo's rule,
+// groups 0-2 and alpha > 0 are drawn, mat_rgba where matid >= 0.  Without it (the synthetic models) the colours are derived: colliding
+// geoms skin, the geoms of free-joint bodies one palette colour per body, non-colliding geoms of a body welded to the world translucent
+// (the die's target), wrap-only geoms (non-colliding, named by a sphere / cylinder wrap) hidden.  Sites are optional (drawn with
+// MYO_RENDER_SITES) and grey, 5 mm.  Default camera: lookat = stat.center, distance = 1.5 stat.extent; without stat, the bounding
+// sphere (centre c, radius r) of the drawn geoms at qpos0 (the body_pos / body_quat chain) with extent = 2 r.
+static void render_vis_table(myo_model* m, const void* blob, size_t nbytes) {
+  const int ng = m->ngeom, ns = m->nsite;
+  m->vis.assign(8 * (size_t)(ng + ns), 0.f);
+  std::vector<double> grgba, mrgba, srgba, ssize, stat;
+  std::vector<int> ggroup, gmat, sgroup, contype, conaff, weld;
+  m->has_visual = get_d(blob, nbytes, "geom_rgba", grgba) && grgba.size() == 4 * (size_t)ng;
+  const bool ok_i = get_i(blob, nbytes, "geom_contype", contype) && get_i(blob, nbytes, "geom_conaffinity", conaff) &&
+                    get_i(blob, nbytes, "body_weldid", weld) && contype.size() == (size_t)ng && conaff.size() == (size_t)ng &&
+                    weld.size() == (size_t)m->nbody;
+  if (m->has_visual) {
+    get_d(blob, nbytes, "mat_rgba", mrgba);
+    const bool gg = get_i(blob, nbytes, "geom_group", ggroup) && ggroup.size() == (size_t)ng;
+    const bool gm = get_i(blob, nbytes, "geom_matid", gmat) && gmat.size() == (size_t)ng;
+    for (int g = 0; g < ng; ++g) {
+      const double* c = &grgba[4 * (size_t)g];
+      const int mid = gm ? gmat[g] : -1;
+      if (mid >= 0 && 4 * (size_t)mid + 4 <= mrgba.size()) c = &mrgba[4 * (size_t)mid];
+      const int grp = gg ? ggroup[g] : 0;
+      for (int k = 0; k < 4; ++k) m->vis[8 * (size_t)g + k] = (float)c[k];
+      if (grp < 0 || grp > 2) m->vis[8 * (size_t)g + 3] = 0.f;
+    }
+  } else {
+    static const float pal[4][3] = {{0.85f, 0.25f, 0.2f}, {0.2f, 0.45f, 0.85f}, {0.9f, 0.75f, 0.2f}, {0.35f, 0.7f, 0.35f}};
+    std::vector<int> wrap_geom(ng, 0), free_ord(m->nbody, -1);
+    for (int w = 0; w < m->nwrap; ++w)
+      if ((m->wrap_type[w] == MYO_WRAP_SPHERE || m->wrap_type[w] == MYO_WRAP_CYLINDER) && m->wrap_objid[w] >= 0 && m->wrap_objid[w] < ng) wrap_geom[m->wrap_objid[w]] = 1;
+    int nfree = 0;
+    for (int b = 0; b < m->nbody; ++b)
+      if (m->body_jntnum[b] > 0 && m->jnt_type[m->body_jntadr[b]] == MYO_JNT_FREE) free_ord[b] = nfree++;
+    for (int g = 0; g < ng; ++g) {
+      float* v = &m->vis[8 * (size_t)g];
+      const int b = m->geom_bodyid[g];
+      const bool coll = ok_i && (contype[g] != 0 || conaff[g] != 0);
+      int root = b;
+      while (root > 0 && free_ord[root] < 0) root = m->body_parentid[root];
+      float c[4] = {0.8f, 0.62f, 0.52f, 1.f};                                    // skin
+      if (root > 0 && free_ord[root] >= 0) { for (int k = 0; k < 3; ++k) c[k] = pal[free_ord[root] % 4][k]; }
+      else if (!coll && wrap_geom[g]) c[3] = 0.f;                                 // wrap-only
+      else if (!coll && ok_i && weld[b] == 0) { c[0] = 0.3f; c[1] = 0.85f; c[2] = 0.4f; c[3] = 0.35f; }      // translucent marker
+      for (int k = 0; k < 4; ++k) v[k] = c[k];
+    }
+  }
+  {
+    const bool vs = m->has_visual && get_d(blob, nbytes, "site_rgba", srgba) && srgba.size() == 4 * (size_t)ns;
+    const bool vz = get_d(blob, nbytes, "site_size", ssize) && ssize.size() == 3 * (size_t)ns;
+    const bool vg = get_i(blob, nbytes, "site_group", sgroup) && sgroup.size() == (size_t)ns;
+    for (int j = 0; j < ns; ++j) {
+      float* v = &m->vis[8 * (size_t)(ng + j)];
+      for (int k = 0; k < 4; ++k) v[k] = vs ? (float)srgba[4 * (size_t)j + k] : (k == 3 ? 1.f : 0.5f);
+      if (vg && (sgroup[j] < 0 || sgroup[j] > 2)) v[3] = 0.f;
+      v[4] = vz ? (float)ssize[3 * (size_t)j] : 0.005f;
+      v[5] = 1.f;
+    }
+  }
+  if (get_d(blob, nbytes, "stat", stat) && stat.size() == 4 && stat[3] > 0) {
+    for (int k = 0; k < 3; ++k) m->cam_lookat[k] = stat[k];
+    m->cam_distance = 1.5 * stat[3];
+    return;
+  }
+  std::vector<double> xp(3 * (size_t)m->nbody, 0.0), xm(9 * (size_t)m->nbody, 0.0);
+  xm[0] = xm[4] = xm[8] = 1;
+  for (int b = 1; b < m->nbody; ++b) {
+    const int p = m->body_parentid[b];
+    double Rl[9], R[9];
+    quat2mat_h(&m->body_quat[4 * (size_t)b], Rl);
+    for (int i = 0; i < 3; ++i) {
+      double t = 0;
+      for (int k = 0; k < 3; ++k) t += xm[9 * (size_t)p + 3 * i + k] * m->body_pos[3 * (size_t)b + k];
+      xp[3 * (size_t)b + i] = xp[3 * (size_t)p + i] + t;
+      for (int j = 0; j < 3; ++j) { double u = 0; for (int k = 0; k < 3; ++k) u += xm[9 * (size_t)p + 3 * i + k] * Rl[3 * k + j]; R[3 * i + j] = u; }
+    }
+    for (int k = 0; k < 9; ++k) xm[9 * (size_t)b + k] = R[k];
+  }
+  std::vector<double> gp;
+  std::vector<double> gr;
+  for (int g = 0; g < ng; ++g) {
+    if (m->vis[8 * (size_t)g + 3] <= 0.f || m->geom_type[g] == MYO_GEOM_PLANE) continue;
+    const int b = m->geom_bodyid[g];
+    for (int i = 0; i < 3; ++i) {
+      double t = xp[3 * (size_t)b + i];
+      for (int k = 0; k < 3; ++k) t += xm[9 * (size_t)b + 3 * i + k] * m->geom_pos[3 * (size_t)g + k];
+      gp.push_back(t);
+    }
+    gr.push_back(m->geom_rbound[g]);
+  }
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, r = 0;
+  for (size_t i = 0; i < gr.size(); ++i)
+    for (int k = 0; k < 3; ++k) {
+      lo[k] = i ? std::min(lo[k], gp[3 * i + k] - gr[i]) : gp[3 * i + k] - gr[i];
+      hi[k] = i ? std::max(hi[k], gp[3 * i + k] + gr[i]) : gp[3 * i + k] + gr[i];
+    }
+  for (int k = 0; k < 3; ++k) m->cam_lookat[k] = 0.5 * (lo[k] + hi[k]);
+  for (size_t i = 0; i < gr.size(); ++i) {
+    double d2 = 0;
+    for (int k = 0; k < 3; ++k) d2 += (gp[3 * i + k] - m->cam_lookat[k]) * (gp[3 * i + k] - m->cam_lookat[k]);
+    r = std::max(r, sqrt(d2) + gr[i]);
+  }
+  m->cam_distance = 1.5 * 2.0 * (r > 0 ? r : 1.0);
 }
 
 static int model_from_blob_impl(const void* blob, size_t nbytes, myo_model** out);
@@ -772,6 +885,7 @@ static int model_from_blob_impl(const void* blob, size_t nbytes, myo_model** out
   m->any_tendon_passive = 0;
   for (int t = 0; t < m->ntendon; ++t) if (m->tendon_stiffness[t] != 0 || m->tendon_damping[t] != 0) m->any_tendon_passive = 1;
 #undef LIM
+  render_vis_table(m, blob, nbytes);
   *out = m;
   return MYO_OK;
 }
@@ -848,6 +962,12 @@ struct myo_batch {
   int* wrap_cnt = nullptr;     // dev int[ngw]: engagement counts of the wrap census (k_wrap_census / k_wrap_reorder); null = one pass of wraps, nothing to order
   bool has_slot_ws = false;    // K.ctrl_ws is the device's shared wave-slot workspace (slot_workspace_acquire / _release)
   bool has_big_ws = false;     // ... and K.big_ws its block of the 48-slot fp64 scratch's records / wrap results
+  float* vis = nullptr;        // dev [nitem, 8]: the model's visual table with this task's targets drawn (myo_batch_geom_poses)
+  int nitem = 0;               // render items: ngeom + nsite
+  double cam_lookat[3] = {0, 0, 0}, cam_distance = 1;      // the model's default camera (myo_model_default_camera)
+  double* render_ws = nullptr; // dev: item poses and cameras of myo_batch_render, grown on demand (not in allocs)
+  size_t render_ws_bytes = 0;
+  std::vector<double> cam_host;      // the cameras of the last myo_batch_render (source of its asynchronous upload)
   MYO_BACKEND_BATCH_FIELDS     // what the backend keeps per batch (the HIP backend: its timing events)
 };
 
@@ -1121,6 +1241,25 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
     }
     if (pl.nparts >= 2) b->plan = pl;
   }
+  if (!rc) {      // render items: the task's target sites are always drawn (the Baoding targets; the die's target is a body)
+    std::vector<float> vis = m->vis;
+    const int ts[2] = {b->K.target1_sid, b->K.target2_sid};
+    if (b->K.kind == MYO_TASK_BAODING_P1 || b->K.kind == MYO_TASK_BAODING_P2)
+      for (int j : ts)
+        if (j >= 0 && j < m->nsite) {
+          float* v = &vis[8 * (size_t)(m->ngeom + j)];
+          v[5] = 0.f;
+          if (!m->has_visual) { v[0] = 0.2f; v[1] = 0.85f; v[2] = 0.3f; v[3] = 1.f; v[4] = 0.01f; }
+        }
+    void* p = nullptr;
+    rc |= be_malloc(&p, vis.size() * sizeof(float));
+    if (p) b->allocs.push_back(p);
+    if (!rc) rc |= be_h2d(p, vis.data(), vis.size() * sizeof(float));
+    b->vis = (float*)p;
+    b->nitem = m->ngeom + m->nsite;
+    for (int k = 0; k < 3; ++k) b->cam_lookat[k] = m->cam_lookat[k];
+    b->cam_distance = m->cam_distance;
+  }
   rc = be_batch_launch_state(b, m, n_envs, rc);      // (the HIP backend: timing events, launch order, the step plan's state, the wrap census)
   if (rc) {
     int r2 = fail(MYO_E_DEVICE, "device allocation/upload failed: %s", be_errstr(rc));
@@ -1137,7 +1276,66 @@ extern "C" void myo_batch_destroy(myo_batch* b) {
   if (!b) return;
   be_batch_release(b, b->device, 1);
   for (void* q : b->allocs) be_free(q);
+  if (b->render_ws) be_free(b->render_ws);
   delete b;
+}
+// ---- rendering (include/myobatch.h; csrc/myo_render.h): what both backends check before their launches
+extern "C" int myo_model_default_camera(const myo_model* m, myo_render_camera* out) {
+  if (!m || !out) return fail(MYO_E_ARG, "myo_model_default_camera: null argument");
+  for (int k = 0; k < 3; ++k) out->lookat[k] = m->cam_lookat[k];
+  out->distance = m->cam_distance;
+  out->azimuth = 90.0; out->elevation = -45.0; out->fovy = 45.0;      // MuJoCo 2.1's mjVisual.global defaults [3P-RECALL]
+  return MYO_OK;
+}
+static int render_check_items(const myo_batch* b, const int32_t* env_idx, int k, const char* fn) {
+  if (!b) return fail(MYO_E_ARG, "%s: null batch", fn);
+  if (!env_idx || k <= 0) return fail(MYO_E_ARG, "%s: env_idx must list k >= 1 envs", fn);
+  if (b->nitem > MYO_RITEM_MAX) return fail(MYO_E_UNSUPPORTED, "%s: %d geoms + sites, at most %d can be drawn", fn, b->nitem, MYO_RITEM_MAX);
+  return MYO_OK;
+}
+// cameras -> the device table's layout (MYO_RCAM_N doubles: pos, forward, right, up, focal length in pixels), MuJoCo's free camera:
+// forward = (cos el cos az, cos el sin az, sin el), up = (-sin el cos az, -sin el sin az, cos el), pos = lookat - distance forward
+static int render_cameras(const myo_render_camera* cams, int ncams, int height, std::vector<double>& out) {
+  out.assign((size_t)ncams * MYO_RCAM_N, 0.0);
+  for (int c = 0; c < ncams; ++c) {
+    const myo_render_camera& C = cams[c];
+    const double d2r = 3.14159265358979323846 / 180.0;
+    bool finite = std::isfinite(C.distance) && std::isfinite(C.azimuth) && std::isfinite(C.elevation) && std::isfinite(C.fovy);
+    for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(C.lookat[k]);
+    if (!finite || !(C.distance > 0) || !(C.fovy > 0 && C.fovy < 180) || fabs(C.elevation) > 90)
+      return fail(MYO_E_ARG, "myo_batch_render: camera %d: distance must be > 0, fovy in (0, 180), |elevation| <= 90, all finite", c);
+    const double ca = cos(C.azimuth * d2r), sa = sin(C.azimuth * d2r), ce = cos(C.elevation * d2r), se = sin(C.elevation * d2r);
+    const double fw[3] = {ce * ca, ce * sa, se}, up[3] = {-se * ca, -se * sa, ce};
+    const double rt[3] = {fw[1] * up[2] - fw[2] * up[1], fw[2] * up[0] - fw[0] * up[2], fw[0] * up[1] - fw[1] * up[0]};
+    double* o = &out[(size_t)c * MYO_RCAM_N];
+    for (int k = 0; k < 3; ++k) { o[k] = C.lookat[k] - C.distance * fw[k]; o[3 + k] = fw[k]; o[6 + k] = rt[k]; o[9 + k] = up[k]; }
+    o[12] = 0.5 * height / tan(0.5 * C.fovy * d2r);
+  }
+  return MYO_OK;
+}
+static int render_check(const myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
+                        int flags, const uint8_t* rgb, const float* depth, const int32_t* segid, std::vector<double>& cam_tab) {
+  int rc = render_check_items(b, env_idx, k, "myo_batch_render");
+  if (rc) return rc;
+  if (!cams || (ncams != 1 && ncams != k)) return fail(MYO_E_ARG, "myo_batch_render: ncams must be 1 or k (%d), got %d", k, ncams);
+  if (width <= 0 || height <= 0 || (long long)width * height > MYO_RENDER_MAX_PIXELS)
+    return fail(MYO_E_ARG, "myo_batch_render: width and height must be >= 1 with width * height <= %d", MYO_RENDER_MAX_PIXELS);
+  if (flags & ~(MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG | MYO_RENDER_SITES)) return fail(MYO_E_ARG, "myo_batch_render: unknown flag bits 0x%x", flags);
+  if (!(flags & (MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG))) return fail(MYO_E_ARG, "myo_batch_render: no output requested");
+  if (((flags & MYO_RENDER_RGB) && !rgb) || ((flags & MYO_RENDER_DEPTH) && !depth) || ((flags & MYO_RENDER_SEG) && !segid))
+    return fail(MYO_E_ARG, "myo_batch_render: a requested output buffer is NULL");
+  if ((long long)k * width * height > (1ll << 31)) return fail(MYO_E_ARG, "myo_batch_render: k * width * height exceeds 2^31 pixels");
+  return render_cameras(cams, ncams, height, cam_tab);
+}
+// the render workspace: k item tables then the cameras (doubles); grown on demand
+static int render_workspace(myo_batch* b, size_t doubles) {
+  if (b->render_ws_bytes >= doubles * sizeof(double)) return MYO_OK;
+  if (b->render_ws) { be_free(b->render_ws); b->render_ws = nullptr; b->render_ws_bytes = 0; }
+  void* p = nullptr;
+  const int e = be_malloc(&p, doubles * sizeof(double));
+  if (e || !p) return fail(MYO_E_DEVICE, "myo_batch_render: workspace allocation failed: %s", be_errstr(e));
+  b->render_ws = (double*)p; b->render_ws_bytes = doubles * sizeof(double);
+  return MYO_OK;
 }
 extern "C" int myo_batch_num_envs(const myo_batch* b) { return b ? b->n : -1; }
 extern "C" int myo_batch_obs_dim(const myo_batch* b) { return b ? b->nobs : -1; }

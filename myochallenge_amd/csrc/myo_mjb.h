@@ -36,6 +36,7 @@ static const char* const kSizeNames[57] = {
 struct File {
   std::map<std::string, long long> sizes;
   double timestep, impratio, tolerance, gravity[3], o_margin, meaninertia;
+  double stat_extent, stat_center[3];             // mjStatistic (rendering's default camera)
   double wind[3], density, viscosity;
   int integrator, collision, cone, iterations, disableflags, enableflags, solver, noslip_iterations;
   std::map<std::string, std::vector<double>> d;   // f64 arrays (row-major)
@@ -96,6 +97,8 @@ static bool parse(const unsigned char* blob, size_t n, File& f, std::string& err
     err = msg; return false;
   }
   memcpy(&f.meaninertia, blob + base - 56, 8);
+  memcpy(&f.stat_extent, blob + base - 32, 8);
+  memcpy(f.stat_center, blob + base - 24, 24);
   // arrays
   size_t pos = 0;
   const char* p = kLayout;
@@ -120,6 +123,10 @@ static bool parse(const unsigned char* blob, size_t n, File& f, std::string& err
     const unsigned char* src = blob + base + pos;
     if (t == 'd') { std::vector<double>& v = f.d[name]; v.resize((size_t)cnt); if (cnt) memcpy(v.data(), src, (size_t)cnt * 8); }
     else if (t == 'i') { std::vector<int>& v = f.i[name]; v.resize((size_t)cnt); if (cnt) memcpy(v.data(), src, (size_t)cnt * 4); }
+    else if (t == 'f' && (!strcmp(name, "geom_rgba") || !strcmp(name, "site_rgba") || !strcmp(name, "mat_rgba"))) {     // (rendering)
+      std::vector<double>& v = f.d[name]; v.resize((size_t)cnt);
+      for (long long k = 0; k < cnt; ++k) { float x; memcpy(&x, src + 4 * k, 4); v[(size_t)k] = x; }
+    }
     else if (t == 'b') { std::vector<int>& v = f.i[name]; v.resize((size_t)cnt); for (long long k = 0; k < cnt; ++k) v[(size_t)k] = src[k]; }
     pos += (size_t)cnt * isz;      // f32 / char arrays (meshes, textures, names) are skipped: nothing in the stepper reads them
   }
@@ -371,6 +378,12 @@ static bool to_blob(File& f, int integrator, int allow_flags, std::vector<unsign
     fd.push_back({"x_xp_solimp", xsolimp}); fd.push_back({"x_xp_friction", xfric});
   }
   fi.push_back({"opt_int", {integrator >= 0 ? integrator : f.integrator, f.cone, f.iterations, f.disableflags}});
+  {   // visual data (rendering; model.py:compile_model writes the same fields)
+    fi.push_back({"geom_group", I("geom_group")}); fi.push_back({"geom_matid", I("geom_matid")}); fi.push_back({"site_group", I("site_group")});
+    fd.push_back({"geom_rgba", D("geom_rgba")}); fd.push_back({"mat_rgba", D("mat_rgba")}); fd.push_back({"site_rgba", D("site_rgba")});
+    fd.push_back({"site_size", D("site_size")});
+    if (f.stat_extent > 0) fd.push_back({"stat", {f.stat_center[0], f.stat_center[1], f.stat_center[2], f.stat_extent}});
+  }
   fd.push_back({"opt_f64", {f.timestep, f.tolerance, f.impratio, f.gravity[0], f.gravity[1], f.gravity[2], f.o_margin, f.meaninertia}});
   const size_t nf = fi.size() + fd.size();
   size_t head = sizeof(myo_blob_header) + nf * sizeof(myo_blob_field);

@@ -1,0 +1,251 @@
+// myo_render.h — rendering of env states (include/myobatch.h: myo_batch_geom_poses, myo_batch_render).
+//   pose pass  env_geom_poses: one wave per listed env; load_env + the stepper's own kinematics, then one lane per item writes its
+//              world pose, the env's geometry (geom_size0_hp / geom_lpos_hp ...), its type and colour.  Reads the record only.
+//   ray cast   render_*: one workgroup of 256 threads per (env, 16x16 tile); the env's items are staged in LDS in fp32 relative to
+//              the camera, a per-tile cull on each item's bounding sphere marks the items the tile can see (the flag is the same for
+//              every thread of the tile: the loop over items stays uniform), then one thread per pixel intersects its ray with them.
+// The per-thread functions take the thread index, so the emulation build (csrc/emu_host.h) runs the same code thread by thread.
+#pragma once
+
+#define MYO_RTILE 16                 // tile edge (pixels); 256 threads per tile
+#define MYO_RITEM_MAX 512            // items (ngeom + nsite) the LDS table holds
+#define MYO_RCAM_N 16                // doubles per camera of the device camera table: pos[3] fwd[3] right[3] up[3] focal (pixels) pad[3]
+
+// ---------------------------------------------------------------------------------------------------------------- pose pass
+// vis: per item 8 floats (host-built, csrc/myo_host.h render_vis_table): rgba[4], site radius, optional (1: a site drawn only with
+// MYO_RENDER_SITES), 0, 0
+template <typename T, int NC>
+DEV void env_geom_poses(const DevModel<T>& M_in, const TaskDev& K_in, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s_in, int env,
+                        const float* vis, double* out) {
+  MYO_BIND_M(T) MYO_BIND_K MYO_BIND_S(T)
+  WAVE_FN_K
+  load_env(M, K, L, rec, s, env);
+  kinematics(M, s);
+  const int goal_b = (K.kind == MYO_TASK_REORIENT_K && K.target1_sid >= 0) ? M.site_bodyid[K.target1_sid] : -1;
+  const int baoding = (K.kind == 1 || K.kind == 2) && K.target1_sid >= 0 && K.target2_sid >= 0;
+  PHASE {
+    for (int i = lane; i < M.ngeom + M.nsite; i += 64) {
+      double* o = out + (size_t)i * MYO_RENDER_ITEM_N;
+      const int is_site = i >= M.ngeom, id = is_site ? i - M.ngeom : i;
+      const int b = is_site ? M.site_bodyid[id] : M.geom_bodyid[id];
+      HP B[9], xp[3], l[3], p[3], R[9], sz[3];
+      if (b == goal_b) {      // the die's target body: at the episode's goal pose (reorient.py sets body_pos / body_quat of `target`)
+        const HP* q = s.goal_quat;
+        const HP n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        const HP qn[4] = {q[0] / n, q[1] / n, q[2] / n, q[3] / n};
+        quat2mat(B, qn);
+        for (int k = 0; k < 3; ++k) xp[k] = s.goal_pos[k];
+      } else {
+        quat2mat(B, S_XQUAT(s) + 4 * b);
+        for (int k = 0; k < 3; ++k) xp[k] = S_XPOS(s)[3 * b + k];
+      }
+      const float* v = vis + 8 * (size_t)i;
+      int type;
+      if (is_site) {
+        for (int k = 0; k < 3; ++k) l[k] = M.h_site_pos[3 * id + k];
+        if (baoding && id == K.target1_sid) { l[0] = s.target_xy[0]; l[1] = s.target_xy[1]; }      // (as baoding_obs_reward places them)
+        if (baoding && id == K.target2_sid) { l[0] = s.target_xy[2]; l[1] = s.target_xy[3]; }
+        for (int k = 0; k < 9; ++k) R[k] = B[k];
+        sz[0] = sz[1] = sz[2] = (HP)v[4];
+        type = MYO_GEOM_SPHERE;
+      } else {
+        geom_lpos_hp(M, K, s, id, l);
+        mulmat3(R, B, M.h_geom_mat + 9 * id);
+        sz[0] = geom_size0_hp(M, K, s, id); sz[1] = geom_size1_hp(M, K, s, id); sz[2] = geom_size2_hp(M, K, s, id);
+        type = M.geom_type[id];
+      }
+      mulmatvec3(p, B, l);
+      for (int k = 0; k < 3; ++k) o[k] = p[k] + xp[k];
+      for (int k = 0; k < 9; ++k) o[3 + k] = R[k];
+      for (int k = 0; k < 3; ++k) o[12 + k] = sz[k];
+      o[15] = type;
+      for (int k = 0; k < 4; ++k) o[16 + k] = v[k];
+      HP rb;
+      switch (type) {
+        case MYO_GEOM_SPHERE: rb = sz[0]; break;
+        case MYO_GEOM_CAPSULE: rb = sz[0] + sz[1]; break;
+        case MYO_GEOM_CYLINDER: rb = sqrt(sz[0] * sz[0] + sz[1] * sz[1]); break;
+        case MYO_GEOM_ELLIPSOID: rb = sz[0] > sz[1] ? (sz[0] > sz[2] ? sz[0] : sz[2]) : (sz[1] > sz[2] ? sz[1] : sz[2]); break;
+        case MYO_GEOM_BOX: rb = sqrt(sz[0] * sz[0] + sz[1] * sz[1] + sz[2] * sz[2]); break;
+        case MYO_GEOM_PLANE: rb = (sz[0] > 0 && sz[1] > 0) ? sqrt(sz[0] * sz[0] + sz[1] * sz[1]) : (HP)-1; break;     // -1: unbounded
+        default: rb = 0;
+      }
+      o[20] = rb; o[21] = v[5]; o[22] = 0; o[23] = 0;
+    }
+  }
+  SYNC();
+  ws_release(K, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- ray cast
+struct RItem {      // one item in LDS: fp32, relative to the camera position
+  float c[3], R[9], sz[3], rgba[4], rb;
+  int type, draw;    // draw: drawn in this tile (cull result)
+};
+
+// stage items i = tid, tid + 256, ... of one env (pose pass output `it`) relative to the camera
+DEV void render_stage(int tid, RItem* lds, const double* it, int nitem, const double* cam, int flags) {
+  for (int i = tid; i < nitem; i += MYO_RTILE * MYO_RTILE) {
+    const double* o = it + (size_t)i * MYO_RENDER_ITEM_N;
+    RItem& r = lds[i];
+    for (int k = 0; k < 3; ++k) r.c[k] = (float)(o[k] - cam[k]);
+    for (int k = 0; k < 9; ++k) r.R[k] = (float)o[3 + k];
+    for (int k = 0; k < 3; ++k) r.sz[k] = (float)o[12 + k];
+    for (int k = 0; k < 4; ++k) r.rgba[k] = (float)o[16 + k];
+    r.rb = (float)o[20];
+    r.type = (int)o[15];
+    r.draw = r.rgba[3] > 0.f && (o[21] == 0.0 || (flags & MYO_RENDER_SITES));
+  }
+}
+
+// per-tile cull: the item's bounding sphere against the tile's four side planes through the camera and the camera plane
+DEV void render_cull(int tid, RItem* lds, int nitem, const double* cam, int W, int H, int tx0, int ty0) {
+  const float f = (float)cam[12];
+  const float fw[3] = {(float)cam[3], (float)cam[4], (float)cam[5]}, rt[3] = {(float)cam[6], (float)cam[7], (float)cam[8]},
+              up[3] = {(float)cam[9], (float)cam[10], (float)cam[11]};
+  const float xa = ((float)tx0 - 0.5f * (float)W) / f, xb = ((float)(tx0 + MYO_RTILE) - 0.5f * (float)W) / f;
+  const float yb = (0.5f * (float)H - (float)(ty0 + MYO_RTILE)) / f, ya = (0.5f * (float)H - (float)ty0) / f;
+  for (int i = tid; i < nitem; i += MYO_RTILE * MYO_RTILE) {
+    RItem& r = lds[i];
+    if (!r.draw || r.rb < 0.f) continue;     // hidden, or an unbounded plane (always tested)
+    const float cz = r.c[0] * fw[0] + r.c[1] * fw[1] + r.c[2] * fw[2], cx = r.c[0] * rt[0] + r.c[1] * rt[1] + r.c[2] * rt[2],
+                cy = r.c[0] * up[0] + r.c[1] * up[1] + r.c[2] * up[2];
+    const float rb = r.rb * 1.0001f + 1e-6f;       // (margin for the fp32 rounding of the tests below)
+    const bool in = cz > -rb && (cx - xa * cz) >= -rb * sqrtf(1.f + xa * xa) && (xb * cz - cx) >= -rb * sqrtf(1.f + xb * xb) &&
+                    (cy - yb * cz) >= -rb * sqrtf(1.f + yb * yb) && (ya * cz - cy) >= -rb * sqrtf(1.f + ya * ya);
+    r.draw = in ? 1 : 0;
+  }
+}
+
+// smallest t > 0 where the ray o + t d meets |x|^2 = r2 in the first `dim` coordinates (a sphere, dim 3; an infinite cylinder, dim 2);
+// INF if none.  Solved about the point of the ray closest to the centre, which keeps fp32's cancellation of |o|^2 - r^2 out of it.
+DEV float rsolve(const float* o, const float* d, int dim, float r2) {
+  float a = 0.f, b = 0.f;
+  for (int k = 0; k < dim; ++k) { a += d[k] * d[k]; b += o[k] * d[k]; }
+  if (a <= 0.f) return INFINITY;
+  const float tc = -b / a;
+  float c = -r2;
+  for (int k = 0; k < dim; ++k) { const float p = o[k] + tc * d[k]; c += p * p; }
+  if (c > 0.f) return INFINITY;
+  const float w = sqrtf(-c / a), t0 = tc - w, t1 = tc + w;
+  return t0 > 0.f ? t0 : (t1 > 0.f ? t1 : INFINITY);
+}
+
+// intersection of the ray o + t d (item-local frame) with the item; returns t (INF: miss) and the local normal
+DEV float render_hit(int type, const float* sz, const float* o, const float* d, float* n) {
+  float t = INFINITY;
+  n[0] = 0.f; n[1] = 0.f; n[2] = 1.f;
+  switch (type) {
+    case MYO_GEOM_SPHERE: {
+      t = rsolve(o, d, 3, sz[0] * sz[0]);
+      for (int k = 0; k < 3; ++k) n[k] = o[k] + t * d[k];
+      break;
+    }
+    case MYO_GEOM_ELLIPSOID: {
+      const float os[3] = {o[0] / sz[0], o[1] / sz[1], o[2] / sz[2]}, ds[3] = {d[0] / sz[0], d[1] / sz[1], d[2] / sz[2]};
+      t = rsolve(os, ds, 3, 1.f);
+      for (int k = 0; k < 3; ++k) n[k] = (o[k] + t * d[k]) / (sz[k] * sz[k]);
+      break;
+    }
+    case MYO_GEOM_CAPSULE:
+    case MYO_GEOM_CYLINDER: {
+      const float r = sz[0], h = sz[1];
+      const float tc = rsolve(o, d, 2, r * r);
+      if (tc < INFINITY && fabsf(o[2] + tc * d[2]) <= h) { t = tc; n[0] = o[0] + tc * d[0]; n[1] = o[1] + tc * d[1]; n[2] = 0.f; }
+      for (int e = -1; e <= 1; e += 2) {
+        const float zc = (float)e * h;
+        if (type == MYO_GEOM_CAPSULE) {      // the two end spheres
+          const float oz = o[2] - zc, oc[3] = {o[0], o[1], oz};
+          const float ts = rsolve(oc, d, 3, r * r);
+          if (ts < t) { t = ts; n[0] = o[0] + ts * d[0]; n[1] = o[1] + ts * d[1]; n[2] = oz + ts * d[2]; }
+        } else if (d[2] != 0.f) {            // the two caps
+          const float tp = (zc - o[2]) / d[2];
+          const float x = o[0] + tp * d[0], y = o[1] + tp * d[1];
+          if (tp > 0.f && tp < t && x * x + y * y <= r * r) { t = tp; n[0] = 0.f; n[1] = 0.f; n[2] = (float)e; }
+        }
+      }
+      break;
+    }
+    case MYO_GEOM_BOX: {
+      float tn = -INFINITY, tf = INFINITY;
+      int ax = 0;
+      float sg = 1.f;
+      for (int k = 0; k < 3; ++k) {
+        if (d[k] == 0.f) {
+          if (fabsf(o[k]) > sz[k]) return INFINITY;
+          continue;
+        }
+        const float ta = (-sz[k] - o[k]) / d[k], tb = (sz[k] - o[k]) / d[k];
+        const float lo = fminf(ta, tb), hi = fmaxf(ta, tb);
+        if (lo > tn) { tn = lo; ax = k; sg = d[k] > 0.f ? -1.f : 1.f; }
+        tf = fminf(tf, hi);
+      }
+      if (tn > tf || tf <= 0.f) return INFINITY;
+      t = tn > 0.f ? tn : tf;
+      n[0] = ax == 0 ? sg : 0.f; n[1] = ax == 1 ? sg : 0.f; n[2] = ax == 2 ? sg : 0.f;
+      break;
+    }
+    case MYO_GEOM_PLANE: {
+      if (d[2] == 0.f) return INFINITY;
+      const float tp = -o[2] / d[2];
+      const float x = o[0] + tp * d[0], y = o[1] + tp * d[1];
+      if (tp > 0.f && (sz[0] <= 0.f || sz[1] <= 0.f || (fabsf(x) <= sz[0] && fabsf(y) <= sz[1]))) t = tp;
+      break;
+    }
+    default: break;
+  }
+  return t;
+}
+
+#define MYO_RBG_R 0.12f      // background colour
+#define MYO_RBG_G 0.14f
+#define MYO_RBG_B 0.18f
+
+DEV float render_shade(const RItem& r, const float* nl, const float* d, float* rgb) {
+  float n[3];
+  for (int k = 0; k < 3; ++k) n[k] = r.R[3 * k] * nl[0] + r.R[3 * k + 1] * nl[1] + r.R[3 * k + 2] * nl[2];      // world = R nl
+  const float nn = sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]), dd = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  const float cs = nn > 0.f ? fabsf(n[0] * d[0] + n[1] * d[1] + n[2] * d[2]) / (nn * dd) : 1.f;
+  const float lam = 0.3f + 0.7f * fminf(cs, 1.f);
+  for (int k = 0; k < 3; ++k) rgb[k] = r.rgba[k] * lam;
+  return r.rgba[3];
+}
+
+// one pixel (row py from the top, column px) of env row `e` of the output
+DEV void render_pixel(const RItem* lds, int nitem, const double* cam, int W, int H, int px, int py, int flags, size_t e,
+                      unsigned char* rgb, float* depth, int* seg) {
+  if (px >= W || py >= H) return;
+  const float f = (float)cam[12];
+  const float tx = ((float)px + 0.5f - 0.5f * (float)W) / f, ty = (0.5f * (float)H - ((float)py + 0.5f)) / f;
+  float d[3];
+  for (int k = 0; k < 3; ++k) d[k] = (float)cam[3 + k] + tx * (float)cam[6 + k] + ty * (float)cam[9 + k];     // forward component 1: t = depth
+  float to = INFINITY, tt = INFINITY, no[3] = {0.f, 0.f, 1.f}, nt[3] = {0.f, 0.f, 1.f};
+  int io = -1, it = -1;
+  for (int i = 0; i < nitem; ++i) {
+    const RItem& r = lds[i];
+    if (!r.draw) continue;
+    float ol[3], dl[3], nl[3];
+    for (int k = 0; k < 3; ++k) {       // local = R^T (x - c)
+      ol[k] = -(r.R[k] * r.c[0] + r.R[3 + k] * r.c[1] + r.R[6 + k] * r.c[2]);
+      dl[k] = r.R[k] * d[0] + r.R[3 + k] * d[1] + r.R[6 + k] * d[2];
+    }
+    const float t = render_hit(r.type, r.sz, ol, dl, nl);
+    if (r.rgba[3] >= 1.f) {
+      if (t < to) { to = t; io = i; no[0] = nl[0]; no[1] = nl[1]; no[2] = nl[2]; }
+    } else if (t < tt) { tt = t; it = i; nt[0] = nl[0]; nt[1] = nl[1]; nt[2] = nl[2]; }
+  }
+  const size_t pix = (e * (size_t)H + (size_t)py) * (size_t)W + (size_t)px;
+  const bool front_t = it >= 0 && tt < to;
+  if (flags & MYO_RENDER_RGB) {
+    float c[3] = {MYO_RBG_R, MYO_RBG_G, MYO_RBG_B};
+    if (io >= 0) render_shade(lds[io], no, d, c);
+    if (front_t) {
+      float ct[3];
+      const float a = render_shade(lds[it], nt, d, ct);
+      for (int k = 0; k < 3; ++k) c[k] = a * ct[k] + (1.f - a) * c[k];
+    }
+    for (int k = 0; k < 3; ++k) rgb[3 * pix + k] = (unsigned char)fminf(255.f, fmaxf(0.f, floorf(c[k] * 255.f + 0.5f)));
+  }
+  if (flags & MYO_RENDER_DEPTH) depth[pix] = front_t ? tt : to;
+  if (flags & MYO_RENDER_SEG) seg[pix] = front_t ? it : io;
+}

@@ -343,6 +343,36 @@ __global__ void __launch_bounds__(64, 2) k_wrap_census(EnvRecordLayout L, double
   const int env = blockIdx.x;
   env_wrap_census<T>(M, K, L, rec + (size_t)env * L.stride, s, env, cnt);
 }
+// render pose pass (csrc/myo_render.h): row r of `out` = env env_idx[r]'s items; a listed index outside [0, n_envs) gets an all-zero
+// row (nothing drawn)
+template <typename T, bool RK, int NC>
+__global__ void __launch_bounds__(64, 2) k_geom_poses(EnvRecordLayout L, double* rec, const int* __restrict__ env_idx, int n_envs,
+                                                   const float* vis, int nitem, double* out) {
+  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
+  s.rk = rk_storage<T, RK, NC>();
+  const DevModel<T>& M = myo_cmodel<T>();
+  const TaskDev& K = c_task;
+  const int env = env_idx[blockIdx.x];
+  double* o = out + (size_t)blockIdx.x * nitem * MYO_RENDER_ITEM_N;
+  if (env < 0 || env >= n_envs) {
+    for (int i = threadIdx.x; i < nitem * MYO_RENDER_ITEM_N; i += 64) o[i] = 0.0;
+    return;
+  }
+  env_geom_poses<T>(M, K, L, rec + (size_t)env * L.stride, s, env, vis, o);
+}
+// render ray cast: workgroup (tile, env row) of 256 threads, one pixel each; the item table in dynamic LDS
+__global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render(const double* __restrict__ items, int nitem, const double* __restrict__ cams,
+                                                                  int ncams, int W, int H, int flags, unsigned char* rgb, float* depth, int* seg) {
+  RItem* lds = reinterpret_cast<RItem*>(myo_lds);
+  const int tid = threadIdx.x, tiles_x = (W + MYO_RTILE - 1) / MYO_RTILE, e = blockIdx.y;
+  const int tx0 = (int)(blockIdx.x % tiles_x) * MYO_RTILE, ty0 = (int)(blockIdx.x / tiles_x) * MYO_RTILE;
+  const double* cam = cams + (size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N;
+  render_stage(tid, lds, items + (size_t)e * nitem * MYO_RENDER_ITEM_N, nitem, cam, flags);
+  __syncthreads();
+  render_cull(tid, lds, nitem, cam, W, H, tx0, ty0);
+  __syncthreads();
+  render_pixel(lds, nitem, cam, W, H, tx0 + tid % MYO_RTILE, ty0 + tid / MYO_RTILE, flags, (size_t)e, rgb, depth, seg);
+}
 // ... and the order that follows from the census: positions sorted by count, most engaged first (ties keep their order), written back
 // into the batch's own tables — gw_elem[k] = path element of position k, wr_i[8 w + 6] = position of element w — and the counts
 // cleared.  One wave; ngw <= 128 (two positions per lane).  Each wrap's arithmetic is its own: the order changes no result bit.
@@ -753,6 +783,42 @@ extern "C" int myo_batch_forward_dump(myo_batch* b, const double* ctrl, double* 
   LAUNCH_RK(b, (void)RKV;
     if (b->dtype == MYO_F64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dump<double, false, MYO_NC_D(NCV)>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, b->D, out);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dump<float, false, NCV>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, b->D, out))
+  LAUNCH_CHECK(b)
+  return MYO_OK;
+}
+
+static void geom_poses_launch(myo_batch* b, const int32_t* env_idx, int k, double* out, hipStream_t st) {
+  LAUNCH_RK(b,
+    if (b->dtype == MYO_F64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_geom_poses<double, RKV, MYO_NC_D(NCV)>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->vis, b->nitem, out);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_geom_poses<float, RKV, NCV>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->vis, b->nitem, out))
+}
+extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
+  int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses");
+  if (rc) return rc;
+  if (!out) return fail(MYO_E_ARG, "myo_batch_geom_poses: null output");
+  hipStream_t st = (hipStream_t)stream;
+  BIND_OR_RETURN(b, st)
+  geom_poses_launch(b, env_idx, k, out, st);
+  LAUNCH_CHECK(b)
+  return MYO_OK;
+}
+extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
+                                int flags, uint8_t* rgb, float* depth, int32_t* segid, void* stream) {
+  std::vector<double> cam_tab;
+  int rc = render_check(b, env_idx, k, cams, ncams, width, height, flags, rgb, depth, segid, cam_tab);
+  if (rc) return rc;
+  if (k > 65535) return fail(MYO_E_ARG, "myo_batch_render: at most 65535 envs per call");
+  hipStream_t st = (hipStream_t)stream;
+  BIND_OR_RETURN(b, st)
+  const size_t item_n = (size_t)k * b->nitem * MYO_RENDER_ITEM_N;
+  if ((rc = render_workspace(b, item_n + cam_tab.size()))) return rc;
+  b->cam_host.swap(cam_tab);      // (kept until the next call: the asynchronous copy reads it)
+  hipError_t e = hipMemcpyAsync(b->render_ws + item_n, b->cam_host.data(), b->cam_host.size() * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return fail(MYO_E_DEVICE, "myo_batch_render: camera upload failed: %s", hipGetErrorString(e));
+  geom_poses_launch(b, env_idx, k, b->render_ws, st);
+  const unsigned tiles = (unsigned)(((width + MYO_RTILE - 1) / MYO_RTILE) * ((height + MYO_RTILE - 1) / MYO_RTILE));
+  hipLaunchKernelGGL(k_render, dim3(tiles, (unsigned)k), dim3(MYO_RTILE * MYO_RTILE), (unsigned)(b->nitem * sizeof(RItem)), st,
+                     b->render_ws, b->nitem, b->render_ws + item_n, ncams, width, height, flags, rgb, depth, segid);
   LAUNCH_CHECK(b)
   return MYO_OK;
 }

@@ -44,7 +44,7 @@ class Box:
 class BaodingVecEnv:
     """``num_envs`` Baoding environments on one GPU (``device`` index)."""
 
-    metadata = {"render.modes": []}
+    metadata = {"render.modes": ["rgb_array"]}
 
     def __init__(self, env_name: str, num_envs: int, config: Optional[dict] = None, *, device: int = 0,
                  seed: int = 0, dtype: str = "mixed", model=None, integrator: Optional[str] = None,
@@ -201,6 +201,61 @@ class BaodingVecEnv:
 
     def env_is_wrapped(self, wrapper_class, indices=None):
         return [False] * self.num_envs
+
+    # ---------------------------------------------------------------- rendering (include/myobatch.h myo_batch_render)
+    def default_camera(self) -> dict:
+        """MuJoCo's free camera defaults for this model: lookat = stat.center, distance = 1.5 stat.extent (a model without stat, such as
+        the synthetic hands: the bounding sphere of the drawn geoms at qpos0), azimuth 90, elevation -45, fovy 45 [3P-RECALL]."""
+        return self._model.default_camera()
+
+    def render_tensor(self, indices=None, width: int = 480, height: int = 480, camera=None, rgb: bool = True, depth: bool = False,
+                      segmentation: bool = False, show_sites: bool = False):
+        """Draw the present state of envs ``indices`` (default: all) on the GPU; device tensors, no host copy.
+
+        camera: None (the default camera), a dict of MuJoCo free-camera keys (lookat, distance, azimuth, elevation, fovy; missing
+        keys take the defaults) for every env, or a list of such dicts, one per env.  Returns a dict with the requested outputs:
+        ``rgb`` uint8 [k, H, W, 3] (row 0 at the top), ``depth`` float32 [k, H, W] (along the camera axis, inf for the background),
+        ``segmentation`` int32 [k, H, W] (geom id, ngeom + site id, -1 for the background).
+
+        Differences from MuJoCo's renderer: primitives ray-cast under a headlight (no model lights, shadows, textures or tendons);
+        model cameras are not available; sites other than the task's targets are drawn only with ``show_sites`` (the synthetic hand
+        has 215 tendon path sites).  Models without visual data (the synthetic ones) get derived colours (include/myobatch.h)."""
+        t = self.torch
+        idx = list(range(self.num_envs)) if indices is None else [int(i) for i in indices]
+        if not idx or min(idx) < 0 or max(idx) >= self.num_envs:
+            raise ValueError(f"render indices must be in [0, {self.num_envs})")
+        base = self.default_camera()
+        cams = camera if isinstance(camera, (list, tuple)) else [camera]
+        cams = [dict(base, **(c or {})) for c in cams]
+        if len(cams) not in (1, len(idx)):
+            raise ValueError("camera: one dict for all envs or one per env")
+        k = len(idx)
+        flags = (native.RENDER_RGB if rgb else 0) | (native.RENDER_DEPTH if depth else 0) | (native.RENDER_SEG if segmentation else 0)
+        flags |= native.RENDER_SITES if show_sites else 0
+        out = {}
+        if rgb:
+            out["rgb"] = t.empty((k, height, width, 3), dtype=t.uint8, device=self.device)
+        if depth:
+            out["depth"] = t.empty((k, height, width), dtype=t.float32, device=self.device)
+        if segmentation:
+            out["segmentation"] = t.empty((k, height, width), dtype=t.int32, device=self.device)
+        env_idx = t.tensor(idx, dtype=t.int32, device=self.device)
+        self.batch.render(env_idx, cams, width, height, flags, out.get("rgb"), out.get("depth"), out.get("segmentation"), self._stream())
+        return out
+
+    def get_images(self, width: int = 480, height: int = 480, camera=None) -> List[np.ndarray]:
+        """SB3 VecEnv.get_images: one [H, W, 3] uint8 array per env."""
+        rgb = self.render_tensor(None, width, height, camera)["rgb"].cpu().numpy()
+        return [rgb[i] for i in range(self.num_envs)]
+
+    def render(self, mode: str = "rgb_array", **kwargs):
+        """SB3 VecEnv.render: "rgb_array" returns the envs' images tiled into one grid (stable_baselines3 tile_images)."""
+        if mode in ("human", "window"):
+            raise NotImplementedError(f"render mode {mode!r} needs a display; this GPU library renders offscreen only: use 'rgb_array'")
+        if mode != "rgb_array":
+            raise ValueError(f"unknown render mode {mode!r}; supported: {self.metadata['render.modes']}")
+        from ..render_io import tile_images
+        return tile_images(self.get_images(**kwargs))
 
     # ---------------------------------------------------------------- state access (parity tests)
     def get_state(self):

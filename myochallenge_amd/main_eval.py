@@ -27,7 +27,10 @@ DEFAULT_CONFIG = {
 
 
 def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBallsP2", config: dict = None,
-             num_episodes: int = 100, num_envs: int = 256, seed: int = 0, deterministic: bool = True, verbose: bool = True):
+             num_episodes: int = 100, num_envs: int = 256, seed: int = 0, deterministic: bool = True, verbose: bool = True,
+             render_dir: str = None, render_envs: int = 1, render_size=(480, 480)):
+    """render_dir: write a PNG of each of the first ``render_envs`` envs after every step (``env{i}_step{t}.png``; the reference
+    script's ``render`` switch, src/main_eval.py:96-97, shows the frames in a window instead)."""
     from .envs.environment_factory import EnvironmentFactory
     from .metrics.evaluation import evaluate_policy, summarize
     from .rl.sb3_zip import load_policy
@@ -41,7 +44,18 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
     venv.norm_reward = False
     policy, _ = load_policy(model_path)
     policy.to(env.device)
-    res = evaluate_policy(policy, env, venv, n_eval_episodes=num_episodes, deterministic=deterministic)
+    on_step = None
+    if render_dir:
+        import os
+        from .render_io import write_png
+        os.makedirs(render_dir, exist_ok=True)
+        k = max(1, min(int(render_envs), env.num_envs))
+
+        def on_step(t):
+            rgb = env.render_tensor(list(range(k)), int(render_size[0]), int(render_size[1]))["rgb"].cpu().numpy()
+            for i in range(k):
+                write_png(os.path.join(render_dir, f"env{i}_step{t:05d}.png"), rgb[i])
+    res = evaluate_policy(policy, env, venv, n_eval_episodes=num_episodes, deterministic=deterministic, on_step=on_step)
     out = summarize(res)
     if verbose:
         print(f"Average len: {out['mean_len']:.2f} +/- {out['len_err']:.2f}")
@@ -60,9 +74,13 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--config", default=None, help="JSON file with the env kwargs (default: the reference script's config)")
     ap.add_argument("--out", default=None, help="write per-episode returns / lengths to this .npz")
+    ap.add_argument("--render-dir", default=None, help="write PNG frames of the first --render-envs envs after every step here")
+    ap.add_argument("--render-envs", type=int, default=1)
+    ap.add_argument("--render-size", type=int, nargs=2, default=(480, 480), metavar=("W", "H"))
     a = ap.parse_args(argv)
     cfg = json.load(open(a.config)) if a.config else None
-    res, _ = evaluate(a.model, a.env_path, a.env_name, cfg, a.num_episodes, a.num_envs, a.seed)
+    res, _ = evaluate(a.model, a.env_path, a.env_name, cfg, a.num_episodes, a.num_envs, a.seed,
+                      render_dir=a.render_dir, render_envs=a.render_envs, render_size=a.render_size)
     if a.out:
         np.savez(a.out, **res)
 

@@ -21,10 +21,11 @@ from .. import native
 
 @torch.no_grad()
 def evaluate_policy(policy, env, normalizer=None, n_eval_episodes: int = 100, deterministic: bool = True,
-                    max_steps: Optional[int] = None) -> Dict[str, np.ndarray]:
+                    max_steps: Optional[int] = None, on_step=None) -> Dict[str, np.ndarray]:
     """Play ``n_eval_episodes`` episodes of ``policy`` on the batched ``env`` (a ``BaodingVecEnv``; NOT a
     VecNormalize wrapper — pass the wrapper, or anything with ``normalize_obs``, as ``normalizer``).
 
+    ``on_step(t)``, if given, is called after env step t (main_eval --render-dir draws the envs there).
     Returns ``{"returns", "lengths", "solved_frac", "truncated"}`` (one entry per episode)."""
     N = env.num_envs
     dev = env.device
@@ -40,9 +41,11 @@ def evaluate_policy(policy, env, normalizer=None, n_eval_episodes: int = 100, de
     j_solved = native.RWD_KEYS.index("solved")
     rets, lens, solved, truncs = [], [], [], []
     horizon = max_steps if max_steps is not None else int(quota.max()) * (getattr(env, "max_episode_steps", 200) + 1) + 1
-    for _ in range(horizon):
+    for t_step in range(horizon):
         actions, _, _, state = policy.act(norm(obs), state, starts, deterministic=deterministic)
         obs, rew, done, trunc, term, comps, ep = env.step_tensor(torch.clamp(actions, -1.0, 1.0))
+        if on_step is not None:
+            on_step(t_step)
         solved_sum += comps[:, j_solved]
         dn = done.bool()
         if bool(dn.any()):

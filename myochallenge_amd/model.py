@@ -352,6 +352,15 @@ def compile_model(m: MjbModel, *, integrator: int | None = None, unsupported_con
     f["x_xp_margin"], f["x_xp_gap"] = xf("pair_margin", 1), xf("pair_gap", 1)
     f["x_xp_solref"], f["x_xp_solimp"] = xf("pair_solref", 2), xf("pair_solimp", 5)
     f["x_xp_friction"] = (np.asarray(m.arrays["pair_friction"], np.float64).reshape(-1, 5)[:npair_x][:, [0, 2, 3]].reshape(-1) if npair_x else np.zeros(0))
+    # visual data (rendering: csrc/myo_host.h render_vis_table), where the model source has it (a real .mjb; the synthetic models have none)
+    if "geom_rgba" in m.arrays:
+        for name in ("geom_group", "geom_matid", "site_group"):
+            f[name] = np.ascontiguousarray(m.arrays[name]).astype(np.int32).reshape(-1)
+        for name in ("geom_rgba", "mat_rgba", "site_rgba", "site_size"):
+            f[name] = np.ascontiguousarray(m.arrays[name]).astype(np.float64).reshape(-1)
+        st = m.stat or {}
+        if float(st.get("extent", 0.0)) > 0:
+            f["stat"] = np.array([*st["center"], st["extent"]], np.float64)
     o = m.opt
     f["opt_int"] = np.array([integrator if integrator is not None else o["integrator"],
                              o["cone"], o["iterations"], o["disableflags"]], np.int32)

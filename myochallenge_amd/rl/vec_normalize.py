@@ -231,6 +231,16 @@ class VecNormalize:
             infos.append(info)
         return nobs.cpu().numpy(), nrew.cpu().numpy(), done_h, infos
 
+    # rendering: forwarded to the wrapped env (SB3 VecEnvWrapper does the same)
+    def render(self, mode: str = "rgb_array", **kwargs):
+        return self.venv.render(mode, **kwargs)
+
+    def get_images(self, *args, **kwargs):
+        return self.venv.get_images(*args, **kwargs)
+
+    def render_tensor(self, *args, **kwargs):
+        return self.venv.render_tensor(*args, **kwargs)
+
     def close(self):
         if self.venv is not None:
             self.venv.close()
