@@ -3400,7 +3400,14 @@ DEV void newton_solve(const DevModel<T>& M_in, Scratch<T, NC>& s_in) {
     )
     PROF(s, 9)
 #ifndef MYO_EMU
-    if (M.arrow_nf > 0) {
+#ifdef MYO_CHOL_NO_MFMA
+    constexpr bool arrow_one_leaf = false;
+#else
+    constexpr bool arrow_one_leaf = sizeof(T) == 8;     // the 16 x 16 factor runs on the matrix cores: one leaf, L in registers
+#endif
+    if (arrow_one_leaf && M.arrow_nf > 0) {
+      arrow_factor_solve<T, NC>(LOFF(s, s.search));    // (PROF 26 / 27 inside)
+    } else if (M.arrow_nf > 0) {
       arrow_eliminate_blocks<T, NC>(LOFF(s, s.search));
       PROF(s, 26)
       chol_factor_solve_reg<T, MYO_ARROW_S, NC>(LOFF(s, s.Mv), MYO_ARROW_S);
