@@ -247,7 +247,9 @@ int myo_batch_dump_offset(const myo_batch* b, const char* name);
 /* ---- rendering of env states (MuJoCo's mjr_render / mjr_readPixels seam: CustomPenEnv.render -> self.sim.render,
  * /root/reference/src/main_eval.py:96-97).  Draws what the stepper holds: every geom at the pose of the env's present state
  * and with the env's own geometry (Baoding P2 ball radius, die size delta), the Baoding target sites where the task puts
- * them, the die's `target` body at the episode's goal_pos / goal_quat.  No tendons, no model cameras, no lights or shadows.
+ * them, the die's `target` body at the episode's goal_pos / goal_quat, and — with MYO_RENDER_TENDONS — the spatial tendons
+ * as capsules along their paths, coloured by muscle activation (myo_batch_tendon_paths).  Wrap arcs are drawn as chords.
+ * No model cameras, no lights or shadows.
  *
  * Render items: the ngeom geoms, then the nsite sites (spheres of site_size[0]).  Visibility and colour: MuJoCo's rule when
  * the model carries geom_rgba (groups 0-2, alpha > 0, mat_rgba where matid >= 0); without visual data (the synthetic models)
@@ -263,7 +265,8 @@ typedef struct myo_render_camera {      /* MuJoCo's free camera (mjvCamera, type
 #define MYO_RENDER_DEPTH 2
 #define MYO_RENDER_SEG 4
 #define MYO_RENDER_SITES 8              /* draw every site, not only the task's targets */
-#define MYO_RENDER_ITEM_N 24            /* doubles per item of myo_batch_geom_poses */
+#define MYO_RENDER_TENDONS 16           /* draw the tendon items of myo_batch_tendon_paths after the geoms and sites */
+#define MYO_RENDER_ITEM_N 24            /* doubles per item of myo_batch_geom_poses / myo_batch_tendon_paths */
 #define MYO_RENDER_MAX_PIXELS (1 << 24) /* width * height */
 
 /* the model's default free camera: lookat = stat.center, distance = 1.5 stat.extent (without stat in the model: the bounding
@@ -278,13 +281,36 @@ int myo_model_default_camera(const myo_model* m, myo_render_camera* out);
  * records only: no record, draw counter, warm start or health counter changes. */
 int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream);
 
+/* Tendon path pass: for envs env_idx[0 .. k) (dev int32; an index outside [0, N) gets an all-zero row), one wave per env loads
+ * the env's state, runs the stepper's kinematics and the stepper's own wrap solver, and writes every straight piece of every
+ * spatial tendon as one item of the pose pass's format into out (dev double[k, ntendon_item, MYO_RENDER_ITEM_N];
+ * ntendon_item = myo_model_size(m, "ntendon_item"), a model constant: 1 slot per site -> site path element, 3 per element
+ * around a sphere / cylinder wrap — an upper bound over all wrap states; unused slots are all-zero rows, alpha 0 = never drawn).
+ * Pieces: site -> site; around an active wrap site -> tangent point, the chord between the two tangent points, tangent point ->
+ * site; site -> site when the wrap is inactive.  A pulley ends a branch: no piece crosses it.  Per item: position [0..3) = the
+ * piece's midpoint, rotation [3..12) with its z axis (third column) along the piece, size [12..15) = radius, half length, 0,
+ * type [15] = capsule, rgba [16..20), bounding radius [20] = radius + half length, 0 [21], tendon id + 1 [22], and [23] the
+ * piece's contribution to the tendon's length in metres: its length (a chord: the arc length of the wrap it stands for), divided by
+ * the divisor of the last pulley before it — the sum of [23] over a tendon's items is ten_length.
+ * Radius and base colour: tendon_width and tendon_rgba (mat_rgba where tendon_matid >= 0; groups 0-2 and alpha > 0 are drawn)
+ * where the model carries visual data; without it (the synthetic models) radius 0.002 m and rgba (0.30, 0.35, 0.75, 1).
+ * Colour rule — this library's own, NOT MuJoCo's (whose tendon colouring is not reproduced or claimed here): a tendon that is the
+ * transmission target of a muscle actuator (the first such actuator) has rgb = (1 - a) base + a active, with a that actuator's
+ * activation clamped to [0, 1] and active = (1.00, 0.90, 0.10); alpha and every other tendon keep the base colour.
+ * Reads the env records only: no record, draw counter, warm start, workspace ownership flag or health counter changes.  A null
+ * output or k < 0 returns MYO_E_ARG before any device call. */
+int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream);
+
 /* Pinhole ray casting of the items of envs env_idx[0 .. k): one ray through every pixel centre, row 0 at the top (gym's
  * rgb_array; mjr_readPixels is bottom-up).  cams: HOST array of ncams cameras, ncams = 1 (all envs) or k (one per env).
  * flags: MYO_RENDER_* ; each requested output is a dev buffer owned by the caller:
  *   rgb   uint8 [k, height, width, 3]  headlight Lambert shading rgb * (0.3 + 0.7 |n . d|) over a fixed background; a
  *                                      translucent item (alpha < 1) nearer than the nearest opaque one is blended over it
  *   depth float [k, height, width]     distance along the camera axis, +inf for the background
- *   segid int32 [k, height, width]     geom id, ngeom + site id for sites, -1 for the background
+ *   segid int32 [k, height, width]     geom id, ngeom + site id for sites, ngeom + nsite + tendon id for tendons, -1 for the background
+ * With MYO_RENDER_TENDONS the tendon items are drawn after the geoms and sites under the same shading, translucency, depth and
+ * tile-culling rules (a second pass of the tile over the same pixels; a model with more than 512 tendon items is refused with
+ * MYO_E_ARG, never truncated).  Without the flag nothing about the call changes.
  * Depth and segmentation are those of the nearest drawn surface, translucent ones included.  Invalid arguments return
  * MYO_E_ARG before any device call. */
 int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,

@@ -282,6 +282,26 @@ extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k,
   emu_geom_poses(b, env_idx, k, out);
   return MYO_OK;
 }
+static void emu_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out) {
+  for (int r = 0; r < k; ++r) {
+    const int e = env_idx[r];
+    double* o = out + (size_t)r * b->ntitem * MYO_RENDER_ITEM_N;
+    if (e < 0 || e >= b->n) { memset(o, 0, sizeof(double) * (size_t)b->ntitem * MYO_RENDER_ITEM_N); continue; }
+#define ONE_ENV(TT, NCV, MD) { Scratch<TT, NCV>* s = new Scratch<TT, NCV>(); memset(s, 0, sizeof *s); RkScratch<TT>* rk = new RkScratch<TT>(); s->rk = rk; \
+      env_tendon_paths<TT>(MD, b->K, b->L, b->rec + (size_t)e * b->L.stride, *s, e, b->tvis, b->titem_adr, o); delete s; delete rk; }
+    if (b->dtype == MYO_F64) { if (b->ncap > MYO_NCON_MAX) ONE_ENV(double, MYO_NCON_BIG, b->Md) else ONE_ENV(double, MYO_NCON_F64, b->Md) }
+    else { if (b->ncap > MYO_NCON_MAX) ONE_ENV(float, MYO_NCON_BIG, b->Mf) else ONE_ENV(float, MYO_NCON_MAX, b->Mf) }
+#undef ONE_ENV
+  }
+}
+extern "C" int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
+  int empty = 0;
+  int rc = tendon_paths_check(b, env_idx, k, out, &empty);
+  if (rc || empty) return rc;
+  (void)stream;
+  emu_tendon_paths(b, env_idx, k, out);
+  return MYO_OK;
+}
 extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
                                 int flags, uint8_t* rgb, float* depth, int32_t* segid, void* stream) {
   std::vector<double> cam_tab;
@@ -290,7 +310,12 @@ extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, con
   (void)stream;
   std::vector<double> items((size_t)k * b->nitem * MYO_RENDER_ITEM_N);
   emu_geom_poses(b, env_idx, k, items.data());
-  std::vector<RItem> lds((size_t)b->nitem);
+  const bool tendons = (flags & MYO_RENDER_TENDONS) && b->ntitem > 0;
+  std::vector<double> titems(tendons ? (size_t)k * b->ntitem * MYO_RENDER_ITEM_N : 0);
+  if (tendons) emu_tendon_paths(b, env_idx, k, titems.data());
+  std::vector<RItem> lds((size_t)(tendons && b->ntitem > b->nitem ? b->ntitem : b->nitem));
+  std::vector<RHit> hits(MYO_RTILE * MYO_RTILE);
+  std::vector<float> dirs(3 * MYO_RTILE * MYO_RTILE);
   const int tiles_x = (width + MYO_RTILE - 1) / MYO_RTILE, tiles_y = (height + MYO_RTILE - 1) / MYO_RTILE, nt = MYO_RTILE * MYO_RTILE;
   for (int e = 0; e < k; ++e) {
     const double* cam = &cam_tab[(size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N];
@@ -298,8 +323,26 @@ extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, con
       for (int tx = 0; tx < tiles_x; ++tx) {
         for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), items.data() + (size_t)e * b->nitem * MYO_RENDER_ITEM_N, b->nitem, cam, flags);
         for (int t = 0; t < nt; ++t) render_cull(t, lds.data(), b->nitem, cam, width, height, tx * MYO_RTILE, ty * MYO_RTILE);
-        for (int t = 0; t < nt; ++t)
-          render_pixel(lds.data(), b->nitem, cam, width, height, tx * MYO_RTILE + t % MYO_RTILE, ty * MYO_RTILE + t / MYO_RTILE, flags, (size_t)e, rgb, depth, segid);
+        if (!tendons) {
+          for (int t = 0; t < nt; ++t)
+            render_pixel(lds.data(), b->nitem, cam, width, height, tx * MYO_RTILE + t % MYO_RTILE, ty * MYO_RTILE + t / MYO_RTILE, flags, (size_t)e, rgb, depth, segid);
+          continue;
+        }
+        // MYO_RENDER_TENDONS (k_render_tendons): trace the geoms' table, restage the tendon items over it, trace them into the same hits
+        const double* it = items.data() + (size_t)e * b->nitem * MYO_RENDER_ITEM_N;
+        const double* tn = titems.data() + (size_t)e * b->ntitem * MYO_RENDER_ITEM_N;
+        auto PX = [&](int t) { return tx * MYO_RTILE + t % MYO_RTILE; };
+        auto PY = [&](int t) { return ty * MYO_RTILE + t / MYO_RTILE; };
+        for (int t = 0; t < nt; ++t) {
+          render_ray(cam, width, height, PX(t), PY(t), &dirs[3 * t], hits[t]);
+          if (PX(t) < width && PY(t) < height) render_trace(lds.data(), b->nitem, 0, &dirs[3 * t], hits[t]);
+        }
+        for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), tn, b->ntitem, cam, flags);
+        for (int t = 0; t < nt; ++t) render_cull(t, lds.data(), b->ntitem, cam, width, height, tx * MYO_RTILE, ty * MYO_RTILE);
+        for (int t = 0; t < nt; ++t) {
+          if (PX(t) < width && PY(t) < height) render_trace(lds.data(), b->ntitem, b->nitem, &dirs[3 * t], hits[t]);
+          render_pixel_finish(it, b->nitem, tn, cam, width, height, PX(t), PY(t), flags, (size_t)e, hits[t], &dirs[3 * t], rgb, depth, segid);
+        }
       }
   }
   return MYO_OK;

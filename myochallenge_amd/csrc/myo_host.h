@@ -73,6 +73,11 @@ struct myo_model {
   // the free camera's default lookat / distance (myo_model_default_camera)
   std::vector<float> vis;
   int has_visual;
+  // tendon items (myo_batch_tendon_paths; render_tendon_table): per tendon base rgba[4], radius, colouring activation (-1), 0, 0; per path
+  // element its first item slot; the item slots per env (1 per site -> site element, 3 per element around a wrap geom)
+  std::vector<float> tvis;
+  std::vector<int> titem_adr;
+  int ntendon_item;
   double cam_lookat[3], cam_distance;
 };
 
@@ -244,6 +249,48 @@ static void sol_precompute(double* ref2, double* imp5, double timestep, int disa
 // (the die's target), wrap-only geoms (non-colliding, named by a sphere / cylinder wrap) hidden.  Sites are optional (drawn with
 // MYO_RENDER_SITES) and grey, 5 mm.  Default camera: lookat = stat.center, distance = 1.5 stat.extent; without stat, the bounding
 // sphere (centre c, radius r) of the drawn geoms at qpos0 (the body_pos / body_quat chain) with extent = 2 r.
+// Visual table of the tendon items (include/myobatch.h, myo_batch_tendon_paths).  With visual data in the blob: radius tendon_width,
+// colour tendon_rgba (mat_rgba where tendon_matid >= 0), groups 0-2 and alpha > 0 drawn.  Without it: MYO_RTEN_RADIUS and MYO_RTEN_BASE_*.
+// A tendon that is the transmission target of a muscle actuator (dyntype muscle, with an activation state; the first such actuator) is
+// coloured by that activation.  Called after render_vis_table (has_visual).
+#define MYO_RTEN_RADIUS 0.002f
+#define MYO_RTEN_BASE_R 0.30f
+#define MYO_RTEN_BASE_G 0.35f
+#define MYO_RTEN_BASE_B 0.75f
+// (the stepper's capacity — path elements that fit the length staging, wrap geoms of the big workspace — keeps every model that loads
+// within the renderer's second LDS pass; render_check still refuses, never truncates)
+static_assert((MYO_H_SIZE - MYO_NB_MAX * 10) * sizeof(float) / sizeof(double) + 2 * MYO_BIGWS_GW <= MYO_RTEN_MAX, "tendon items of a loadable model fit MYO_RTEN_MAX");
+static void render_tendon_table(myo_model* m, const void* blob, size_t nbytes, const std::vector<int>& trntype) {
+  const int nt = m->ntendon;
+  m->tvis.assign(8 * (size_t)(nt > 0 ? nt : 1), 0.f);
+  std::vector<double> trgba, twidth, mrgba;
+  std::vector<int> tgroup, tmat;
+  const bool vt = m->has_visual && get_d(blob, nbytes, "tendon_rgba", trgba) && trgba.size() == 4 * (size_t)nt &&
+                  get_d(blob, nbytes, "tendon_width", twidth) && twidth.size() == (size_t)nt;
+  if (vt) get_d(blob, nbytes, "mat_rgba", mrgba);
+  const bool tg = vt && get_i(blob, nbytes, "tendon_group", tgroup) && tgroup.size() == (size_t)nt;
+  const bool tm = vt && get_i(blob, nbytes, "tendon_matid", tmat) && tmat.size() == (size_t)nt;
+  for (int t = 0; t < nt; ++t) {
+    float* v = &m->tvis[8 * (size_t)t];
+    if (vt) {
+      const double* c = &trgba[4 * (size_t)t];
+      const int mid = tm ? tmat[t] : -1;
+      if (mid >= 0 && 4 * (size_t)mid + 4 <= mrgba.size()) c = &mrgba[4 * (size_t)mid];
+      for (int k = 0; k < 4; ++k) v[k] = (float)c[k];
+      if (tg && (tgroup[t] < 0 || tgroup[t] > 2)) v[3] = 0.f;
+      v[4] = (float)twidth[t];
+    } else { v[0] = MYO_RTEN_BASE_R; v[1] = MYO_RTEN_BASE_G; v[2] = MYO_RTEN_BASE_B; v[3] = 1.f; v[4] = MYO_RTEN_RADIUS; }
+    v[5] = -1.f;
+  }
+  for (int i = m->nu - 1; i >= 0; --i) {      // (descending: the first muscle of a tendon wins)
+    const int ia = i - (m->nu - m->na), t = m->actuator_tendon[i];
+    if (ia >= 0 && m->actuator_dyntype[i] == 3 && (size_t)i < trntype.size() && trntype[i] == MYO_TRN_TENDON && t >= 0 && t < nt) m->tvis[8 * (size_t)t + 5] = (float)ia;
+  }
+  m->titem_adr.assign(m->nte > 0 ? m->nte : 1, 0);
+  int n = 0;
+  for (int e = 0; e < m->nte; ++e) { m->titem_adr[e] = n; n += m->te_i[4 * (size_t)e + 2] >= 0 ? 3 : 1; }
+  m->ntendon_item = n;
+}
 static void render_vis_table(myo_model* m, const void* blob, size_t nbytes) {
   const int ng = m->ngeom, ns = m->nsite;
   m->vis.assign(8 * (size_t)(ng + ns), 0.f);
@@ -886,6 +933,7 @@ static int model_from_blob_impl(const void* blob, size_t nbytes, myo_model** out
   for (int t = 0; t < m->ntendon; ++t) if (m->tendon_stiffness[t] != 0 || m->tendon_damping[t] != 0) m->any_tendon_passive = 1;
 #undef LIM
   render_vis_table(m, blob, nbytes);
+  render_tendon_table(m, blob, nbytes, trntype);
   *out = m;
   return MYO_OK;
 }
@@ -921,7 +969,7 @@ extern "C" void myo_model_destroy(myo_model* m) { delete m; }
 extern "C" int myo_model_size(const myo_model* m, const char* n) {
   if (!m || !n) return -1;
 #define S(x) if (!strcmp(n, #x)) return m->x;
-  S(nq) S(nv) S(nu) S(na) S(nbody) S(njnt) S(ngeom) S(nsite) S(ntendon) S(nwrap) S(npair) S(nM) S(integrator) S(nlead) S(arrow_nf) S(ld_nfq) S(ld_nsq)
+  S(nq) S(nv) S(nu) S(na) S(nbody) S(njnt) S(ngeom) S(nsite) S(ntendon) S(nwrap) S(npair) S(nM) S(integrator) S(nlead) S(arrow_nf) S(ld_nfq) S(ld_nsq) S(ntendon_item)
 #undef S
   return -1;
 }
@@ -964,6 +1012,9 @@ struct myo_batch {
   bool has_big_ws = false;     // ... and K.big_ws its block of the 48-slot fp64 scratch's records / wrap results
   float* vis = nullptr;        // dev [nitem, 8]: the model's visual table with this task's targets drawn (myo_batch_geom_poses)
   int nitem = 0;               // render items: ngeom + nsite
+  float* tvis = nullptr;       // dev [ntendon, 8] and dev int[nte]: the model's tendon tables (myo_batch_tendon_paths)
+  int* titem_adr = nullptr;
+  int ntitem = 0;              // tendon item slots per env
   double cam_lookat[3] = {0, 0, 0}, cam_distance = 1;      // the model's default camera (myo_model_default_camera)
   double* render_ws = nullptr; // dev: item poses and cameras of myo_batch_render, grown on demand (not in allocs)
   size_t render_ws_bytes = 0;
@@ -1257,6 +1308,14 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
     if (!rc) rc |= be_h2d(p, vis.data(), vis.size() * sizeof(float));
     b->vis = (float*)p;
     b->nitem = m->ngeom + m->nsite;
+    void *pt = nullptr, *pa = nullptr;
+    rc |= be_malloc(&pt, m->tvis.size() * sizeof(float));
+    if (pt) b->allocs.push_back(pt);
+    rc |= be_malloc(&pa, m->titem_adr.size() * sizeof(int));
+    if (pa) b->allocs.push_back(pa);
+    if (!rc) rc |= be_h2d(pt, m->tvis.data(), m->tvis.size() * sizeof(float));
+    if (!rc) rc |= be_h2d(pa, m->titem_adr.data(), m->titem_adr.size() * sizeof(int));
+    b->tvis = (float*)pt; b->titem_adr = (int*)pa; b->ntitem = m->ntendon_item;
     for (int k = 0; k < 3; ++k) b->cam_lookat[k] = m->cam_lookat[k];
     b->cam_distance = m->cam_distance;
   }
@@ -1285,6 +1344,16 @@ extern "C" int myo_model_default_camera(const myo_model* m, myo_render_camera* o
   for (int k = 0; k < 3; ++k) out->lookat[k] = m->cam_lookat[k];
   out->distance = m->cam_distance;
   out->azimuth = 90.0; out->elevation = -45.0; out->fovy = 45.0;      // MuJoCo 2.1's mjVisual.global defaults [3P-RECALL]
+  return MYO_OK;
+}
+// myo_batch_tendon_paths: null output / k < 0 / null list are refused before any device call; k = 0 or a model without tendon items
+// is an empty result (*empty)
+static int tendon_paths_check(const myo_batch* b, const int32_t* env_idx, int k, const double* out, int* empty) {
+  if (!b) return fail(MYO_E_ARG, "myo_batch_tendon_paths: null batch");
+  if (k < 0) return fail(MYO_E_ARG, "myo_batch_tendon_paths: k must be >= 0, got %d", k);
+  if (!out) return fail(MYO_E_ARG, "myo_batch_tendon_paths: null output");
+  if (k > 0 && !env_idx) return fail(MYO_E_ARG, "myo_batch_tendon_paths: null env_idx");
+  *empty = (k == 0 || b->ntitem == 0);
   return MYO_OK;
 }
 static int render_check_items(const myo_batch* b, const int32_t* env_idx, int k, const char* fn) {
@@ -1320,8 +1389,10 @@ static int render_check(const myo_batch* b, const int32_t* env_idx, int k, const
   if (!cams || (ncams != 1 && ncams != k)) return fail(MYO_E_ARG, "myo_batch_render: ncams must be 1 or k (%d), got %d", k, ncams);
   if (width <= 0 || height <= 0 || (long long)width * height > MYO_RENDER_MAX_PIXELS)
     return fail(MYO_E_ARG, "myo_batch_render: width and height must be >= 1 with width * height <= %d", MYO_RENDER_MAX_PIXELS);
-  if (flags & ~(MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG | MYO_RENDER_SITES)) return fail(MYO_E_ARG, "myo_batch_render: unknown flag bits 0x%x", flags);
+  if (flags & ~(MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG | MYO_RENDER_SITES | MYO_RENDER_TENDONS)) return fail(MYO_E_ARG, "myo_batch_render: unknown flag bits 0x%x", flags);
   if (!(flags & (MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG))) return fail(MYO_E_ARG, "myo_batch_render: no output requested");
+  if ((flags & MYO_RENDER_TENDONS) && b->ntitem > MYO_RTEN_MAX)
+    return fail(MYO_E_ARG, "myo_batch_render: MYO_RENDER_TENDONS: %d tendon items, at most %d can be drawn", b->ntitem, MYO_RTEN_MAX);
   if (((flags & MYO_RENDER_RGB) && !rgb) || ((flags & MYO_RENDER_DEPTH) && !depth) || ((flags & MYO_RENDER_SEG) && !segid))
     return fail(MYO_E_ARG, "myo_batch_render: a requested output buffer is NULL");
   if ((long long)k * width * height > (1ll << 31)) return fail(MYO_E_ARG, "myo_batch_render: k * width * height exceeds 2^31 pixels");

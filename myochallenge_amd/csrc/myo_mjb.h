@@ -123,7 +123,7 @@ static bool parse(const unsigned char* blob, size_t n, File& f, std::string& err
     const unsigned char* src = blob + base + pos;
     if (t == 'd') { std::vector<double>& v = f.d[name]; v.resize((size_t)cnt); if (cnt) memcpy(v.data(), src, (size_t)cnt * 8); }
     else if (t == 'i') { std::vector<int>& v = f.i[name]; v.resize((size_t)cnt); if (cnt) memcpy(v.data(), src, (size_t)cnt * 4); }
-    else if (t == 'f' && (!strcmp(name, "geom_rgba") || !strcmp(name, "site_rgba") || !strcmp(name, "mat_rgba"))) {     // (rendering)
+    else if (t == 'f' && (!strcmp(name, "geom_rgba") || !strcmp(name, "site_rgba") || !strcmp(name, "mat_rgba") || !strcmp(name, "tendon_rgba"))) {     // (rendering)
       std::vector<double>& v = f.d[name]; v.resize((size_t)cnt);
       for (long long k = 0; k < cnt; ++k) { float x; memcpy(&x, src + 4 * k, 4); v[(size_t)k] = x; }
     }
@@ -382,6 +382,8 @@ static bool to_blob(File& f, int integrator, int allow_flags, std::vector<unsign
     fi.push_back({"geom_group", I("geom_group")}); fi.push_back({"geom_matid", I("geom_matid")}); fi.push_back({"site_group", I("site_group")});
     fd.push_back({"geom_rgba", D("geom_rgba")}); fd.push_back({"mat_rgba", D("mat_rgba")}); fd.push_back({"site_rgba", D("site_rgba")});
     fd.push_back({"site_size", D("site_size")});
+    fi.push_back({"tendon_group", I("tendon_group")}); fi.push_back({"tendon_matid", I("tendon_matid")});
+    fd.push_back({"tendon_rgba", D("tendon_rgba")}); fd.push_back({"tendon_width", D("tendon_width")});
     if (f.stat_extent > 0) fd.push_back({"stat", {f.stat_center[0], f.stat_center[1], f.stat_center[2], f.stat_extent}});
   }
   fd.push_back({"opt_f64", {f.timestep, f.tolerance, f.impratio, f.gravity[0], f.gravity[1], f.gravity[2], f.o_margin, f.meaninertia}});

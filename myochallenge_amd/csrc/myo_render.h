@@ -4,11 +4,17 @@
 //   ray cast   render_*: one workgroup of 256 threads per (env, 16x16 tile); the env's items are staged in LDS in fp32 relative to
 //              the camera, a per-tile cull on each item's bounding sphere marks the items the tile can see (the flag is the same for
 //              every thread of the tile: the loop over items stays uniform), then one thread per pixel intersects its ray with them.
+//   path pass  env_tendon_paths: one wave per listed env; load_env + kinematics, then one lane per tendon path element (the host-resolved
+//              te_i walk) runs the stepper's wrap_geom and writes the element's straight pieces as capsule items (include/myobatch.h).
+//   tendons    MYO_RENDER_TENDONS (k_render_tendons): the same tile runs a SECOND LDS pass over the same pixels — the geoms' table is
+//              traced, then the tendon items are staged over it, culled and traced into the same per-pixel hit; the hit items are shaded
+//              from their global rows.  The LDS allocation is max(items, tendon items) * sizeof(RItem), not their sum.
 // The per-thread functions take the thread index, so the emulation build (csrc/emu_host.h) runs the same code thread by thread.
 #pragma once
 
 #define MYO_RTILE 16                 // tile edge (pixels); 256 threads per tile
 #define MYO_RITEM_MAX 512            // items (ngeom + nsite) the LDS table holds
+#define MYO_RTEN_MAX MYO_RITEM_MAX    // tendon items the second LDS pass holds
 #define MYO_RCAM_N 16                // doubles per camera of the device camera table: pos[3] fwd[3] right[3] up[3] focal (pixels) pad[3]
 
 // ---------------------------------------------------------------------------------------------------------------- pose pass
@@ -77,6 +83,88 @@ DEV void env_geom_poses(const DevModel<T>& M_in, const TaskDev& K_in, const EnvR
   ws_release(K, s);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- path pass
+#define MYO_RTEN_ACT_R 1.00      // the "active" colour a muscle's tendon is blended toward by its activation (include/myobatch.h)
+#define MYO_RTEN_ACT_G 0.90
+#define MYO_RTEN_ACT_B 0.10
+// one straight piece a -> b as a capsule item: midpoint, z axis along the piece, size [radius, half length, 0]; [22] = tendon + 1,
+// [23] = the piece's contribution to the tendon's length
+DEV void tendon_item(double* o, const HP* a, const HP* b, HP radius, const HP* rgba, int t, HP contrib) {
+  HP z[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+  const HP n = sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);
+  if (n > 0) { z[0] /= n; z[1] /= n; z[2] /= n; } else { z[0] = 0; z[1] = 0; z[2] = 1; }
+  // x: the coordinate axis z is least aligned with, made orthogonal to z; y = z x x
+  const HP az[3] = {fabs(z[0]), fabs(z[1]), fabs(z[2])};
+  const int im = az[0] <= az[1] ? (az[0] <= az[2] ? 0 : 2) : (az[1] <= az[2] ? 1 : 2);
+  const HP ax[3] = {im == 0 ? (HP)1 : (HP)0, im == 1 ? (HP)1 : (HP)0, im == 2 ? (HP)1 : (HP)0};
+  HP x[3], y[3];
+  cross3(x, ax, z);
+  normalize3(x);
+  cross3(y, z, x);
+  for (int k = 0; k < 3; ++k) {
+    o[k] = (HP)0.5 * (a[k] + b[k]);
+    o[3 + 3 * k] = x[k]; o[4 + 3 * k] = y[k]; o[5 + 3 * k] = z[k];
+  }
+  o[12] = radius; o[13] = (HP)0.5 * n; o[14] = 0;
+  o[15] = MYO_GEOM_CAPSULE;
+  for (int k = 0; k < 4; ++k) o[16 + k] = rgba[k];
+  o[20] = radius + (HP)0.5 * n; o[21] = 0; o[22] = t + 1; o[23] = contrib;
+}
+// tvis: per tendon 8 floats (host-built, csrc/myo_host.h render_tendon_table): base rgba[4], radius, index of the activation that
+// colours it (-1: none), 0, 0.  tadr[e]: first item slot of path element e (1 slot for site -> site, 3 around a wrap geom).
+template <typename T, int NC>
+DEV void env_tendon_paths(const DevModel<T>& M_in, const TaskDev& K_in, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s_in, int env,
+                          const float* tvis, const int* tadr, double* out) {
+  MYO_BIND_M(T) MYO_BIND_K MYO_BIND_S(T)
+  WAVE_FN_K
+  load_env(M, K, L, rec, s, env);
+  kinematics(M, s);
+  PHASE {
+    for (int e = lane; e < M.nte; e += 64) {
+      const int i0 = M.te_i[4 * e], iend = M.te_i[4 * e + 1], ig = M.te_i[4 * e + 2], t = M.te_i[4 * e + 3];
+      const HP div = (HP)M.te_div[e];
+      double* o = out + (size_t)tadr[e] * MYO_RENDER_ITEM_N;
+      const float* v = tvis + 8 * (size_t)t;
+      HP rgba[4] = {(HP)v[0], (HP)v[1], (HP)v[2], (HP)v[3]};
+      const int ia = (int)v[5];
+      if (ia >= 0 && ia < M.na) {      // rgb = (1 - a) base + a active, a = the muscle's activation clamped to [0, 1]
+        HP a = S_ACT(M, s)[ia];
+        a = a < 0 ? (HP)0 : (a > 1 ? (HP)1 : a);
+        const HP act[3] = {(HP)MYO_RTEN_ACT_R, (HP)MYO_RTEN_ACT_G, (HP)MYO_RTEN_ACT_B};
+        for (int k = 0; k < 3; ++k) rgba[k] = ((HP)1 - a) * rgba[k] + a * act[k];
+      }
+      const HP radius = (HP)v[4];
+      HP q0[3], q1[3];
+      body_point_hp(s, M.wr_i[8 * i0 + 1], M.h_wr_p + 4 * i0, q0);
+      body_point_hp(s, M.wr_i[8 * iend + 1], M.h_wr_p + 4 * iend, q1);
+      HP wlen = -1, pts[6] = {0, 0, 0, 0, 0, 0};
+      if (ig >= 0) {       // the stepper's wrap solver on the same operands as its tendon_wrap_pass (absolute positions here)
+        const int body = M.wr_i[8 * ig + 1], side_body = M.wr_i[8 * ig + 3];
+        HP gmat[9], bm[9], side[3] = {0, 0, 0}, gp[3];
+        quat2mat(bm, S_XQUAT(s) + 4 * body);
+        mulmat3(gmat, bm, M.h_wr_m + 12 * ig);
+        if (side_body >= 0) body_point_hp(s, side_body, M.h_wr_m + 12 * ig + 9, side);
+        body_point_hp(s, body, M.h_wr_p + 4 * ig, gp);
+        wlen = wrap_geom(pts, q0, q1, gp, gmat, geom_size0_hp(M, K, s, M.wr_i[8 * ig + 2]), M.wr_i[8 * ig], side, side_body >= 0);
+      }
+      if (wlen >= 0) {
+        HP d0[3], d1[3];
+        for (int k = 0; k < 3; ++k) { d0[k] = pts[k] - q0[k]; d1[k] = q1[k] - pts[3 + k]; }
+        tendon_item(o, q0, pts, radius, rgba, t, norm3(d0) / div);
+        tendon_item(o + MYO_RENDER_ITEM_N, pts, pts + 3, radius, rgba, t, wlen / div);       // the chord stands for the arc
+        tendon_item(o + 2 * MYO_RENDER_ITEM_N, pts + 3, q1, radius, rgba, t, norm3(d1) / div);
+      } else {
+        HP d0[3];
+        for (int k = 0; k < 3; ++k) d0[k] = q1[k] - q0[k];
+        tendon_item(o, q0, q1, radius, rgba, t, norm3(d0) / div);
+        if (ig >= 0) for (int k = 0; k < 2 * MYO_RENDER_ITEM_N; ++k) o[MYO_RENDER_ITEM_N + k] = 0;      // the wrap's two unused slots
+      }
+    }
+  }
+  SYNC();
+  ws_release(K, s);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- ray cast
 struct RItem {      // one item in LDS: fp32, relative to the camera position
   float c[3], R[9], sz[3], rgba[4], rb;
@@ -84,18 +172,17 @@ struct RItem {      // one item in LDS: fp32, relative to the camera position
 };
 
 // stage items i = tid, tid + 256, ... of one env (pose pass output `it`) relative to the camera
+DEV void render_load(RItem& r, const double* o, const double* cam, int flags) {
+  for (int k = 0; k < 3; ++k) r.c[k] = (float)(o[k] - cam[k]);
+  for (int k = 0; k < 9; ++k) r.R[k] = (float)o[3 + k];
+  for (int k = 0; k < 3; ++k) r.sz[k] = (float)o[12 + k];
+  for (int k = 0; k < 4; ++k) r.rgba[k] = (float)o[16 + k];
+  r.rb = (float)o[20];
+  r.type = (int)o[15];
+  r.draw = r.rgba[3] > 0.f && (o[21] == 0.0 || (flags & MYO_RENDER_SITES));
+}
 DEV void render_stage(int tid, RItem* lds, const double* it, int nitem, const double* cam, int flags) {
-  for (int i = tid; i < nitem; i += MYO_RTILE * MYO_RTILE) {
-    const double* o = it + (size_t)i * MYO_RENDER_ITEM_N;
-    RItem& r = lds[i];
-    for (int k = 0; k < 3; ++k) r.c[k] = (float)(o[k] - cam[k]);
-    for (int k = 0; k < 9; ++k) r.R[k] = (float)o[3 + k];
-    for (int k = 0; k < 3; ++k) r.sz[k] = (float)o[12 + k];
-    for (int k = 0; k < 4; ++k) r.rgba[k] = (float)o[16 + k];
-    r.rb = (float)o[20];
-    r.type = (int)o[15];
-    r.draw = r.rgba[3] > 0.f && (o[21] == 0.0 || (flags & MYO_RENDER_SITES));
-  }
+  for (int i = tid; i < nitem; i += MYO_RTILE * MYO_RTILE) render_load(lds[i], it + (size_t)i * MYO_RENDER_ITEM_N, cam, flags);
 }
 
 // per-tile cull: the item's bounding sphere against the tile's four side planes through the camera and the camera plane
@@ -211,16 +298,16 @@ DEV float render_shade(const RItem& r, const float* nl, const float* d, float* r
   return r.rgba[3];
 }
 
-// one pixel (row py from the top, column px) of env row `e` of the output
-DEV void render_pixel(const RItem* lds, int nitem, const double* cam, int W, int H, int px, int py, int flags, size_t e,
-                      unsigned char* rgb, float* depth, int* seg) {
-  if (px >= W || py >= H) return;
+// the nearest opaque and the nearest translucent hit of one pixel's ray; item indices count from `base` of the table traced
+struct RHit { float to, tt, no[3], nt[3]; int io, it; };
+DEV void render_ray(const double* cam, int W, int H, int px, int py, float* d, RHit& h) {
   const float f = (float)cam[12];
   const float tx = ((float)px + 0.5f - 0.5f * (float)W) / f, ty = (0.5f * (float)H - ((float)py + 0.5f)) / f;
-  float d[3];
   for (int k = 0; k < 3; ++k) d[k] = (float)cam[3 + k] + tx * (float)cam[6 + k] + ty * (float)cam[9 + k];     // forward component 1: t = depth
-  float to = INFINITY, tt = INFINITY, no[3] = {0.f, 0.f, 1.f}, nt[3] = {0.f, 0.f, 1.f};
-  int io = -1, it = -1;
+  h.to = INFINITY; h.tt = INFINITY; h.io = -1; h.it = -1;
+  h.no[0] = 0.f; h.no[1] = 0.f; h.no[2] = 1.f; h.nt[0] = 0.f; h.nt[1] = 0.f; h.nt[2] = 1.f;
+}
+DEV void render_trace(const RItem* lds, int nitem, int base, const float* d, RHit& h) {
   for (int i = 0; i < nitem; ++i) {
     const RItem& r = lds[i];
     if (!r.draw) continue;
@@ -231,21 +318,56 @@ DEV void render_pixel(const RItem* lds, int nitem, const double* cam, int W, int
     }
     const float t = render_hit(r.type, r.sz, ol, dl, nl);
     if (r.rgba[3] >= 1.f) {
-      if (t < to) { to = t; io = i; no[0] = nl[0]; no[1] = nl[1]; no[2] = nl[2]; }
-    } else if (t < tt) { tt = t; it = i; nt[0] = nl[0]; nt[1] = nl[1]; nt[2] = nl[2]; }
+      if (t < h.to) { h.to = t; h.io = base + i; h.no[0] = nl[0]; h.no[1] = nl[1]; h.no[2] = nl[2]; }
+    } else if (t < h.tt) { h.tt = t; h.it = base + i; h.nt[0] = nl[0]; h.nt[1] = nl[1]; h.nt[2] = nl[2]; }
   }
-  const size_t pix = (e * (size_t)H + (size_t)py) * (size_t)W + (size_t)px;
-  const bool front_t = it >= 0 && tt < to;
+}
+// the pixel's outputs from its hits: ro / rt the opaque / translucent item hit (read only where h.io / h.it >= 0), so / st their ids
+DEV void render_write(const RItem* ro, const RItem* rt, int so, int st, const RHit& h, const float* d, int flags, size_t pix,
+                      unsigned char* rgb, float* depth, int* seg) {
+  const bool front_t = h.it >= 0 && h.tt < h.to;
   if (flags & MYO_RENDER_RGB) {
     float c[3] = {MYO_RBG_R, MYO_RBG_G, MYO_RBG_B};
-    if (io >= 0) render_shade(lds[io], no, d, c);
+    if (h.io >= 0) render_shade(*ro, h.no, d, c);
     if (front_t) {
       float ct[3];
-      const float a = render_shade(lds[it], nt, d, ct);
+      const float a = render_shade(*rt, h.nt, d, ct);
       for (int k = 0; k < 3; ++k) c[k] = a * ct[k] + (1.f - a) * c[k];
     }
     for (int k = 0; k < 3; ++k) rgb[3 * pix + k] = (unsigned char)fminf(255.f, fmaxf(0.f, floorf(c[k] * 255.f + 0.5f)));
   }
-  if (flags & MYO_RENDER_DEPTH) depth[pix] = front_t ? tt : to;
-  if (flags & MYO_RENDER_SEG) seg[pix] = front_t ? it : io;
+  if (flags & MYO_RENDER_DEPTH) depth[pix] = front_t ? h.tt : h.to;
+  if (flags & MYO_RENDER_SEG) seg[pix] = front_t ? st : so;
+}
+
+// one pixel (row py from the top, column px) of env row `e` of the output
+DEV void render_pixel(const RItem* lds, int nitem, const double* cam, int W, int H, int px, int py, int flags, size_t e,
+                      unsigned char* rgb, float* depth, int* seg) {
+  if (px >= W || py >= H) return;
+  float d[3];
+  RHit h;
+  render_ray(cam, W, H, px, py, d, h);
+  render_trace(lds, nitem, 0, d, h);
+  const size_t pix = (e * (size_t)H + (size_t)py) * (size_t)W + (size_t)px;
+  render_write(lds + (h.io >= 0 ? h.io : 0), lds + (h.it >= 0 ? h.it : 0), h.io, h.it, h, d, flags, pix, rgb, depth, seg);
+}
+// ... with MYO_RENDER_TENDONS, after both tables were traced into h: the hit items come from their global rows (`it`: the env's nitem
+// items, `tn`: its tendon items; the LDS table holds the tendons by now); a tendon item's id is nitem + its tendon ([22] - 1)
+DEV void render_pixel_finish(const double* it, int nitem, const double* tn, const double* cam, int W, int H, int px, int py, int flags, size_t e,
+                             const RHit& h, const float* d, unsigned char* rgb, float* depth, int* seg) {
+  if (px >= W || py >= H) return;
+  RItem ro, rt;
+  int so = h.io, st = h.it;
+  if (h.io >= 0) {
+    const double* o = h.io < nitem ? it + (size_t)h.io * MYO_RENDER_ITEM_N : tn + (size_t)(h.io - nitem) * MYO_RENDER_ITEM_N;
+    render_load(ro, o, cam, flags);
+    if (h.io >= nitem) so = nitem + (int)o[22] - 1;
+  }
+  if (h.it >= 0) {
+    const double* o = h.it < nitem ? it + (size_t)h.it * MYO_RENDER_ITEM_N : tn + (size_t)(h.it - nitem) * MYO_RENDER_ITEM_N;
+    render_load(rt, o, cam, flags);
+    if (h.it >= nitem) st = nitem + (int)o[22] - 1;
+  }
+  const size_t pix = (e * (size_t)H + (size_t)py) * (size_t)W + (size_t)px;
+  render_write(&ro, &rt, so, st, h, d, flags, pix, rgb, depth, seg);
 }

@@ -373,6 +373,51 @@ __global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render(const double* 
   __syncthreads();
   render_pixel(lds, nitem, cam, W, H, tx0 + tid % MYO_RTILE, ty0 + tid / MYO_RTILE, flags, (size_t)e, rgb, depth, seg);
 }
+// render path pass (csrc/myo_render.h): row r of `out` = the tendon items of env env_idx[r]; an index outside [0, n_envs): all zero
+template <typename T, bool RK, int NC>
+__global__ void __launch_bounds__(64, 2) k_tendon_paths(EnvRecordLayout L, double* rec, const int* __restrict__ env_idx, int n_envs,
+                                                     const float* tvis, const int* tadr, int ntitem, double* out) {
+  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
+  s.rk = rk_storage<T, RK, NC>();
+  const DevModel<T>& M = myo_cmodel<T>();
+  const TaskDev& K = c_task;
+  const int env = env_idx[blockIdx.x];
+  double* o = out + (size_t)blockIdx.x * ntitem * MYO_RENDER_ITEM_N;
+  if (env < 0 || env >= n_envs) {
+    for (int i = threadIdx.x; i < ntitem * MYO_RENDER_ITEM_N; i += 64) o[i] = 0.0;
+    return;
+  }
+  env_tendon_paths<T>(M, K, L, rec + (size_t)env * L.stride, s, env, tvis, tadr, o);
+}
+// ray cast with MYO_RENDER_TENDONS: the geoms' table is traced, then the tendon items take its place in LDS and are traced into the
+// same per-pixel hit (an instantiation of its own: k_render is what it was)
+__global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render_tendons(const double* __restrict__ items, int nitem, const double* __restrict__ titems,
+                                                                          int ntitem, const double* __restrict__ cams, int ncams, int W, int H, int flags,
+                                                                          unsigned char* rgb, float* depth, int* seg) {
+  RItem* lds = reinterpret_cast<RItem*>(myo_lds);
+  const int tid = threadIdx.x, tiles_x = (W + MYO_RTILE - 1) / MYO_RTILE, e = blockIdx.y;
+  const int tx0 = (int)(blockIdx.x % tiles_x) * MYO_RTILE, ty0 = (int)(blockIdx.x / tiles_x) * MYO_RTILE;
+  const int px = tx0 + tid % MYO_RTILE, py = ty0 + tid / MYO_RTILE;
+  const double* cam = cams + (size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N;
+  const double* it = items + (size_t)e * nitem * MYO_RENDER_ITEM_N;
+  const double* tn = titems + (size_t)e * ntitem * MYO_RENDER_ITEM_N;
+  const bool inside = px < W && py < H;
+  float d[3];
+  RHit h;
+  render_ray(cam, W, H, px, py, d, h);
+  render_stage(tid, lds, it, nitem, cam, flags);
+  __syncthreads();
+  render_cull(tid, lds, nitem, cam, W, H, tx0, ty0);
+  __syncthreads();
+  if (inside) render_trace(lds, nitem, 0, d, h);
+  __syncthreads();
+  render_stage(tid, lds, tn, ntitem, cam, flags);
+  __syncthreads();
+  render_cull(tid, lds, ntitem, cam, W, H, tx0, ty0);
+  __syncthreads();
+  if (inside) render_trace(lds, ntitem, nitem, d, h);
+  render_pixel_finish(it, nitem, tn, cam, W, H, px, py, flags, (size_t)e, h, d, rgb, depth, seg);
+}
 // ... and the order that follows from the census: positions sorted by count, most engaged first (ties keep their order), written back
 // into the batch's own tables — gw_elem[k] = path element of position k, wr_i[8 w + 6] = position of element w — and the counts
 // cleared.  One wave; ngw <= 128 (two positions per lane).  Each wrap's arithmetic is its own: the order changes no result bit.
@@ -802,6 +847,21 @@ extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k,
   LAUNCH_CHECK(b)
   return MYO_OK;
 }
+static void tendon_paths_launch(myo_batch* b, const int32_t* env_idx, int k, double* out, hipStream_t st) {
+  LAUNCH_RK(b,
+    if (b->dtype == MYO_F64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tendon_paths<double, RKV, MYO_NC_D(NCV)>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->tvis, b->titem_adr, b->ntitem, out);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tendon_paths<float, RKV, NCV>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->tvis, b->titem_adr, b->ntitem, out))
+}
+extern "C" int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
+  int empty = 0;
+  int rc = tendon_paths_check(b, env_idx, k, out, &empty);
+  if (rc || empty) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  BIND_OR_RETURN(b, st)
+  tendon_paths_launch(b, env_idx, k, out, st);
+  LAUNCH_CHECK(b)
+  return MYO_OK;
+}
 extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
                                 int flags, uint8_t* rgb, float* depth, int32_t* segid, void* stream) {
   std::vector<double> cam_tab;
@@ -810,15 +870,24 @@ extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, con
   if (k > 65535) return fail(MYO_E_ARG, "myo_batch_render: at most 65535 envs per call");
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
-  const size_t item_n = (size_t)k * b->nitem * MYO_RENDER_ITEM_N;
+  const bool tendons = (flags & MYO_RENDER_TENDONS) && b->ntitem > 0;
+  const size_t geom_n = (size_t)k * b->nitem * MYO_RENDER_ITEM_N;
+  const size_t item_n = geom_n + (tendons ? (size_t)k * b->ntitem * MYO_RENDER_ITEM_N : 0);      // the geoms' tables, then the tendons'
   if ((rc = render_workspace(b, item_n + cam_tab.size()))) return rc;
   b->cam_host.swap(cam_tab);      // (kept until the next call: the asynchronous copy reads it)
   hipError_t e = hipMemcpyAsync(b->render_ws + item_n, b->cam_host.data(), b->cam_host.size() * sizeof(double), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return fail(MYO_E_DEVICE, "myo_batch_render: camera upload failed: %s", hipGetErrorString(e));
   geom_poses_launch(b, env_idx, k, b->render_ws, st);
   const unsigned tiles = (unsigned)(((width + MYO_RTILE - 1) / MYO_RTILE) * ((height + MYO_RTILE - 1) / MYO_RTILE));
-  hipLaunchKernelGGL(k_render, dim3(tiles, (unsigned)k), dim3(MYO_RTILE * MYO_RTILE), (unsigned)(b->nitem * sizeof(RItem)), st,
-                     b->render_ws, b->nitem, b->render_ws + item_n, ncams, width, height, flags, rgb, depth, segid);
+  if (tendons) {
+    tendon_paths_launch(b, env_idx, k, b->render_ws + geom_n, st);
+    const int nmax = b->nitem > b->ntitem ? b->nitem : b->ntitem;
+    hipLaunchKernelGGL(k_render_tendons, dim3(tiles, (unsigned)k), dim3(MYO_RTILE * MYO_RTILE), (unsigned)(nmax * sizeof(RItem)), st,
+                       b->render_ws, b->nitem, b->render_ws + geom_n, b->ntitem, b->render_ws + item_n, ncams, width, height, flags, rgb, depth, segid);
+  } else {
+    hipLaunchKernelGGL(k_render, dim3(tiles, (unsigned)k), dim3(MYO_RTILE * MYO_RTILE), (unsigned)(b->nitem * sizeof(RItem)), st,
+                       b->render_ws, b->nitem, b->render_ws + item_n, ncams, width, height, flags, rgb, depth, segid);
+  }
   LAUNCH_CHECK(b)
   return MYO_OK;
 }

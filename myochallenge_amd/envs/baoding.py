@@ -209,16 +209,18 @@ class BaodingVecEnv:
         return self._model.default_camera()
 
     def render_tensor(self, indices=None, width: int = 480, height: int = 480, camera=None, rgb: bool = True, depth: bool = False,
-                      segmentation: bool = False, show_sites: bool = False):
+                      segmentation: bool = False, show_sites: bool = False, tendons: bool = False):
         """Draw the present state of envs ``indices`` (default: all) on the GPU; device tensors, no host copy.
 
         camera: None (the default camera), a dict of MuJoCo free-camera keys (lookat, distance, azimuth, elevation, fovy; missing
         keys take the defaults) for every env, or a list of such dicts, one per env.  Returns a dict with the requested outputs:
         ``rgb`` uint8 [k, H, W, 3] (row 0 at the top), ``depth`` float32 [k, H, W] (along the camera axis, inf for the background),
-        ``segmentation`` int32 [k, H, W] (geom id, ngeom + site id, -1 for the background).
+        ``segmentation`` int32 [k, H, W] (geom id, ngeom + site id, ngeom + nsite + tendon id, -1 for the background).
+        ``tendons``: also draw the spatial tendons (``tendon_paths``), coloured by muscle activation — this library's own colour
+        rule, not MuJoCo's (include/myobatch.h).
 
-        Differences from MuJoCo's renderer: primitives ray-cast under a headlight (no model lights, shadows, textures or tendons);
-        model cameras are not available; sites other than the task's targets are drawn only with ``show_sites`` (the synthetic hand
+        Differences from MuJoCo's renderer: primitives ray-cast under a headlight (no model lights, shadows or textures; tendon
+        arcs around wrap geoms are drawn as chords); model cameras are not available; sites other than the task's targets are drawn only with ``show_sites`` (the synthetic hand
         has 215 tendon path sites).  Models without visual data (the synthetic ones) get derived colours (include/myobatch.h)."""
         t = self.torch
         idx = list(range(self.num_envs)) if indices is None else [int(i) for i in indices]
@@ -232,6 +234,7 @@ class BaodingVecEnv:
         k = len(idx)
         flags = (native.RENDER_RGB if rgb else 0) | (native.RENDER_DEPTH if depth else 0) | (native.RENDER_SEG if segmentation else 0)
         flags |= native.RENDER_SITES if show_sites else 0
+        flags |= native.RENDER_TENDONS if tendons else 0
         out = {}
         if rgb:
             out["rgb"] = t.empty((k, height, width, 3), dtype=t.uint8, device=self.device)
@@ -243,19 +246,33 @@ class BaodingVecEnv:
         self.batch.render(env_idx, cams, width, height, flags, out.get("rgb"), out.get("depth"), out.get("segmentation"), self._stream())
         return out
 
-    def get_images(self, width: int = 480, height: int = 480, camera=None) -> List[np.ndarray]:
+    def tendon_paths(self, indices=None):
+        """The tendon path items of envs ``indices`` (default: all): a device tensor float64 [k, ntendon_item, 24], one capsule item
+        per straight piece of every spatial tendon (midpoint, rotation with z along the piece, radius and half length, rgba blended
+        by muscle activation, tendon id + 1 in [22], the piece's share of the tendon's length in [23]; unused slots are zero rows:
+        include/myobatch.h myo_batch_tendon_paths)."""
+        t = self.torch
+        idx = list(range(self.num_envs)) if indices is None else [int(i) for i in indices]
+        if not idx or min(idx) < 0 or max(idx) >= self.num_envs:
+            raise ValueError(f"tendon_paths indices must be in [0, {self.num_envs})")
+        out = t.zeros((len(idx), self._model.size("ntendon_item"), native.RENDER_ITEM_N), dtype=t.float64, device=self.device)
+        if out.numel():
+            self.batch.tendon_paths(t.tensor(idx, dtype=t.int32, device=self.device), out, self._stream())
+        return out
+
+    def get_images(self, width: int = 480, height: int = 480, camera=None, tendons: bool = False) -> List[np.ndarray]:
         """SB3 VecEnv.get_images: one [H, W, 3] uint8 array per env."""
-        rgb = self.render_tensor(None, width, height, camera)["rgb"].cpu().numpy()
+        rgb = self.render_tensor(None, width, height, camera, tendons=tendons)["rgb"].cpu().numpy()
         return [rgb[i] for i in range(self.num_envs)]
 
-    def render(self, mode: str = "rgb_array", **kwargs):
+    def render(self, mode: str = "rgb_array", tendons: bool = False, **kwargs):
         """SB3 VecEnv.render: "rgb_array" returns the envs' images tiled into one grid (stable_baselines3 tile_images)."""
         if mode in ("human", "window"):
             raise NotImplementedError(f"render mode {mode!r} needs a display; this GPU library renders offscreen only: use 'rgb_array'")
         if mode != "rgb_array":
             raise ValueError(f"unknown render mode {mode!r}; supported: {self.metadata['render.modes']}")
         from ..render_io import tile_images
-        return tile_images(self.get_images(**kwargs))
+        return tile_images(self.get_images(tendons=tendons, **kwargs))
 
     # ---------------------------------------------------------------- state access (parity tests)
     def get_state(self):

@@ -28,8 +28,8 @@ DEFAULT_CONFIG = {
 
 def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBallsP2", config: dict = None,
              num_episodes: int = 100, num_envs: int = 256, seed: int = 0, deterministic: bool = True, verbose: bool = True,
-             render_dir: str = None, render_envs: int = 1, render_size=(480, 480)):
-    """render_dir: write a PNG of each of the first ``render_envs`` envs after every step (``env{i}_step{t}.png``; the reference
+             render_dir: str = None, render_envs: int = 1, render_size=(480, 480), render_tendons: bool = False):
+    """render_tendons: draw the tendons, coloured by muscle activation, into the frames.  render_dir: write a PNG of each of the first ``render_envs`` envs after every step (``env{i}_step{t}.png``; the reference
     script's ``render`` switch, src/main_eval.py:96-97, shows the frames in a window instead)."""
     from .envs.environment_factory import EnvironmentFactory
     from .metrics.evaluation import evaluate_policy, summarize
@@ -52,7 +52,7 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
         k = max(1, min(int(render_envs), env.num_envs))
 
         def on_step(t):
-            rgb = env.render_tensor(list(range(k)), int(render_size[0]), int(render_size[1]))["rgb"].cpu().numpy()
+            rgb = env.render_tensor(list(range(k)), int(render_size[0]), int(render_size[1]), tendons=render_tendons)["rgb"].cpu().numpy()
             for i in range(k):
                 write_png(os.path.join(render_dir, f"env{i}_step{t:05d}.png"), rgb[i])
     res = evaluate_policy(policy, env, venv, n_eval_episodes=num_episodes, deterministic=deterministic, on_step=on_step)
@@ -77,10 +77,13 @@ def main(argv=None):
     ap.add_argument("--render-dir", default=None, help="write PNG frames of the first --render-envs envs after every step here")
     ap.add_argument("--render-envs", type=int, default=1)
     ap.add_argument("--render-size", type=int, nargs=2, default=(480, 480), metavar=("W", "H"))
+    ap.add_argument("--render-tendons", action="store_true", help="with --render-dir: draw the tendons, coloured by muscle activation")
     a = ap.parse_args(argv)
+    if a.render_tendons and not a.render_dir:
+        ap.error("--render-tendons needs --render-dir")
     cfg = json.load(open(a.config)) if a.config else None
     res, _ = evaluate(a.model, a.env_path, a.env_name, cfg, a.num_episodes, a.num_envs, a.seed,
-                      render_dir=a.render_dir, render_envs=a.render_envs, render_size=a.render_size)
+                      render_dir=a.render_dir, render_envs=a.render_envs, render_size=a.render_size, render_tendons=a.render_tendons)
     if a.out:
         np.savez(a.out, **res)
 

@@ -354,9 +354,9 @@ def compile_model(m: MjbModel, *, integrator: int | None = None, unsupported_con
     f["x_xp_friction"] = (np.asarray(m.arrays["pair_friction"], np.float64).reshape(-1, 5)[:npair_x][:, [0, 2, 3]].reshape(-1) if npair_x else np.zeros(0))
     # visual data (rendering: csrc/myo_host.h render_vis_table), where the model source has it (a real .mjb; the synthetic models have none)
     if "geom_rgba" in m.arrays:
-        for name in ("geom_group", "geom_matid", "site_group"):
+        for name in ("geom_group", "geom_matid", "site_group", "tendon_group", "tendon_matid"):
             f[name] = np.ascontiguousarray(m.arrays[name]).astype(np.int32).reshape(-1)
-        for name in ("geom_rgba", "mat_rgba", "site_rgba", "site_size"):
+        for name in ("geom_rgba", "mat_rgba", "site_rgba", "site_size", "tendon_rgba", "tendon_width"):
             f[name] = np.ascontiguousarray(m.arrays[name]).astype(np.float64).reshape(-1)
         st = m.stat or {}
         if float(st.get("extent", 0.0)) > 0:

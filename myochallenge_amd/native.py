@@ -98,8 +98,8 @@ class RenderCamera(C.Structure):
                 ("fovy", C.c_double)]
 
 
-RENDER_RGB, RENDER_DEPTH, RENDER_SEG, RENDER_SITES = 1, 2, 4, 8
-RENDER_ITEM_N = 24      # doubles per item of myo_batch_geom_poses
+RENDER_RGB, RENDER_DEPTH, RENDER_SEG, RENDER_SITES, RENDER_TENDONS = 1, 2, 4, 8, 16
+RENDER_ITEM_N = 24      # doubles per item of myo_batch_geom_poses / myo_batch_tendon_paths
 
 
 class MyoError(RuntimeError):
@@ -154,6 +154,7 @@ class NativeLib:
         L.myo_batch_enable_timing.argtypes = [vp, i32]
         L.myo_model_default_camera.argtypes = [vp, C.POINTER(RenderCamera)]
         L.myo_batch_geom_poses.argtypes = [vp, vp, i32, vp, vp]
+        L.myo_batch_tendon_paths.argtypes = [vp, vp, i32, vp, vp]
         L.myo_batch_render.argtypes = [vp, vp, i32, C.POINTER(RenderCamera), i32, i32, i32, i32, vp, vp, vp, vp]
         if b"MYO_EMU" in L.myo_version():
             return      # the emulation build (test tooling, csrc/emu_host.h) implements the env path only: ENV_PATH_SYMBOLS
@@ -230,7 +231,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_dump_size", "myo_batch_dump_offset", "myo_batch_kernel_ms",
     "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
     "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_clip_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_adam_apply", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_last_error", "myo_version",
-    "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_render",
+    "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
 ]
 
 # ... of which the lane-serial emulation build (tests/emu/libmyobatch_emu.so: csrc/myobatch_emu.cpp + csrc/emu_host.h, test tooling) has the env
@@ -242,7 +243,7 @@ ENV_PATH_SYMBOLS = [
     "myo_batch_set_bad_state_buffer", "myo_batch_set_object_group", "myo_batch_set_state", "myo_batch_set_step_generation", "myo_batch_set_task",
     "myo_batch_step", "myo_batch_step_inner", "myo_batch_step_inner_idx", "myo_batch_tune_wrap_order", "myo_batch_warmstart", "myo_debug_wave_slots",
     "myo_last_error", "myo_model_destroy", "myo_model_from_blob", "myo_model_load_mjb", "myo_model_size", "myo_version",
-    "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_render",
+    "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
 ]
 
 
@@ -386,6 +387,11 @@ class Batch:
     def geom_poses(self, env_idx, out, stream=None):
         """pose pass of the renderer: env_idx int32[k] -> out float64 [k, ngeom + nsite, RENDER_ITEM_N] (include/myobatch.h)"""
         self.lib.check(self.lib.L.myo_batch_geom_poses(self.h, _ptr(env_idx), int(env_idx.shape[0]), _ptr(out), stream))
+
+    def tendon_paths(self, env_idx, out, stream=None):
+        """path pass of the renderer: env_idx int32[k] -> out float64 [k, ntendon_item, RENDER_ITEM_N], the straight pieces of every
+        spatial tendon as capsule items (include/myobatch.h)"""
+        self.lib.check(self.lib.L.myo_batch_tendon_paths(self.h, _ptr(env_idx), int(env_idx.shape[0]), _ptr(out), stream))
 
     def render(self, env_idx, cams, width, height, flags, rgb=None, depth=None, segid=None, stream=None):
         """ray cast of envs env_idx int32[k]; cams: a list of 1 or k camera dicts (lookat, distance, azimuth, elevation, fovy)"""

@@ -241,6 +241,9 @@ class VecNormalize:
     def render_tensor(self, *args, **kwargs):
         return self.venv.render_tensor(*args, **kwargs)
 
+    def tendon_paths(self, *args, **kwargs):
+        return self.venv.tendon_paths(*args, **kwargs)
+
     def close(self):
         if self.venv is not None:
             self.venv.close()
