@@ -340,6 +340,16 @@ int myo_ppo_loss_grad(const float* mean, const float* values, const float* actio
                       uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
                       float* g_log_std, float* g_bias_pi, float* g_bias_vf, void* stream);
 
+/* myo_ppo_loss_grad with the PPO hyper-parameter block `hp` (layout below, beside myo_ppo_mlp_desc).  hp == NULL: exactly
+ * myo_ppo_loss_grad.  Otherwise clip_range is hp[MYO_HP_CLIP] (`clip` is ignored), `work` has ceil(B/64) * (2A+6) floats (three
+ * more columns: approx_kl, clip fraction, entropy loss) and the second launch records the minibatch in the block and raises its
+ * stop flag when approx_kl > hp[MYO_HP_KL_LIMIT]. */
+int myo_ppo_loss_grad_hp(const float* mean, const float* values, const float* actions, const float* old_logp,
+                         const float* adv, const float* returns, const float* log_std, const float* adv_stats,
+                         int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
+                         uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
+                         float* g_log_std, float* g_bias_pi, float* g_bias_vf, float* hp, void* stream);
+
 /* Minibatch gather of one optimiser step (SB3 RolloutBuffer.get + the per-minibatch advantage
  * normalisation statistics of PPO.train): rows idx[0..bs) (dev int64) of obs[N,obs_dim] act[N,act_dim]
  * oldlp[N] adv[N] ret[N] (dev float32) -> obs_bf16 [copies, bs, obs_dim] (bfloat16), act_mb, oldlp_mb,
@@ -490,6 +500,34 @@ int myo_gae(const float* rew, const float* val, const float* starts, const float
  * workspace: device memory of myo_ppo_mlp_workspace_bytes() bytes, ZERO-FILLED ONCE by the caller and then owned by these
  * calls (weight images, feature-major activations, split-K slabs).  Deterministic: no float atomics.  Returns
  * MYO_E_UNSUPPORTED for other shapes (hidden != 256, obs > 128, act > 48, B not a multiple of 1024). */
+/* The PPO hyper-parameter block: MYO_HP_WORDS 32-bit words of device memory per PPO instance, read by the loss and Adam kernels
+ * at RUN time, so a hipGraph captured once follows a learning-rate / clip-range schedule and can stop an update on the device
+ * (SB3 PPO.train: learning_rate and clip_range schedules, target_kl).  The host writes it with plain asynchronous copies before
+ * an update, outside any graph.  Words (float unless marked int32):
+ *   MYO_HP_LR            learning rate of the Adam kernels
+ *   MYO_HP_CLIP          clip_range of the loss kernels
+ *   MYO_HP_KL_LIMIT      1.5 * target_kl; <= 0: no KL stop (also what N > 1 ranks write: they decide on the all-reduced value)
+ *   MYO_HP_STOP          int32, STICKY: raised by the kernel that finishes a minibatch's loss sums when approx_kl > limit.  While
+ *                        it is up the gradient-norm / Adam kernels leave p, m, v, the bf16 shadow and the step counter alone and
+ *                        nothing below is updated, so the rest of a replayed chunk of steps changes nothing.  Host-cleared.
+ *   MYO_HP_APPLIED       int32: optimizer steps applied (advanced by the Adam kernel)
+ *   MYO_HP_COUNT         int32: minibatches recorded in the three sums (the one that raised the flag included, as in SB3)
+ *   MYO_HP_SUM_KL, MYO_HP_SUM_CLIPFRAC, MYO_HP_SUM_ENTLOSS   sums over the recorded minibatches of approx_kl =
+ *                        mean((ratio - 1) - log ratio), mean(|ratio - 1| > clip_range) and -mean(entropy)
+ *   MYO_HP_LAST_KL, MYO_HP_LAST_PL, MYO_HP_LAST_VL           approx_kl, policy loss, value loss of the last recorded minibatch */
+#define MYO_HP_LR 0
+#define MYO_HP_CLIP 1
+#define MYO_HP_KL_LIMIT 2
+#define MYO_HP_STOP 3
+#define MYO_HP_APPLIED 4
+#define MYO_HP_COUNT 5
+#define MYO_HP_SUM_KL 6
+#define MYO_HP_SUM_CLIPFRAC 7
+#define MYO_HP_SUM_ENTLOSS 8
+#define MYO_HP_LAST_KL 9
+#define MYO_HP_LAST_PL 10
+#define MYO_HP_LAST_VL 11
+#define MYO_HP_WORDS 16
 typedef struct myo_ppo_mlp_desc {
   const float *obs, *act, *oldlp, *adv, *ret;
   const int64_t* idx;
@@ -509,6 +547,9 @@ typedef struct myo_ppo_mlp_desc {
    * instead of myo_adam_clip_step.  Not for N > 1 ranks: there the gradient changes (all-reduce) before it is clipped. */
   float* sqnorm_part;
   int32_t* adam_step;
+  /* hyper-parameter block (above) or NULL = as without it: clip_range comes from it instead of `clip`, and the launch that
+   * finishes the loss sums records the minibatch, takes the KL-stop decision and, stopped, does not advance adam_step. */
+  float* hp;
 } myo_ppo_mlp_desc;
 int myo_ppo_mlp_sqnorm_parts(int act_dim);
 long long myo_ppo_mlp_workspace_bytes(int B, int obs_dim, int act_dim, int hidden, long long G);
@@ -553,6 +594,14 @@ int myo_adam_clip_step(float* p, const float* g, float* m, float* v, int n, floa
 int myo_adam_apply(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
                    float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
                    uint16_t* p_bf16, void* stream);
+/* Both with the hyper-parameter block (NULL: exactly the calls above): lr is hp[MYO_HP_LR] (`lr` is ignored); with the stop
+ * flag up p, m, v, p_bf16 and `step` stay untouched; otherwise hp[MYO_HP_APPLIED] advances by one. */
+int myo_adam_clip_step_hp(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                          float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
+                          float* hp, void* stream);
+int myo_adam_apply_hp(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                      float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
+                      uint16_t* p_bf16, float* hp, void* stream);
 
 const char* myo_last_error(void);
 const char* myo_version(void);

@@ -42,6 +42,7 @@ struct MlpArgs {
   float* part;                                     // loss partials, column-major [(2A+3)][NB]
   int B, O, A, OP, NB;
   float clip, vf_coef;
+  const float* hp;                                 // hyper-parameter block (include/myobatch.h) or NULL: clip_range is read from it
 };
 
 __device__ __forceinline__ unsigned short mlp_f2bf(float x) {   // round-to-nearest-even (finite inputs)
@@ -375,12 +376,14 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
         logp += -0.5f * z * z - s_ls[a] - 0.9189385332046727f;
       }
       const float an = (s_row[r] - P.adv_stats[0]) / (P.adv_stats[1] + 1e-8f);
-      const float ratio = __expf(logp - s_row[64 + r]);
+      const float clip = P.hp ? P.hp[MYO_HP_CLIP] : P.clip;
+      const float lr_i = logp - s_row[64 + r];
+      const float ratio = __expf(lr_i);
       const float s1 = an * ratio;
-      const float rc = fminf(fmaxf(ratio, 1.f - P.clip), 1.f + P.clip);
+      const float rc = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
       const float s2 = an * rc;
       float pl_i = on ? -fminf(s1, s2) / B : 0.f;
-      const bool inside = (ratio > 1.f - P.clip) && (ratio < 1.f + P.clip);
+      const bool inside = (ratio > 1.f - clip) && (ratio < 1.f + clip);
       const float dlogp = -(an * ratio) * ((s1 <= s2) ? 1.f : (inside ? 1.f : 0.f)) / B;
       if (on) {
         for (int a = 0; a < A; ++a) {
@@ -395,6 +398,19 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
       }
       for (int off = 32; off >= 1; off >>= 1) pl_i += __shfl_xor(pl_i, off, 64);
       if (lane == 0) P.part[(size_t)A * NB + blk] = pl_i;
+      if (P.hp) {          // approx_kl, clip fraction and entropy loss of the block's rows (k_ppo_loss's three extra columns)
+        float ent = 0.f;
+        for (int a = 0; a < A; ++a) ent += s_ls[a] + 1.4189385332046727f;
+        float kl_i = on ? ((ratio - 1.f) - lr_i) / B : 0.f, cf_i = on ? (fabsf(ratio - 1.f) > clip ? 1.f : 0.f) / B : 0.f;
+        float el_i = on ? -ent / B : 0.f;
+        for (int off = 32; off >= 1; off >>= 1) {
+          kl_i += __shfl_xor(kl_i, off, 64); cf_i += __shfl_xor(cf_i, off, 64); el_i += __shfl_xor(el_i, off, 64);
+        }
+        if (lane == 0) {
+          P.part[(size_t)(2 * A + 3) * NB + blk] = kl_i; P.part[(size_t)(2 * A + 4) * NB + blk] = cf_i;
+          P.part[(size_t)(2 * A + 5) * NB + blk] = el_i;
+        }
+      }
     } else {
       const float dv = So[r * SOS] - s_row[128 + r];
       float vl_i = on ? dv * dv / B : 0.f, dv_i = on ? P.vf_coef * 2.f / B * dv : 0.f;
@@ -676,6 +692,7 @@ struct MlpRfArgs {
   const float* part; float* acc; int NB, A; float ent_coef;
   long long off_log_std, off_bh0, off_bh1;
   float* sq_part; int* adam_step;
+  float* hp;       // hyper-parameter block or NULL: block 0 records the minibatch's diagnostics and takes the KL-stop decision
 };
 __global__ void __launch_bounds__(256) k_mlp_reduce_finish(MlpRfArgs P) {
   __shared__ float red[4];
@@ -691,10 +708,19 @@ __global__ void __launch_bounds__(256) k_mlp_reduce_finish(MlpRfArgs P) {
     }
     for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
     if ((t & 63) == 0) red[t >> 6] = sq;
+    float pl = 0.f, vl = 0.f, kl = 0.f, cf = 0.f, el = 0.f;
+    if (P.hp && blockIdx.x == 0 && t < 64) {       // the loss columns this decision needs, in the column blocks' order
+      pl = myo_col_sum(P.part, A, P.NB, t); vl = myo_col_sum(P.part, A + 1, P.NB, t);
+      kl = myo_col_sum(P.part, 2 * A + 3, P.NB, t); cf = myo_col_sum(P.part, 2 * A + 4, P.NB, t); el = myo_col_sum(P.part, 2 * A + 5, P.NB, t);
+    }
     __syncthreads();
     if (t == 0) {
       P.sq_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-      if (blockIdx.x == 0) { const int done = P.adam_step[1]; P.adam_step[0] = done; P.adam_step[1] = done + 1; }
+      if (blockIdx.x == 0) {
+        // the stop flag has one reader and one writer in this launch (this thread); k_adam reads it after the kernel boundary
+        const bool stopped = P.hp ? myo_hp_record(P.hp, pl, vl, kl, cf, el) : false;
+        if (!stopped) { const int done = P.adam_step[1]; P.adam_step[0] = done; P.adam_step[1] = done + 1; }
+      }
     }
     return;
   }

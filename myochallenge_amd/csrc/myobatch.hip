@@ -933,8 +933,9 @@ __global__ void __launch_bounds__(64) k_ppo_loss(const float* __restrict__ mean,
                                                  int B, int A, float clip, float vf_coef, float* __restrict__ dmean,
                                                  float* __restrict__ dvalue, float* __restrict__ acc,
                                                  unsigned short* __restrict__ dmean_h, unsigned short* __restrict__ dvalue_h,
-                                                 float* __restrict__ part) {
+                                                 float* __restrict__ part, const float* __restrict__ hp) {
   __shared__ float t_mean[64 * 64], t_act[64 * 64], s_ls[64], s_inv[64];
+  if (hp) clip = hp[MYO_HP_CLIP];          // the device-resident hyper-parameters (include/myobatch.h) override the launch scalar
   const int lane = threadIdx.x, r0 = blockIdx.x * 64;
   const int rows = (B - r0) < 64 ? (B - r0) : 64;
   const int n = rows * A;
@@ -948,15 +949,20 @@ __global__ void __launch_bounds__(64) k_ppo_loss(const float* __restrict__ mean,
   __syncthreads();
   const int i = r0 + lane;
   const bool on = lane < rows;
-  float pl_i = 0.f, vl_i = 0.f, dlogp = 0.f, dv_i = 0.f;
+  float pl_i = 0.f, vl_i = 0.f, dlogp = 0.f, dv_i = 0.f, kl_i = 0.f, cf_i = 0.f, el_i = 0.f;
   if (on) {
-    float logp = 0.f;
+    float logp = 0.f, ent = 0.f;
     for (int a = 0; a < A; ++a) {
       const float z = (t_act[lane * A + a] - t_mean[lane * A + a]) * s_inv[a];
       logp += -0.5f * z * z - s_ls[a] - 0.9189385332046727f;
+      ent += s_ls[a] + 1.4189385332046727f;
     }
     const float an = (adv[i] - adv_stats[0]) / (adv_stats[1] + 1e-8f);
-    const float ratio = __expf(logp - old_logp[i]);
+    const float lr_i = logp - old_logp[i];
+    const float ratio = __expf(lr_i);
+    kl_i = ((ratio - 1.f) - lr_i) / B;                            // SB3's approx_kl, clip_fraction and entropy_loss terms of this row
+    cf_i = (fabsf(ratio - 1.f) > clip ? 1.f : 0.f) / B;
+    el_i = -ent / B;
     const float s1 = an * ratio;
     const float rc = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
     const float s2 = an * rc;
@@ -999,14 +1005,51 @@ __global__ void __launch_bounds__(64) k_ppo_loss(const float* __restrict__ mean,
     part[(size_t)A * NB + blockIdx.x] = pl_i; part[(size_t)(A + 1) * NB + blockIdx.x] = vl_i;
     part[(size_t)(2 * A + 2) * NB + blockIdx.x] = dv_i;
   }
+  if (hp) {                // three more columns: what the diagnostics and the KL stop of the hyper-parameter block are made of
+    for (int off = 32; off >= 1; off >>= 1) {
+      kl_i += __shfl_xor(kl_i, off, 64); cf_i += __shfl_xor(cf_i, off, 64); el_i += __shfl_xor(el_i, off, 64);
+    }
+    if (lane == 0) {
+      part[(size_t)W * NB + blockIdx.x] = kl_i; part[(size_t)(W + 1) * NB + blockIdx.x] = cf_i;
+      part[(size_t)(W + 2) * NB + blockIdx.x] = el_i;
+    }
+  }
+}
+// One finished minibatch loss entered into the hyper-parameter block (layout: include/myobatch.h) by ONE thread of the kernel that
+// finishes the loss sums.  Returns true when the optimizer step that follows must not be applied: the stop flag was already up
+// (sticky: nothing is recorded, the flag and the diagnostics of the minibatch that raised it stay), or this minibatch's
+// approx_kl exceeds the limit (its diagnostics are recorded, as SB3 appends them before it breaks).
+__device__ __forceinline__ bool myo_hp_record(float* __restrict__ hp, float pl, float vl, float kl, float cf, float el) {
+  int* hi = reinterpret_cast<int*>(hp);
+  if (hi[MYO_HP_STOP]) return true;
+  hp[MYO_HP_SUM_KL] += kl; hp[MYO_HP_SUM_CLIPFRAC] += cf; hp[MYO_HP_SUM_ENTLOSS] += el;
+  hi[MYO_HP_COUNT] += 1;
+  hp[MYO_HP_LAST_KL] = kl; hp[MYO_HP_LAST_PL] = pl; hp[MYO_HP_LAST_VL] = vl;
+  const float lim = hp[MYO_HP_KL_LIMIT];
+  if (lim > 0.f && kl > lim) { hi[MYO_HP_STOP] = 1; return true; }
+  return false;
+}
+// sum over blocks of column c of the loss partials, by one wave: the order k_colmajor_finish adds them in
+__device__ __forceinline__ float myo_col_sum(const float* __restrict__ part, int c, int NB, int lane) {
+  float a = 0.f;
+  for (int b = lane; b < NB; b += 64) a += part[(size_t)c * NB + b];
+  for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
+  return a;
 }
 // acc[c] = sum over blocks of part[c, block] (fixed order: deterministic); one wave per column.
 // A separate launch instead of a last-block epilogue: an in-kernel release fence writes back the
 // whole L2 of the XCD on this chip (measured: +90 us), a kernel boundary is cheaper.
 __global__ void __launch_bounds__(64) k_colmajor_finish(const float* __restrict__ part, float* __restrict__ acc, int NB, int A,
                                                         float ent_coef, float* __restrict__ g_log_std,
-                                                        float* __restrict__ g_bias_pi, float* __restrict__ g_bias_vf) {
+                                                        float* __restrict__ g_bias_pi, float* __restrict__ g_bias_vf,
+                                                        float* __restrict__ hp) {
   const int c = blockIdx.x, lane = threadIdx.x;
+  if (c == 2 * A + 3) {       // (launched with a hyper-parameter block only) diagnostics and the KL stop
+    const float pl = myo_col_sum(part, A, NB, lane), vl = myo_col_sum(part, A + 1, NB, lane);
+    const float kl = myo_col_sum(part, c, NB, lane), cf = myo_col_sum(part, c + 1, NB, lane), el = myo_col_sum(part, c + 2, NB, lane);
+    if (lane == 0) (void)myo_hp_record(hp, pl, vl, kl, cf, el);
+    return;
+  }
   float a = 0.f;
   for (int b = lane; b < NB; b += 64) a += part[(size_t)c * NB + b];
   for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
@@ -1017,11 +1060,11 @@ __global__ void __launch_bounds__(64) k_colmajor_finish(const float* __restrict_
     if (g_bias_vf && c == 2 * A + 2) g_bias_vf[0] = a;
   }
 }
-extern "C" int myo_ppo_loss_grad(const float* mean, const float* values, const float* actions, const float* old_logp,
-                                 const float* adv, const float* returns, const float* log_std, const float* adv_stats,
-                                 int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
-                                 uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
-                                 float* g_log_std, float* g_bias_pi, float* g_bias_vf, void* stream) {
+static int ppo_loss_grad(const float* mean, const float* values, const float* actions, const float* old_logp,
+                         const float* adv, const float* returns, const float* log_std, const float* adv_stats,
+                         int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
+                         uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
+                         float* g_log_std, float* g_bias_pi, float* g_bias_vf, float* hp, void* stream) {
   if (!mean || !values || !actions || !old_logp || !adv || !returns || !log_std || !adv_stats || !dmean || !dvalue || !acc ||
       !work || B <= 0 || A <= 0 || A > 64)
     return fail(MYO_E_ARG, "myo_ppo_loss_grad: bad arguments");
@@ -1029,14 +1072,30 @@ extern "C" int myo_ppo_loss_grad(const float* mean, const float* values, const f
   const int nblk = (B + 63) / 64;
   if (in_bf16)
     hipLaunchKernelGGL(k_ppo_loss<true>, dim3(nblk), dim3(64), 0, st, mean, values, actions, old_logp, adv, returns,
-                       log_std, adv_stats, B, A, clip, vf_coef, dmean, dvalue, acc, dmean_bf16, dvalue_bf16, work);
+                       log_std, adv_stats, B, A, clip, vf_coef, dmean, dvalue, acc, dmean_bf16, dvalue_bf16, work, (const float*)hp);
   else
     hipLaunchKernelGGL(k_ppo_loss<false>, dim3(nblk), dim3(64), 0, st, mean, values, actions, old_logp, adv, returns,
-                       log_std, adv_stats, B, A, clip, vf_coef, dmean, dvalue, acc, dmean_bf16, dvalue_bf16, work);
-  hipLaunchKernelGGL(k_colmajor_finish, dim3(2 * A + 3), dim3(64), 0, st, work, acc, nblk, A, ent_coef, g_log_std, g_bias_pi,
-                     g_bias_vf);
+                       log_std, adv_stats, B, A, clip, vf_coef, dmean, dvalue, acc, dmean_bf16, dvalue_bf16, work, (const float*)hp);
+  hipLaunchKernelGGL(k_colmajor_finish, dim3(2 * A + 3 + (hp ? 1 : 0)), dim3(64), 0, st, work, acc, nblk, A, ent_coef, g_log_std, g_bias_pi,
+                     g_bias_vf, hp);
   LAUNCH_CHECK(0)
   return MYO_OK;
+}
+extern "C" int myo_ppo_loss_grad(const float* mean, const float* values, const float* actions, const float* old_logp,
+                                 const float* adv, const float* returns, const float* log_std, const float* adv_stats,
+                                 int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
+                                 uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
+                                 float* g_log_std, float* g_bias_pi, float* g_bias_vf, void* stream) {
+  return ppo_loss_grad(mean, values, actions, old_logp, adv, returns, log_std, adv_stats, B, A, clip, vf_coef, dmean, dvalue, acc,
+                       dmean_bf16, dvalue_bf16, work, in_bf16, ent_coef, g_log_std, g_bias_pi, g_bias_vf, nullptr, stream);
+}
+extern "C" int myo_ppo_loss_grad_hp(const float* mean, const float* values, const float* actions, const float* old_logp,
+                                    const float* adv, const float* returns, const float* log_std, const float* adv_stats,
+                                    int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
+                                    uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
+                                    float* g_log_std, float* g_bias_pi, float* g_bias_vf, float* hp, void* stream) {
+  return ppo_loss_grad(mean, values, actions, old_logp, adv, returns, log_std, adv_stats, B, A, clip, vf_coef, dmean, dvalue, acc,
+                       dmean_bf16, dvalue_bf16, work, in_bf16, ent_coef, g_log_std, g_bias_pi, g_bias_vf, hp, stream);
 }
 
 // ------------------------------------------------------------------------------------------ split-K
@@ -1796,7 +1855,7 @@ extern "C" int myo_gae(const float* rew, const float* val, const float* starts, 
 // scratch[0..63] <- per-block sums of (g*gs)^2 (fixed order inside a block: no float atomics);
 // step[0] <- committed step count, step[1] <- pending (= this step's ordinal)
 __global__ void __launch_bounds__(256) k_grad_sqnorm(const float* __restrict__ g, int n, float gs, float* __restrict__ part,
-                                                     int* __restrict__ step) {
+                                                     int* __restrict__ step, const float* __restrict__ hp) {
   float acc = 0.f;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += MYO_SQN_BLOCKS * 256) { const float x = g[i] * gs; acc += x * x; }
   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
@@ -1805,13 +1864,19 @@ __global__ void __launch_bounds__(256) k_grad_sqnorm(const float* __restrict__ g
   __syncthreads();
   if (threadIdx.x == 0) {
     part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-    if (blockIdx.x == 0) { const int done = step[1]; step[0] = done; step[1] = done + 1; }
+    // (hyper-parameter block with its stop flag up: this step is not taken, the counter stays)
+    if (blockIdx.x == 0 && !(hp && reinterpret_cast<const int*>(hp)[MYO_HP_STOP])) { const int done = step[1]; step[0] = done; step[1] = done + 1; }
   }
 }
 __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                               float* __restrict__ v, int n, float lr, float b1, float b2, float eps,
                                               float max_norm, float gs, const int* __restrict__ step,
-                                              const float* __restrict__ part, unsigned short* __restrict__ p_bf16, int nparts) {
+                                              const float* __restrict__ part, unsigned short* __restrict__ p_bf16, int nparts,
+                                              float* __restrict__ hp) {
+  if (hp) {       // lr from the hyper-parameter block; stop flag up: p, m, v and the bf16 shadow stay as they are
+    if (reinterpret_cast<const int*>(hp)[MYO_HP_STOP]) return;
+    lr = hp[MYO_HP_LR];
+  }
   // |g|^2 from the partial sums: every block adds them in the same tree order (256 lanes, strided, then halving) — a serial
   // loop over them was one dependent scalar load per partial, 4 us for 64 and 21 us for 337
   __shared__ float sq_red[256];
@@ -1837,28 +1902,49 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float
     p[i] = pn;
     if (p_bf16) p_bf16[i] = myo_f2bf(pn);          // the bf16 shadow the GEMMs read: no separate cast pass
   }
+  if (hp && blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<int*>(hp)[MYO_HP_APPLIED] += 1;
+}
+static int adam_clip_step(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                          float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
+                          float* hp, void* stream) {
+  if (!p || !g || !m || !v || !step || !scratch || n <= 0) return fail(MYO_E_ARG, "myo_adam_clip_step: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
+  hipLaunchKernelGGL(k_grad_sqnorm, dim3(MYO_SQN_BLOCKS), dim3(256), 0, st, g, n, grad_scale, scratch, step, (const float*)hp);
+  hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch,
+                     (unsigned short*)p_bf16, MYO_SQN_BLOCKS, hp);
+  LAUNCH_CHECK(0)
+  return MYO_OK;
 }
 extern "C" int myo_adam_clip_step(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
                                   float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
                                   void* stream) {
-  if (!p || !g || !m || !v || !step || !scratch || n <= 0) return fail(MYO_E_ARG, "myo_adam_clip_step: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
+  return adam_clip_step(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, p_bf16, nullptr, stream);
+}
+extern "C" int myo_adam_clip_step_hp(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                                     float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
+                                     float* hp, void* stream) {
+  return adam_clip_step(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, p_bf16, hp, stream);
+}
+static int adam_apply(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                      float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
+                      uint16_t* p_bf16, float* hp, void* stream) {
+  if (!p || !g || !m || !v || !step || !scratch || n <= 0 || nparts <= 0) return fail(MYO_E_ARG, "myo_adam_apply: bad arguments");
   const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
-  hipLaunchKernelGGL(k_grad_sqnorm, dim3(MYO_SQN_BLOCKS), dim3(256), 0, st, g, n, grad_scale, scratch, step);
-  hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch,
-                     (unsigned short*)p_bf16, MYO_SQN_BLOCKS);
+  hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch,
+                     (unsigned short*)p_bf16, nparts, hp);
   LAUNCH_CHECK(0)
   return MYO_OK;
 }
 extern "C" int myo_adam_apply(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
                               float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
                               uint16_t* p_bf16, void* stream) {
-  if (!p || !g || !m || !v || !step || !scratch || n <= 0 || nparts <= 0) return fail(MYO_E_ARG, "myo_adam_apply: bad arguments");
-  const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
-  hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch,
-                     (unsigned short*)p_bf16, nparts);
-  LAUNCH_CHECK(0)
-  return MYO_OK;
+  return adam_apply(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, nparts, p_bf16, nullptr, stream);
+}
+extern "C" int myo_adam_apply_hp(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                                 float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
+                                 uint16_t* p_bf16, float* hp, void* stream) {
+  return adam_apply(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, nparts, p_bf16, hp, stream);
 }
 
 // ------------------------------------------------------------------------------------------ fused MLP PPO step
@@ -1876,7 +1962,7 @@ static MlpWs mlp_carve(unsigned char* base, int B, int OP, int A, long long G) {
   w.H1T = (unsigned short*)take(2 * H * (size_t)B * 2); w.H2T = (unsigned short*)take(2 * H * (size_t)B * 2);
   w.dH1T = (unsigned short*)take(2 * H * (size_t)B * 2); w.dH2T = (unsigned short*)take(2 * H * (size_t)B * 2);
   w.dOT = (unsigned short*)take((size_t)256 * B * 2);
-  w.part = (float*)take((size_t)(2 * A + 3) * (B / MLP_BM) * 4);
+  w.part = (float*)take((size_t)(2 * A + 6) * (B / MLP_BM) * 4);       // (+ 3 columns: approx_kl, clip fraction, entropy loss)
   w.slab = (float*)take((size_t)MLP_SPLITK * G * 4);
   w.advpart = (float*)take(3 * MLP_ADV_BLOCKS * 4);            // slices of the advantage moments
   w.bytes = o;
@@ -1922,7 +2008,7 @@ extern "C" int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream) {
   a.log_std = d->params + d->off_log_std; a.adv_stats = d->adv_stats;
   a.W1p = w.W1p; a.W2 = w.W2; a.W2T = w.W2T; a.Whp = w.Whp; a.WhT = w.WhT; a.bias = w.bias;
   a.XT = w.XT; a.H1T = w.H1T; a.H2T = w.H2T; a.dH1T = w.dH1T; a.dH2T = w.dH2T; a.dOT = w.dOT; a.part = w.part;
-  a.B = B; a.O = O; a.A = A; a.OP = OP; a.NB = B / MLP_BM; a.clip = d->clip; a.vf_coef = d->vf_coef;
+  a.B = B; a.O = O; a.A = A; a.OP = OP; a.NB = B / MLP_BM; a.clip = d->clip; a.vf_coef = d->vf_coef; a.hp = d->hp;
   hipLaunchKernelGGL(k_mlp_fwdbwd, dim3(B / MLP_BM, 2), dim3(256), MLP_FWDBWD_LDS, st, a);
   MlpWgradArgs g;
   g.njobs = 0; g.B = B; g.rows_per_split = B / MLP_SPLITK; g.G = d->G; g.slab = w.slab;
@@ -1941,12 +2027,12 @@ extern "C" int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream) {
     MlpRfArgs rf;
     rf.slab = w.slab; rf.g = d->grads; rf.G = d->G; rf.splits = MLP_SPLITK; rf.part = w.part; rf.acc = d->acc; rf.NB = B / MLP_BM; rf.A = A;
     rf.ent_coef = d->ent_coef; rf.off_log_std = d->off_log_std; rf.off_bh0 = d->off_bh[0]; rf.off_bh1 = d->off_bh[1];
-    rf.sq_part = d->sqnorm_part; rf.adam_step = d->adam_step;
+    rf.sq_part = d->sqnorm_part; rf.adam_step = d->adam_step; rf.hp = d->hp;
     hipLaunchKernelGGL(k_mlp_reduce_finish, dim3(MLP_RF_BLOCKS + 2 * A + 3), dim3(256), 0, st, rf);
   } else {
     hipLaunchKernelGGL(k_mlp_reduce, dim3((unsigned)((d->G + 255) / 256)), dim3(256), 0, st, (const float*)w.slab, d->grads, d->G, MLP_SPLITK);
-    hipLaunchKernelGGL(k_colmajor_finish, dim3(2 * A + 3), dim3(64), 0, st, (const float*)w.part, d->acc, B / MLP_BM, A, d->ent_coef,
-                       d->grads + d->off_log_std, d->grads + d->off_bh[0], d->grads + d->off_bh[1]);
+    hipLaunchKernelGGL(k_colmajor_finish, dim3(2 * A + 3 + (d->hp ? 1 : 0)), dim3(64), 0, st, (const float*)w.part, d->acc, B / MLP_BM, A, d->ent_coef,
+                       d->grads + d->off_log_std, d->grads + d->off_bh[0], d->grads + d->off_bh[1], d->hp);
   }
   LAUNCH_CHECK(0)
   return MYO_OK;

@@ -76,8 +76,13 @@ class PpoMlpDesc(C.Structure):
         ("off_Wh", C.c_int64 * 2), ("off_bh", C.c_int64 * 2), ("off_log_std", C.c_int64),
         ("clip", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("compute_adv_stats", C.c_int32),
         ("adv_stats", C.c_void_p), ("acc", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-        ("sqnorm_part", C.c_void_p), ("adam_step", C.c_void_p),
+        ("sqnorm_part", C.c_void_p), ("adam_step", C.c_void_p), ("hp", C.c_void_p),
     ]
+
+
+# word indices of the PPO hyper-parameter block (MYO_HP_* of include/myobatch.h)
+HP_LR, HP_CLIP, HP_KL_LIMIT, HP_STOP, HP_APPLIED, HP_COUNT, HP_SUM_KL, HP_SUM_CLIPFRAC, HP_SUM_ENTLOSS, HP_LAST_KL, HP_LAST_PL, HP_LAST_VL = range(12)
+HP_WORDS = 16
 
 
 class PpoMlpRolloutDesc(C.Structure):
@@ -159,6 +164,7 @@ class NativeLib:
         if b"MYO_EMU" in L.myo_version():
             return      # the emulation build (test tooling, csrc/emu_host.h) implements the env path only: ENV_PATH_SYMBOLS
         L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp]
+        L.myo_ppo_loss_grad_hp.argtypes = L.myo_ppo_loss_grad.argtypes[:-1] + [vp, vp]
         L.myo_ppo_gather.argtypes = [vp] * 6 + [i32, i32, i32, vp, i32] + [vp] * 7
         L.myo_bias_relu_bf16.argtypes = [vp, vp, i32, i32, i32, vp]
         L.myo_splitk_reduce.argtypes = [vp, i32, vp, i32, i32, i32, vp]
@@ -182,6 +188,8 @@ class NativeLib:
         L.myo_lstm_seq_bwd.argtypes = [vp, C.c_longlong, C.c_longlong] + [vp] * 5 + [i32] * 5 + [vp] * 2
         L.myo_adam_clip_step.argtypes = [vp] * 4 + [i32] + [C.c_float] * 6 + [vp, vp, vp, vp]
         L.myo_adam_apply.argtypes = [vp] * 4 + [i32] + [C.c_float] * 6 + [vp, vp, i32, vp, vp]
+        L.myo_adam_clip_step_hp.argtypes = L.myo_adam_clip_step.argtypes[:-1] + [vp, vp]
+        L.myo_adam_apply_hp.argtypes = L.myo_adam_apply.argtypes[:-1] + [vp, vp]
         L.myo_ppo_mlp_workspace_bytes.restype = C.c_longlong
         L.myo_ppo_mlp_workspace_bytes.argtypes = [i32, i32, i32, i32, C.c_longlong]
         L.myo_ppo_mlp_step.argtypes = [C.POINTER(PpoMlpDesc), vp]
@@ -230,7 +238,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_set_state", "myo_batch_warmstart", "myo_batch_set_bad_state_buffer", "myo_batch_set_task", "myo_batch_get_task", "myo_batch_set_object_group", "myo_batch_object_friction", "myo_batch_bind_constants", "myo_batch_tune_wrap_order", "myo_batch_forward_dump",
     "myo_batch_dump_size", "myo_batch_dump_offset", "myo_batch_kernel_ms",
     "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
-    "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_clip_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_adam_apply", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_last_error", "myo_version",
+    "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_clip_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_adam_apply", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_ppo_loss_grad_hp", "myo_adam_clip_step_hp", "myo_adam_apply_hp", "myo_last_error", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
 ]
 

@@ -138,6 +138,21 @@ def flatten_parameters(policy, pad: int = 64):
     return policy._flat
 
 
+def hp_record_torch(hp, pl, vl, kl, cf, el):
+    """The bookkeeping the loss-finishing HIP kernels do in the PPO hyper-parameter block (include/myobatch.h: myo_hp_record of
+    csrc/myobatch.hip), as capturable torch ops — for the loss stages that are torch (gSDE, the autograd recurrent graph)."""
+    from ..native import HP_COUNT, HP_KL_LIMIT, HP_LAST_KL, HP_LAST_VL, HP_STOP, HP_SUM_ENTLOSS, HP_SUM_KL
+    hi = hp.view(torch.int32)
+    live = hi[HP_STOP] == 0
+    zero = torch.zeros((), device=hp.device)
+    hp[HP_SUM_KL:HP_SUM_ENTLOSS + 1].add_(torch.where(live, torch.stack([kl, cf, el]).float(), zero))
+    hi[HP_COUNT].add_(live.to(torch.int32))
+    last = hp[HP_LAST_KL:HP_LAST_VL + 1]
+    last.copy_(torch.where(live, torch.stack([kl, pl, vl]).float(), last))
+    lim = hp[HP_KL_LIMIT]
+    hi[HP_STOP].bitwise_or_((live & (lim > 0) & (kl > lim)).to(torch.int32))
+
+
 class FlatAdam:
     """clip_grad_norm_ + Adam over the flat vector in libmyobatch (2 launches, capturable)."""
 
@@ -150,6 +165,7 @@ class FlatAdam:
         self.sq = torch.zeros(512, device=dev)   # partial sums of |g|^2 (64 of myo_adam_clip_step, or those myo_ppo_mlp_step leaves)
         self.presummed = 0        # > 0: the gradient's producer has left that many partial sums in `sq` and advanced the step counter
         self.shadow = None        # bf16 copy of the flat parameters kept in step by the Adam kernel (FusedPPOStep sets it)
+        self.hp = None            # PPO hyper-parameter block (include/myobatch.h): lr and the stop flag are read from it at run time
 
     @property
     def step_count(self):
@@ -163,6 +179,18 @@ class FlatAdam:
         f = self.flat
         stream = torch.cuda.current_stream(f["p"].device).cuda_stream
         p = lambda t: C.c_void_p(t.data_ptr())
+        if self.hp is not None:
+            sh = p(self.shadow) if self.shadow is not None else None
+            if self.presummed > 0:
+                self.lib.check(self.lib.L.myo_adam_apply_hp(
+                    p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
+                    self.eps, self.max_norm, float(grad_scale), p(self._step), p(self.sq), int(self.presummed), sh, p(self.hp),
+                    C.c_void_p(stream)))
+            else:
+                self.lib.check(self.lib.L.myo_adam_clip_step_hp(
+                    p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
+                    self.eps, self.max_norm, float(grad_scale), p(self._step), p(self.sq), sh, p(self.hp), C.c_void_p(stream)))
+            return
         if self.presummed > 0:      # single-rank fused step: myo_ppo_mlp_step has done the squares and the step counter
             self.lib.check(self.lib.L.myo_adam_apply(
                 p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
@@ -226,6 +254,7 @@ class FusedPPOStep:
         self._mfma = {}                      # per minibatch size: (descriptor, workspace) of myo_ppo_mlp_step
         self.use_mfma_step = True            # the one-launch-per-stage path (csrc/myo_ppo_mlp.h) whenever the shapes fit
         self.adam = None                     # FlatAdam whose |g|^2 partials / step counter the fused step fills (single rank; PPO sets it)
+        self.hp = None                       # PPO hyper-parameter block (include/myobatch.h): clip_range read at run time, diagnostics, KL stop
 
     # ---- fused forward / loss / backward on the matrix cores (libmyobatch: myo_ppo_mlp_step)
     def _mfma_desc(self, B, obs_all, act_all, oldlp_all, adv_all, ret_all, idx):
@@ -252,6 +281,7 @@ class FusedPPOStep:
             d = hit[0]
             if d is not None:
                 d.obs, d.act, d.oldlp, d.adv, d.ret, d.idx = (t.data_ptr() for t in (obs_all, act_all, oldlp_all, adv_all, ret_all, idx))
+                d.hp = self.hp.data_ptr() if self.hp is not None else None
             return d
         nbytes = self.lib.L.myo_ppo_mlp_workspace_bytes(B, O, self.A, hid, G)
         if nbytes <= 0:
@@ -272,6 +302,7 @@ class FusedPPOStep:
         d.clip, d.vf_coef, d.ent_coef = self.clip, self.vf, self.ent
         d.adv_stats, d.acc = self.stats.data_ptr(), self.acc.data_ptr()
         d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
+        d.hp = self.hp.data_ptr() if self.hp is not None else None
         if self.adam is not None and self.lib.L.myo_ppo_mlp_sqnorm_parts(self.A) <= self.adam.sq.numel():
             d.sqnorm_part, d.adam_step = self.adam.sq.data_ptr(), self.adam._step.data_ptr()
         self._mfma[key] = (d, ws)
@@ -408,9 +439,15 @@ class FusedPPOStep:
         d = direct or (None, None, None)
         dev = mean.device
         dmean, dvalue = torch.empty((B, A), device=dev), torch.empty(B, device=dev)
-        work = self._workbuf("loss", ((B + 63) // 64) * (2 * A + 3))
+        work = self._workbuf("loss", ((B + 63) // 64) * (2 * A + 6))
         stream = torch.cuda.current_stream(dev).cuda_stream
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if self.hp is not None:
+            self.lib.check(self.lib.L.myo_ppo_loss_grad_hp(
+                p(mean), p(values), p(actions), p(old_logp), p(adv), p(returns), p(pol.log_std.data), p(self.stats),
+                B, A, self.clip, self.vf, p(dmean), p(dvalue), p(self.acc), p(dmean_h), p(dvalue_h), p(work), in_bf16, self.ent,
+                p(d[0]), p(d[1]), p(d[2]), p(self.hp), C.c_void_p(stream)))
+            return dmean, dvalue
         self.lib.check(self.lib.L.myo_ppo_loss_grad(
             p(mean), p(values), p(actions), p(old_logp), p(adv), p(returns), p(pol.log_std.data), p(self.stats),
             B, A, self.clip, self.vf, p(dmean), p(dvalue), p(self.acc), p(dmean_h), p(dvalue_h), p(work), in_bf16, self.ent,
@@ -434,8 +471,12 @@ class FusedPPOStep:
         logp = (-0.5 * z2 / var - 0.5 * torch.log(var)).sum(-1) - 0.5 * A * math.log(2 * math.pi)
         advn = (adv - self.stats[0]) / (self.stats[1] + 1e-8)
         ratio = torch.exp(logp - old_logp)
-        s1, s2 = advn * ratio, advn * torch.clamp(ratio, 1 - self.clip, 1 + self.clip)
-        inside = (ratio > 1 - self.clip) & (ratio < 1 + self.clip)
+        clip = self.clip
+        if self.hp is not None:            # clip_range from the hyper-parameter block: a captured graph follows its schedule
+            from ..native import HP_CLIP
+            clip = self.hp[HP_CLIP]
+        s1, s2 = advn * ratio, advn * torch.clamp(ratio, 1 - clip, 1 + clip)
+        inside = (ratio > 1 - clip) & (ratio < 1 + clip)
         dlogp = -(advn * ratio) * torch.where(s1 <= s2, torch.ones_like(ratio), inside.to(ratio.dtype)) / B
         dmean = dlogp.unsqueeze(-1) * diff / var
         dvar = dlogp.unsqueeze(-1) * (0.5 * z2 / (var * var) - 0.5 / var) - (self.ent / B) * 0.5 / var      # entropy: sum_a 0.5 log var + const
@@ -448,6 +489,11 @@ class FusedPPOStep:
         self.acc[A + 1].copy_(sums[1] / B)
         pi_head.bias.grad.copy_(_colsum(dmean))
         vf_head.bias.grad.copy_(_colsum(dvalue.unsqueeze(-1)))
+        if self.hp is not None:            # diagnostics and the KL stop (per-sample entropy sum_a 0.5 log var + const)
+            lr_ = logp - old_logp
+            ent = (0.5 * torch.log(var)).sum(-1) + 0.5 * A * (1.0 + math.log(2 * math.pi))
+            d3 = _colsum(torch.stack([(ratio - 1) - lr_, (torch.abs(ratio - 1) > clip).float(), -ent], -1)) / B
+            hp_record_torch(self.hp, self.acc[A], self.acc[A + 1], d3[0], d3[1], d3[2])
         return dmean.to(torch.bfloat16), dvalue.to(torch.bfloat16).unsqueeze(-1)
 
     @torch.no_grad()

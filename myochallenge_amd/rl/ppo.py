@@ -46,6 +46,21 @@ class PPOConfig:
     # the build machine does not have — a capture failure there must not cost the scaling run.  Falls back to the eager
     # collective when the capture raises.
     graph_allreduce: bool = False
+    # SB3 schedules f(progress_remaining) -> value, evaluated by train() once per update; learning_rate / clip_range above stay
+    # plain floats (the schedules' values at progress 1.0, or the constants when there is no schedule)
+    lr_schedule: Optional[Callable] = None
+    clip_range_schedule: Optional[Callable] = None
+    # SB3's KL early stop: a minibatch whose approx_kl exceeds 1.5 * target_kl is not applied and ends the update
+    target_kl: Optional[float] = None
+    clip_range_vf: Optional[float] = None   # value-function clipping is not implemented: anything but None is refused
+
+    def __post_init__(self):
+        if self.clip_range_vf is not None:
+            raise NotImplementedError("clip_range_vf (value-function clipping) is not implemented; leave it None")
+        if self.lr_schedule is not None:
+            self.learning_rate = float(self.lr_schedule(1.0))
+        if self.clip_range_schedule is not None:
+            self.clip_range = float(self.clip_range_schedule(1.0))
 
 
 def compute_gae(rewards, values, episode_starts, last_values, last_dones, gamma, lam):
@@ -83,6 +98,9 @@ class PPO:
         self.device = env.device
         self.policy.to(self.device)
         on_gpu = self.device.type == "cuda"
+        if cfg.target_kl is not None and (cfg.graph_allreduce or os.environ.get("MYO_GRAPH_ALLREDUCE") == "1"):
+            raise ValueError("target_kl needs the host between gradient and optimizer step on N > 1 ranks (the all-reduced approx_kl "
+                             "decides): it cannot be combined with graph_allreduce")
         if not policy.recurrent and (cfg.n_steps * env.num_envs) % min(cfg.batch_size, cfg.n_steps * env.num_envs):
             # SB3 warns here too and then trains on the truncated last minibatch of each epoch; every update path of this
             # class works on fixed-size minibatches (one captured graph) and SKIPS that remainder instead
@@ -130,6 +148,20 @@ class PPO:
                     self._fused_rec.adam_syncs_shadow = True
                     self._fused_rec.refresh_shadow()
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        # the device-resident hyper-parameter block of the fused update paths (layout: include/myobatch.h): lr, clip_range, KL limit,
+        # stop flag, applied-step count and the diagnostics' sums.  train() writes it before every update, outside the graphs.
+        self._hp = None
+        if self._flat_adam is not None:
+            from ..native import HP_WORDS
+            self._hp = torch.zeros(HP_WORDS, device=self.device)
+            self._flat_adam.hp = self._hp
+            for fused in (self._fused, self._fused_rec):
+                if fused is not None:
+                    fused.hp = self._hp
+        self._current_progress_remaining = 1.0
+        self._total_timesteps = None
+        self._lr_now, self._clip_now = float(cfg.learning_rate), float(cfg.clip_range)
+        self._hp_write()                 # (a minibatch step run before the first train(), as the tests do, reads the block too)
         if self._fused is not None and self._flat_adam is not None and self.world == 1 and os.environ.get("MYO_ADAM_SEPARATE") != "1":
             self._fused.adam = self._flat_adam   # nothing is exchanged between gradient and clip: the fused step also squares the gradient
         self.rank = dist.get_rank() if self.world > 1 else 0
@@ -613,17 +645,94 @@ class PPO:
                 mean, std = adv.mean(), adv.std()
             adv = (adv - mean) / (std + 1e-8)
         ratio = torch.exp(logp - old_logp)
-        pl = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - cfg.clip_range, 1 + cfg.clip_range)).mean()
+        if self._hp is not None:     # (the autograd recurrent graph: clip_range from the hyper-parameter block, read at replay time)
+            from ..native import HP_CLIP
+            clip = self._hp[HP_CLIP]
+        else:
+            clip = self._clip_now
+        pl = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - clip, 1 + clip)).mean()
         vl = torch.nn.functional.mse_loss(values, returns)
         ent = entropy.mean() if torch.is_tensor(entropy) and entropy.dim() > 0 else entropy      # gSDE: per sample
+        with torch.no_grad():        # SB3's diagnostics of the minibatch: approx_kl, clip_fraction, entropy_loss
+            log_ratio = logp - old_logp
+            kl = ((torch.exp(log_ratio) - 1) - log_ratio).mean()
+            cf = (torch.abs(ratio - 1) > clip).float().mean()
+            el = -torch.as_tensor(ent, device=kl.device).detach().float()
+            self._last_diag = (kl, cf, el)
+            if self._hp is not None:
+                from .fused_mlp import hp_record_torch
+                hp_record_torch(self._hp, pl.detach(), vl.detach(), kl, cf, el)
         return pl + cfg.ent_coef * (-ent) + cfg.vf_coef * vl, pl.detach(), vl.detach()
 
+    # ---------------------------------------------------------------- schedules, KL stop, diagnostics
+    def _update_hyper(self):
+        """learning_rate / clip_range of this update from the schedules at the current progress_remaining, written everywhere an update
+        path reads them: the torch optimiser, FlatAdam, the fused steps' launch scalars and the hyper-parameter block (one small
+        asynchronous copy that also clears the stop flag, the applied count and the diagnostics)."""
+        cfg = self.cfg
+        prog = self._current_progress_remaining
+        self._lr_now = float(cfg.lr_schedule(prog)) if cfg.lr_schedule is not None else float(cfg.learning_rate)
+        self._clip_now = float(cfg.clip_range_schedule(prog)) if cfg.clip_range_schedule is not None else float(cfg.clip_range)
+        for group in self.optimizer.param_groups:
+            group["lr"] = self._lr_now
+        if self._flat_adam is not None:
+            self._flat_adam.lr = self._lr_now
+        for fused in (self._fused, self._fused_rec):
+            if fused is not None:
+                fused.clip = self._clip_now
+        self._hp_write()
+
+    def _hp_write(self):
+        if self._hp is not None:
+            from ..native import HP_WORDS
+            cfg = self.cfg
+            # N > 1 ranks decide on the all-reduced approx_kl on the host (between the two graphs): no limit on the device
+            limit = 1.5 * cfg.target_kl if (cfg.target_kl is not None and self.world == 1) else 0.0
+            self._hp.copy_(torch.tensor([self._lr_now, self._clip_now, limit] + [0.0] * (HP_WORDS - 3)), non_blocking=True)
+
+    def _hp_new_epoch(self):
+        """The diagnostics are means over the minibatches of the last epoch run: their sums start again with every epoch."""
+        from ..native import HP_COUNT, HP_SUM_ENTLOSS
+        self._hp[HP_COUNT:HP_SUM_ENTLOSS + 1].zero_()
+
+    def _hp_stopped(self) -> bool:
+        """The stop flag of the hyper-parameter block: one 4-byte copy to the host (only ever called with target_kl set)."""
+        from ..native import HP_STOP
+        return bool(self._hp[HP_STOP:HP_STOP + 1].view(torch.int32).cpu().item())
+
+    def _kl_exceeded(self, kl) -> bool:
+        """SB3's `approx_kl > 1.5 * target_kl` on the host (eager paths; N > 1 ranks: on the rank mean, so every rank stops at the
+        same step)."""
+        if self.cfg.target_kl is None:
+            return False
+        if self.world > 1:
+            kl = kl.detach().clone().reshape(1)
+            dist.all_reduce(kl)
+            kl = kl / self.world
+        return float(kl) > 1.5 * self.cfg.target_kl
+
+    def _kl_exceeded_ranks(self) -> bool:
+        """N > 1 ranks on a fused path: the approx_kl the loss kernel has just recorded, all-reduced (mean), against the limit."""
+        from ..native import HP_LAST_KL
+        return self._kl_exceeded(self._hp[HP_LAST_KL])
+
     def train(self) -> Dict[str, float]:
+        """One PPO update on the current rollout (SB3 PPO.train / sb3-contrib RecurrentPPO.train [3P-RECALL]): learning_rate and
+        clip_range from their schedules at the current progress_remaining; with target_kl, a minibatch whose approx_kl =
+        mean((ratio - 1) - log ratio) exceeds 1.5 * target_kl is NOT applied and ends the update, its remaining epochs included.
+
+        Returns policy_loss / value_loss (last minibatch processed), n_updates (optimizer steps applied so far), approx_kl,
+        clip_fraction and entropy_loss — all three MEANS OVER THE MINIBATCHES PROCESSED IN THE LAST EPOCH RUN, the minibatch that
+        stopped the update included (SB3 resets approx_kl per epoch too, but averages the other two over all epochs) —
+        explained_variance (1 - Var(returns - values) / Var(returns) over the rollout buffer), the learning_rate and clip_range used,
+        and early_stopped.  On the fused paths the three means come from the hyper-parameter block's sums."""
         cfg, pol = self.cfg, self.policy
         T, N = cfg.n_steps, self.env.num_envs
+        self._update_hyper()
         adv, ret = compute_gae(self.rew_buf, self.val_buf, self.start_buf, self._last_values,
                                self._last_starts, cfg.gamma, cfg.gae_lambda)
         stats = {}
+        self._early_stopped, diag = False, []
         if self._fused is not None:
             pl, vl = self._train_graphed(adv, ret)
         elif not pol.recurrent:
@@ -632,24 +741,32 @@ class PPO:
             oldlp, advf, retf = self.logp_buf.view(B), adv.view(B), ret.view(B)
             bs = min(cfg.batch_size, B)
             for _ in range(cfg.n_epochs):
+                diag = []
                 perm = torch.randperm(B, generator=self.gen, device=self.device)
                 for s in range(0, B - bs + 1, bs):
                     idx = perm[s:s + bs]
                     with self._autocast():
                         v, lp, ent = pol.evaluate_actions(obs[idx], act[idx])
                     loss, pl, vl = self._loss(v, lp, ent, oldlp[idx], advf[idx], retf[idx])
+                    diag.append(torch.stack(self._last_diag))
+                    if self._kl_exceeded(self._last_diag[0]):
+                        self._early_stopped = True
+                        break
                     self.optimizer.zero_grad(set_to_none=True)
                     loss.backward()
                     self._allreduce_grads()
                     torch.nn.utils.clip_grad_norm_(pol.parameters(), cfg.max_grad_norm)
                     self.optimizer.step()
                     self.n_updates += 1
+                if self._early_stopped:
+                    break
         elif self._flat_adam is not None:
             pl, vl = self._train_recurrent_graphed(adv, ret)
         else:
             # sequences = whole rollouts of a subset of envs, initial LSTM state = state at rollout start
             envs_per_mb = max(1, min(N, cfg.batch_size // T))
             for _ in range(cfg.n_epochs):
+                diag = []
                 perm = torch.randperm(N, generator=self.gen, device=self.device)
                 for s in range(0, N - envs_per_mb + 1, envs_per_mb):
                     idx = perm[s:s + envs_per_mb]
@@ -659,13 +776,37 @@ class PPO:
                                                           self.start_buf[:, idx])
                     loss, pl, vl = self._loss(v.reshape(-1), lp.reshape(-1), ent, self.logp_buf[:, idx].reshape(-1),
                                               adv[:, idx].reshape(-1), ret[:, idx].reshape(-1))
+                    diag.append(torch.stack(self._last_diag))
+                    if self._kl_exceeded(self._last_diag[0]):
+                        self._early_stopped = True
+                        break
                     self.optimizer.zero_grad(set_to_none=True)
                     loss.backward()
                     self._allreduce_grads()
                     torch.nn.utils.clip_grad_norm_(pol.parameters(), cfg.max_grad_norm)
                     self.optimizer.step()
                     self.n_updates += 1
-        stats.update(policy_loss=float(pl), value_loss=float(vl), n_updates=self.n_updates)
+                if self._early_stopped:
+                    break
+        if self._hp is not None:        # fused paths: the block's sums, ONE copy to the host (it also carries pl / vl)
+            from ..native import HP_APPLIED, HP_COUNT, HP_LAST_PL, HP_LAST_VL, HP_STOP, HP_SUM_KL
+            hp = self._hp.cpu()
+            hi = hp.view(torch.int32)
+            cnt = max(1, int(hi[HP_COUNT]))
+            kl, cf, el = (float(x) / cnt for x in hp[HP_SUM_KL:HP_SUM_KL + 3])
+            if cfg.target_kl is not None:
+                if self.world == 1:
+                    self.n_updates += int(hi[HP_APPLIED])
+                    self._early_stopped = bool(hi[HP_STOP])
+                pl, vl = hp[HP_LAST_PL], hp[HP_LAST_VL]       # (of the last minibatch processed: later replayed steps changed nothing)
+        else:
+            kl, cf, el = (float(x) for x in torch.stack(diag).mean(0)) if diag else (float("nan"),) * 3
+        y, err = ret.reshape(-1), (ret - self.val_buf).reshape(-1)
+        var_y = float(y.var(unbiased=False))
+        ev = float("nan") if var_y == 0 else 1.0 - float(err.var(unbiased=False)) / var_y       # SB3 utils.explained_variance
+        stats.update(policy_loss=float(pl), value_loss=float(vl), n_updates=self.n_updates, approx_kl=kl, clip_fraction=cf,
+                     entropy_loss=el, explained_variance=ev, learning_rate=self._lr_now, clip_range=self._clip_now,
+                     early_stopped=self._early_stopped)
         return stats
 
     # ---------------------------------------------------------------- hipGraph-captured minibatch step
@@ -770,26 +911,38 @@ class PPO:
             self._graph = None
         if self._graph != (B, bs):
             self._build_graphs(B, bs)
+            self._hp_write()             # (the capture's warm-up steps have left their marks in the block)
         g = self._gs
         g["adv"].copy_(adv.view(B)); g["ret"].copy_(ret.view(B))
         if not cfg.normalize_advantage:
             self._fused.stats.copy_(torch.tensor([0.0, 1.0], device=self.device))
         if getattr(self, "_graph_epoch", None) is not None and not ext:
             k, n_mb = self._epoch_chunk, B // bs
+            tkl = cfg.target_kl is not None      # then: the stop flag is read once per chunk replay / epoch (n_updates: from the block)
+            stopped = False
             for _ in range(cfg.n_epochs):
+                self._hp_new_epoch()
                 perm = torch.randperm(B, generator=self.gen, device=self.device)
                 done = 0
-                while n_mb - done >= k:                        # whole chunks: one replay each
+                while n_mb - done >= k and not stopped:        # whole chunks: one replay each
                     g["perm"].copy_(perm[done * bs:(done + k) * bs])
                     self._graph_epoch.replay()
                     done += k
-                for j in range(done, n_mb):                    # what is left of the epoch: the per-step graph
-                    g["idx"].copy_(perm[j * bs:(j + 1) * bs])
-                    self._graph_fb.replay()
-                self.n_updates += n_mb
+                    stopped = tkl and done < n_mb and self._hp_stopped()
+                if not stopped:
+                    for j in range(done, n_mb):                # what is left of the epoch: the per-step graph
+                        g["idx"].copy_(perm[j * bs:(j + 1) * bs])
+                        self._graph_fb.replay()
+                    stopped = tkl and self._hp_stopped()
+                if not tkl:
+                    self.n_updates += n_mb
+                if stopped:
+                    break
             self._fused.refresh_shadow()
             return g["pl"], g["vl"]
+        tkl, stopped = cfg.target_kl is not None, False
         for _ in range(cfg.n_epochs):
+            self._hp_new_epoch()
             perm = torch.randperm(B, generator=self.gen, device=self.device)
             for s in range(0, B - bs + 1, bs):
                 g["idx"].copy_(perm[s:s + bs])
@@ -803,6 +956,9 @@ class PPO:
                 self._graph_fb.replay()
                 if self.world > 1 and not self._allreduce_in_graph:
                     dist.all_reduce(self._flat_grad, op=dist.ReduceOp.SUM)
+                    if tkl and self._kl_exceeded_ranks():      # the decision between the two graphs: this step is not applied
+                        self._early_stopped = stopped = True
+                        break
                     if self._dp_check:
                         self._dp_compare("gradient after the all-reduce", self._flat_grad)
                         self._dp_compare("parameters before the optimizer step", self._flat_adam.flat["p"])
@@ -814,7 +970,12 @@ class PPO:
                         self._dp_compare("gradient after the optimizer step", self._flat_grad)
                         self._dp_compare("|g|^2 partial sums", self._flat_adam.sq[:64].contiguous())
                         self._dp_compare("parameters after the optimizer step", self._flat_adam.flat["p"])
-                self.n_updates += 1
+                if not (tkl and self.world == 1):              # (one rank with target_kl: the block's applied count, see train)
+                    self.n_updates += 1
+            if tkl and self.world == 1 and not stopped:        # steps after a stop changed nothing: one read per epoch
+                stopped = self._hp_stopped()
+            if stopped:
+                break
         self._fused.refresh_shadow()     # rollout inference reads the bf16 shadow weights
         return g["pl"], g["vl"]
 
@@ -888,6 +1049,7 @@ class PPO:
                 self._rgraph = None
         if getattr(self, "_rgraph", None) != (T, N, m):
             self._build_recurrent_graphs(T, N, m)
+            self._hp_write()             # (the capture's warm-up steps have left their marks in the block)
         g = self._rg
         g["adv"].copy_(adv); g["ret"].copy_(ret)
         for dst, src in zip(g["state0"], self._rollout_state0):
@@ -908,7 +1070,9 @@ class PPO:
         T, N = cfg.n_steps, self.env.num_envs
         m = max(1, min(N, cfg.batch_size // T))
         g, fr = self._rec_stage(adv, ret, T, N, m), self._fused_rec
+        tkl, stopped = cfg.target_kl is not None, False
         for _ in range(cfg.n_epochs):
+            self._hp_new_epoch()
             perm = torch.randperm(N, generator=self.gen, device=self.device)
             for s in range(0, N - m + 1, m):
                 g["idx"].copy_(perm[s:s + m])
@@ -922,8 +1086,16 @@ class PPO:
                 self._rgraph_fb.replay()
                 if self.world > 1:
                     dist.all_reduce(self._flat_grad, op=dist.ReduceOp.SUM)
+                    if tkl and self._kl_exceeded_ranks():      # the decision between the two graphs: this step is not applied
+                        self._early_stopped = stopped = True
+                        break
                     self._rgraph_ap.replay()
-                self.n_updates += 1
+                if not (tkl and self.world == 1):
+                    self.n_updates += 1
+            if tkl and self.world == 1 and not stopped:        # steps after a stop changed nothing: one read per epoch
+                stopped = self._hp_stopped()
+            if stopped:
+                break
         return g["pl"], g["vl"]
 
     # ---------------------------------------------------------------- persistence (SB3 zip layout)
@@ -984,6 +1156,9 @@ class PPO:
         cfg = self.cfg
         hyper = {k: getattr(cfg, k) for k in ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "ent_coef", "vf_coef",
                                               "max_grad_norm", "learning_rate", "clip_range", "normalize_advantage")}
+        # schedules are pickled as constant functions of their CURRENT value, next to the progress they were evaluated at
+        hyper.update(learning_rate=self._lr_now, clip_range=self._clip_now, target_kl=cfg.target_kl,
+                     _current_progress_remaining=float(self._current_progress_remaining))
         last = self._last_obs.detach().cpu().numpy() if self._last_obs is not None else None
         orig = getattr(self.env, "old_obs", None)
         save_sb3_zip(path, self.policy, hyper, n_envs=self.env.num_envs, num_timesteps=self.num_timesteps, n_updates=self.n_updates,
@@ -1005,8 +1180,11 @@ class PPO:
         Logged: time/fps, time/total_timesteps, rollout/ep_rew_mean and rollout/ep_len_mean (last 100 finished episodes, raw returns:
         SB3's Monitor / ep_info_buffer semantics), train/*."""
         t_start = time.time()
+        self._total_timesteps = total_timesteps
         while self.num_timesteps < total_timesteps:
             self.collect_rollouts()
+            # SB3 1.6.2 _update_current_progress_remaining [3P-RECALL]: after the rollout, before train()
+            self._current_progress_remaining = 1.0 - float(self.num_timesteps) / float(total_timesteps)
             if callback is not None:
                 callback(self)
             stats = self.train()

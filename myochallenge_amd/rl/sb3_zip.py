@@ -134,7 +134,7 @@ def save_sb3_zip(path: str, policy: ActorCriticPolicy, hyper: Dict[str, Any], *,
                                          "<class 'numpy.ndarray'>"),
             "_last_original_obs": _ser(zeros_obs.astype(np.float64) if last_original_obs is None else np.asarray(last_original_obs, np.float64),
                                        "<class 'numpy.ndarray'>"),
-            "_episode_num": 0, "use_sde": bool(getattr(policy, "use_sde", False)), "sde_sample_freq": -1, "_current_progress_remaining": 0.0,
+            "_episode_num": 0, "use_sde": bool(getattr(policy, "use_sde", False)), "sde_sample_freq": -1, "_current_progress_remaining": float(hyper.get("_current_progress_remaining", 0.0)),
             "ep_info_buffer": _ser(collections.deque(maxlen=100), "<class 'collections.deque'>"),
             "ep_success_buffer": _ser(collections.deque(maxlen=100), "<class 'collections.deque'>"),
             "_n_updates": int(n_updates), "n_steps": int(hyper.get("n_steps", 256)), "gamma": float(hyper.get("gamma", 0.99)),
@@ -142,7 +142,7 @@ def save_sb3_zip(path: str, policy: ActorCriticPolicy, hyper: Dict[str, Any], *,
             "vf_coef": float(hyper.get("vf_coef", 0.5)), "max_grad_norm": float(hyper.get("max_grad_norm", 0.5)),
             "batch_size": int(hyper.get("batch_size", 64)), "n_epochs": int(hyper.get("n_epochs", 10)),
             "clip_range": _ser((lambda v: (lambda _: v))(clip), "<class 'function'>"), "clip_range_vf": None,
-            "normalize_advantage": bool(hyper.get("normalize_advantage", True)), "target_kl": None,
+            "normalize_advantage": bool(hyper.get("normalize_advantage", True)), "target_kl": hyper.get("target_kl"),
         }
         if recurrent:
             data["_last_lstm_states"] = _ser(lstm_states, "<class 'sb3_contrib.common.recurrent.type_aliases.RNNStates'>")

@@ -5,7 +5,8 @@ The reference wraps sb3-contrib's ``RecurrentPPO``: ``_init_agent`` either loads
 new ``RecurrentPPO("MlpLstmPolicy", envs, verbose=2, tensorboard_log=log_dir, **model_config)``; ``train``
 calls ``agent.learn(total_timesteps, callback=callbacks, reset_num_timesteps=True)``; ``save`` writes
 ``final_model.pkl`` (a model zip, despite the suffix) and ``final_env.pkl``.  ``model_config`` keys are SB3's
-constructor keywords; callables (``lambda _: 5e-05``) are evaluated at progress 1.0 like SB3 schedules.
+constructor keywords; callables (``lambda _: 5e-05``, ``lambda p: 3e-4 * p``) are SB3 schedules of progress_remaining and
+reach the agent as such (``PPOConfig.lr_schedule`` / ``clip_range_schedule``); ``target_kl`` is the agent's KL early stop.
 One addition: ``model_config["policy"] = "MlpPolicy"`` selects the MLP actor-critic (the hipGraph fast
 path); the default stays ``"MlpLstmPolicy"``.
 """
@@ -21,12 +22,11 @@ from ..rl.ppo import PPO, PPOConfig
 
 _PPO_KEYS = ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "ent_coef", "vf_coef", "max_grad_norm",
              "normalize_advantage")
-_IGNORED = ("verbose", "tensorboard_log", "device", "lr_schedule", "clip_range_vf", "target_kl", "sde_sample_freq",
-            "create_eval_env", "_init_setup_model")
+_IGNORED = ("verbose", "tensorboard_log", "device", "sde_sample_freq", "create_eval_env", "_init_setup_model")
 
 
 def _const(v):
-    """SB3 accepts floats or schedules f(progress_remaining); the reference only ever passes constants."""
+    """SB3 accepts floats or schedules f(progress_remaining): the value at the start of training (progress 1.0)."""
     return float(v(1.0)) if callable(v) else float(v)
 
 
@@ -55,10 +55,14 @@ class MyoTrainer:
         kw = {k: base[k] for k in _PPO_KEYS if k in base}
         kw.update({k: mc[k] for k in _PPO_KEYS if k in mc})
         lr = mc.get("learning_rate", mc.get("lr_schedule", base.get("learning_rate", 3e-4)))
-        kw["learning_rate"] = _const(lr)
-        kw["clip_range"] = _const(mc.get("clip_range", base.get("clip_range", 0.2)))
-        unknown = [k for k in mc if k not in _PPO_KEYS + _IGNORED + ("learning_rate", "clip_range", "policy", "policy_kwargs",
-                                                                    "seed", "use_sde")]
+        clip = mc.get("clip_range", base.get("clip_range", 0.2))
+        kw["learning_rate"], kw["clip_range"] = _const(lr), _const(clip)
+        kw["lr_schedule"] = lr if callable(lr) else None              # schedules stay schedules: PPO.train evaluates them per update
+        kw["clip_range_schedule"] = clip if callable(clip) else None
+        kw["target_kl"] = mc.get("target_kl")
+        kw["clip_range_vf"] = mc.get("clip_range_vf")                 # (PPOConfig refuses anything but None)
+        unknown = [k for k in mc if k not in _PPO_KEYS + _IGNORED + ("learning_rate", "lr_schedule", "clip_range", "clip_range_vf",
+                                                                    "target_kl", "policy", "policy_kwargs", "seed", "use_sde")]
         if unknown:
             raise TypeError(f"unexpected model_config keys {unknown}")
         return PPOConfig(**kw)

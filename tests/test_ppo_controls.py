@@ -1,0 +1,415 @@
+"""PPO controls of stable-baselines3 on every update path: learning_rate / clip_range schedules, the target_kl early stop and
+the train/* diagnostics (approx_kl, clip_fraction, entropy_loss, explained_variance, learning_rate, clip_range).
+
+CPU tests run the eager paths against a plain-torch restatement of SB3's train(); GPU tests run the fused MLP / fused recurrent
+steps, whose lr, clip_range, stop flag and diagnostics live in the device-resident hyper-parameter block (include/myobatch.h)."""
+import copy
+import math
+
+import pytest
+import torch
+
+from helpers import make_env
+from myochallenge_amd import native
+from myochallenge_amd.rl.policy import ActorCriticPolicy
+from myochallenge_amd.rl.ppo import PPO, PPOConfig, compute_gae
+from myochallenge_amd.rl.vec_normalize import VecNormalize
+
+KL_DELTA = 0.5
+KL_OF_DELTA = math.exp(KL_DELTA) - 1 - KL_DELTA          # approx_kl of a minibatch whose every log ratio is KL_DELTA: 0.1487
+
+
+# ------------------------------------------------------------------------------------------------ SB3 restatement (plain torch)
+def sb3_train(algo, policy, lr, clip, target_kl, gen):
+    """SB3 PPO.train / sb3-contrib RecurrentPPO.train [3P-RECALL] on algo's rollout buffers with a policy copy and the minibatch
+    permutations of `gen`: per-minibatch advantage normalisation, clipped surrogate + vf_coef * MSE + ent_coef * entropy loss,
+    approx_kl = mean((ratio - 1) - log ratio) checked against 1.5 * target_kl BEFORE the step, clip_grad_norm_, Adam(eps=1e-5).
+    The MLP minibatches are rows of the flattened buffer; the recurrent ones whole rollouts of a subset of envs (this project's
+    sequences: nothing is padded, so the mean over the unmasked entries is the mean).  Returns what it recorded."""
+    cfg = algo.cfg
+    T, N = cfg.n_steps, algo.env.num_envs
+    adv, ret = compute_gae(algo.rew_buf, algo.val_buf, algo.start_buf, algo._last_values, algo._last_starts, cfg.gamma, cfg.gae_lambda)
+    opt = torch.optim.Adam(policy.parameters(), lr=lr, eps=1e-5)
+    rec = policy.recurrent
+    n_items, per = (N, max(1, min(N, cfg.batch_size // T))) if rec else (T * N, min(cfg.batch_size, T * N))
+    out = {"kls": [], "n_updates": 0, "stopped_at": None}
+    for epoch in range(cfg.n_epochs):
+        kls, cfs = [], []
+        perm = torch.randperm(n_items, generator=gen)
+        for j, s in enumerate(range(0, n_items - per + 1, per)):
+            idx = perm[s:s + per]
+            if rec:
+                st0 = tuple(x[:, idx] for x in algo._rollout_state0)
+                v, lp, ent = policy.evaluate_actions(algo.obs_buf[:, idx], algo.act_buf[:, idx], st0, algo.start_buf[:, idx])
+                v, lp = v.reshape(-1), lp.reshape(-1)
+                old, a, r = algo.logp_buf[:, idx].reshape(-1), adv[:, idx].reshape(-1), ret[:, idx].reshape(-1)
+            else:
+                v, lp, ent = policy.evaluate_actions(algo.obs_buf.view(T * N, -1)[idx], algo.act_buf.view(T * N, -1)[idx])
+                old, a, r = algo.logp_buf.view(-1)[idx], adv.view(-1)[idx], ret.view(-1)[idx]
+            a = (a - a.mean()) / (a.std() + 1e-8)
+            ratio = torch.exp(lp - old)
+            pl = -torch.min(a * ratio, a * torch.clamp(ratio, 1 - clip, 1 + clip)).mean()
+            cfs.append(float((torch.abs(ratio - 1) > clip).float().mean()))
+            vl = torch.nn.functional.mse_loss(v, r)
+            loss = pl + cfg.ent_coef * (-ent.mean()) + cfg.vf_coef * vl
+            with torch.no_grad():
+                log_ratio = lp - old
+                kl = float(((torch.exp(log_ratio) - 1) - log_ratio).mean())
+            kls.append(kl)
+            out["kls"].append(kl)
+            if target_kl is not None and kl > 1.5 * target_kl:
+                out["stopped_at"] = (epoch, j)
+                break
+            opt.zero_grad()
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(policy.parameters(), cfg.max_grad_norm)
+            opt.step()
+            out["n_updates"] += 1
+        out["approx_kl"], out["clip_fraction"] = sum(kls) / len(kls), sum(cfs) / len(cfs)        # of the last epoch run
+        if out["stopped_at"] is not None:
+            break
+    return out
+
+
+def _cpu_algo(emu_lib, hidden, **cfg):
+    torch.manual_seed(0)
+    env = make_env("CustomMyoBaodingBallsP1", emu_lib, num_envs=6, seed=2, dtype="f64")
+    pol = ActorCriticPolicy(86, 39, (16, 16), (16, 16), lstm_hidden_size=hidden)
+    base = dict(n_steps=4, batch_size=8, n_epochs=3, bf16=False, learning_rate=3e-3, ent_coef=0.01)
+    base.update(cfg)
+    return env, PPO(env, pol, PPOConfig(**base), seed=0)
+
+
+def _threshold_with_margin(kls):
+    """target_kl such that 1.5 * target_kl lies a factor >= 2 below the first approx_kl that crosses it and a factor >= 2 above
+    every approx_kl before it: the crossing is then the first entry that is >= 4 x everything before it (None: no such entry)."""
+    found = (None, None)
+    for k in range(1, len(kls)):
+        before = max(kls[:k])
+        if kls[k] >= 4 * before and kls[k] > 0:
+            limit = math.sqrt(kls[k] * before) if before > 0 else kls[k] / 2       # geometric middle: >= 2 x away from both
+            found = (k, limit / 1.5)         # (the last such entry: the largest values, furthest from rounding noise)
+    return found
+
+
+@pytest.mark.parametrize("hidden", [None, 8], ids=["mlp", "lstm"])
+def test_train_matches_sb3_restatement(emu_lib, hidden):
+    """PPO.train() (eager paths) == the SB3 restatement on the same rollout and permutations: parameters, the minibatch at which
+    the update stops, n_updates, approx_kl and clip_fraction — with target_kl chosen from the restatement's own approx_kl
+    sequence (margin asserted), with a target_kl nothing reaches, and with a linear-schedule value of lr / clip_range."""
+    env, algo = _cpu_algo(emu_lib, hidden)
+    algo.collect_rollouts()
+    snap = copy.deepcopy(algo.policy.state_dict())
+    gen_state = algo.gen.get_state()
+    lr, clip = 3e-3 * 0.5, 0.2 * 0.5
+    probe = sb3_train(algo, copy.deepcopy(algo.policy), lr, clip, None, torch.Generator().set_state(gen_state))
+    kls = probe["kls"]
+    assert abs(kls[0]) < 1e-6                   # first minibatch of an update: ratio == 1 up to rounding
+    k, tkl = _threshold_with_margin(kls)
+    assert k is not None, kls
+    assert kls[k] >= 2 * 1.5 * tkl and all(2 * x <= 1.5 * tkl for x in kls[:k])           # the factor-2 margin, both sides
+    per_epoch = len(kls) // algo.cfg.n_epochs
+    for target in (tkl, 1e6):
+        ref_pol = copy.deepcopy(algo.policy)
+        ref_pol.load_state_dict(snap)
+        ref = sb3_train(algo, ref_pol, lr, clip, target, torch.Generator().set_state(gen_state))
+        algo.policy.load_state_dict(snap)
+        algo.optimizer = torch.optim.Adam(algo.policy.parameters(), lr=1.0, eps=1e-5)      # fresh moments; train() sets the lr
+        algo.gen.set_state(gen_state)
+        algo.n_updates = 0
+        algo.cfg.target_kl = target
+        algo.cfg.lr_schedule, algo.cfg.clip_range_schedule = (lambda p: 3e-3 * p), (lambda p: 0.2 * p)
+        algo._current_progress_remaining = 0.5
+        st = algo.train()
+        assert st["learning_rate"] == lr and st["clip_range"] == clip
+        if target == tkl:
+            assert ref["stopped_at"] == divmod(k, per_epoch) and st["early_stopped"] and ref["n_updates"] == k
+        else:
+            assert ref["stopped_at"] is None and not st["early_stopped"] and ref["n_updates"] == len(kls)
+        assert st["n_updates"] == algo.n_updates == ref["n_updates"]
+        assert st["approx_kl"] == pytest.approx(ref["approx_kl"], rel=1e-6, abs=1e-6)
+        assert st["clip_fraction"] == pytest.approx(ref["clip_fraction"], rel=1e-6, abs=1e-6)
+        for (n, p), q in zip(algo.policy.named_parameters(), ref_pol.parameters()):
+            assert torch.allclose(p, q, rtol=1e-6, atol=1e-6), n
+        assert math.isfinite(st["entropy_loss"]) and math.isfinite(st["explained_variance"])
+    env.close()
+
+
+def test_linear_schedule_through_learn(emu_lib):
+    """learn() over 3 rollouts: train() reports the schedules' values at 1 - num_timesteps / total (SB3 updates the progress
+    after the rollout, before train()); cfg.learning_rate stays the float at progress 1.0."""
+    env, algo = _cpu_algo(emu_lib, None, lr_schedule=lambda p: 1e-3 * p, clip_range_schedule=lambda p: 0.1 + 0.2 * p, n_epochs=1)
+    assert algo.cfg.learning_rate == 1e-3 and algo.cfg.clip_range == pytest.approx(0.3)
+    logs = []
+    per, total = 4 * 6, 3 * 4 * 6
+    algo.learn(total, log=logs.append)
+    assert len(logs) == 3
+    for i, row in enumerate(logs):
+        p = 1.0 - (i + 1) * per / total
+        assert row["train/learning_rate"] == pytest.approx(1e-3 * p, rel=1e-12, abs=1e-15)
+        assert row["train/clip_range"] == pytest.approx(0.1 + 0.2 * p, rel=1e-12)
+        for key in ("approx_kl", "clip_fraction", "entropy_loss", "explained_variance", "early_stopped"):
+            assert "train/" + key in row
+    assert isinstance(algo.cfg.learning_rate, float) and algo.cfg.learning_rate == 1e-3
+    env.close()
+
+
+def test_myotrainer_passes_the_controls_on(emu_lib, tmp_path):
+    from myochallenge_amd.train.trainer import MyoTrainer
+    env = make_env("CustomMyoBaodingBallsP1", emu_lib, num_envs=2, seed=3, dtype="f64")
+    mk = lambda **mc: MyoTrainer(envs=VecNormalize(env), env_config={}, load_model_path=None, log_dir=str(tmp_path / "run"),
+                                 model_config={"n_steps": 4, "batch_size": 8, "n_epochs": 1, "policy": "MlpPolicy",
+                                               "policy_kwargs": {"net_arch": [{"pi": [8], "vf": [8]}]}, **mc})
+    tr = mk(learning_rate=lambda p: 1e-3 * p, clip_range=lambda p: 0.2 * p, target_kl=0.01, clip_range_vf=None)
+    cfg = tr.agent.cfg
+    assert cfg.lr_schedule(0.25) == 2.5e-4 and cfg.clip_range_schedule(0.5) == 0.1 and cfg.learning_rate == 1e-3
+    assert cfg.target_kl == 0.01
+    with pytest.raises(NotImplementedError):
+        mk(clip_range_vf=0.2)
+    with pytest.raises(NotImplementedError):
+        PPOConfig(clip_range_vf=0.2)
+    with pytest.raises(ValueError):
+        PPO(env, ActorCriticPolicy(86, 39, (8,), (8,), lstm_hidden_size=None), PPOConfig(target_kl=0.01, graph_allreduce=True))
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------ GPU: the hyper-parameter block
+def _hp_block(dev, lr, clip, limit):
+    hp = torch.zeros(native.HP_WORDS, device=dev)
+    hp[:3] = torch.tensor([lr, clip, limit], device=dev)
+    return hp
+
+
+def _adam_state(fa):
+    return [t.clone() for t in (fa.flat["p"], fa.m, fa.v, fa.shadow, fa._step)]
+
+
+@pytest.mark.gpu
+def test_stop_flag_fused_mlp_step(hip_lib):
+    """Kernel level, fused MLP step (myo_ppo_mlp_step + myo_adam_apply_hp) at its smallest batch: old_logp = logp - 0.5 makes
+    approx_kl = e^0.5 - 1.5 for every row.  Limit at half of it: two steps change nothing (parameters, m, v, bf16 shadow, step
+    counter bit-identical), stop is up, applied == 0.  Limit at twice it: bit-identical to the step without a block, stop down,
+    applied == 2.  approx_kl vs the fp32 torch value: the bound the fused-step test uses for policy_loss (2e-3)."""
+    from myochallenge_amd.rl.fused_mlp import FlatAdam, FusedPPOStep, flatten_parameters
+    dev = torch.device("cuda:0")
+    B, LR = 1024, 1e-5            # (a small step: the second minibatch's approx_kl stays at the first one's, far below 2 x)
+
+    def make(hp):
+        torch.manual_seed(0)
+        pol = ActorCriticPolicy(86, 39, (256, 256), (256, 256), lstm_hidden_size=None).to(dev)
+        fa = FlatAdam(flatten_parameters(pol), hip_lib, LR, 0.5)
+        step = FusedPPOStep(pol, hip_lib, 0.2, 0.01, 0.5)
+        fa.shadow, step.adam_syncs_shadow, step.adam = step.half[0], True, fa
+        step.refresh_shadow()
+        fa.hp = step.hp = hp
+        return pol, fa, step
+
+    pol, fa, step = make(None)
+    g = torch.Generator(device=dev).manual_seed(1)
+    obs = torch.randn(B, 86, device=dev, generator=g)
+    with torch.no_grad():
+        act = pol.act(obs, None, None)[0]
+        logp = pol.evaluate_actions(obs, act)[1]
+    oldlp = logp - KL_DELTA
+    kl32 = float(((torch.exp(logp - oldlp) - 1) - (logp - oldlp)).mean())
+    assert kl32 == pytest.approx(KL_OF_DELTA, rel=1e-4)
+    adv, ret = torch.randn(B, device=dev, generator=g), torch.randn(B, device=dev, generator=g)
+    idx = torch.arange(B, device=dev)
+
+    def two_steps(fa, step):
+        for _ in range(2):
+            step.run_indexed(obs, act, oldlp, adv, ret, idx)
+            assert fa.presummed > 0                       # the matrix-core step with the fused gradient tail
+            fa.step()
+        torch.cuda.synchronize()
+
+    two_steps(fa, step)
+    plain = _adam_state(fa)
+    assert int(fa._step[1]) == 2
+    # limit at half the minibatch's approx_kl: nothing moves
+    hp = _hp_block(dev, LR, 0.2, 0.5 * KL_OF_DELTA)
+    pol, fa, step = make(hp)
+    before = _adam_state(fa)
+    for n in (1, 2):
+        step.run_indexed(obs, act, oldlp, adv, ret, idx)
+        fa.step()
+        torch.cuda.synchronize()
+        for x, y in zip(before, _adam_state(fa)):
+            assert torch.equal(x, y)
+        hi = hp.view(torch.int32)
+        assert int(hi[native.HP_STOP]) == 1 and int(hi[native.HP_APPLIED]) == 0 and int(hi[native.HP_COUNT]) == 1
+    print("approx_kl fused", float(hp[native.HP_LAST_KL]), "fp32", kl32)
+    assert abs(float(hp[native.HP_LAST_KL]) - kl32) < 2e-3
+    assert float(hp[native.HP_SUM_CLIPFRAC]) == 1.0       # |e^0.5 - 1| > 0.2 on every row
+    # limit at twice it: the step without a block, bit for bit
+    hp = _hp_block(dev, LR, 0.2, 2.0 * KL_OF_DELTA)
+    pol, fa, step = make(hp)
+    two_steps(fa, step)
+    for x, y in zip(plain, _adam_state(fa)):
+        assert torch.equal(x, y)
+    hi = hp.view(torch.int32)
+    assert int(hi[native.HP_STOP]) == 0 and int(hi[native.HP_APPLIED]) == 2 and int(hi[native.HP_COUNT]) == 2
+
+
+def _gpu_mlp_algo(schedules, epochs=2, **cfg):
+    from myochallenge_amd.envs.environment_factory import EnvironmentFactory
+    torch.manual_seed(0)
+    env = EnvironmentFactory.create("CustomMyoBaodingBallsP1", num_envs=256, seed=5)
+    pol = ActorCriticPolicy(86, 39, (256, 256), (256, 256), lstm_hidden_size=None)
+    kw = dict(n_steps=8, batch_size=1024, n_epochs=epochs, learning_rate=1e-3, clip_range=0.3)
+    if schedules:
+        kw.update(lr_schedule=lambda p: 1e-3 * p, clip_range_schedule=lambda p: 0.1 + 0.2 * p)
+    kw.update(cfg)
+    return env, PPO(VecNormalize(env), pol, PPOConfig(**kw), seed=0)
+
+
+def _three_rollouts(algo, by_hand, rebuild):
+    """3 rollouts of learn(); by_hand: no schedule — the constants are set to the schedule's values before every update, and the
+    update's graphs are rebuilt (so the values enter them however they are passed)."""
+    total = 3 * algo.cfg.n_steps * algo.env.num_envs
+    seen = []
+    for i in range(3):
+        algo.collect_rollouts()
+        p = 1.0 - algo.num_timesteps / total
+        if by_hand:
+            algo.cfg.learning_rate, algo.cfg.clip_range = 1e-3 * p, 0.1 + 0.2 * p
+            rebuild(algo)
+        else:
+            algo._current_progress_remaining = p
+        st = algo.train()
+        seen.append((st["learning_rate"], st["clip_range"]))
+        assert st["learning_rate"] == 1e-3 * p and st["clip_range"] == 0.1 + 0.2 * p
+    torch.cuda.synchronize()
+    fa = algo._flat_adam
+    return [t.clone() for t in (fa.flat["p"], fa.m, fa.v, fa._step)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("epoch_graph", [True, False], ids=["epoch-chunk-graph", "per-step-graph"])
+def test_schedules_through_captured_mlp_graphs(hip_lib, monkeypatch, epoch_graph):
+    """Fused MLP path, graphs captured ONCE, linear lr / clip_range schedules over 3 rollouts == a run without schedules whose
+    constants are set by hand and whose graphs are rebuilt before every update: bit-identical parameters and Adam state."""
+    monkeypatch.setenv("MYO_EPOCH_GRAPH", "1" if epoch_graph else "0")
+    out = []
+    for by_hand in (False, True):
+        env, algo = _gpu_mlp_algo(schedules=not by_hand)
+        out.append(_three_rollouts(algo, by_hand, lambda a: setattr(a, "_graph", None)))
+        assert (algo._graph_epoch is not None) == epoch_graph and algo._fused is not None
+        env.close()
+    assert int(out[0][3][1]) == 3 * 2 * 2
+    for x, y in zip(*out):
+        assert torch.equal(x, y)
+
+
+def _gpu_lstm_algo(schedules, **cfg):
+    from myochallenge_amd.envs.environment_factory import EnvironmentFactory
+    torch.manual_seed(0)
+    env = EnvironmentFactory.create("CustomMyoReorientP1", num_envs=64, seed=3, max_episode_steps=5)    # episode starts inside the window
+    pol = ActorCriticPolicy(env.obs_dim, env.act_dim, (64, 64), (64, 64), lstm_hidden_size=32)
+    kw = dict(n_steps=8, batch_size=8 * 16, n_epochs=2, learning_rate=1e-3, clip_range=0.3)
+    if schedules:
+        kw.update(lr_schedule=lambda p: 1e-3 * p, clip_range_schedule=lambda p: 0.1 + 0.2 * p)
+    kw.update(cfg)
+    return env, PPO(VecNormalize(env), pol, PPOConfig(**kw), seed=0)
+
+
+@pytest.mark.gpu
+def test_schedules_through_captured_recurrent_graph(hip_lib):
+    """The same on the fused recurrent path (16 sequences of 8 steps per minibatch, LSTM 32: the sequence kernels' smallest)."""
+    out = []
+    for by_hand in (False, True):
+        env, algo = _gpu_lstm_algo(schedules=not by_hand)
+        assert algo._fused_rec is not None
+        out.append(_three_rollouts(algo, by_hand, lambda a: setattr(a, "_rgraph", None)))
+        assert float(algo.start_buf[1:].sum()) > 0
+        env.close()
+    assert int(out[0][3][1]) == 3 * 2 * 4
+    for x, y in zip(*out):
+        assert torch.equal(x, y)
+
+
+@pytest.mark.gpu
+def test_stop_flag_fused_recurrent_step(hip_lib):
+    """Kernel level, fused recurrent minibatch step (run_sequences: myo_ppo_loss_grad_hp, then myo_adam_clip_step_hp) on a window
+    with episode starts inside it: old_logp = (the fp32 policy's log pi) - 0.5, so the fp32 approx_kl over the entries (all
+    unmasked: the sequences are whole rollouts, nothing is padded) is e^0.5 - 1.5.  Same three cases as the MLP step."""
+    env, algo = _gpu_lstm_algo(schedules=False)
+    algo.collect_rollouts()
+    assert float(algo.start_buf[1:].sum()) > 0
+    T, N, m, LR = 8, 64, 16, 1e-5
+    adv, ret = compute_gae(algo.rew_buf, algo.val_buf, algo.start_buf, algo._last_values, algo._last_starts, 0.99, 0.95)
+    with torch.no_grad():
+        lp = algo.policy.evaluate_actions(algo.obs_buf, algo.act_buf, algo._rollout_state0, algo.start_buf)[1]
+    algo.logp_buf.copy_(lp.float() - KL_DELTA)
+    g = algo._rec_stage(adv, ret, T, N, m)
+    g["idx"].copy_(torch.arange(m, device=algo.device))
+    fa, hp, hi = algo._flat_adam, algo._hp, algo._hp.view(torch.int32)
+
+    def two_steps(limit, check=None):
+        algo._lr_now, algo._clip_now = LR, 0.3
+        algo._hp_write()
+        hp[native.HP_KL_LIMIT] = limit
+        for _ in range(2):
+            algo._rec_forward_backward()
+            algo._mb_apply()
+            torch.cuda.synchronize()
+            if check is not None:
+                check()
+
+    snap = fa.snapshot()
+    before = _adam_state(fa)
+    two_steps(0.0)                                      # no limit: what the applied case has to reproduce
+    plain = _adam_state(fa)
+    assert int(hi[native.HP_APPLIED]) == 2 and not torch.equal(plain[0], before[0])
+    fa.restore(snap)
+
+    def unchanged():
+        for x, y in zip(before, _adam_state(fa)):
+            assert torch.equal(x, y)
+        assert int(hi[native.HP_STOP]) == 1 and int(hi[native.HP_APPLIED]) == 0 and int(hi[native.HP_COUNT]) == 1
+    two_steps(0.5 * KL_OF_DELTA, unchanged)
+    print("approx_kl fused recurrent", float(hp[native.HP_LAST_KL]), "fp32", KL_OF_DELTA)
+    assert abs(float(hp[native.HP_LAST_KL]) - KL_OF_DELTA) < 2e-3
+    fa.restore(snap)
+    two_steps(2.0 * KL_OF_DELTA)
+    for x, y in zip(plain, _adam_state(fa)):
+        assert torch.equal(x, y)
+    assert int(hi[native.HP_STOP]) == 0 and int(hi[native.HP_APPLIED]) == 2 and int(hi[native.HP_COUNT]) == 2
+    env.close()
+
+
+@pytest.mark.gpu
+def test_target_kl_end_to_end_fused_mlp(hip_lib, monkeypatch):
+    """PPO.train() on the fused MLP path stops in the same epoch and minibatch as an fp32 eager run on the same rollout and
+    permutations, with target_kl chosen from the eager run's approx_kl sequence (factor-2 margin on both sides, asserted)."""
+    env, fused = _gpu_mlp_algo(schedules=False, epochs=4, learning_rate=3e-3)
+    fused.collect_rollouts()
+    pol32 = ActorCriticPolicy(86, 39, (256, 256), (256, 256), lstm_hidden_size=None)
+    pol32.load_state_dict(fused.policy.state_dict())
+    eager = PPO(fused.env, pol32, PPOConfig(n_steps=8, batch_size=1024, n_epochs=4, learning_rate=3e-3, clip_range=0.3, bf16=False,
+                                            use_graphs=False), seed=0)
+    assert eager._fused is None and eager._hp is None
+    eager.optimizer = torch.optim.Adam(eager.policy.parameters(), lr=3e-3, eps=1e-5)
+    for name in ("obs_buf", "act_buf", "rew_buf", "val_buf", "logp_buf", "start_buf"):
+        getattr(eager, name).copy_(getattr(fused, name))
+    eager._last_values, eager._last_starts = fused._last_values.clone(), fused._last_starts.clone()
+    eager.gen.set_state(fused.gen.get_state())
+    gen_state = fused.gen.get_state()
+    snap = copy.deepcopy(eager.policy.state_dict())
+    kls = []
+    orig = eager._kl_exceeded
+    monkeypatch.setattr(eager, "_kl_exceeded", lambda kl: (kls.append(float(kl)), orig(kl))[1])
+    eager.train()
+    k, tkl = _threshold_with_margin(kls)
+    print("eager approx_kl sequence", kls, "crossing", k, "target_kl", tkl)
+    assert k is not None, kls
+    assert kls[k] >= 2 * 1.5 * tkl and all(2 * x <= 1.5 * tkl for x in kls[:k])
+    eager.policy.load_state_dict(snap)
+    eager.optimizer = torch.optim.Adam(eager.policy.parameters(), lr=3e-3, eps=1e-5)
+    eager.gen.set_state(gen_state)
+    eager.n_updates, eager.cfg.target_kl, fused.cfg.target_kl = 0, tkl, tkl
+    se, sf = eager.train(), fused.train()
+    assert se["early_stopped"] and sf["early_stopped"] is True
+    assert se["n_updates"] == k and sf["n_updates"] == k             # same epoch, same minibatch: 2 minibatches per epoch
+    assert int(fused._flat_adam._step[1]) == k
+    env.close()
