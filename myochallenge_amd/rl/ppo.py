@@ -15,12 +15,19 @@ from __future__ import annotations
 
 import os
 import time
+import warnings
+from collections import deque
 from dataclasses import dataclass, field
 from typing import Callable, Dict, Optional
 
 import torch
 import torch.distributed as dist
 
+from .. import native
+from ..native import (HP_APPLIED, HP_CLIP, HP_COUNT, HP_LAST_KL, HP_LAST_PL, HP_LAST_VL, HP_STOP, HP_SUM_ENTLOSS, HP_SUM_KL,
+                      HP_WORDS)
+from .fused_lstm import FusedRecurrentPPOStep
+from .fused_mlp import FlatAdam, FusedPPOStep, flatten_parameters, hp_record_torch
 from .policy import ActorCriticPolicy
 
 
@@ -70,7 +77,6 @@ def compute_gae(rewards, values, episode_starts, last_values, last_dones, gamma,
     T = rewards.shape[0]
     if rewards.is_cuda and rewards.dtype == torch.float32:
         import ctypes as C
-        from .. import native
         lib = native.load()
         adv, ret = torch.empty_like(rewards), torch.empty_like(rewards)
         p = lambda t: C.c_void_p(t.contiguous().data_ptr())
@@ -104,65 +110,47 @@ class PPO:
         if not policy.recurrent and (cfg.n_steps * env.num_envs) % min(cfg.batch_size, cfg.n_steps * env.num_envs):
             # SB3 warns here too and then trains on the truncated last minibatch of each epoch; every update path of this
             # class works on fixed-size minibatches (one captured graph) and SKIPS that remainder instead
-            import warnings
             warnings.warn(f"rollout of {cfg.n_steps * env.num_envs} samples is not a multiple of batch_size={cfg.batch_size}: the last "
                           f"{(cfg.n_steps * env.num_envs) % cfg.batch_size} samples of every epoch's permutation are not trained on "
                           "(stable-baselines3 would train on them as a truncated minibatch)")
+        self._fused = None           # FusedPPOStep: the hand-derived MLP minibatch step
+        self._fused_rec = None       # FusedRecurrentPPOStep: the hand-derived recurrent minibatch step
+        self._flat_adam = None       # FlatAdam over the flat parameter vector: every captured update path has one
+        fused = None
+        if cfg.use_graphs and on_gpu:
+            # flat parameter / gradient vectors (before any graph captures addresses) and the one-kernel optimiser, so that a whole
+            # minibatch step (forward, backward, clip + Adam) is ONE hipGraph.  The forward / backward of it is hand-derived
+            # (rl/fused_mlp.py, rl/fused_lstm.py) or, for a recurrent policy without such a step, autograd on the flat vectors.
+            lib = native.load()
+            self._flat_adam = FlatAdam(flatten_parameters(self.policy), lib, cfg.learning_rate, cfg.max_grad_norm)
+            if not policy.recurrent:
+                self._fused = FusedPPOStep(self.policy, lib, cfg.clip_range, cfg.ent_coef, cfg.vf_coef)
+                if getattr(policy, "use_sde", False) and self._fused.merged is None:
+                    self._fused = self._flat_adam = None         # gSDE has a loss stage on the stacked-trunk path only: eager autograd
+            elif cfg.bf16 and os.environ.get("MYO_RECURRENT_AUTOGRAD") != "1":
+                # (None when the layout has no stacked actor/critic views)
+                self._fused_rec = FusedRecurrentPPOStep.create(self.policy, lib, cfg.clip_range, cfg.ent_coef, cfg.vf_coef)
+            fused = self._fused if self._fused is not None else self._fused_rec
+            if fused is not None:        # one bf16 shadow of the flat vector: the Adam kernel keeps it in step
+                self._flat_adam.shadow = fused.half[0]
+                fused.adam_syncs_shadow = True
+                fused.refresh_shadow()
         self.optimizer = torch.optim.Adam(self.policy.parameters(), lr=cfg.learning_rate, eps=1e-5,
                                           capturable=on_gpu, foreach=True if on_gpu else None)
-        self._graph = None
-        self._t_host = 0
-        self._fused = None
-        self._fused_rec = None
-        self._flat_adam = None
-        sde = getattr(policy, "use_sde", False)
-        if cfg.use_graphs and on_gpu and not policy.recurrent:      # (gSDE: same fused step with its own loss stage, FusedPPOStep._sde_loss)
-            # flat parameter/grad vectors (before any graph captures addresses) + the one-kernel optimiser
-            from .. import native
-            from .fused_mlp import FlatAdam, flatten_parameters
-            self._flat_adam = FlatAdam(flatten_parameters(self.policy), native.load(), cfg.learning_rate,
-                                       cfg.max_grad_norm)
-            from .fused_mlp import FusedPPOStep
-            self._fused = FusedPPOStep(self.policy, native.load(), cfg.clip_range, cfg.ent_coef, cfg.vf_coef)
-            if sde and self._fused.merged is None:       # gSDE has a loss stage on the stacked-trunk path only: keep autograd
-                self._fused = self._flat_adam = None
-                self.optimizer = torch.optim.Adam(self.policy.parameters(), lr=cfg.learning_rate, eps=1e-5, capturable=on_gpu,
-                                                  foreach=True if on_gpu else None)
-            if self._fused is not None and len(self._fused.half) == 1:       # one bf16 shadow of the flat vector: Adam keeps it in step
-                self._flat_adam.shadow = self._fused.half[0]
-                self._fused.adam_syncs_shadow = True
-                self._fused.refresh_shadow()
-        elif cfg.use_graphs and on_gpu and policy.recurrent:
-            # recurrent policy: autograd does forward / BPTT, but on flat parameter / gradient vectors so that the
-            # whole minibatch step (zero, forward, backward, clip + Adam) is ONE hipGraph (_train_recurrent_graphed)
-            from .. import native
-            from .fused_mlp import FlatAdam, flatten_parameters
-            self._flat_adam = FlatAdam(flatten_parameters(self.policy), native.load(), cfg.learning_rate,
-                                       cfg.max_grad_norm)
-            if cfg.bf16 and os.environ.get("MYO_RECURRENT_AUTOGRAD") != "1":
-                # hand-derived minibatch step (rl/fused_lstm.py); None when the layout has no stacked actor/critic views
-                from .fused_lstm import FusedRecurrentPPOStep
-                self._fused_rec = FusedRecurrentPPOStep.create(self.policy, native.load(), cfg.clip_range, cfg.ent_coef, cfg.vf_coef)
-                if self._fused_rec is not None:          # one bf16 shadow of the flat vector, kept in step by the Adam kernel
-                    self._flat_adam.shadow = self._fused_rec.half[0]
-                    self._fused_rec.adam_syncs_shadow = True
-                    self._fused_rec.refresh_shadow()
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # the device-resident hyper-parameter block of the fused update paths (layout: include/myobatch.h): lr, clip_range, KL limit,
         # stop flag, applied-step count and the diagnostics' sums.  train() writes it before every update, outside the graphs.
         self._hp = None
         if self._flat_adam is not None:
-            from ..native import HP_WORDS
             self._hp = torch.zeros(HP_WORDS, device=self.device)
             self._flat_adam.hp = self._hp
-            for fused in (self._fused, self._fused_rec):
-                if fused is not None:
-                    fused.hp = self._hp
+            if fused is not None:
+                fused.hp = self._hp
         self._current_progress_remaining = 1.0
         self._total_timesteps = None
         self._lr_now, self._clip_now = float(cfg.learning_rate), float(cfg.clip_range)
         self._hp_write()                 # (a minibatch step run before the first train(), as the tests do, reads the block too)
-        if self._fused is not None and self._flat_adam is not None and self.world == 1 and os.environ.get("MYO_ADAM_SEPARATE") != "1":
+        if self._fused is not None and self.world == 1 and os.environ.get("MYO_ADAM_SEPARATE") != "1":
             self._fused.adam = self._flat_adam   # nothing is exchanged between gradient and clip: the fused step also squares the gradient
         self.rank = dist.get_rank() if self.world > 1 else 0
         N, T, O, A = env.num_envs, cfg.n_steps, env.obs_dim, env.act_dim
@@ -186,6 +174,22 @@ class PPO:
         nparam = sum(p.numel() for p in self.policy.parameters())
         self._flat_grad = self.policy._flat["g"] if self._flat_adam is not None else torch.zeros(nparam, device=d)
         self.timers: Dict[str, float] = {"rollout": 0.0, "gae": 0.0, "update": 0.0}
+        # state that later calls fill in: the rollout graphs (rollout_step) ...
+        self._rollout_ready = False      # the rollout graphs are captured
+        self._native = False             # ... and they are the HIP-kernel rollout (_init_native_rollout)
+        self._gB2 = None                 # second half of graph B with a rank-synchronised normaliser
+        self._sde_W = None               # gSDE exploration matrices of the HIP-kernel rollout
+        self._t_host = 0
+        self._last_values = None
+        self.vn_allreduce_seconds, self.vn_allreduce_calls = 0.0, 0
+        # ... the episode log (_log_episodes, episode_stats) ...
+        self._ep_log, self._ep_t, self._ep_nan_t, self.ep_info_buffer = None, 0, None, None
+        # ... and the update: the captured MLP step (_build_graphs) and the captured recurrent step (_build_recurrent_graphs), each
+        # with the shape it was captured for, its static tensors and its graphs
+        self._graph, self._gs, self._graph_fb, self._graph_ap, self._graph_epoch, self._epoch_chunk = None, None, None, None, None, 0
+        self._rgraph, self._rg, self._rgraph_fb, self._rgraph_ap = None, None, None, None
+        self._allreduce_in_graph = False
+        self._early_stopped, self._last_diag = False, None
 
     def _autocast(self):
         on = self.cfg.bf16 and self.device.type == "cuda"
@@ -465,7 +469,7 @@ class PPO:
 
     def rollout_step(self) -> None:
         """One environment step for the whole batch (graphed path only)."""
-        if not getattr(self, "_rollout_ready", False):
+        if not self._rollout_ready:
             if self._native_rollout():
                 self._init_native_rollout()
             else:
@@ -474,29 +478,28 @@ class PPO:
             self.env.begin_rollout()         # (per-rollout normaliser synchronisation: snapshot at the first step; a no-op otherwise)
         if self.policy.recurrent:
             if self._t_host == 0:      # LSTM state at the start of the rollout: initial state of the update's sequences
-                self._rollout_state0 = self._native_state() if getattr(self, "_native", False) else tuple(s.clone() for s in self._state_s)
+                self._rollout_state0 = self._native_state() if self._native else tuple(s.clone() for s in self._state_s)
             self._t_host = (self._t_host + 1) % self.cfg.n_steps
         self._gA.replay()
         raw = self._raw.step_tensor(self._clip_s)
         self._log_episodes(raw[2], raw[6])
         self._gB.replay()
-        if getattr(self, "_gB2", None) is not None:      # rank-synchronised normaliser (see _init_native_rollout)
+        if self._gB2 is not None:      # rank-synchronised normaliser (see _init_native_rollout)
             # (host time of the eager collective between the two graph replays — enqueue + whatever the call blocks on — accumulated for
             #  the bench line of an N > 1 run: `normalizer_allreduce_ms_per_step`)
             t0 = time.perf_counter()
             dist.all_reduce(self._vn_batch)
-            self.vn_allreduce_seconds = getattr(self, "vn_allreduce_seconds", 0.0) + (time.perf_counter() - t0)
-            self.vn_allreduce_calls = getattr(self, "vn_allreduce_calls", 0) + 1
+            self.vn_allreduce_seconds += time.perf_counter() - t0
+            self.vn_allreduce_calls += 1
             self._gB2.replay()
 
     def _log_episodes(self, done, ep) -> None:
         """Monitor statistics (SB3's ep_info_buffer): the (raw return, length) the kernel reports for every env that finished an
         episode in this step go into row t of a [T, N, 2] log, NaN elsewhere — one small launch per step; episode_stats() reads it."""
         T, N = self.cfg.n_steps, self.env.num_envs
-        if getattr(self, "_ep_log", None) is None or self._ep_log.shape[:2] != (T, N):
+        if self._ep_log is None or self._ep_log.shape[:2] != (T, N):
             self._ep_log = torch.full((T, N, 2), float("nan"), device=self.device)
             self._ep_t = 0
-            from collections import deque
             self.ep_info_buffer = deque(maxlen=100)
         if ep is None:
             return
@@ -505,7 +508,7 @@ class PPO:
 
     @property
     def _ep_nan(self):
-        if getattr(self, "_ep_nan_t", None) is None:
+        if self._ep_nan_t is None:
             self._ep_nan_t = torch.full((1, 1), float("nan"), device=self.device)
         return self._ep_nan_t
 
@@ -513,7 +516,7 @@ class PPO:
         """rollout/ep_rew_mean and rollout/ep_len_mean as SB3 logs them: means over the last 100 finished episodes (Monitor's raw,
         un-normalised returns; /root/reference/src/main_baoding.py runs under SB3's logger).  Reads the rollout's episode log once
         (one host synchronisation per call)."""
-        log = getattr(self, "_ep_log", None)
+        log = self._ep_log
         if log is not None and self._ep_t > 0:
             T = log.shape[0]
             rows = min(self._ep_t, T)
@@ -526,7 +529,7 @@ class PPO:
                 self.ep_info_buffer.append((r, l))
             log.fill_(float("nan"))
             self._ep_t = 0
-        buf = getattr(self, "ep_info_buffer", None)
+        buf = self.ep_info_buffer
         if not buf:
             return {}
         return {"rollout/ep_rew_mean": float(sum(r for r, _ in buf) / len(buf)), "rollout/ep_len_mean": float(sum(l for _, l in buf) / len(buf))}
@@ -535,12 +538,12 @@ class PPO:
         if hasattr(self.env, "end_rollout"):
             self.env.end_rollout()
         with torch.no_grad(), self._autocast():
-            if getattr(self, "_native", False) and not self.policy.recurrent:
+            if self._native and not self.policy.recurrent:
                 # timeout bootstrap for the whole rollout at once: r += gamma V(terminal_obs) where truncated
                 T, N = self.trunc_buf.shape
                 tv = self.policy.predict_values(self.term_buf.view(T * N, -1)).view(T, N)
                 self.rew_buf.add_(self.cfg.gamma * tv * self.trunc_buf)
-            elif getattr(self, "_native", False):
+            elif self._native:
                 # same with the critic's LSTM state after each step, episode_start False (sb3-contrib [3P-RECALL]); time limits are
                 # rare events (one step in max_episode_steps), so the pass is skipped when the rollout has none (one host sync)
                 self._state_s = self._native_state()
@@ -563,7 +566,7 @@ class PPO:
         size) cannot move it."""
         pol = self.policy
         gen = self.gen if self.gen.device == pol.log_std.device else None
-        W = getattr(self, "_sde_W", None)
+        W = self._sde_W
         if W is not None and W.shape[1:] == tuple(pol.log_std.shape):
             pol.reset_noise(W.shape[0], gen, out=W)
         else:
@@ -580,7 +583,7 @@ class PPO:
                 self._fused.refresh_shadow()        # rollout inference runs on the bf16 shadow weights
             if self._fused_rec is not None:
                 self._fused_rec.refresh_shadow()
-                if getattr(self, "_native", False):
+                if self._native:
                     self._refresh_rollout_lstm()
             for _ in range(cfg.n_steps):
                 self.rollout_step()
@@ -633,20 +636,25 @@ class PPO:
             p.grad = self._flat_grad[off:off + n].view_as(p).clone()
             off += n
 
+    def _global_adv_moments(self, a):
+        """(mean, unbiased std) of the advantages `a` of this rank's minibatch taken over the minibatches of ALL ranks: one all-reduce of
+        (sum, sum of squares, count), in the dtype of `a`."""
+        m = torch.stack([a.sum(), (a * a).sum(), torch.tensor(float(a.numel()), dtype=a.dtype, device=a.device)])
+        if self.world > 1:
+            dist.all_reduce(m)
+        mean = m[0] / m[2]
+        return mean, torch.sqrt(torch.clamp(m[1] / m[2] - mean * mean, min=0.0) * m[2] / (m[2] - 1))
+
     def _loss(self, values, logp, entropy, old_logp, adv, returns):
         cfg = self.cfg
         if cfg.normalize_advantage and adv.numel() > 1:
             if cfg.sync_adv_moments and self.world > 1:
-                m = torch.stack([adv.sum(), (adv * adv).sum(), torch.tensor(float(adv.numel()), device=adv.device)])
-                dist.all_reduce(m)
-                mean = m[0] / m[2]
-                std = torch.sqrt(torch.clamp(m[1] / m[2] - mean * mean, min=0.0) * m[2] / (m[2] - 1))
+                mean, std = self._global_adv_moments(adv)
             else:
                 mean, std = adv.mean(), adv.std()
             adv = (adv - mean) / (std + 1e-8)
         ratio = torch.exp(logp - old_logp)
         if self._hp is not None:     # (the autograd recurrent graph: clip_range from the hyper-parameter block, read at replay time)
-            from ..native import HP_CLIP
             clip = self._hp[HP_CLIP]
         else:
             clip = self._clip_now
@@ -660,7 +668,6 @@ class PPO:
             el = -torch.as_tensor(ent, device=kl.device).detach().float()
             self._last_diag = (kl, cf, el)
             if self._hp is not None:
-                from .fused_mlp import hp_record_torch
                 hp_record_torch(self._hp, pl.detach(), vl.detach(), kl, cf, el)
         return pl + cfg.ent_coef * (-ent) + cfg.vf_coef * vl, pl.detach(), vl.detach()
 
@@ -684,7 +691,6 @@ class PPO:
 
     def _hp_write(self):
         if self._hp is not None:
-            from ..native import HP_WORDS
             cfg = self.cfg
             # N > 1 ranks decide on the all-reduced approx_kl on the host (between the two graphs): no limit on the device
             limit = 1.5 * cfg.target_kl if (cfg.target_kl is not None and self.world == 1) else 0.0
@@ -692,12 +698,10 @@ class PPO:
 
     def _hp_new_epoch(self):
         """The diagnostics are means over the minibatches of the last epoch run: their sums start again with every epoch."""
-        from ..native import HP_COUNT, HP_SUM_ENTLOSS
         self._hp[HP_COUNT:HP_SUM_ENTLOSS + 1].zero_()
 
     def _hp_stopped(self) -> bool:
         """The stop flag of the hyper-parameter block: one 4-byte copy to the host (only ever called with target_kl set)."""
-        from ..native import HP_STOP
         return bool(self._hp[HP_STOP:HP_STOP + 1].view(torch.int32).cpu().item())
 
     def _kl_exceeded(self, kl) -> bool:
@@ -713,7 +717,6 @@ class PPO:
 
     def _kl_exceeded_ranks(self) -> bool:
         """N > 1 ranks on a fused path: the approx_kl the loss kernel has just recorded, all-reduced (mean), against the limit."""
-        from ..native import HP_LAST_KL
         return self._kl_exceeded(self._hp[HP_LAST_KL])
 
     def train(self) -> Dict[str, float]:
@@ -726,8 +729,7 @@ class PPO:
         stopped the update included (SB3 resets approx_kl per epoch too, but averages the other two over all epochs) —
         explained_variance (1 - Var(returns - values) / Var(returns) over the rollout buffer), the learning_rate and clip_range used,
         and early_stopped.  On the fused paths the three means come from the hyper-parameter block's sums."""
-        cfg, pol = self.cfg, self.policy
-        T, N = cfg.n_steps, self.env.num_envs
+        cfg = self.cfg
         self._update_hyper()
         adv, ret = compute_gae(self.rew_buf, self.val_buf, self.start_buf, self._last_values,
                                self._last_starts, cfg.gamma, cfg.gae_lambda)
@@ -735,61 +737,11 @@ class PPO:
         self._early_stopped, diag = False, []
         if self._fused is not None:
             pl, vl = self._train_graphed(adv, ret)
-        elif not pol.recurrent:
-            B = T * N
-            obs, act = self.obs_buf.view(B, -1), self.act_buf.view(B, -1)
-            oldlp, advf, retf = self.logp_buf.view(B), adv.view(B), ret.view(B)
-            bs = min(cfg.batch_size, B)
-            for _ in range(cfg.n_epochs):
-                diag = []
-                perm = torch.randperm(B, generator=self.gen, device=self.device)
-                for s in range(0, B - bs + 1, bs):
-                    idx = perm[s:s + bs]
-                    with self._autocast():
-                        v, lp, ent = pol.evaluate_actions(obs[idx], act[idx])
-                    loss, pl, vl = self._loss(v, lp, ent, oldlp[idx], advf[idx], retf[idx])
-                    diag.append(torch.stack(self._last_diag))
-                    if self._kl_exceeded(self._last_diag[0]):
-                        self._early_stopped = True
-                        break
-                    self.optimizer.zero_grad(set_to_none=True)
-                    loss.backward()
-                    self._allreduce_grads()
-                    torch.nn.utils.clip_grad_norm_(pol.parameters(), cfg.max_grad_norm)
-                    self.optimizer.step()
-                    self.n_updates += 1
-                if self._early_stopped:
-                    break
         elif self._flat_adam is not None:
             pl, vl = self._train_recurrent_graphed(adv, ret)
         else:
-            # sequences = whole rollouts of a subset of envs, initial LSTM state = state at rollout start
-            envs_per_mb = max(1, min(N, cfg.batch_size // T))
-            for _ in range(cfg.n_epochs):
-                diag = []
-                perm = torch.randperm(N, generator=self.gen, device=self.device)
-                for s in range(0, N - envs_per_mb + 1, envs_per_mb):
-                    idx = perm[s:s + envs_per_mb]
-                    st0 = tuple(x[:, idx] for x in self._rollout_state0)
-                    with self._autocast():
-                        v, lp, ent = pol.evaluate_actions(self.obs_buf[:, idx], self.act_buf[:, idx], st0,
-                                                          self.start_buf[:, idx])
-                    loss, pl, vl = self._loss(v.reshape(-1), lp.reshape(-1), ent, self.logp_buf[:, idx].reshape(-1),
-                                              adv[:, idx].reshape(-1), ret[:, idx].reshape(-1))
-                    diag.append(torch.stack(self._last_diag))
-                    if self._kl_exceeded(self._last_diag[0]):
-                        self._early_stopped = True
-                        break
-                    self.optimizer.zero_grad(set_to_none=True)
-                    loss.backward()
-                    self._allreduce_grads()
-                    torch.nn.utils.clip_grad_norm_(pol.parameters(), cfg.max_grad_norm)
-                    self.optimizer.step()
-                    self.n_updates += 1
-                if self._early_stopped:
-                    break
+            pl, vl, diag = self._train_eager(adv, ret)
         if self._hp is not None:        # fused paths: the block's sums, ONE copy to the host (it also carries pl / vl)
-            from ..native import HP_APPLIED, HP_COUNT, HP_LAST_PL, HP_LAST_VL, HP_STOP, HP_SUM_KL
             hp = self._hp.cpu()
             hi = hp.view(torch.int32)
             cnt = max(1, int(hi[HP_COUNT]))
@@ -809,6 +761,51 @@ class PPO:
                      early_stopped=self._early_stopped)
         return stats
 
+    # ---------------------------------------------------------------- eager update (CPU, use_graphs=False, gSDE without stacked trunks)
+    def _train_eager(self, adv, ret):
+        """Autograd + torch Adam.  MLP policy: minibatches are rows of the flattened buffer; recurrent policy: whole rollouts of a
+        subset of envs, initial LSTM state = state at rollout start.  Returns the last minibatch's losses and the last epoch's
+        diagnostics."""
+        cfg, pol = self.cfg, self.policy
+        T, N = cfg.n_steps, self.env.num_envs
+        if pol.recurrent:
+            n_items, k = N, max(1, min(N, cfg.batch_size // T))
+
+            def evaluate(idx):
+                st0 = tuple(x[:, idx] for x in self._rollout_state0)
+                with self._autocast():
+                    v, lp, ent = pol.evaluate_actions(self.obs_buf[:, idx], self.act_buf[:, idx], st0, self.start_buf[:, idx])
+                return self._loss(v.reshape(-1), lp.reshape(-1), ent, self.logp_buf[:, idx].reshape(-1),
+                                  adv[:, idx].reshape(-1), ret[:, idx].reshape(-1))
+        else:
+            n_items = B = T * N
+            k = min(cfg.batch_size, B)
+            obs, act = self.obs_buf.view(B, -1), self.act_buf.view(B, -1)
+            oldlp, advf, retf = self.logp_buf.view(B), adv.view(B), ret.view(B)
+
+            def evaluate(idx):
+                with self._autocast():
+                    v, lp, ent = pol.evaluate_actions(obs[idx], act[idx])
+                return self._loss(v, lp, ent, oldlp[idx], advf[idx], retf[idx])
+        for _ in range(cfg.n_epochs):
+            diag = []
+            perm = torch.randperm(n_items, generator=self.gen, device=self.device)
+            for s in range(0, n_items - k + 1, k):
+                loss, pl, vl = evaluate(perm[s:s + k])
+                diag.append(torch.stack(self._last_diag))
+                if self._kl_exceeded(self._last_diag[0]):
+                    self._early_stopped = True
+                    break
+                self.optimizer.zero_grad(set_to_none=True)
+                loss.backward()
+                self._allreduce_grads()
+                torch.nn.utils.clip_grad_norm_(pol.parameters(), cfg.max_grad_norm)
+                self.optimizer.step()
+                self.n_updates += 1
+            if self._early_stopped:
+                break
+        return pl, vl, diag
+
     # ---------------------------------------------------------------- hipGraph-captured minibatch step
     def _mb_forward_backward(self):
         g, cfg = self._gs, self.cfg
@@ -819,6 +816,147 @@ class PPO:
     def _mb_apply(self):
         self._flat_adam.step(1.0 / self.world)    # all-reduce SUM ran in place on the flat gradient
 
+    def _capture_step(self, forward_backward, g, graph_allreduce=False, epoch_steps=0):
+        """Capture one minibatch step — forward_backward() on the static tensors `g`, then _mb_apply() — and return
+        (fb, ap, epoch, allreduce_inside).  One rank: `fb` is the whole step.  N > 1 ranks: `fb` ends with the gradient, the RCCL
+        all-reduce runs eagerly, and `ap` is clip + Adam; or, with graph_allreduce on the nccl backend, `fb` is the whole step with the
+        collective inside it (ap None, allreduce_inside True).  epoch_steps = k > 0 also captures `epoch`: k minibatch steps, each
+        with its index copy out of g["perm"] (allocated here), in one graph.  The parameters and the Adam state come out as they
+        went in."""
+        d = self.device
+        side = torch.cuda.Stream(device=d)
+        # warm-up and capture must not move the parameters.  The snapshot is taken BEFORE the side stream is told to wait: its copies run
+        # on the current stream, and a warm-up optimizer step on the side stream that overtook them left some ranks restoring a state two
+        # Adam steps ahead (replicas of >= 4 ranks sharing a GPU differed; found by the config-D-shape test)
+        snap = self._flat_adam.snapshot()
+        side.wait_stream(torch.cuda.current_stream(d))
+        with torch.cuda.stream(side):       # eager warm-up (library handles, workspaces)
+            for _ in range(2):
+                forward_backward()
+                if self.world > 1:
+                    dist.all_reduce(self._flat_grad)
+                self._mb_apply()
+        torch.cuda.current_stream(d).wait_stream(side)
+        torch.cuda.synchronize(d)
+        fb, ap, epoch, inside = torch.cuda.CUDAGraph(), None, None, False
+        # The gradient all-reduce INSIDE the optimizer hipGraph (forward / backward -> RCCL all-reduce -> clip + Adam, one replay per
+        # minibatch): opt-in, nccl (= RCCL) only.  There is no in-process fallback from a failed capture: measured on a one-GPU box with a
+        # backend that synchronises inside the capture (gloo), the capture is invalidated, capture_end throws inside torch's graph
+        # destructor and the process dies (tests/test_gpu_parity.py).  So a backend that cannot be captured is refused up front
+        # (warning, eager collective between two graphs — the tested default), and a capture failure on nccl is raised as an error.
+        if graph_allreduce and dist.get_backend() != "nccl":
+            warnings.warn(f"graph_allreduce needs the nccl (RCCL) backend, this process group is {dist.get_backend()!r}: "
+                          "using the eager all-reduce between the two optimizer graphs")
+        elif graph_allreduce:
+            try:
+                with torch.cuda.graph(fb, capture_error_mode="thread_local"):
+                    forward_backward()
+                    dist.all_reduce(self._flat_grad, op=dist.ReduceOp.SUM)
+                    self._mb_apply()
+            except Exception as exc:        # noqa: BLE001
+                raise RuntimeError("capturing the RCCL gradient all-reduce inside the optimizer hipGraph failed; run without "
+                                   "graph_allreduce / MYO_GRAPH_ALLREDUCE (the eager collective between two graphs)") from exc
+            inside = True
+        if not inside:
+            with torch.cuda.graph(fb, capture_error_mode="thread_local"):
+                forward_backward()
+                if self.world == 1:             # single GPU: forward, backward and optimiser in ONE graph
+                    self._mb_apply()
+            if self.world > 1:                  # the RCCL all-reduce runs between the two graphs
+                ap = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(ap, capture_error_mode="thread_local"):
+                    self._mb_apply()
+        if epoch_steps:
+            bs = g["idx"].numel()
+            g["perm"] = torch.zeros(epoch_steps * bs, dtype=torch.long, device=d)
+            g["perm"].copy_(torch.arange(epoch_steps * bs, device=d))
+            torch.cuda.synchronize(d)
+            epoch = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(epoch, capture_error_mode="thread_local"):
+                for s in range(0, epoch_steps * bs, bs):
+                    g["idx"].copy_(g["perm"][s:s + bs])
+                    forward_backward()
+                    self._mb_apply()
+        self._flat_adam.restore(snap)
+        return fb, ap, epoch, inside
+
+    def _run_captured(self, n_items, k, g, fb, ap, stats=None, epoch=None):
+        """The epochs and minibatches of a captured update: a permutation of n_items per epoch, k of them per minibatch, staged by
+        copying their indices into g["idx"] and run by replaying `fb` (one rank, or the all-reduce inside the graph: the whole step;
+        else gradient -> eager all-reduce -> `ap`).  stats: where the moments of the GLOBAL minibatch's advantages go when the step
+        does not compute them itself.  epoch: the graph of _epoch_chunk whole steps, which then runs the epoch (_replay_epoch_chunked)."""
+        cfg = self.cfg
+        tkl = cfg.target_kl is not None
+        # one rank with target_kl: the step itself compares approx_kl with the limit in the hyper-parameter block and, past it, raises
+        # the block's stop flag and applies nothing more.  The host reads the flag once per epoch and takes n_updates from the block's
+        # applied count (train).  Everywhere else n_updates is counted here.
+        device_stop = tkl and self.world == 1
+        stopped = False
+        for _ in range(cfg.n_epochs):
+            self._hp_new_epoch()
+            perm = torch.randperm(n_items, generator=self.gen, device=self.device)
+            if epoch is not None:
+                stopped = self._replay_epoch_chunked(perm, g, k, n_items // k, epoch, fb, device_stop)
+                if not device_stop:
+                    self.n_updates += n_items // k
+            else:
+                for s in range(0, n_items - k + 1, k):
+                    g["idx"].copy_(perm[s:s + k])
+                    if stats is not None:
+                        mean, std = self._global_adv_moments(g["adv"][..., perm[s:s + k]].double())
+                        stats.copy_(torch.stack([mean, std]).float())
+                    fb.replay()
+                    if ap is not None:
+                        dist.all_reduce(self._flat_grad, op=dist.ReduceOp.SUM)
+                        if tkl and self._kl_exceeded_ranks():      # the decision between the two graphs: this step is not applied
+                            self._early_stopped = stopped = True
+                            break
+                        if self._dp_check:
+                            self._dp_compare("gradient after the all-reduce", self._flat_grad)
+                            self._dp_compare("parameters before the optimizer step", self._flat_adam.flat["p"])
+                            self._dp_compare("Adam m before the optimizer step", self._flat_adam.m)
+                            self._dp_compare("Adam v before the optimizer step", self._flat_adam.v)
+                            self._dp_compare("Adam step counter before the optimizer step", self._flat_adam._step)
+                        ap.replay()
+                        if self._dp_check:
+                            self._dp_compare("gradient after the optimizer step", self._flat_grad)
+                            self._dp_compare("|g|^2 partial sums", self._flat_adam.sq[:64].contiguous())
+                            self._dp_compare("parameters after the optimizer step", self._flat_adam.flat["p"])
+                    if not device_stop:
+                        self.n_updates += 1
+                if device_stop and not stopped:                      # steps after a stop changed nothing: one read per epoch
+                    stopped = self._hp_stopped()
+            if stopped:
+                break
+
+    def _replay_epoch_chunked(self, perm, g, bs, n_mb, epoch, fb, device_stop) -> bool:
+        """One epoch (one rank) as replays of the chunk graph `epoch`, each fed _epoch_chunk minibatches of `perm` through g["perm"],
+        and what is left of the epoch on the per-step graph.  Returns whether the stop flag is up: read after a chunk that does not
+        end the epoch, and once after the tail."""
+        k, done, stopped = self._epoch_chunk, 0, False
+        while n_mb - done >= k and not stopped:        # whole chunks: one replay each
+            g["perm"].copy_(perm[done * bs:(done + k) * bs])
+            epoch.replay()
+            done += k
+            stopped = device_stop and done < n_mb and self._hp_stopped()
+        if not stopped:
+            for j in range(done, n_mb):                # what is left of the epoch: the per-step graph
+                g["idx"].copy_(perm[j * bs:(j + 1) * bs])
+                fb.replay()
+            stopped = device_stop and self._hp_stopped()
+        return stopped
+
+    _dp_check = bool(os.environ.get("MYO_DP_CHECK"))
+
+    def _dp_compare(self, what: str, x: torch.Tensor) -> None:
+        """MYO_DP_CHECK=1 (developer diagnostic of the N > 1 path): a bit-level checksum of `x` must be the same on every rank."""
+        cs = x.detach().contiguous().view(torch.int32).to(torch.int64).sum().reshape(1)
+        lo, hi = cs.clone(), cs.clone()
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+        if int(lo[0]) != int(hi[0]) and dist.get_rank() == 0:
+            print(f"MYO_DP_CHECK: {what} differs across ranks at optimizer step {self.n_updates}", flush=True)
+
+    # ---------------------------------------------------------------- MLP policy: the fused step, captured per step and per epoch chunk
     def _build_graphs(self, B, bs):
         d = self.device
         self._gs = {"idx": torch.zeros(bs, dtype=torch.long, device=d),
@@ -826,77 +964,21 @@ class PPO:
                     "adv": torch.zeros(B, device=d), "ret": torch.zeros(B, device=d),
                     "pl": torch.zeros((), device=d), "vl": torch.zeros((), device=d)}
         self._gs["idx"].copy_(torch.arange(bs, device=d))
-        side = torch.cuda.Stream(device=d)
-        # warm-up and capture must not move the parameters.  The snapshot is taken BEFORE the side stream is told to wait: its copies run
-        # on the current stream, and a warm-up optimizer step on the side stream that overtook them left some ranks restoring a state two
-        # Adam steps ahead (round 5: replicas of >= 4 ranks sharing a GPU differed; found by the config-D-shape test)
-        snap = self._flat_adam.snapshot()
-        side.wait_stream(torch.cuda.current_stream(d))
-        with torch.cuda.stream(side):       # eager warm-up (library handles, workspaces)
-            for _ in range(2):
-                self._mb_forward_backward()
-                if self.world > 1:
-                    dist.all_reduce(self._flat_grad)
-                self._mb_apply()
-        torch.cuda.current_stream(d).wait_stream(side)
-        torch.cuda.synchronize(d)
-        self._graph_fb, self._graph_ap = torch.cuda.CUDAGraph(), None
-        import os
-        # The gradient all-reduce INSIDE the optimizer hipGraph (forward / backward -> RCCL all-reduce -> clip + Adam, one replay per
-        # minibatch): opt-in, nccl (= RCCL) only.  There is no in-process fallback from a failed capture: measured on a one-GPU box with a
-        # backend that synchronises inside the capture (gloo), the capture is invalidated, capture_end throws inside torch's graph
-        # destructor and the process dies (round 5, tests/test_gpu_parity.py).  So a backend that cannot be captured is refused up front
-        # (warning, eager collective between two graphs — the tested default), and a capture failure on nccl is raised as an error.
-        asked = self.world > 1 and (self.cfg.graph_allreduce or os.environ.get("MYO_GRAPH_ALLREDUCE") == "1")
-        want_inside = asked and dist.get_backend() == "nccl"
-        if asked and not want_inside:
-            import warnings
-            warnings.warn(f"graph_allreduce needs the nccl (RCCL) backend, this process group is {dist.get_backend()!r}: "
-                          "using the eager all-reduce between the two optimizer graphs")
-        self._allreduce_in_graph = False
-        if want_inside:
-            g_all = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(g_all, capture_error_mode="thread_local"):
-                    self._mb_forward_backward()
-                    dist.all_reduce(self._flat_grad, op=dist.ReduceOp.SUM)
-                    self._mb_apply()
-            except Exception as exc:        # noqa: BLE001
-                raise RuntimeError("capturing the RCCL gradient all-reduce inside the optimizer hipGraph failed; run without "
-                                   "graph_allreduce / MYO_GRAPH_ALLREDUCE (the eager collective between two graphs)") from exc
-            self._graph_fb, self._allreduce_in_graph = g_all, True
-        if not self._allreduce_in_graph:
-            with torch.cuda.graph(self._graph_fb, capture_error_mode="thread_local"):
-                self._mb_forward_backward()
-                if self.world == 1:             # single GPU: forward, backward and optimiser in ONE graph
-                    self._mb_apply()
-            if self.world > 1:                  # the RCCL all-reduce runs between the two graphs
-                self._graph_ap = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._graph_ap, capture_error_mode="thread_local"):
-                    self._mb_apply()
         # One GPU: a whole EPOCH in one graph — every minibatch's index copy (from a permutation buffer filled before the replay), forward /
         # backward and optimizer step: one replay instead of B / bs, no launch gap between two minibatch steps and none around the index
         # copy (13 us + a 5 us copy kernel per 135 us step at config B).  Same kernels in the same order as the per-step graph
         # (MYO_EPOCH_GRAPH=0), so the parameters come out bit-identical (tests/test_gpu_parity.py).
-        # The capture unrolls its minibatch steps, so it is CHUNKED (ADVICE r05): an SB3-style batch_size of 64 on 4096 x 64 samples is
+        # The capture unrolls its minibatch steps, so it is CHUNKED: an SB3-style batch_size of 64 on 4096 x 64 samples is
         # 4,096 steps an epoch — one graph of that would be hundreds of thousands of nodes to capture, instantiate and hold.  A chunk
         # graph holds at most MYO_EPOCH_GRAPH_STEPS (64) steps, reads its minibatches from the first k * bs entries of a chunk-sized
         # window buffer, and is replayed ceil(n / k) times per epoch (the last, shorter chunk: the per-step graph).
-        self._graph_epoch = None
         n_mb = B // bs
+        self._epoch_chunk = 0
         if self.world == 1 and os.environ.get("MYO_EPOCH_GRAPH") != "0" and n_mb > 1:
-            k = max(1, min(n_mb, int(os.environ.get("MYO_EPOCH_GRAPH_STEPS", "64"))))
-            self._epoch_chunk = k
-            self._gs["perm"] = torch.zeros(k * bs, dtype=torch.long, device=d)
-            self._gs["perm"].copy_(torch.arange(k * bs, device=d))
-            torch.cuda.synchronize(d)
-            self._graph_epoch = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph_epoch, capture_error_mode="thread_local"):
-                for s in range(0, k * bs, bs):
-                    self._gs["idx"].copy_(self._gs["perm"][s:s + bs])
-                    self._mb_forward_backward()
-                    self._mb_apply()
-        self._flat_adam.restore(snap)
+            self._epoch_chunk = max(1, min(n_mb, int(os.environ.get("MYO_EPOCH_GRAPH_STEPS", "64"))))
+        asked = self.world > 1 and (self.cfg.graph_allreduce or os.environ.get("MYO_GRAPH_ALLREDUCE") == "1")
+        self._graph_fb, self._graph_ap, self._graph_epoch, self._allreduce_in_graph = self._capture_step(
+            self._mb_forward_backward, self._gs, graph_allreduce=asked, epoch_steps=self._epoch_chunk)
         self._graph = (B, bs)
 
     def _train_graphed(self, adv, ret):
@@ -916,78 +998,11 @@ class PPO:
         g["adv"].copy_(adv.view(B)); g["ret"].copy_(ret.view(B))
         if not cfg.normalize_advantage:
             self._fused.stats.copy_(torch.tensor([0.0, 1.0], device=self.device))
-        if getattr(self, "_graph_epoch", None) is not None and not ext:
-            k, n_mb = self._epoch_chunk, B // bs
-            tkl = cfg.target_kl is not None      # then: the stop flag is read once per chunk replay / epoch (n_updates: from the block)
-            stopped = False
-            for _ in range(cfg.n_epochs):
-                self._hp_new_epoch()
-                perm = torch.randperm(B, generator=self.gen, device=self.device)
-                done = 0
-                while n_mb - done >= k and not stopped:        # whole chunks: one replay each
-                    g["perm"].copy_(perm[done * bs:(done + k) * bs])
-                    self._graph_epoch.replay()
-                    done += k
-                    stopped = tkl and done < n_mb and self._hp_stopped()
-                if not stopped:
-                    for j in range(done, n_mb):                # what is left of the epoch: the per-step graph
-                        g["idx"].copy_(perm[j * bs:(j + 1) * bs])
-                        self._graph_fb.replay()
-                    stopped = tkl and self._hp_stopped()
-                if not tkl:
-                    self.n_updates += n_mb
-                if stopped:
-                    break
-            self._fused.refresh_shadow()
-            return g["pl"], g["vl"]
-        tkl, stopped = cfg.target_kl is not None, False
-        for _ in range(cfg.n_epochs):
-            self._hp_new_epoch()
-            perm = torch.randperm(B, generator=self.gen, device=self.device)
-            for s in range(0, B - bs + 1, bs):
-                g["idx"].copy_(perm[s:s + bs])
-                if ext and cfg.normalize_advantage:
-                    a = g["adv"][perm[s:s + bs]].double()
-                    m = torch.stack([a.sum(), (a * a).sum(), torch.tensor(float(bs), dtype=torch.float64, device=self.device)])
-                    dist.all_reduce(m)
-                    mean = m[0] / m[2]
-                    std = torch.sqrt(torch.clamp(m[1] / m[2] - mean * mean, min=0.0) * m[2] / (m[2] - 1))
-                    self._fused.stats.copy_(torch.stack([mean, std]).float())
-                self._graph_fb.replay()
-                if self.world > 1 and not self._allreduce_in_graph:
-                    dist.all_reduce(self._flat_grad, op=dist.ReduceOp.SUM)
-                    if tkl and self._kl_exceeded_ranks():      # the decision between the two graphs: this step is not applied
-                        self._early_stopped = stopped = True
-                        break
-                    if self._dp_check:
-                        self._dp_compare("gradient after the all-reduce", self._flat_grad)
-                        self._dp_compare("parameters before the optimizer step", self._flat_adam.flat["p"])
-                        self._dp_compare("Adam m before the optimizer step", self._flat_adam.m)
-                        self._dp_compare("Adam v before the optimizer step", self._flat_adam.v)
-                        self._dp_compare("Adam step counter before the optimizer step", self._flat_adam._step)
-                    self._graph_ap.replay()
-                    if self._dp_check:
-                        self._dp_compare("gradient after the optimizer step", self._flat_grad)
-                        self._dp_compare("|g|^2 partial sums", self._flat_adam.sq[:64].contiguous())
-                        self._dp_compare("parameters after the optimizer step", self._flat_adam.flat["p"])
-                if not (tkl and self.world == 1):              # (one rank with target_kl: the block's applied count, see train)
-                    self.n_updates += 1
-            if tkl and self.world == 1 and not stopped:        # steps after a stop changed nothing: one read per epoch
-                stopped = self._hp_stopped()
-            if stopped:
-                break
+        self._run_captured(B, bs, g, self._graph_fb, self._graph_ap,
+                           stats=self._fused.stats if ext and cfg.normalize_advantage else None,
+                           epoch=None if ext else self._graph_epoch)
         self._fused.refresh_shadow()     # rollout inference reads the bf16 shadow weights
         return g["pl"], g["vl"]
-
-    _dp_check = bool(__import__("os").environ.get("MYO_DP_CHECK"))
-
-    def _dp_compare(self, what: str, x: torch.Tensor) -> None:
-        """MYO_DP_CHECK=1 (developer diagnostic of the N > 1 path): a bit-level checksum of `x` must be the same on every rank."""
-        cs = x.detach().contiguous().view(torch.int32).to(torch.int64).sum().reshape(1)
-        lo, hi = cs.clone(), cs.clone()
-        dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
-        if int(lo[0]) != int(hi[0]) and dist.get_rank() == 0:
-            print(f"MYO_DP_CHECK: {what} differs across ranks at optimizer step {self.n_updates}", flush=True)
 
     # ---------------------------------------------------------------- recurrent policy: one hipGraph per minibatch step
     def _rec_forward_backward(self):
@@ -1016,27 +1031,9 @@ class PPO:
         if self._fused_rec is not None:           # stacked (actor, critic) LSTM state of the rollout start
             H = self.policy.hidden
             self._rg["h0"], self._rg["c0"] = torch.zeros((2, N, H), device=d), torch.zeros((2, N, H), device=d)
-        side = torch.cuda.Stream(device=d)
-        snap = self._flat_adam.snapshot()        # (before the side stream waits: see _build_graphs)
-        side.wait_stream(torch.cuda.current_stream(d))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._rec_forward_backward()
-                if self.world > 1:
-                    dist.all_reduce(self._flat_grad)
-                self._mb_apply()
-        torch.cuda.current_stream(d).wait_stream(side)
-        torch.cuda.synchronize(d)
-        self._rgraph_fb, self._rgraph_ap = torch.cuda.CUDAGraph(), None
-        with torch.cuda.graph(self._rgraph_fb, capture_error_mode="thread_local"):
-            self._rec_forward_backward()
-            if self.world == 1:
-                self._mb_apply()
-        if self.world > 1:
-            self._rgraph_ap = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._rgraph_ap, capture_error_mode="thread_local"):
-                self._mb_apply()
-        self._flat_adam.restore(snap)
+        # (BPTT over n_steps is one graph per minibatch already: no all-reduce inside the graph and no epoch-chunk graph here)
+        self._rgraph_fb, self._rgraph_ap, _, _ = self._capture_step(self._rec_forward_backward, self._rg, graph_allreduce=False,
+                                                                    epoch_steps=0)
         self._rgraph = (T, N, m)
 
     def _rec_stage(self, adv, ret, T, N, m):
@@ -1047,7 +1044,7 @@ class PPO:
             if self._fused_rec.external_adv_stats != ext:
                 self._fused_rec.external_adv_stats = ext
                 self._rgraph = None
-        if getattr(self, "_rgraph", None) != (T, N, m):
+        if self._rgraph != (T, N, m):
             self._build_recurrent_graphs(T, N, m)
             self._hp_write()             # (the capture's warm-up steps have left their marks in the block)
         g = self._rg
@@ -1070,32 +1067,8 @@ class PPO:
         T, N = cfg.n_steps, self.env.num_envs
         m = max(1, min(N, cfg.batch_size // T))
         g, fr = self._rec_stage(adv, ret, T, N, m), self._fused_rec
-        tkl, stopped = cfg.target_kl is not None, False
-        for _ in range(cfg.n_epochs):
-            self._hp_new_epoch()
-            perm = torch.randperm(N, generator=self.gen, device=self.device)
-            for s in range(0, N - m + 1, m):
-                g["idx"].copy_(perm[s:s + m])
-                if fr is not None and fr.external_adv_stats and cfg.normalize_advantage:      # moments of the GLOBAL minibatch
-                    a = g["adv"][:, perm[s:s + m]].double()
-                    mom = torch.stack([a.sum(), (a * a).sum(), torch.tensor(float(a.numel()), dtype=torch.float64, device=self.device)])
-                    dist.all_reduce(mom)
-                    mean = mom[0] / mom[2]
-                    std = torch.sqrt(torch.clamp(mom[1] / mom[2] - mean * mean, min=0.0) * mom[2] / (mom[2] - 1))
-                    fr.stats.copy_(torch.stack([mean, std]).float())
-                self._rgraph_fb.replay()
-                if self.world > 1:
-                    dist.all_reduce(self._flat_grad, op=dist.ReduceOp.SUM)
-                    if tkl and self._kl_exceeded_ranks():      # the decision between the two graphs: this step is not applied
-                        self._early_stopped = stopped = True
-                        break
-                    self._rgraph_ap.replay()
-                if not (tkl and self.world == 1):
-                    self.n_updates += 1
-            if tkl and self.world == 1 and not stopped:        # steps after a stop changed nothing: one read per epoch
-                stopped = self._hp_stopped()
-            if stopped:
-                break
+        global_moments = fr is not None and fr.external_adv_stats and cfg.normalize_advantage
+        self._run_captured(N, m, g, self._rgraph_fb, self._rgraph_ap, stats=fr.stats if global_moments else None)
         return g["pl"], g["vl"]
 
     # ---------------------------------------------------------------- persistence (SB3 zip layout)

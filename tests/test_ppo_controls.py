@@ -173,6 +173,34 @@ def test_myotrainer_passes_the_controls_on(emu_lib, tmp_path):
     env.close()
 
 
+@pytest.mark.parametrize("dtype,rel", [(torch.float32, 1e-6), (torch.float64, 1e-12)], ids=["f32", "f64"])
+def test_global_adv_moments_one_rank(emu_lib, dtype, rel):
+    """One rank: the all-reduced moments are the minibatch's own mean and unbiased std, in the dtype given."""
+    env, algo = _cpu_algo(emu_lib, None)
+    a = torch.randn(7, dtype=dtype, generator=torch.Generator().manual_seed(3))
+    mean, std = algo._global_adv_moments(a)
+    assert mean.dtype == dtype and std.dtype == dtype
+    assert float(mean) == pytest.approx(float(a.mean()), rel=rel) and float(std) == pytest.approx(float(a.std()), rel=rel)
+    env.close()
+
+
+@pytest.mark.parametrize("hidden", [None, 8], ids=["mlp", "lstm"])
+def test_init_sets_every_attribute(emu_lib, hidden):
+    """PPO.__init__ gives every attribute a value: the state that rollout, update and episode log fill in later is there from the
+    start (None / False / 0), and a rollout, an update and episode_stats() add no attribute."""
+    env, algo = _cpu_algo(emu_lib, hidden)
+    at_init = set(vars(algo))
+    late = {"_native", "_rollout_ready", "_gB2", "_sde_W", "vn_allreduce_seconds", "vn_allreduce_calls", "_ep_log", "_ep_nan_t",
+            "ep_info_buffer", "_graph", "_gs", "_graph_fb", "_graph_ap", "_graph_epoch", "_rgraph", "_rg", "_rgraph_fb", "_rgraph_ap",
+            "_allreduce_in_graph", "_last_values", "_early_stopped", "_last_diag", "_fused", "_fused_rec", "_flat_adam", "_hp"}
+    assert late <= at_init, sorted(late - at_init)
+    assert algo._native is False and algo._rollout_ready is False and algo._graph_epoch is None and algo._rgraph is None
+    assert algo.vn_allreduce_seconds == 0.0 and algo.vn_allreduce_calls == 0
+    algo.collect_rollouts(); algo.train(); algo.episode_stats()
+    assert set(vars(algo)) == at_init, sorted(set(vars(algo)) - at_init)
+    env.close()
+
+
 # ------------------------------------------------------------------------------------------------ GPU: the hyper-parameter block
 def _hp_block(dev, lr, clip, limit):
     hp = torch.zeros(native.HP_WORDS, device=dev)

@@ -497,7 +497,7 @@ def test_recurrent_update_graph_matches_eager(hip_lib, monkeypatch):
     b._last_values, b._last_starts = a._last_values.clone(), a._last_starts.clone()
     b._rollout_state0 = tuple(x.clone() for x in a._rollout_state0)
     sa, sb = a.train(), b.train()
-    assert hasattr(a, "_rgraph_fb") and a.n_updates == b.n_updates == 1
+    assert a._rgraph_fb is not None and a.n_updates == b.n_updates == 1
     assert abs(sa["policy_loss"] - sb["policy_loss"]) < 1e-4 * (1 + abs(sb["policy_loss"]))
     assert abs(sa["value_loss"] - sb["value_loss"]) < 1e-4 * (1 + abs(sb["value_loss"]))
     for (n, p), q in zip(pol.named_parameters(), pol2.parameters()):
