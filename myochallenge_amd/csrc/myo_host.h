@@ -1,7 +1,8 @@
 // myo_host.h — the host side both builds of libmyobatch share: error reporting, the host model (blob -> tables), the batch
-// (records, layouts, task block) and myo_batch_create / _destroy.  Included by csrc/myobatch.hip (the product: the HIP backend, the
-// kernels and every entry point) and by csrc/myobatch_emu.cpp (test tooling: csrc/emu_host.h runs the same kernel SOURCE lane by lane
-// on the CPU).  The including file defines, before the include:
+// (records, layouts, task block), myo_batch_create / _destroy, the kernel variant of a batch (with_variant) with its LDS footprint,
+// the entry points that only read or write env records, and the argument checks of the others.  Included by csrc/myobatch.hip (the
+// product: the HIP backend, the kernels and the launching entry points) and by csrc/myobatch_emu.cpp (test tooling: csrc/emu_host.h runs
+// the same kernel SOURCE lane by lane on the CPU).  The including file defines, before the include:
 //   MYO_BACKEND_NAME           "gfx950" | "MYO_EMU lane-serial test build"   (myo_version)
 //   MYO_BACKEND_DENSE_NEWTON   0 | 1: factor the Newton system densely (no block-arrow tables)
 //   MYO_BACKEND_BATCH_FIELDS   members the backend keeps in struct myo_batch
@@ -37,6 +38,12 @@ static const char* be_errstr(int e);
 static int be_batch_workspaces(myo_batch* b, int n_envs, int device);                      // the fp64 stepper's workspaces (TaskDev::ctrl_ws / big_ws); returns error bits
 static int be_batch_launch_state(myo_batch* b, const myo_model* m, int n_envs, int rc);    // what the launches need beside the records; returns rc | its own error bits
 static void be_batch_release(myo_batch* b, int device, int destroying);                    // ... and their release (destroying = 0: a failed myo_batch_create)
+// record gather / scatter: field [off, off + cnt) of every env's record <-> ext[n, cnt] (to_ext = 1: record -> ext); a null ext is skipped.
+// `stream` is the ABI's (a hipStream_t, or unused)
+static void be_xfer(myo_batch* b, int off, int cnt, double* ext, int to_ext, void* stream);
+static void be_xfer_i(myo_batch* b, int off, int cnt, int* ext, int to_ext, void* stream);   // ... of a field that holds integers
+static int be_launch_status();                                                             // MYO_OK, or what became of the launches just issued (MYO_E_DEVICE)
+static void be_task_changed(myo_batch* b);                                                 // the host's task block (b->K) changed: what was issued is waited for, the next launch uploads it again
 
 static thread_local char g_err[4096] = "";      // (room for a loader report that lists every unsupported feature of a model)
 static int fail(int code, const char* fmt, ...) {
@@ -1022,6 +1029,33 @@ struct myo_batch {
   MYO_BACKEND_BATCH_FIELDS     // what the backend keeps per batch (the HIP backend: its timing events)
 };
 
+// ---- the kernel variant of a batch.  Every kernel that works on an env, and the lane-serial emulation of it, exists per arithmetic T,
+// per integrator (RK: the model integrates with RK4 and the variant has the stage storage) and per contact capacity NC of the scratch
+// (each arithmetic's base capacity, or MYO_NCON_BIG for models with extended collision pairs or a die: myo_batch::ncap).  with_variant
+// is the one place that maps a batch to its variant: f(KernelVariant<T, RK, NC>{}) is called with the batch's, and its result returned.
+template <typename T_, bool RK_, int NC_>
+struct KernelVariant { using T = T_; static constexpr bool RK = RK_; static constexpr int NC = NC_; };
+template <typename F>
+static auto with_variant(const myo_batch* b, F&& f) {
+  const bool rk = b->integrator == 1, big = b->ncap > MYO_NCON_MAX;
+  if (b->dtype == MYO_F64) {
+    if (big) return rk ? f(KernelVariant<double, true, MYO_NCON_BIG>{}) : f(KernelVariant<double, false, MYO_NCON_BIG>{});
+    return rk ? f(KernelVariant<double, true, MYO_NCON_F64>{}) : f(KernelVariant<double, false, MYO_NCON_F64>{});
+  }
+  if (big) return rk ? f(KernelVariant<float, true, MYO_NCON_BIG>{}) : f(KernelVariant<float, false, MYO_NCON_BIG>{});
+  return rk ? f(KernelVariant<float, true, MYO_NCON_MAX>{}) : f(KernelVariant<float, false, MYO_NCON_MAX>{});
+}
+// Dynamic LDS of a variant's workgroup: the scratch, and behind it (aligned) the RK4 stage storage where that lives in LDS — the mixed
+// stepper with the base contact capacity (16,384 + 1,360 B: still eight workgroups per CU; the per-workgroup block in global memory
+// cost a global round trip in each of the ~5 bookkeeping phases of a stage); elsewhere it is in global memory (fp64: 31.6 KB + 1.8 KB
+// would lose the fifth workgroup per CU).  The kernels' rk_storage() places the block by the same two macros.
+#define MYO_LDS_ALIGN(n) (((n) + 15) / 16 * 16)
+#define MYO_RK_IN_LDS(T, NC) (sizeof(T) == 4 && (NC) == MYO_NCON_MAX)
+template <typename T, bool RK, int NC>
+constexpr size_t variant_lds_bytes() {
+  return RK && MYO_RK_IN_LDS(T, NC) ? MYO_LDS_ALIGN(sizeof(Scratch<T, NC>)) + sizeof(RkScratch<T>) : sizeof(Scratch<T, NC>);
+}
+
 template <typename T>
 static int upload_model(const myo_model* m, DevModel<T>& D, std::vector<void*>& allocs) {
   D.nq = m->nq; D.nv = m->nv; D.nu = m->nu; D.na = m->na; D.nbody = m->nbody; D.njnt = m->njnt; D.ngeom = m->ngeom;
@@ -1412,11 +1446,7 @@ extern "C" int myo_batch_num_envs(const myo_batch* b) { return b ? b->n : -1; }
 extern "C" int myo_batch_obs_dim(const myo_batch* b) { return b ? b->nobs : -1; }
 extern "C" int myo_batch_lds_bytes(const myo_batch* b) {
   if (!b) return -1;
-  const bool big = b->ncap > MYO_NCON_MAX;
-  if (b->dtype == MYO_F64) return big ? (int)sizeof(Scratch<double, MYO_NCON_BIG>) : (int)sizeof(Scratch<double, MYO_NCON_F64>);
-  if (big) return (int)sizeof(Scratch<float, MYO_NCON_BIG>);
-  // mixed stepper, base capacity: an RK4 model keeps its stage storage behind the scratch (MYO_RK_IN_LDS); elsewhere it is in global memory
-  return (int)(((sizeof(Scratch<float>) + 15) / 16 * 16) * (b->integrator == 1 ? 1 : 0) + (b->integrator == 1 ? sizeof(RkScratch<float>) : sizeof(Scratch<float>)));
+  return with_variant(b, [](auto v) { using V = decltype(v); return (int)variant_lds_bytes<typename V::T, V::RK, V::NC>(); });
 }
 extern "C" int myo_batch_dump_size(const myo_batch* b) { return b ? b->D.total : -1; }
 extern "C" int myo_batch_dump_offset(const myo_batch* b, const char* n) {
@@ -1428,3 +1458,113 @@ extern "C" int myo_batch_dump_offset(const myo_batch* b, const char* n) {
   return -1;
 }
 
+// ---- the entry points that only read or write env records: the same in both backends (include/myobatch.h documents them)
+static int batch_check(const myo_batch* b) { return b ? MYO_OK : fail(MYO_E_ARG, "null batch"); }
+extern "C" int myo_batch_get_state(myo_batch* b, double* qpos, double* qvel, double* act, double* time, void* stream) {
+  if (int rc = batch_check(b)) return rc;
+  be_xfer(b, b->L.off_qpos, b->nq, qpos, 1, stream); be_xfer(b, b->L.off_qvel, b->nv, qvel, 1, stream);
+  be_xfer(b, b->L.off_act, b->na, act, 1, stream); be_xfer(b, b->L.off_time, 1, time, 1, stream);
+  return be_launch_status();
+}
+extern "C" int myo_batch_set_state(myo_batch* b, const double* qpos, const double* qvel, const double* act,
+                                   const double* time, void* stream) {
+  if (int rc = batch_check(b)) return rc;
+  be_xfer(b, b->L.off_qpos, b->nq, (double*)qpos, 0, stream); be_xfer(b, b->L.off_qvel, b->nv, (double*)qvel, 0, stream);
+  be_xfer(b, b->L.off_act, b->na, (double*)act, 0, stream); be_xfer(b, b->L.off_time, 1, (double*)time, 0, stream);
+  return be_launch_status();
+}
+extern "C" int myo_batch_set_bad_state_buffer(myo_batch* b, uint8_t* bad_state) {
+  if (int rc = batch_check(b)) return rc;
+  b->bad_state = bad_state;
+  return MYO_OK;
+}
+extern "C" int myo_batch_warmstart(myo_batch* b, double* get_w, const double* set_w, void* stream) {
+  if (int rc = batch_check(b)) return rc;
+  be_xfer(b, b->L.off_warm, b->nv, get_w, 1, stream); be_xfer(b, b->L.off_warm, b->nv, (double*)set_w, 0, stream);
+  return be_launch_status();
+}
+// task_i, task_d and ball_d of myo_batch_set_task / _get_task; what task_d is depends on the task kind
+static void task_xfer(myo_batch* b, int32_t* task_i, double* task_d, double* ball_d, int to_ext, void* stream) {
+  be_xfer_i(b, b->L.off_misc, 2, (int*)task_i, to_ext, stream);
+  if (b->K.kind == MYO_TASK_POSE) be_xfer(b, b->L.off_pose, 2 * b->nq, task_d, to_ext, stream);     // target_qpos | init_qpos
+  else be_xfer(b, b->L.off_taskd, MYO_TASKD_N, task_d, to_ext, stream);
+  be_xfer(b, b->L.off_balld, MYO_BALLD_N, ball_d, to_ext, stream);
+}
+extern "C" int myo_batch_set_task(myo_batch* b, const int32_t* task_i, const double* task_d, const double* ball_d, void* stream) {
+  if (int rc = batch_check(b)) return rc;
+  task_xfer(b, (int32_t*)task_i, (double*)task_d, (double*)ball_d, 0, stream);
+  return be_launch_status();
+}
+extern "C" int myo_batch_get_task(myo_batch* b, int32_t* task_i, double* task_d, double* ball_d, void* stream) {
+  if (int rc = batch_check(b)) return rc;
+  task_xfer(b, task_i, task_d, ball_d, 1, stream);
+  return be_launch_status();
+}
+extern "C" int myo_batch_set_object_group(myo_batch* b, int gid0, int gidn) {
+  if (int rc = batch_check(b)) return rc;
+  if (!(gid0 == -1 && gidn == -1) && (gid0 < 0 || gidn <= gid0 || gidn > b->ngeom)) return fail(MYO_E_ARG, "bad geom range");
+  if (b->K.kind != MYO_TASK_NONE) return fail(MYO_E_STATE, "object groups are for physics-only batches (the reorient task owns its own; the Baoding tasks have the two balls)");
+  if (gidn - gid0 > MYO_OBJG_MAX) return fail(MYO_E_UNSUPPORTED, "an object group holds at most %d geoms", MYO_OBJG_MAX);
+  b->K.objg_gid0 = gid0; b->K.objg_gidn = gidn;
+  void* tmp = nullptr;
+  if (gidn > 0) {   // every env starts from the model's friction of the group's geoms
+    const int cnt = 3 * (gidn - gid0);
+    std::vector<double> host((size_t)b->n * cnt);
+    for (int e = 0; e < b->n; ++e) for (int j = 0; j < cnt; ++j) host[(size_t)e * cnt + j] = b->geom_friction[3 * gid0 + j];
+    int rc = be_malloc(&tmp, host.size() * sizeof(double));
+    if (!rc) rc = be_h2d(tmp, host.data(), host.size() * sizeof(double));
+    if (rc) { if (tmp) be_free(tmp); return fail(MYO_E_DEVICE, "object group upload failed: %s", be_errstr(rc)); }
+    be_xfer(b, b->L.off_objfric, cnt, (double*)tmp, 0, nullptr);
+  }
+  be_task_changed(b);
+  if (tmp) be_free(tmp);
+  return MYO_OK;
+}
+extern "C" int myo_batch_object_friction(myo_batch* b, const double* set_fric, double* get_fric, void* stream) {
+  if (int rc = batch_check(b)) return rc;
+  if (b->K.objg_gidn <= 0) return fail(MYO_E_STATE, "batch has no object group");
+  const int cnt = 3 * (b->K.objg_gidn - b->K.objg_gid0);
+  be_xfer(b, b->L.off_objfric, cnt, (double*)set_fric, 0, stream); be_xfer(b, b->L.off_objfric, cnt, get_fric, 1, stream);
+  return be_launch_status();
+}
+extern "C" int myo_batch_enable_timing(myo_batch* b, int on) {
+  if (int rc = batch_check(b)) return rc;
+  b->timing = on;
+  return MYO_OK;
+}
+
+// ---- what both backends check before the launches of the other entry points
+static int task_layer_check(const myo_batch* b) { return b->K.kind ? MYO_OK : fail(MYO_E_STATE, "batch has no task layer"); }
+static int reset_check(const myo_batch* b) {
+  if (int rc = batch_check(b)) return rc;
+  return task_layer_check(b);
+}
+static int step_check(const myo_batch* b, const float* act, const float* obs, const float* rew, const uint8_t* done) {
+  if (!b || !act || !obs || !rew || !done) return fail(MYO_E_ARG, "myo_batch_step: act/obs/rew/done are required");
+  return task_layer_check(b);
+}
+static int step_inner_check(const myo_batch* b, const float* act, const float* obs) {
+  if (!b || !act || !obs) return fail(MYO_E_ARG, "myo_batch_step_inner: act/obs are required");
+  return task_layer_check(b);
+}
+static int step_inner_idx_check(const myo_batch* b, const int* idx, int n_idx, const float* act, const float* obs) {
+  if (!b || !idx || !act || !obs || n_idx <= 0) return fail(MYO_E_ARG, "myo_batch_step_inner_idx: idx/act/obs are required");
+  return task_layer_check(b);
+}
+static int physics_step_check(const myo_batch* b, int nsub) { return b && nsub >= 0 ? MYO_OK : fail(MYO_E_ARG, "bad arguments"); }
+static int forward_dump_check(const myo_batch* b, const double* out) { return b && out ? MYO_OK : fail(MYO_E_ARG, "bad arguments"); }
+// k = 0 is an empty copy (*empty)
+static int copy_envs_check(const myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, int* empty) {
+  if (!dst || !src || !dst_idx || !src_idx || k < 0) return fail(MYO_E_ARG, "myo_batch_copy_envs: null argument");
+  if (dst->L.stride != src->L.stride || dst->nq != src->nq || dst->nv != src->nv || dst->na != src->na || dst->K.kind != src->K.kind || dst->device != src->device)
+    return fail(MYO_E_ARG, "myo_batch_copy_envs: the two batches differ in model, task kind or device");
+  *empty = k == 0;
+  return MYO_OK;
+}
+// out is zeroed; a batch without counters has nothing more to report (*empty)
+static int health_check(const myo_batch* b, int out[4], int* empty) {
+  if (!b || !out) return fail(MYO_E_ARG, "null argument");
+  for (int k = 0; k < 4; ++k) out[k] = 0;
+  *empty = !b->K.health;
+  return MYO_OK;
+}

@@ -1,7 +1,8 @@
-// myobatch.hip — libmyobatch (C ABI in include/myobatch.h): the HIP backend, the gfx950 kernels and every entry point.
+// myobatch.hip — libmyobatch (C ABI in include/myobatch.h): the HIP backend, the gfx950 kernels and the entry points that launch them.
 //   hipcc --offload-arch=gfx950  -> libmyobatch.so   (the product; no CPU path)
 // One workgroup = one wavefront = one environment; grid = number of environments.
-// The host side it shares with the test tooling (model tables, batch records, myo_batch_create) is csrc/myo_host.h; the lane-serial
+// The host side it shares with the test tooling (model tables, batch records, myo_batch_create, the kernel variant of a batch, the record
+// accessors and the argument checks) is csrc/myo_host.h; the lane-serial
 // emulation of the same kernel SOURCE is another translation unit (csrc/myobatch_emu.cpp + csrc/emu_host.h), not a path of this one.
 #include <hip/hip_runtime.h>
 #include <utility>
@@ -12,7 +13,6 @@
 #include "myo_host.h"
 
 // ------------------------------------------------------------------------------------------ backend
-typedef hipStream_t be_stream;
 static int be_malloc(void** p, size_t n) { return (int)hipMalloc(p, n ? n : 1); }
 static void be_free(void* p) { (void)hipFree(p); }
 static int be_h2d(void* d, const void* h, size_t n) { return (int)hipMemcpy(d, h, n, hipMemcpyHostToDevice); }
@@ -116,7 +116,6 @@ static int bind_constants(myo_batch* b, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------ kernels
-#define MYO_LDS_ALIGN(n) (((n) + 15) / 16 * 16)
 #ifdef MYO_PROF
 __device__ unsigned long long g_prof[MYO_NPROF];
 extern "C" int myo_debug_read_prof(double* out16, int reset) {     /* out16: MYO_NPROF (32) doubles */
@@ -127,10 +126,8 @@ extern "C" int myo_debug_read_prof(double* out16, int reset) {     /* out16: MYO
   return 0;
 }
 #endif
-// RK4 stage storage of this workgroup: behind the scratch in LDS for the mixed stepper with the base contact capacity (18,384 +
-// 1,360 B: still eight workgroups per CU; the per-workgroup block in global memory cost a global round trip in each of the
-// ~5 bookkeeping phases of a stage), in global memory otherwise (fp64: 31.6 KB + 1.8 KB would lose the fifth workgroup per CU)
-#define MYO_RK_IN_LDS(T, NC) (sizeof(T) == 4 && (NC) == MYO_NCON_MAX)
+// RK4 stage storage of this workgroup: behind the scratch in LDS where MYO_RK_IN_LDS says so (csrc/myo_host.h: variant_lds_bytes sizes
+// the launch by the same macros), in global memory otherwise
 static_assert(MYO_LDS_ALIGN(sizeof(Scratch<float, MYO_NCON_MAX>)) + sizeof(RkScratch<float>) <= 20480, "RK4 stage storage next to the scratch: eight workgroups per CU");
 template <typename T, bool RK, int NC>
 __device__ __forceinline__ RkScratch<T>* rk_storage() {
@@ -447,11 +444,7 @@ __global__ void k_state_i(double* rec, int stride, int off, int cnt, int n, int*
   const int e = (int)(i / cnt), k = (int)(i % cnt);
   if (to_ext) ext[i] = (int)rec[(size_t)e * stride + off + k]; else rec[(size_t)e * stride + off + k] = (double)ext[i];
 }
-#define LAUNCH_CHECK(b)                                                                          \
-  {                                                                                              \
-    hipError_t _e = hipGetLastError();                                                           \
-    if (_e != hipSuccess) return fail(MYO_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(_e)); \
-  }
+#define LAUNCH_CHECK(b) { if (int _rc = be_launch_status()) return _rc; }      /* (the PPO-side entry points below) */
 static void timing_begin(myo_batch* b, hipStream_t st) {
   if (!b->timing) return;
   hipEvent_t a, c;
@@ -536,109 +529,32 @@ static void be_batch_release(myo_batch* b, int device, int destroying) {
   if (b->has_big_ws) big_workspace_release(b->device);
 }
 
-static void xfer(myo_batch* b, int off, int cnt, double* ext, int to_ext, be_stream st) {
+static void be_xfer(myo_batch* b, int off, int cnt, double* ext, int to_ext, void* stream) {
   if (!ext) return;
   DeviceGuard guard(b->device);
   const long long tot = (long long)b->n * cnt;
-  hipLaunchKernelGGL(k_state, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, b->rec, b->L.stride, off, cnt, b->n, ext, to_ext);
+  hipLaunchKernelGGL(k_state, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, b->rec, b->L.stride, off, cnt, b->n, ext, to_ext);
 }
-static void xfer_i(myo_batch* b, int off, int cnt, int* ext, int to_ext, be_stream st) {
+static void be_xfer_i(myo_batch* b, int off, int cnt, int* ext, int to_ext, void* stream) {
   if (!ext) return;
   DeviceGuard guard(b->device);
   const long long tot = (long long)b->n * cnt;
-  hipLaunchKernelGGL(k_state_i, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, b->rec, b->L.stride, off, cnt, b->n, ext, to_ext);
+  hipLaunchKernelGGL(k_state_i, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, b->rec, b->L.stride, off, cnt, b->n, ext, to_ext);
+}
+static int be_launch_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MYO_OK : fail(MYO_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
+}
+static void be_task_changed(myo_batch* b) {
+  (void)hipStreamSynchronize((hipStream_t)0);
+  unbind(b, b->device);              // the task block in __constant__ memory is re-uploaded at the next launch
 }
 
-extern "C" int myo_batch_get_state(myo_batch* b, double* qpos, double* qvel, double* act, double* time, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
-  be_stream st = (be_stream)stream;
-  xfer(b, b->L.off_qpos, b->nq, qpos, 1, st); xfer(b, b->L.off_qvel, b->nv, qvel, 1, st);
-  xfer(b, b->L.off_act, b->na, act, 1, st); xfer(b, b->L.off_time, 1, time, 1, st);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
-}
-extern "C" int myo_batch_set_state(myo_batch* b, const double* qpos, const double* qvel, const double* act,
-                                   const double* time, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
-  be_stream st = (be_stream)stream;
-  xfer(b, b->L.off_qpos, b->nq, (double*)qpos, 0, st); xfer(b, b->L.off_qvel, b->nv, (double*)qvel, 0, st);
-  xfer(b, b->L.off_act, b->na, (double*)act, 0, st); xfer(b, b->L.off_time, 1, (double*)time, 0, st);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
-}
-extern "C" int myo_batch_set_bad_state_buffer(myo_batch* b, uint8_t* bad_state) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
-  b->bad_state = bad_state;
-  return MYO_OK;
-}
-extern "C" int myo_batch_warmstart(myo_batch* b, double* get_w, const double* set_w, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
-  be_stream st = (be_stream)stream;
-  xfer(b, b->L.off_warm, b->nv, get_w, 1, st); xfer(b, b->L.off_warm, b->nv, (double*)set_w, 0, st);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
-}
-extern "C" int myo_batch_set_task(myo_batch* b, const int32_t* task_i, const double* task_d, const double* ball_d, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
-  be_stream st = (be_stream)stream;
-  xfer_i(b, b->L.off_misc, 2, (int*)task_i, 0, st);
-  if (b->K.kind == MYO_TASK_POSE) xfer(b, b->L.off_pose, 2 * b->nq, (double*)task_d, 0, st);     // target_qpos | init_qpos
-  else xfer(b, b->L.off_taskd, MYO_TASKD_N, (double*)task_d, 0, st);
-  xfer(b, b->L.off_balld, MYO_BALLD_N, (double*)ball_d, 0, st);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
-}
-extern "C" int myo_batch_set_object_group(myo_batch* b, int gid0, int gidn) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
-  if (!(gid0 == -1 && gidn == -1) && (gid0 < 0 || gidn <= gid0 || gidn > b->ngeom)) return fail(MYO_E_ARG, "bad geom range");
-  if (b->K.kind != MYO_TASK_NONE) return fail(MYO_E_STATE, "object groups are for physics-only batches (the reorient task owns its own; the Baoding tasks have the two balls)");
-  if (gidn - gid0 > MYO_OBJG_MAX) return fail(MYO_E_UNSUPPORTED, "an object group holds at most %d geoms", MYO_OBJG_MAX);
-  b->K.objg_gid0 = gid0; b->K.objg_gidn = gidn;
-  if (gidn > 0) {   // every env starts from the model's friction of the group's geoms
-    const int cnt = 3 * (gidn - gid0);
-    std::vector<double> host((size_t)b->n * cnt);
-    for (int e = 0; e < b->n; ++e) for (int j = 0; j < cnt; ++j) host[(size_t)e * cnt + j] = b->geom_friction[3 * gid0 + j];
-    void* tmp = nullptr;
-    int rc = be_malloc(&tmp, host.size() * sizeof(double));
-    if (!rc) rc = be_h2d(tmp, host.data(), host.size() * sizeof(double));
-    if (rc) { if (tmp) be_free(tmp); return fail(MYO_E_DEVICE, "object group upload failed: %s", be_errstr(rc)); }
-    xfer(b, b->L.off_objfric, cnt, (double*)tmp, 0, (be_stream)0);
-    (void)hipStreamSynchronize((hipStream_t)0);
-    be_free(tmp);
-  }
-  unbind(b, b->device);              // the task block in __constant__ memory is re-uploaded at the next launch
-  return MYO_OK;
-}
-extern "C" int myo_batch_object_friction(myo_batch* b, const double* set_fric, double* get_fric, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
-  if (b->K.objg_gidn <= 0) return fail(MYO_E_STATE, "batch has no object group");
-  be_stream st = (be_stream)stream;
-  const int cnt = 3 * (b->K.objg_gidn - b->K.objg_gid0);
-  xfer(b, b->L.off_objfric, cnt, (double*)set_fric, 0, st); xfer(b, b->L.off_objfric, cnt, get_fric, 1, st);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
-}
 extern "C" int myo_batch_bind_constants(myo_batch* b, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
+  if (int rc = batch_check(b)) return rc;
   DeviceGuard guard(b->device);
   return bind_constants(b, (hipStream_t)stream);
 }
-extern "C" int myo_batch_get_task(myo_batch* b, int32_t* task_i, double* task_d, double* ball_d, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
-  be_stream st = (be_stream)stream;
-  xfer_i(b, b->L.off_misc, 2, (int*)task_i, 1, st);
-  if (b->K.kind == MYO_TASK_POSE) xfer(b, b->L.off_pose, 2 * b->nq, task_d, 1, st);
-  else xfer(b, b->L.off_taskd, MYO_TASKD_N, task_d, 1, st);
-  xfer(b, b->L.off_balld, MYO_BALLD_N, ball_d, 1, st);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
-}
-
-// the RK4 stage storage is only allocated (LDS) by the kernel variants of RK4 models
-// ... and the scratch's contact capacity (NCV) is the batch's: MYO_NCON_BIG for models with extended collision pairs or a die
-#define MYO_NC_D(n) ((n) == MYO_NCON_MAX ? MYO_NCON_F64 : (n))     /* the fp64 stepper's scratch has its own base capacity */
-#define LAUNCH_RK1(b, ...) if ((b)->integrator == 1) { constexpr bool RKV = true; __VA_ARGS__; } else { constexpr bool RKV = false; __VA_ARGS__; }
-#define LAUNCH_RK(b, ...) if ((b)->ncap > MYO_NCON_MAX) { constexpr int NCV = MYO_NCON_BIG; LAUNCH_RK1(b, __VA_ARGS__) } else { constexpr int NCV = MYO_NCON_MAX; LAUNCH_RK1(b, __VA_ARGS__) }
 
 // census of the wraps over the envs' present states, then the new order (both on the stream: usable between any two steps, also while
 // a graph of steps exists — the tables are rewritten in place)
@@ -647,47 +563,45 @@ static void wrap_order_launch(myo_batch* b, hipStream_t st) {
   int* gw = const_cast<int*>(b->dtype == MYO_F64 ? b->Md.gw_elem.p : b->Mf.gw_elem.p);
   int* wr = const_cast<int*>(b->dtype == MYO_F64 ? b->Md.wr_i.p : b->Mf.wr_i.p);
   const int ngw = b->dtype == MYO_F64 ? b->Md.ngw : b->Mf.ngw;
-  LAUNCH_RK(b,
-    if (b->dtype == MYO_F64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wrap_census<double, RKV, MYO_NC_D(NCV)>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, b->wrap_cnt);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wrap_census<float, RKV, NCV>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, b->wrap_cnt))
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wrap_census<typename V::T, V::RK, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, b->wrap_cnt);
+  });
   hipLaunchKernelGGL(k_wrap_reorder, dim3(1), dim3(64), 0, st, ngw, b->wrap_cnt, gw, wr);
 }
 extern "C" int myo_batch_tune_wrap_order(myo_batch* b, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
+  if (int rc = batch_check(b)) return rc;
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
   wrap_order_launch(b, st);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
+  return be_launch_status();
 }
 
 extern "C" int myo_batch_reset(myo_batch* b, const uint8_t* mask, float* obs, void* stream) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
-  if (!b->K.kind) return fail(MYO_E_STATE, "batch has no task layer");
+  if (int rc = reset_check(b)) return rc;
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
-  LAUNCH_RK(b,
-    if (b->dtype == MYO_F64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reset<double, RKV, MYO_NC_D(NCV)>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, mask, obs);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reset<float, RKV, NCV>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, mask, obs))
-  LAUNCH_CHECK(b)
-  if (!mask) { wrap_order_launch(b, st); b->wrap_tune_in = 16; LAUNCH_CHECK(b) }       // a reset of every env: the wrap order from the reset states, again 16 steps on
-  return MYO_OK;
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reset<typename V::T, V::RK, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, mask, obs);
+  });
+  if (int rc = be_launch_status()) return rc;
+  if (!mask) { wrap_order_launch(b, st); b->wrap_tune_in = 16; }       // a reset of every env: the wrap order from the reset states, again 16 steps on
+  return be_launch_status();
 }
 
 extern "C" int myo_batch_step(myo_batch* b, const float* act, float* obs, float* rew, uint8_t* done, uint8_t* trunc,
                               float* term_obs, float* comps, float* ep_info, void* stream) {
-  if (!b || !act || !obs || !rew || !done) return fail(MYO_E_ARG, "myo_batch_step: act/obs/rew/done are required");
-  if (!b->K.kind) return fail(MYO_E_STATE, "batch has no task layer");
+  if (int rc = step_check(b, act, obs, rew, done)) return rc;
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
   timing_begin(b, st);
-  LAUNCH_RK(b,
-    if (b->dtype == MYO_F64)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step<double, RKV, MYO_NC_D(NCV)>), dim3(b->plan.nparts * b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, act, obs, rew, done, trunc, term_obs, comps, ep_info, b->bad_state, b->order, b->ticks, b->part_state, b->step_gen, b->plan);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step<float, RKV, NCV>), dim3(b->plan.nparts * b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, act, obs, rew, done, trunc, term_obs, comps, ep_info, b->bad_state, b->order, b->ticks, b->part_state, b->step_gen, b->plan))
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step<typename V::T, V::RK, V::NC>), dim3(b->plan.nparts * b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, act, obs, rew, done, trunc, term_obs, comps, ep_info, b->bad_state, b->order, b->ticks, b->part_state, b->step_gen, b->plan);
+  });
   timing_end(b, st);
-  LAUNCH_CHECK(b)                 // the generation below only advances behind a k_step that was launched
+  if (int rc = be_launch_status()) return rc;      // the generation below only advances behind a k_step that was launched
   if (b->wrap_cnt && --b->wrap_tune_in <= 0) {       // the wrap order follows the states the envs are in (env_wrap_census)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(st, &cap);
@@ -695,14 +609,13 @@ extern "C" int myo_batch_step(myo_batch* b, const float* act, float* obs, float*
     else b->wrap_tune_in = 1;
   }
   if (b->order || b->step_gen) hipLaunchKernelGGL(k_step_order, dim3(1), dim3(b->order ? 1024 : 64), 0, st, (const unsigned int*)b->ticks, b->cost, b->n, b->order, b->step_gen);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
+  return be_launch_status();
 }
 
 // test hook: put the step plan's generation counter (and every env's state, consistently) at `gen` — the counter wraps after
 // 2^28 steps and the protocol's arithmetic is modulo 2^32 (tests/test_step_parts.py steps across the wrap)
 extern "C" int myo_batch_set_step_generation(myo_batch* b, unsigned int gen) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
+  if (int rc = batch_check(b)) return rc;
   if (!b->part_state) return MYO_OK;
   DeviceGuard guard(b->device);
   std::vector<int> st((size_t)b->n, (int)(16u * gen));
@@ -716,9 +629,9 @@ extern "C" int myo_batch_set_step_generation(myo_batch* b, unsigned int gen) {
 // generation than the launch's (see the protocol comment at k_step); out[1]: substeps in which an env had more contacts than its
 // scratch holds (the surplus was dropped); out[2]: the same for limit rows; out[3]: the most contact slots such a substep asked for.  All 0 in a healthy batch.
 extern "C" int myo_batch_health(myo_batch* b, int out[4]) {
-  if (!b || !out) return fail(MYO_E_ARG, "null argument");
-  for (int k = 0; k < 4; ++k) out[k] = 0;
-  if (!b->K.health) return MYO_OK;
+  int empty = 0;
+  int rc = health_check(b, out, &empty);
+  if (rc || empty) return rc;
   DeviceGuard guard(b->device);
   if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, b->K.health, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
     return fail(MYO_E_DEVICE, "myo_batch_health: copy failed");
@@ -758,34 +671,28 @@ extern "C" int myo_debug_wave_slots(int device, int n_workgroups, int lds_bytes,
 }
 
 extern "C" int myo_batch_step_inner(myo_batch* b, const uint8_t* mask, const float* act, float* obs, uint8_t* done, void* stream) {
-  if (!b || !act || !obs) return fail(MYO_E_ARG, "myo_batch_step_inner: act/obs are required");
-  if (!b->K.kind) return fail(MYO_E_STATE, "batch has no task layer");
+  if (int rc = step_inner_check(b, act, obs)) return rc;
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
-  LAUNCH_RK(b,
-    if (b->dtype == MYO_F64)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step_inner<double, RKV, MYO_NC_D(NCV)>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, mask, act, obs, done);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step_inner<float, RKV, NCV>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, mask, act, obs, done))
-  LAUNCH_CHECK(b)
-  return MYO_OK;
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step_inner<typename V::T, V::RK, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, mask, act, obs, done);
+  });
+  return be_launch_status();
 }
 
 // Compact form of myo_batch_step_inner: the envs idx[0 .. n_idx) (dev int32; -1 = empty slot) take one unwrapped env step with
 // row r of act [n_idx, nu]; row r of obs [n_idx, obs_dim] and done [n_idx] (may be NULL) receive env idx[r]'s results.  An env
 // must not be listed twice.  MixtureModelBaodingEnv's base phase runs the few envs that were just reset this way.
 extern "C" int myo_batch_step_inner_idx(myo_batch* b, const int* idx, int n_idx, const float* act, float* obs, uint8_t* done, void* stream) {
-  if (!b || !idx || !act || !obs || n_idx <= 0) return fail(MYO_E_ARG, "myo_batch_step_inner_idx: idx/act/obs are required");
-  if (!b->K.kind) return fail(MYO_E_STATE, "batch has no task layer");
+  if (int rc = step_inner_idx_check(b, idx, n_idx, act, obs)) return rc;
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
-  LAUNCH_RK(b,
-    if (b->dtype == MYO_F64)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step_inner_idx<double, RKV, MYO_NC_D(NCV)>), dim3(n_idx), dim3(64), lds_dyn(b), st, b->L, b->rec, idx, b->n, act, obs, done);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step_inner_idx<float, RKV, NCV>), dim3(n_idx), dim3(64), lds_dyn(b), st, b->L, b->rec, idx, b->n, act, obs, done))
-  LAUNCH_CHECK(b)
-  return MYO_OK;
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step_inner_idx<typename V::T, V::RK, V::NC>), dim3(n_idx), dim3(64), lds_dyn(b), st, b->L, b->rec, idx, b->n, act, obs, done);
+  });
+  return be_launch_status();
 }
 
 // Whole env records from one batch into another (same model, same task kind): dst env dst_idx[r] <- src env src_idx[r], r < k.
@@ -798,44 +705,43 @@ __global__ void k_copy_envs(double* dst, const int* __restrict__ dst_idx, int n_
   for (int i = threadIdx.x; i < stride; i += blockDim.x) dst[(size_t)d * stride + i] = src[(size_t)s * stride + i];
 }
 extern "C" int myo_batch_copy_envs(myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, void* stream) {
-  if (!dst || !src || !dst_idx || !src_idx || k < 0) return fail(MYO_E_ARG, "myo_batch_copy_envs: null argument");
-  if (dst->L.stride != src->L.stride || dst->nq != src->nq || dst->nv != src->nv || dst->na != src->na || dst->K.kind != src->K.kind || dst->device != src->device)
-    return fail(MYO_E_ARG, "myo_batch_copy_envs: the two batches differ in model, task kind or device");
-  if (k == 0) return MYO_OK;
+  int empty = 0;
+  int rc = copy_envs_check(dst, dst_idx, src, src_idx, k, &empty);
+  if (rc || empty) return rc;
   DeviceGuard guard(dst->device);
   hipLaunchKernelGGL(k_copy_envs, dim3(k), dim3(64), 0, (hipStream_t)stream, dst->rec, dst_idx, dst->n, src->rec, src_idx, src->n, dst->L.stride);
-  LAUNCH_CHECK(dst)
-  return MYO_OK;
+  return be_launch_status();
 }
 
 extern "C" int myo_batch_physics_step(myo_batch* b, const double* ctrl, int nsub, void* stream) {
-  if (!b || nsub < 0) return fail(MYO_E_ARG, "bad arguments");
+  if (int rc = physics_step_check(b, nsub)) return rc;
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
   timing_begin(b, st);
-  LAUNCH_RK(b,
-    if (b->dtype == MYO_F64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_physics<double, RKV, MYO_NC_D(NCV)>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, nsub);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_physics<float, RKV, NCV>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, nsub))
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_physics<typename V::T, V::RK, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, nsub);
+  });
   timing_end(b, st);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
+  return be_launch_status();
 }
 
 extern "C" int myo_batch_forward_dump(myo_batch* b, const double* ctrl, double* out, void* stream) {
-  if (!b || !out) return fail(MYO_E_ARG, "bad arguments");
+  if (int rc = forward_dump_check(b, out)) return rc;
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
-  LAUNCH_RK(b, (void)RKV;
-    if (b->dtype == MYO_F64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dump<double, false, MYO_NC_D(NCV)>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, b->D, out);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dump<float, false, NCV>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, b->D, out))
-  LAUNCH_CHECK(b)
-  return MYO_OK;
+  with_variant(b, [&](auto v) {      // RK = false whatever the integrator: forward dynamics integrate nothing, so k_dump has no RK4 variants
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dump<typename V::T, false, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, b->D, out);
+  });
+  return be_launch_status();
 }
 
 static void geom_poses_launch(myo_batch* b, const int32_t* env_idx, int k, double* out, hipStream_t st) {
-  LAUNCH_RK(b,
-    if (b->dtype == MYO_F64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_geom_poses<double, RKV, MYO_NC_D(NCV)>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->vis, b->nitem, out);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_geom_poses<float, RKV, NCV>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->vis, b->nitem, out))
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_geom_poses<typename V::T, V::RK, V::NC>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->vis, b->nitem, out);
+  });
 }
 extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
   int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses");
@@ -844,13 +750,13 @@ extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k,
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
   geom_poses_launch(b, env_idx, k, out, st);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
+  return be_launch_status();
 }
 static void tendon_paths_launch(myo_batch* b, const int32_t* env_idx, int k, double* out, hipStream_t st) {
-  LAUNCH_RK(b,
-    if (b->dtype == MYO_F64) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tendon_paths<double, RKV, MYO_NC_D(NCV)>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->tvis, b->titem_adr, b->ntitem, out);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tendon_paths<float, RKV, NCV>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->tvis, b->titem_adr, b->ntitem, out))
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tendon_paths<typename V::T, V::RK, V::NC>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->tvis, b->titem_adr, b->ntitem, out);
+  });
 }
 extern "C" int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
   int empty = 0;
@@ -859,8 +765,7 @@ extern "C" int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int 
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
   tendon_paths_launch(b, env_idx, k, out, st);
-  LAUNCH_CHECK(b)
-  return MYO_OK;
+  return be_launch_status();
 }
 extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
                                 int flags, uint8_t* rgb, float* depth, int32_t* segid, void* stream) {
@@ -888,15 +793,9 @@ extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, con
     hipLaunchKernelGGL(k_render, dim3(tiles, (unsigned)k), dim3(MYO_RTILE * MYO_RTILE), (unsigned)(b->nitem * sizeof(RItem)), st,
                        b->render_ws, b->nitem, b->render_ws + item_n, ncams, width, height, flags, rgb, depth, segid);
   }
-  LAUNCH_CHECK(b)
-  return MYO_OK;
+  return be_launch_status();
 }
 
-extern "C" int myo_batch_enable_timing(myo_batch* b, int on) {
-  if (!b) return fail(MYO_E_ARG, "null batch");
-  b->timing = on;
-  return MYO_OK;
-}
 extern "C" double myo_batch_kernel_ms(myo_batch* b) {
   if (!b) return -1.0;
   double sum = 0;

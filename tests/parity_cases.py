@@ -759,3 +759,20 @@ def reorient_drift(lib, dtype, n=16, nsteps=150, horizon=150, env_name="CustomMy
     b.close()
     return {"streams": [[sigma, 100 + e] for e in range(n)], "err_qpos_rel": err_q, "err_obs_abs": err_obs, "episode_ends": ends,
             "episode_end_disagreement_at": split}
+
+
+def lds_bytes_of_the_variants(lib):
+    """myo_batch_lds_bytes of the eight kernel variants (csrc/myo_host.h: with_variant): the two synthetic models under
+    myochallenge_amd/assets (the Baoding hand has the base contact capacity, the die the big one) x integrator x arithmetic,
+    2 physics-only envs each, created and destroyed only."""
+    from myochallenge_amd.model import compile_model
+    from myochallenge_amd.synth_hand import synthetic_hand, synthetic_hand_die
+    out = {}
+    for name, mj in (("baoding", synthetic_hand()), ("die", synthetic_hand_die())):
+        for integ in (0, 1):
+            m = native.Model(compile_model(mj, integrator=integ), lib)
+            for dn, dt in (("f64", native.MYO_F64), ("mixed", native.MYO_MIXED)):
+                b = native.Batch(m, None, 2, 0, 0, dt)
+                out[(name, integ, dn)] = b.lds_bytes
+                b.close()
+    return out

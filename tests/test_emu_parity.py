@@ -126,3 +126,89 @@ def test_episode_trajectory_with_torsional_and_rolling_friction(emu_lib, models,
     r = pc.episode_drift(emu_lib, mj, native.MYO_F64, [(0.08, 0), (0.135, 1)], 120, env_name="CustomMyoBaodingBallsP2", resync=True)
     assert all(x is None for x in r["episode_end_disagreement_at"])
     assert r["err_qpos_rel"].max() <= 1e-9 and r["err_obs_abs"].max() <= 1e-7, (r["err_qpos_rel"].max(1), r["err_obs_abs"].max(1))
+
+
+def _refused(code, fn, *args):
+    with pytest.raises(native.MyoError, match=r"error %d:" % code):
+        fn(*args)
+
+
+def test_record_accessors_round_trip_and_refusals(emu_lib, models):
+    """The entry points that only read or write env records, and the argument checks of the others, are defined once for both
+    backends (csrc/myo_host.h).  Distinct values per env go in and come back exactly, a second batch of the same model stays as it
+    was, and every shared check refuses with the code it always had."""
+    from myochallenge_amd.envs.config import make_task_cfg
+    from myochallenge_amd.envs.pose import make_pose_cfg
+    from myochallenge_amd.model import compile_model
+    from myochallenge_amd.synth_hand import synthetic_hand_pose
+    E_ARG, E_STATE = -1, -4
+    f64 = native.MYO_F64
+
+    def distinct(shape, base):
+        return base + np.arange(int(np.prod(shape)), dtype=np.float64).reshape(shape) / 8
+
+    def state(b, nq, nv, na):
+        out = [np.zeros((b.n, nq)), np.zeros((b.n, nv)), np.zeros((b.n, na)), np.zeros(b.n), np.zeros((b.n, nv))]
+        b.get_state(*out[:4]); b.warmstart(out[4], None)
+        return out
+
+    # ---- physics-only batches of the smallest model: state, warm start, object group, whole records
+    cm = compile_model(models["finger"], unsupported_contacts="drop")
+    nq, nv, na, ng = (cm.size(k) for k in ("nq", "nv", "na", "ngeom"))
+    m = native.Model(cm, emu_lib)
+    a, other = native.Batch(m, None, 3, 0, 0, f64), native.Batch(m, None, 3, 0, 0, f64)
+    before = state(other, nq, nv, na)
+    put = [distinct((3, nq), 1), distinct((3, nv), 100), distinct((3, na), 200), distinct((3,), 300), distinct((3, nv), 400)]
+    a.set_state(*put[:4]); a.warmstart(None, put[4])
+    assert all(np.array_equal(x, y) for x, y in zip(state(a, nq, nv, na), put))
+    assert all(np.array_equal(x, y) for x, y in zip(state(other, nq, nv, na), before))
+    g = min(2, ng)
+    a.set_object_group(0, g)
+    fr = np.zeros((3, g, 3)); a.object_friction(None, fr)
+    assert np.array_equal(fr, np.tile(np.asarray(cm.fields["geom_friction"], float).reshape(-1, 3)[:g], (3, 1, 1)))      # the model's, in every env
+    fput, fget = distinct((3, g, 3), 0.5), np.zeros((3, g, 3))
+    a.object_friction(fput, fget)
+    assert np.array_equal(fget, fput)
+    _refused(E_STATE, other.object_friction, None, fr)                       # no group there: the other batch has none of it
+    _refused(E_ARG, a.set_object_group, 1, 1)
+    other.copy_envs_from(a, np.array([0, 7, 2], np.int32), np.array([2, 0, -1], np.int32))      # env 0 <- a's env 2; the other two entries are skipped
+    got = state(other, nq, nv, na)
+    assert all(np.array_equal(x[0], y[2]) for x, y in zip(got, put))
+    assert all(np.array_equal(x[1:], y[1:]) for x, y in zip(got, before))
+    assert all(np.array_equal(x, y) for x, y in zip(state(a, nq, nv, na), put))
+    _refused(E_STATE, a.reset)
+    _refused(E_STATE, a.step, np.zeros((3, na), np.float32), np.zeros((3, 1), np.float32), np.zeros(3, np.float32), np.zeros(3, np.uint8))
+    _refused(E_ARG, a.step, None, None, None, None)
+    _refused(E_ARG, a.step_inner, None, None, None)
+    _refused(E_ARG, a.step_inner_idx, np.zeros(0, np.int32), np.zeros((1, na), np.float32), np.zeros((1, 1), np.float32))
+    _refused(E_ARG, a.physics_step, None, -1)
+    _refused(E_ARG, a.forward_dump, None, None)
+    assert emu_lib.L.myo_batch_health(a.h, None) == E_ARG
+
+    # ---- task blocks: a Baoding batch (task_d = the nine goal scalars) and a pose batch (task_d = target_qpos | init_qpos)
+    hand = compile_model(models["hand"])
+    pose = compile_model(synthetic_hand_pose())
+    for cmt, cfg, nd in ((hand, make_task_cfg("CustomMyoBaodingBallsP1", hand), 9), (pose, make_pose_cfg("CustomMyoHandPoseRandom", pose), 2 * pose.size("nq"))):
+        mt = native.Model(cmt, emu_lib)
+        t, t2 = native.Batch(mt, cfg, 2, 0, 0, f64), native.Batch(mt, cfg, 2, 0, 0, f64)
+
+        def task(b):
+            out = [np.zeros((2, 2), np.int32), np.zeros((2, nd)), np.zeros((2, 10))]
+            b.get_task(*out)
+            return out
+        before = task(t2)
+        put = [np.array([[1, 5], [2, 9]], np.int32), distinct((2, nd), 3), distinct((2, 10), 50)]
+        t.set_task(*put)
+        assert all(np.array_equal(x, y) for x, y in zip(task(t), put))
+        assert all(np.array_equal(x, y) for x, y in zip(task(t2), before))
+        _refused(E_STATE, t.set_object_group, 0, 1)
+        _refused(E_ARG, t.copy_envs_from, a, np.array([0], np.int32), np.array([0], np.int32))      # another model
+
+
+def test_lds_bytes_of_the_eight_variants(emu_lib):
+    """myo_batch_lds_bytes is the variant dispatch applied to the one LDS-size function.  The literals are what the emulation build
+    of the commit before that function existed returned (its myo_batch_lds_bytes spelled the eight cases out by hand); the
+    emulation build's Scratch differs from the gfx950 one, whose values test_gpu_parity.py holds."""
+    want = {("baoding", 0, "f64"): 20352, ("baoding", 0, "mixed"): 16384, ("baoding", 1, "f64"): 20352, ("baoding", 1, "mixed"): 17744,
+            ("die", 0, "f64"): 20336, ("die", 0, "mixed"): 19712, ("die", 1, "f64"): 20336, ("die", 1, "mixed"): 19712}
+    assert pc.lds_bytes_of_the_variants(emu_lib) == want

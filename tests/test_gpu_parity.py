@@ -13,6 +13,15 @@ def test_native_library_is_the_hip_build(hip_lib):
     assert "gfx950" in hip_lib.version and not hip_lib.is_emulation
 
 
+def test_lds_bytes_of_the_eight_variants(hip_lib):
+    """myo_batch_lds_bytes — what every env kernel is launched with — for the eight kernel variants.  The literals were read once on
+    an MI355X from the HIP build of the commit before the variant dispatch and its LDS-size function existed (that
+    myo_batch_lds_bytes spelled the cases out by hand); create and destroy only, no launch."""
+    want = {("baoding", 0, "f64"): 20352, ("baoding", 0, "mixed"): 16384, ("baoding", 1, "f64"): 20352, ("baoding", 1, "mixed"): 17744,
+            ("die", 0, "f64"): 20336, ("die", 0, "mixed"): 19712, ("die", 1, "f64"): 20336, ("die", 1, "mixed"): 19712}
+    assert pc.lds_bytes_of_the_variants(hip_lib) == want
+
+
 def test_forward_stages_f64(hip_lib, models):
     pc.case_forward_stages(hip_lib, models, native.MYO_F64, 1e-9)
 
