@@ -27,6 +27,7 @@ extern "C" {
 
 #define MYO_OK 0
 #define MYO_E_ARG -1      /* bad argument / malformed blob */
+#define MYO_E_BADARG MYO_E_ARG
 #define MYO_E_UNSUPPORTED -2 /* model uses a feature the stepper lacks or exceeds its limits */
 #define MYO_E_DEVICE -3   /* HIP runtime error */
 #define MYO_E_STATE -4    /* call sequence error */
@@ -243,6 +244,49 @@ int myo_batch_tune_wrap_order(myo_batch* b, void* stream);
 int myo_batch_forward_dump(myo_batch* b, const double* ctrl, double* out, void* stream);
 int myo_batch_dump_size(const myo_batch* b);
 int myo_batch_dump_offset(const myo_batch* b, const char* name);
+
+/* ---- per-env contact and muscle read-out (MuJoCo's data.contact[i], mj_contactForce, data.cfrc_ext, data.qfrc_constraint,
+ * data.actuator_length / _velocity / _force, data.act, data.ten_length / ten_velocity — what the reference reads from sim.data).
+ * One wave per env runs the stepper's forward pass at the env's PRESENT state — kinematics, tendons, collision, constraint rows and the
+ * Newton solve seeded from the env's qacc_warmstart, with the env's own ball / die parameters: what the next substep would compute —
+ * and publishes the arrays below.  Controls are not part of an env's state between two steps: the pass runs with ctrl = 0, which
+ * enters the activation rates only.  Reads the env records only: no record, warm start, draw counter, step generation or wrap order
+ * changes; a pass that has to drop contacts beyond the capacity counts it in myo_batch_health like a substep.
+ *
+ * myo_sense_out: caller-owned DEVICE arrays, any of them NULL (not wanted); `size` = sizeof(myo_sense_out), first, so that the
+ * struct can grow.  N = envs, cap = myo_batch_contact_capacity (contact slots per env: 24, 22 in the fp64 stepper, 48 for models
+ * with extended collision pairs or a die):
+ *   ncon            int32 [N]             active contacts (the capacity when a surplus was dropped)
+ *   con_geom        int32 [N, cap, 2]     geom1, geom2; -1 in unused slots
+ *   con_d           double[N, cap, 13]    dist, pos[3] (world), normal[3] (world, from geom1 to geom2), force[6] in the contact frame
+ *                                         (normal, tangent 1, tangent 2, torsional, rolling 1, rolling 2 — mj_contactForce: the normal
+ *                                         force is the sum of the contact's pyramid edge forces, component i is (f[2i] - f[2i+1]) mu_i;
+ *                                         condim 1: the normal force alone); unused components and slots are 0.  The frame's tangents
+ *                                         are mju_makeFrame's of the normal; the force acts on geom2's body, its opposite on geom1's
+ *   body_wrench     double[N, nbody, 6]   net contact force [0..3) and torque [3..6) on each body, world frame, torque about the body's
+ *                                         xpos (cfrc_ext restricted to contacts)
+ *   qfrc_constraint double[N, nv]         constraint forces in joint space (contacts, joint / tendon limits, friction loss)
+ *   act_length, act_velocity, act_force   double[N, nu]
+ *   activation      double[N, na]
+ *   ten_length, ten_velocity              double[N, ntendon]
+ * Contacts are listed in the stepper's pair order, which is not MuJoCo's.  A NULL batch / struct or another `size` returns
+ * MYO_E_BADARG (= MYO_E_ARG) before any device call. */
+typedef struct myo_sense_out {
+  size_t size;
+  int32_t* ncon;
+  int32_t* con_geom;
+  double* con_d;
+  double* body_wrench;
+  double* qfrc_constraint;
+  double* act_length;
+  double* act_velocity;
+  double* act_force;
+  double* activation;
+  double* ten_length;
+  double* ten_velocity;
+} myo_sense_out;
+int myo_batch_contact_capacity(const myo_batch* b);
+int myo_batch_sense(myo_batch* b, const myo_sense_out* out, void* stream);
 
 /* ---- rendering of env states (MuJoCo's mjr_render / mjr_readPixels seam: CustomPenEnv.render -> self.sim.render,
  * /root/reference/src/main_eval.py:96-97).  Draws what the stepper holds: every geom at the pose of the env's present state

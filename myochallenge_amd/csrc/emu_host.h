@@ -142,6 +142,13 @@ extern "C" int myo_batch_forward_dump(myo_batch* b, const double* ctrl, double* 
   return MYO_OK;
 }
 
+extern "C" int myo_batch_sense(myo_batch* b, const myo_sense_out* out, void*) {
+  if (int rc = sense_check(b, out)) return rc;
+  const SenseDev O = sense_dev(b, out);
+  with_scratch(b, [&](auto& M, auto& s) { for (int env = 0; env < b->n; ++env) env_sense(M, b->K, b->L, env_rec(b, env), s, env, O); });
+  return MYO_OK;
+}
+
 // rendering: the pose pass env by env, then the ray cast tile by tile with the kernel's three thread phases one after the other
 static void emu_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out) {
   with_scratch(b, [&](auto& M, auto& s) {

@@ -25,6 +25,7 @@
 #include "myo_mjb.h"
 #include "myo_task.h"
 #include "myo_render.h"
+#include "myo_sense.h"
 
 
 // ------------------------------------------------------------------------------------------ backend (defined by the including file)
@@ -1553,6 +1554,27 @@ static int step_inner_idx_check(const myo_batch* b, const int* idx, int n_idx, c
 }
 static int physics_step_check(const myo_batch* b, int nsub) { return b && nsub >= 0 ? MYO_OK : fail(MYO_E_ARG, "bad arguments"); }
 static int forward_dump_check(const myo_batch* b, const double* out) { return b && out ? MYO_OK : fail(MYO_E_ARG, "bad arguments"); }
+// myo_batch_sense (csrc/myo_sense.h): the struct's size is its version.  A k_step launch runs every part of an env step, so a call that is
+// stream-ordered behind the steps never meets an env between two parts of one.
+static int sense_check(const myo_batch* b, const myo_sense_out* out) {
+  if (!b || !out) return fail(MYO_E_BADARG, "myo_batch_sense: null batch or output struct");
+  if (out->size != sizeof(myo_sense_out)) return fail(MYO_E_BADARG, "myo_batch_sense: myo_sense_out.size is %zu, this library's struct has %zu bytes", out->size, sizeof(myo_sense_out));
+  return MYO_OK;
+}
+// the sense rows of the variant table: k_sense / env_sense exist per arithmetic and contact capacity, keyed as k_step is (the integrator
+// does not enter: a forward pass integrates nothing); a row's capacity is its scratch's record slots
+static int sense_capacity(const myo_batch* b) {
+  return with_variant(b, [](auto v) { using V = decltype(v); return (int)Scratch<typename V::T, V::NC>::NREC; });
+}
+static SenseDev sense_dev(const myo_batch* b, const myo_sense_out* o) {
+  SenseDev d;
+  d.ncon = o->ncon; d.con_geom = o->con_geom; d.con_d = o->con_d; d.body_wrench = o->body_wrench; d.qfrc_constraint = o->qfrc_constraint;
+  d.act_length = o->act_length; d.act_velocity = o->act_velocity; d.act_force = o->act_force; d.activation = o->activation;
+  d.ten_length = o->ten_length; d.ten_velocity = o->ten_velocity;
+  d.cap = sense_capacity(b);
+  return d;
+}
+extern "C" int myo_batch_contact_capacity(const myo_batch* b) { return b ? sense_capacity(b) : -1; }
 // k = 0 is an empty copy (*empty)
 static int copy_envs_check(const myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, int* empty) {
   if (!dst || !src || !dst_idx || !src_idx || k < 0) return fail(MYO_E_ARG, "myo_batch_copy_envs: null argument");

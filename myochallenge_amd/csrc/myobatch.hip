@@ -331,6 +331,16 @@ __global__ void __launch_bounds__(64, 2) k_dump(EnvRecordLayout L, double* rec, 
   const int env = blockIdx.x;
   env_forward_dump<T>(M, K, L, rec + (size_t)env * L.stride, s, env, ctrl, D, out);
 }
+// the contact and muscle read-out (csrc/myo_sense.h): one forward pass at the env's present state, nothing written back to the record
+template <typename T, int NC>
+__global__ void __launch_bounds__(64, 2) k_sense(EnvRecordLayout L, double* rec, SenseDev O) {
+  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
+  s.rk = nullptr;
+  const DevModel<T>& M = myo_cmodel<T>();
+  const TaskDev& K = c_task;
+  const int env = blockIdx.x;
+  env_sense<T>(M, K, L, rec + (size_t)env * L.stride, s, env, O);
+}
 template <typename T, bool RK, int NC>
 __global__ void __launch_bounds__(64, 2) k_wrap_census(EnvRecordLayout L, double* rec, int* cnt) {
   Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
@@ -733,6 +743,18 @@ extern "C" int myo_batch_forward_dump(myo_batch* b, const double* ctrl, double* 
   with_variant(b, [&](auto v) {      // RK = false whatever the integrator: forward dynamics integrate nothing, so k_dump has no RK4 variants
     using V = decltype(v);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dump<typename V::T, false, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, b->D, out);
+  });
+  return be_launch_status();
+}
+
+extern "C" int myo_batch_sense(myo_batch* b, const myo_sense_out* out, void* stream) {
+  if (int rc = sense_check(b, out)) return rc;
+  const SenseDev O = sense_dev(b, out);
+  hipStream_t st = (hipStream_t)stream;
+  BIND_OR_RETURN(b, st)
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sense<typename V::T, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, O);
   });
   return be_launch_status();
 }

@@ -189,6 +189,9 @@ class BaodingVecEnv:
             self.batch.get_task(t, None, None, self._stream())
             w = t[:, 0].cpu().numpy()
             return [int(w[i]) for i in idx]
+        if attr_name in self._SENSOR_ATTRS:
+            v = self.sensors([self._SENSOR_ATTRS[attr_name]])[self._SENSOR_ATTRS[attr_name]].cpu().numpy()
+            return [v[i].copy() for i in idx]
         if attr_name in self.params:
             return [self.params[attr_name] for _ in idx]
         raise AttributeError(attr_name)
@@ -273,6 +276,60 @@ class BaodingVecEnv:
             raise ValueError(f"unknown render mode {mode!r}; supported: {self.metadata['render.modes']}")
         from ..render_io import tile_images
         return tile_images(self.get_images(tendons=tendons, **kwargs))
+
+    # ---------------------------------------------------------------- contact and muscle read-out (include/myobatch.h myo_batch_sense)
+    # get_attr names (MuJoCo's mjData names and the short ones) -> sensors() keys
+    _SENSOR_ATTRS = {"contact_forces": "con_d", "contact_geoms": "con_geom", "ncon": "ncon", "cfrc_ext": "body_wrench",
+                     "qfrc_constraint": "qfrc_constraint", "actuator_length": "act_length",
+                     "actuator_velocity": "act_velocity", "actuator_force": "act_force", "activation": "activation",
+                     "ten_length": "ten_length", "ten_velocity": "ten_velocity"}
+
+    def sensors(self, keys=None, indices=None) -> dict:
+        """What the hand does to the objects and what the muscles do, for the envs' PRESENT states: one forward pass on the GPU
+        (contacts, constraint solve from the env's warm start), nothing about the envs changes.  Device tensors, no host copy.
+
+        keys (default: all): ``ncon`` int32 [k]; ``con_geom`` int32 [k, cap, 2] (geom ids, -1 in unused slots; ``geom_names``);
+        ``con_d`` float64 [k, cap, 13] = dist, pos[3], normal[3] (world, geom1 -> geom2), force[6] in the contact frame
+        (mj_contactForce); ``body_wrench`` float64 [k, nbody, 6] net contact force and torque about xpos, world frame
+        (``body_names``); ``qfrc_constraint`` [k, nv]; ``act_length`` / ``act_velocity`` / ``act_force`` [k, nu]; ``activation``
+        [k, na]; ``ten_length`` / ``ten_velocity`` [k, ntendon].  indices: the envs' rows to return (default: all; the pass itself
+        always runs the whole batch)."""
+        t = self.torch
+        shapes = self.batch.sense_shapes()
+        keys = list(shapes) if keys is None else list(keys)
+        for k in keys:
+            if k not in shapes:
+                raise KeyError(f"unknown sensor key {k!r}; known: {sorted(shapes)}")
+        tdt = {np.int32: t.int32, np.float64: t.float64}
+        out = {k: t.zeros((self.num_envs,) + shapes[k][0], dtype=tdt[shapes[k][1]], device=self.device) for k in keys}
+        self.batch.sense(self._stream(), **out)
+        if indices is not None:
+            idx = t.as_tensor([int(i) for i in indices], dtype=t.long, device=self.device)
+            out = {k: v[idx] for k, v in out.items()}
+        return out
+
+    @property
+    def geom_names(self) -> List[str]:
+        return list(self.compiled.names.get("geom", []))
+
+    @property
+    def body_names(self) -> List[str]:
+        return list(self.compiled.names.get("body", []))
+
+    def object_body_ids(self) -> List[int]:
+        """ids of the task's free objects (the two balls; the die; none for the pose tasks): rows of ``body_wrench``"""
+        kind = int(self._cfg.kind)
+        if kind in (native.TASK_BAODING_P1, native.TASK_BAODING_P2):
+            return [int(self._cfg.obj1_bid), int(self._cfg.obj2_bid)]
+        return [int(self._cfg.obj1_bid)] if kind == native.TASK_REORIENT else []
+
+    def contact_table(self, i: int) -> list:
+        """Env i's contacts for humans: a list of (geom1_name, geom2_name, dist, normal_force)."""
+        s = self.sensors(["ncon", "con_geom", "con_d"], [i])
+        n, g, d = int(s["ncon"][0]), s["con_geom"][0].cpu().numpy(), s["con_d"][0].cpu().numpy()
+        names = self.geom_names
+        name = lambda k: names[k] if 0 <= k < len(names) and names[k] else f"geom{k}"
+        return [(name(int(g[c, 0])), name(int(g[c, 1])), float(d[c, 0]), float(d[c, 7])) for c in range(n)]
 
     # ---------------------------------------------------------------- state access (parity tests)
     def get_state(self):

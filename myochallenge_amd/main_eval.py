@@ -28,8 +28,13 @@ DEFAULT_CONFIG = {
 
 def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBallsP2", config: dict = None,
              num_episodes: int = 100, num_envs: int = 256, seed: int = 0, deterministic: bool = True, verbose: bool = True,
-             render_dir: str = None, render_envs: int = 1, render_size=(480, 480), render_tendons: bool = False):
-    """render_tendons: draw the tendons, coloured by muscle activation, into the frames.  render_dir: write a PNG of each of the first ``render_envs`` envs after every step (``env{i}_step{t}.png``; the reference
+             render_dir: str = None, render_envs: int = 1, render_size=(480, 480), render_tendons: bool = False,
+             record_dir: str = None, env=None):
+    """record_dir: write ``batch00000.npz`` there — per env step t and env n: ``qpos``, ``qvel``, ``act`` (the state after the step: the
+    reset state where the episode ended), ``actuator_length`` / ``actuator_velocity`` / ``actuator_force`` [T, N, nu], ``ncon`` [T, N] and
+    ``object_wrench`` [T, N, nobj, 6] (net contact force and torque on the task's objects, ``object_body_ids``), from ``env.sensors``.
+    env: an already built env to evaluate on instead of ``EnvironmentFactory.create(env_name, ...)``.
+    render_tendons: draw the tendons, coloured by muscle activation, into the frames.  render_dir: write a PNG of each of the first ``render_envs`` envs after every step (``env{i}_step{t}.png``; the reference
     script's ``render`` switch, src/main_eval.py:96-97, shows the frames in a window instead)."""
     from .envs.environment_factory import EnvironmentFactory
     from .metrics.evaluation import evaluate_policy, summarize
@@ -38,15 +43,16 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
     if config is None:             # the reference script's Baoding config; other envs: their registration defaults
         config = DEFAULT_CONFIG if env_name.startswith("CustomMyoBaoding") or env_name == "MixtureModelBaodingEnv" else {}
     config = dict(config)
-    env = EnvironmentFactory.create(env_name, num_envs=min(num_envs, num_episodes), seed=seed, **config)
+    if env is None:
+        env = EnvironmentFactory.create(env_name, num_envs=min(num_envs, num_episodes), seed=seed, **config)
     venv = VecNormalize.load(env_path, env)
     venv.training = False          # src/main_eval.py:66-67
     venv.norm_reward = False
     policy, _ = load_policy(model_path)
     policy.to(env.device)
     on_step = None
+    import os
     if render_dir:
-        import os
         from .render_io import write_png
         os.makedirs(render_dir, exist_ok=True)
         k = max(1, min(int(render_envs), env.num_envs))
@@ -55,7 +61,23 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
             rgb = env.render_tensor(list(range(k)), int(render_size[0]), int(render_size[1]), tendons=render_tendons)["rgb"].cpu().numpy()
             for i in range(k):
                 write_png(os.path.join(render_dir, f"env{i}_step{t:05d}.png"), rgb[i])
+    rec = None
+    if record_dir:
+        os.makedirs(record_dir, exist_ok=True)
+        rec = {k: [] for k in ("qpos", "qvel", "act", "actuator_length", "actuator_velocity", "actuator_force", "ncon", "object_wrench")}
+        obj, draw = env.object_body_ids(), on_step
+
+        def on_step(t):
+            if draw is not None:
+                draw(t)
+            qp, qv, ac, _ = env.get_state()
+            s = env.sensors(["act_length", "act_velocity", "act_force", "ncon", "body_wrench"])
+            for k, v in (("qpos", qp), ("qvel", qv), ("act", ac), ("actuator_length", s["act_length"]), ("actuator_velocity", s["act_velocity"]),
+                         ("actuator_force", s["act_force"]), ("ncon", s["ncon"]), ("object_wrench", s["body_wrench"][:, obj])):
+                rec[k].append(v.cpu().numpy())
     res = evaluate_policy(policy, env, venv, n_eval_episodes=num_episodes, deterministic=deterministic, on_step=on_step)
+    if rec is not None:
+        np.savez(os.path.join(record_dir, "batch00000.npz"), object_body_ids=np.asarray(obj, np.int64), **{k: np.stack(v) for k, v in rec.items()})
     out = summarize(res)
     if verbose:
         print(f"Average len: {out['mean_len']:.2f} +/- {out['len_err']:.2f}")
@@ -78,12 +100,15 @@ def main(argv=None):
     ap.add_argument("--render-envs", type=int, default=1)
     ap.add_argument("--render-size", type=int, nargs=2, default=(480, 480), metavar=("W", "H"))
     ap.add_argument("--render-tendons", action="store_true", help="with --render-dir: draw the tendons, coloured by muscle activation")
+    ap.add_argument("--record-dir", default=None, help="write per-step qpos / qvel / act, actuator length / velocity / force, ncon and the "
+                                                       "objects' contact wrenches of the evaluated batch to batch00000.npz here")
     a = ap.parse_args(argv)
     if a.render_tendons and not a.render_dir:
         ap.error("--render-tendons needs --render-dir")
     cfg = json.load(open(a.config)) if a.config else None
     res, _ = evaluate(a.model, a.env_path, a.env_name, cfg, a.num_episodes, a.num_envs, a.seed,
-                      render_dir=a.render_dir, render_envs=a.render_envs, render_size=a.render_size, render_tendons=a.render_tendons)
+                      render_dir=a.render_dir, render_envs=a.render_envs, render_size=a.render_size, render_tendons=a.render_tendons,
+                      record_dir=a.record_dir)
     if a.out:
         np.savez(a.out, **res)
 

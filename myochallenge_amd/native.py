@@ -107,6 +107,17 @@ RENDER_RGB, RENDER_DEPTH, RENDER_SEG, RENDER_SITES, RENDER_TENDONS = 1, 2, 4, 8,
 RENDER_ITEM_N = 24      # doubles per item of myo_batch_geom_poses / myo_batch_tendon_paths
 
 
+class SenseOut(C.Structure):
+    """myo_sense_out of include/myobatch.h: caller-owned device arrays of myo_batch_sense, any of them NULL."""
+    _fields_ = [("size", C.c_size_t), ("ncon", C.c_void_p), ("con_geom", C.c_void_p), ("con_d", C.c_void_p), ("body_wrench", C.c_void_p),
+                ("qfrc_constraint", C.c_void_p), ("act_length", C.c_void_p), ("act_velocity", C.c_void_p), ("act_force", C.c_void_p),
+                ("activation", C.c_void_p), ("ten_length", C.c_void_p), ("ten_velocity", C.c_void_p)]
+
+
+SENSE_KEYS = tuple(f[0] for f in SenseOut._fields_[1:])
+SENSE_CON_N = 13        # doubles per contact of con_d: dist, pos[3], normal[3], force[6]
+
+
 class MyoError(RuntimeError):
     pass
 
@@ -161,6 +172,8 @@ class NativeLib:
         L.myo_batch_geom_poses.argtypes = [vp, vp, i32, vp, vp]
         L.myo_batch_tendon_paths.argtypes = [vp, vp, i32, vp, vp]
         L.myo_batch_render.argtypes = [vp, vp, i32, C.POINTER(RenderCamera), i32, i32, i32, i32, vp, vp, vp, vp]
+        L.myo_batch_contact_capacity.argtypes = [vp]
+        L.myo_batch_sense.argtypes = [vp, C.POINTER(SenseOut), vp]
         if b"MYO_EMU" in L.myo_version():
             return      # the emulation build (test tooling, csrc/emu_host.h) implements the env path only: ENV_PATH_SYMBOLS
         L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp]
@@ -240,6 +253,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
     "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_clip_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_adam_apply", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_ppo_loss_grad_hp", "myo_adam_clip_step_hp", "myo_adam_apply_hp", "myo_last_error", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
+    "myo_batch_contact_capacity", "myo_batch_sense",
 ]
 
 # ... of which the lane-serial emulation build (tests/emu/libmyobatch_emu.so: csrc/myobatch_emu.cpp + csrc/emu_host.h, test tooling) has the env
@@ -252,6 +266,7 @@ ENV_PATH_SYMBOLS = [
     "myo_batch_step", "myo_batch_step_inner", "myo_batch_step_inner_idx", "myo_batch_tune_wrap_order", "myo_batch_warmstart", "myo_debug_wave_slots",
     "myo_last_error", "myo_model_destroy", "myo_model_from_blob", "myo_model_load_mjb", "myo_model_size", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
+    "myo_batch_contact_capacity", "myo_batch_sense",
 ]
 
 
@@ -409,6 +424,31 @@ class Batch:
             c.distance, c.azimuth, c.elevation, c.fovy = (float(d[k]) for k in ("distance", "azimuth", "elevation", "fovy"))
         self.lib.check(self.lib.L.myo_batch_render(self.h, _ptr(env_idx), int(env_idx.shape[0]), arr, len(cams), int(width), int(height),
                                                    int(flags), _ptr(rgb), _ptr(depth), _ptr(segid), stream))
+
+    @property
+    def contact_capacity(self) -> int:
+        """contact slots per env of this batch's stepper (24; 22 in the fp64 stepper; 48 with extended collision pairs or a die)"""
+        return self.lib.L.myo_batch_contact_capacity(self.h)
+
+    def sense_shapes(self) -> dict:
+        """key -> (per-env shape, numpy dtype) of the arrays of sense()"""
+        m, cap = self.model, self.contact_capacity
+        nu, na, nt = m.size("nu"), m.size("na"), m.size("ntendon")
+        return {"ncon": ((), np.int32), "con_geom": ((cap, 2), np.int32), "con_d": ((cap, SENSE_CON_N), np.float64),
+                "body_wrench": ((m.size("nbody"), 6), np.float64), "qfrc_constraint": ((m.size("nv"),), np.float64),
+                "act_length": ((nu,), np.float64), "act_velocity": ((nu,), np.float64), "act_force": ((nu,), np.float64),
+                "activation": ((na,), np.float64), "ten_length": ((nt,), np.float64), "ten_velocity": ((nt,), np.float64)}
+
+    def sense(self, stream=None, **arrays):
+        """contact and muscle read-out of the envs' present states (myo_batch_sense): keyword = a key of SENSE_KEYS, value = the
+        device array that receives it ([N, *sense_shapes()[key]]); keys not given are not computed"""
+        out = SenseOut()
+        out.size = C.sizeof(SenseOut)
+        for k, v in arrays.items():
+            if k not in SENSE_KEYS:
+                raise KeyError(k)
+            setattr(out, k, _ptr(v))
+        self.lib.check(self.lib.L.myo_batch_sense(self.h, C.byref(out), stream))
 
     @property
     def dump_size(self) -> int:

@@ -244,6 +244,13 @@ class VecNormalize:
     def tendon_paths(self, *args, **kwargs):
         return self.venv.tendon_paths(*args, **kwargs)
 
+    # contact and muscle read-out: forwarded likewise (raw physical quantities, nothing to normalise)
+    def sensors(self, *args, **kwargs):
+        return self.venv.sensors(*args, **kwargs)
+
+    def contact_table(self, *args, **kwargs):
+        return self.venv.contact_table(*args, **kwargs)
+
     def close(self):
         if self.venv is not None:
             self.venv.close()
