@@ -404,6 +404,21 @@ int myo_ppo_gather(const float* obs, const float* act, const float* oldlp, const
                    float* act_mb, float* oldlp_mb, float* adv_mb, float* ret_mb, float* adv_stats /* NULL: not computed */, float* work,
                    void* stream);
 
+/* The gather for a minibatch of m CHUNKS of L consecutive rollout steps (recurrent PPO with PPOConfig.seq_len; sb3-contrib
+ * RecurrentRolloutBuffer._get_samples: a sequence starts from the LSTM state stored with its first transition).  chunk[j] = s*N + n
+ * (dev int64) names steps [s*L, (s+1)*L) of env n; output row r = t*m + j (t-major) takes rollout row (s*L + t)*N + n.
+ * obs [T,N,obs_dim] act [T,N,act_dim] oldlp / adv / ret / starts [T,N] (dev float32), T % L == 0, S = T / L; h_snap bfloat16 and
+ * c_snap float32 [S,G,N,H] (H % 8 == 0): the state that entered step s*L of the rollout, before the episode-start mask.
+ * -> obs_bf16 [copies, L*m, obs_dim], act_mb [L*m, act_dim], oldlp_mb / adv_mb / ret_mb [L*m], keep [L,m] = 1 - starts,
+ *    hm0 bfloat16 [G,m,H] = h_snap * keep[0], cm0 bfloat16 [G,m,H] and c0_32 float32 [G,m,H] = c_snap * keep[0] (c0_32 unrounded),
+ *    adv_stats[2] as above (same partition and merge: bit-identical to the plain gather on the same rows; NULL: not computed).
+ * work: dev float32 [2*ceil(L*m/16)].  MYO_E_ARG for NULLs, m < 1, L < 1, T % L != 0. */
+int myo_ppo_gather_seq(const float* obs, const float* act, const float* oldlp, const float* adv, const float* ret,
+                       const float* starts, const void* h_snap, const float* c_snap, const int64_t* chunk, int T, int N, int L, int m,
+                       int G, int H, int obs_dim, int act_dim, uint16_t* obs_bf16, int copies, float* act_mb, float* oldlp_mb,
+                       float* adv_mb, float* ret_mb, float* keep, uint16_t* hm0, uint16_t* cm0, float* c0_32,
+                       float* adv_stats /* NULL: not computed */, float* work, void* stream);
+
 /* h <- max(h + bias, 0) in place: bfloat16 h[groups, rows, cols], bias[groups, cols] (cols even). */
 int myo_bias_relu_bf16(uint16_t* h, const uint16_t* bias, int groups, int rows, int cols, void* stream);
 
@@ -464,6 +479,12 @@ int myo_vecnorm_finish(const float* obs, const float* rew, const uint8_t* done, 
                        float* starts, const int32_t* t_idx, float* rew_buf, float* start_buf, float* term_buf, float* trunc_buf,
                        const double* batch, void* stream);
 int myo_rollout_advance(int32_t* t_idx, int T, uint64_t* draw_counter, void* stream);
+/* LSTM state entering a chunk of seq_len steps, taken inside the per-step graph (the predicate is read on the device):
+ * if (*t_idx % seq_len == 0): h_snap[*t_idx / seq_len] <- h, c_snap[...] <- c32; otherwise nothing, and a slot >= S writes nothing.
+ * h bfloat16 [G,N,H], c32 float32 [G,N,H], h_snap bfloat16 [S,G,N,H], c_snap float32 [S,G,N,H]; G*N*H a multiple of 8.
+ * MYO_E_ARG for NULLs, seq_len < 1, S < 1. */
+int myo_rollout_state_snapshot(const void* h, const float* c32, int G, int N, int H, const int32_t* t_idx, int seq_len, int S,
+                               void* h_snap, float* c_snap, void* stream);
 
 /* One time step of G stacked one-layer LSTMs (gate order i, f, g, o) around the recurrent GEMM: the pointwise
  * part of RecurrentActorCriticPolicy's lstm_actor / lstm_critic in collect_rollouts / train

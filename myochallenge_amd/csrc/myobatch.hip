@@ -1090,19 +1090,14 @@ __global__ void __launch_bounds__(256) k_bias_relu(unsigned* __restrict__ h, con
 // by k_moments_finish in block order: deterministic).  Replaces 5 index kernels, 3 casts/copies and
 // the var_mean reduction.
 #define MYO_GATHER_ROWS 16
-__global__ void __launch_bounds__(256) k_ppo_gather(const float* __restrict__ obs, const float* __restrict__ act,
-                                                    const float* __restrict__ oldlp, const float* __restrict__ adv,
-                                                    const float* __restrict__ ret, const long long* __restrict__ idx, int bs,
-                                                    int O, int A, unsigned short* __restrict__ obs_h, int copies,
-                                                    float* __restrict__ act_mb, float* __restrict__ oldlp_mb,
-                                                    float* __restrict__ adv_mb, float* __restrict__ ret_mb,
-                                                    float* __restrict__ part) {
-  constexpr int R = MYO_GATHER_ROWS;
-  __shared__ long long s_idx[R];
-  const int t = threadIdx.x, r0 = blockIdx.x * R;
-  const int rows = (bs - r0) < R ? (bs - r0) : R;
-  if (t < rows) s_idx[t] = idx[r0 + t];
-  __syncthreads();
+// (the body of a gather block: output rows r0 .. r0 + rows take the rollout rows s_idx[0 .. rows), which the caller has put into LDS)
+__device__ __forceinline__ void myo_gather_block(const float* __restrict__ obs, const float* __restrict__ act,
+                                                 const float* __restrict__ oldlp, const float* __restrict__ adv,
+                                                 const float* __restrict__ ret, const long long* s_idx, int rows, int r0, int bs,
+                                                 int O, int A, unsigned short* __restrict__ obs_h, int copies,
+                                                 float* __restrict__ act_mb, float* __restrict__ oldlp_mb,
+                                                 float* __restrict__ adv_mb, float* __restrict__ ret_mb, float* __restrict__ part) {
+  const int t = threadIdx.x;
 #pragma unroll 2
   for (int e = t; e < rows * O; e += 256) {
     const int r = e / O, c = e - r * O;
@@ -1129,6 +1124,96 @@ __global__ void __launch_bounds__(256) k_ppo_gather(const float* __restrict__ ob
     for (int off = 32; off >= 1; off >>= 1) m2 += __shfl_xor(m2, off, 64);
     if (t == 0) { part[2 * blockIdx.x] = mean; part[2 * blockIdx.x + 1] = m2; }
   }
+}
+__global__ void __launch_bounds__(256) k_ppo_gather(const float* __restrict__ obs, const float* __restrict__ act,
+                                                    const float* __restrict__ oldlp, const float* __restrict__ adv,
+                                                    const float* __restrict__ ret, const long long* __restrict__ idx, int bs,
+                                                    int O, int A, unsigned short* __restrict__ obs_h, int copies,
+                                                    float* __restrict__ act_mb, float* __restrict__ oldlp_mb,
+                                                    float* __restrict__ adv_mb, float* __restrict__ ret_mb,
+                                                    float* __restrict__ part) {
+  constexpr int R = MYO_GATHER_ROWS;
+  __shared__ long long s_idx[R];
+  const int t = threadIdx.x, r0 = blockIdx.x * R;
+  const int rows = (bs - r0) < R ? (bs - r0) : R;
+  if (t < rows) s_idx[t] = idx[r0 + t];
+  __syncthreads();
+  myo_gather_block(obs, act, oldlp, adv, ret, s_idx, rows, r0, bs, O, A, obs_h, copies, act_mb, oldlp_mb, adv_mb, ret_mb, part);
+}
+// The same gather for a minibatch of m CHUNKS of L consecutive steps (recurrent PPO with seq_len): chunk[j] = s * N + n names steps
+// [s L, (s + 1) L) of env n, output row r = t m + j takes rollout row (s L + t) N + n.  The first nb blocks are gather blocks as
+// above (same partition, same moments) and also leave keep = 1 - starts of their rows; the blocks behind them fetch the LSTM state
+// that entered each chunk from the rollout's snapshots, times keep of the chunk's first step: 8 elements = one 16-byte load of h,
+// two of c per thread.
+struct GatherSeq {
+  const float *obs, *act, *oldlp, *adv, *ret, *starts, *c_snap;
+  const unsigned short* h_snap;
+  const long long* chunk;
+  int N, L, m, S, G, H, O, A, copies, nb;
+  unsigned short *obs_h, *hm0, *cm0;
+  float *act_mb, *oldlp_mb, *adv_mb, *ret_mb, *keep, *c0_32, *part;
+};
+__device__ __forceinline__ unsigned short myo_bf_mul(unsigned short x, float k) { return myo_f2bf(__uint_as_float((unsigned)x << 16) * k); }
+__global__ void __launch_bounds__(256) k_ppo_gather_seq(GatherSeq a) {
+  constexpr int R = MYO_GATHER_ROWS;
+  __shared__ long long s_idx[R];
+  const int t = threadIdx.x;
+  const long long items = (long long)a.N * a.S;
+  if ((int)blockIdx.x < a.nb) {                       // block-uniform branch
+    const int bs = a.L * a.m, r0 = blockIdx.x * R;
+    const int rows = (bs - r0) < R ? (bs - r0) : R;
+    if (t < rows) {
+      const int r = r0 + t, tt = r / a.m, j = r - tt * a.m;
+      long long c = a.chunk[j];
+      c = c < 0 ? 0 : (c >= items ? items - 1 : c);   // (a permutation of the items never leaves the range)
+      const long long s = c / a.N, n = c - s * a.N;
+      const long long src = (s * a.L + tt) * a.N + n;
+      s_idx[t] = src;
+      a.keep[r] = 1.f - a.starts[src];
+    }
+    __syncthreads();
+    myo_gather_block(a.obs, a.act, a.oldlp, a.adv, a.ret, s_idx, rows, r0, bs, a.O, a.A, a.obs_h, a.copies, a.act_mb, a.oldlp_mb,
+                     a.adv_mb, a.ret_mb, a.part);
+    return;
+  }
+  const int H8 = a.H / 8;
+  const long long v = (long long)(blockIdx.x - a.nb) * 256 + t;          // vector of 8 of the [G, m, H] outputs
+  if (v >= (long long)a.G * a.m * H8) return;
+  const int hv = (int)(v % H8), j = (int)((v / H8) % a.m), g = (int)(v / ((long long)H8 * a.m));
+  long long c = a.chunk[j];
+  c = c < 0 ? 0 : (c >= items ? items - 1 : c);
+  const long long s = c / a.N, n = c - s * a.N;
+  const float k0 = 1.f - a.starts[(s * a.L) * a.N + n];
+  const size_t src = (((size_t)s * a.G + g) * a.N + n) * a.H + 8 * hv, dst = (size_t)v * 8;
+  const uint4 h = *reinterpret_cast<const uint4*>(a.h_snap + src);
+  const float4 c_lo = *reinterpret_cast<const float4*>(a.c_snap + src), c_hi = *reinterpret_cast<const float4*>(a.c_snap + src + 4);
+  const unsigned hw[4] = {h.x, h.y, h.z, h.w};
+  const float cw[8] = {c_lo.x * k0, c_lo.y * k0, c_lo.z * k0, c_lo.w * k0, c_hi.x * k0, c_hi.y * k0, c_hi.z * k0, c_hi.w * k0};
+  unsigned ho[4], co[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ho[i] = (unsigned)myo_bf_mul((unsigned short)(hw[i] & 0xffffu), k0) | ((unsigned)myo_bf_mul((unsigned short)(hw[i] >> 16), k0) << 16);
+    co[i] = (unsigned)myo_f2bf(cw[2 * i]) | ((unsigned)myo_f2bf(cw[2 * i + 1]) << 16);
+  }
+  *reinterpret_cast<uint4*>(a.hm0 + dst) = make_uint4(ho[0], ho[1], ho[2], ho[3]);
+  *reinterpret_cast<uint4*>(a.cm0 + dst) = make_uint4(co[0], co[1], co[2], co[3]);
+  *reinterpret_cast<float4*>(a.c0_32 + dst) = make_float4(cw[0], cw[1], cw[2], cw[3]);
+  *reinterpret_cast<float4*>(a.c0_32 + dst + 4) = make_float4(cw[4], cw[5], cw[6], cw[7]);
+}
+// LSTM state entering a chunk of the rollout (recurrent PPO with seq_len), taken inside the per-step graph: the step index is read
+// on the device, steps that open no chunk return at once.  A thread moves 8 elements: one 16-byte vector of h, two of c.
+__global__ void __launch_bounds__(256) k_state_snapshot(const uint4* __restrict__ h, const float4* __restrict__ c32, size_t n8,
+                                                        const int* __restrict__ t_idx, int seq_len, int S,
+                                                        uint4* __restrict__ h_snap, float4* __restrict__ c_snap) {
+  const int t = *t_idx;
+  if (t < 0 || t % seq_len) return;
+  const int slot = t / seq_len;
+  if (slot >= S) return;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  h_snap[(size_t)slot * n8 + i] = h[i];
+  c_snap[((size_t)slot * n8 + i) * 2] = c32[2 * i];
+  c_snap[((size_t)slot * n8 + i) * 2 + 1] = c32[2 * i + 1];
 }
 // merges the block moments of k_ppo_gather in block order (Chan): mean and unbiased std
 __global__ void __launch_bounds__(64) k_moments_finish(const float* __restrict__ part, int nb, int bs, float* __restrict__ adv_stats) {
@@ -1236,6 +1321,41 @@ extern "C" int myo_ppo_gather(const float* obs, const float* act, const float* o
   if (adv_stats)      // NULL: the caller supplies the advantage moments itself (cross-rank moments, or no normalisation)
     hipLaunchKernelGGL(k_moments_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, work,
                        (bs + MYO_GATHER_ROWS - 1) / MYO_GATHER_ROWS, bs, adv_stats);
+  LAUNCH_CHECK(0)
+  return MYO_OK;
+}
+extern "C" int myo_ppo_gather_seq(const float* obs, const float* act, const float* oldlp, const float* adv, const float* ret,
+                                  const float* starts, const void* h_snap, const float* c_snap, const int64_t* chunk, int T, int N,
+                                  int L, int m, int G, int H, int obs_dim, int act_dim, uint16_t* obs_bf16, int copies, float* act_mb,
+                                  float* oldlp_mb, float* adv_mb, float* ret_mb, float* keep, uint16_t* hm0, uint16_t* cm0,
+                                  float* c0_32, float* adv_stats, float* work, void* stream) {
+  if (!obs || !act || !oldlp || !adv || !ret || !starts || !h_snap || !c_snap || !chunk || !obs_bf16 || !act_mb || !oldlp_mb ||
+      !adv_mb || !ret_mb || !keep || !hm0 || !cm0 || !c0_32 || !work || T < 1 || N < 1 || L < 1 || m < 1 || T % L || G < 1 || H < 8 ||
+      (H & 7) || obs_dim <= 0 || act_dim <= 0 || copies <= 0 || (long long)L * m > 0x7fffffffLL)
+    return fail(MYO_E_ARG, "myo_ppo_gather_seq: bad arguments");
+  GatherSeq a;
+  a.obs = obs; a.act = act; a.oldlp = oldlp; a.adv = adv; a.ret = ret; a.starts = starts; a.c_snap = c_snap;
+  a.h_snap = (const unsigned short*)h_snap; a.chunk = (const long long*)chunk;
+  a.N = N; a.L = L; a.m = m; a.S = T / L; a.G = G; a.H = H; a.O = obs_dim; a.A = act_dim; a.copies = copies;
+  const int bs = L * m;
+  a.nb = (bs + MYO_GATHER_ROWS - 1) / MYO_GATHER_ROWS;
+  a.obs_h = obs_bf16; a.hm0 = hm0; a.cm0 = cm0; a.act_mb = act_mb; a.oldlp_mb = oldlp_mb; a.adv_mb = adv_mb; a.ret_mb = ret_mb;
+  a.keep = keep; a.c0_32 = c0_32; a.part = work;
+  const long long vecs = (long long)G * m * (H / 8);
+  hipLaunchKernelGGL(k_ppo_gather_seq, dim3((unsigned)(a.nb + (vecs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  if (adv_stats)      // NULL: the caller supplies the advantage moments itself, as for myo_ppo_gather
+    hipLaunchKernelGGL(k_moments_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, work, a.nb, bs, adv_stats);
+  LAUNCH_CHECK(0)
+  return MYO_OK;
+}
+extern "C" int myo_rollout_state_snapshot(const void* h, const float* c32, int G, int N, int H, const int32_t* t_idx, int seq_len, int S,
+                                          void* h_snap, float* c_snap, void* stream) {
+  const long long n = (long long)G * N * H;
+  if (!h || !c32 || !t_idx || !h_snap || !c_snap || G < 1 || N < 1 || H < 1 || seq_len < 1 || S < 1 || (n & 7))
+    return fail(MYO_E_ARG, "myo_rollout_state_snapshot: bad arguments");
+  const size_t n8 = (size_t)(n / 8);
+  hipLaunchKernelGGL(k_state_snapshot, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)h,
+                     (const float4*)c32, n8, t_idx, seq_len, S, (uint4*)h_snap, (float4*)c_snap);
   LAUNCH_CHECK(0)
   return MYO_OK;
 }

@@ -179,6 +179,8 @@ class NativeLib:
         L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp]
         L.myo_ppo_loss_grad_hp.argtypes = L.myo_ppo_loss_grad.argtypes[:-1] + [vp, vp]
         L.myo_ppo_gather.argtypes = [vp] * 6 + [i32, i32, i32, vp, i32] + [vp] * 7
+        L.myo_ppo_gather_seq.argtypes = [vp] * 9 + [i32] * 8 + [vp, i32] + [vp] * 11
+        L.myo_rollout_state_snapshot.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
         L.myo_bias_relu_bf16.argtypes = [vp, vp, i32, i32, i32, vp]
         L.myo_splitk_reduce.argtypes = [vp, i32, vp, i32, i32, i32, vp]
         L.myo_splitk_reduce2.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp]
@@ -250,7 +252,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_reset", "myo_batch_step", "myo_batch_step_inner", "myo_batch_step_inner_idx", "myo_batch_copy_envs", "myo_batch_physics_step", "myo_batch_get_state",
     "myo_batch_set_state", "myo_batch_warmstart", "myo_batch_set_bad_state_buffer", "myo_batch_set_task", "myo_batch_get_task", "myo_batch_set_object_group", "myo_batch_object_friction", "myo_batch_bind_constants", "myo_batch_tune_wrap_order", "myo_batch_forward_dump",
     "myo_batch_dump_size", "myo_batch_dump_offset", "myo_batch_kernel_ms",
-    "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
+    "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_ppo_gather_seq", "myo_rollout_state_snapshot", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
     "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_clip_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_adam_apply", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_ppo_loss_grad_hp", "myo_adam_clip_step_hp", "myo_adam_apply_hp", "myo_last_error", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
     "myo_batch_contact_capacity", "myo_batch_sense",

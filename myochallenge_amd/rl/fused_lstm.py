@@ -122,16 +122,22 @@ class FusedRecurrentPPOStep(FusedPPOStep):
         return t
 
     @torch.no_grad()
-    def run_sequences(self, obs_buf, act_buf, start_buf, logp_buf, adv, ret, h0, c0, idx):
+    def run_sequences(self, obs_buf, act_buf, start_buf, logp_buf, adv, ret, h0, c0, idx, seq_len=None):
         """One minibatch step on the whole-rollout sequences of envs `idx`.
 
         obs_buf [T,N,O], act_buf [T,N,A], start_buf / logp_buf / adv / ret [T,N] (float32), h0 / c0 [2,N,H] float32
         (actor, critic LSTM state at the rollout start), idx int64 [m].  Returns (policy loss, value loss) as views of
-        the loss kernel's accumulator."""
+        the loss kernel's accumulator.
+
+        seq_len = L: the minibatch is m CHUNKS of L steps instead, idx holds item ids s * N + n (steps [s L, (s + 1) L) of env n)
+        and h0 / c0 are the rollout's snapshots, bf16 / float32 [T // L, 2, N, H] (the state that entered step s L, unmasked).
+        ``myo_ppo_gather_seq`` is the front of that step; everything behind it is the same code with L time steps."""
         lib, L = self.lib, self.lstm
         if self.adam is not None:
             self.adam.presummed = 0
         T, N, O = obs_buf.shape
+        if seq_len is not None:
+            return self._run_rows(*self._gather_chunks(obs_buf, act_buf, start_buf, logp_buf, adv, ret, h0, c0, idx, seq_len))
         m, A = idx.shape[0], self.A
         B, H = T * m, self.policy.lstm_actor.hidden_size
         dev, bf = obs_buf.device, torch.bfloat16
@@ -158,6 +164,41 @@ class FusedRecurrentPPOStep(FusedPPOStep):
         torch.mul(h0.index_select(1, idx), k0, out=hm[0])
         c0m = c0.index_select(1, idx).float() * k0                        # the masked cell state entering step 0, UNROUNDED: the forward
         cm[0].copy_(c0m)                                                  # pass carries c in float32 (the bf16 slots are the backward pass's)
+        return self._run_rows(x, act, oldlp, adv_mb, ret_mb, keep, hm, cm, c0m)
+
+    def _gather_chunks(self, obs_buf, act_buf, start_buf, logp_buf, adv, ret, h_snap, c_snap, idx, seq_len):
+        """The minibatch of m chunks of seq_len steps, one launch (+ the moments' merge): what _run_rows takes."""
+        lib = self.lib
+        Tr, N, O = obs_buf.shape
+        T, m, A, G = seq_len, idx.shape[0], self.A, 2
+        B, H = T * m, self.policy.lstm_actor.hidden_size
+        dev, bf = obs_buf.device, torch.bfloat16
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if not self.adam_syncs_shadow:
+            self.refresh_shadow()
+        x = torch.empty((1, B, O), device=dev, dtype=bf)
+        act, oldlp = torch.empty((B, A), device=dev), torch.empty(B, device=dev)
+        adv_mb, ret_mb, keep = torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty((T, m), device=dev)
+        hm = torch.empty((T + 1, G, m, H), dtype=bf, device=dev)
+        cm = torch.empty_like(hm)
+        c0m = torch.empty((G, m, H), device=dev)
+        work = self._workbuf("gather", 2 * ((B + 15) // 16))
+        lib.check(lib.L.myo_ppo_gather_seq(p(obs_buf), p(act_buf), p(logp_buf), p(adv), p(ret), p(start_buf), p(h_snap), p(c_snap), p(idx),
+                                           Tr, N, T, m, G, H, O, A, p(x), 1, p(act), p(oldlp), p(adv_mb), p(ret_mb), p(keep), p(hm[0]),
+                                           p(cm[0]), p(c0m), None if self.external_adv_stats else p(self.stats), p(work), st))
+        return x, act, oldlp, adv_mb, ret_mb, keep, hm, cm, c0m
+
+    def _run_rows(self, x, act, oldlp, adv_mb, ret_mb, keep, hm, cm, c0m):
+        """The step on a gathered minibatch: x bf16 [1, T*m, O] and the other rows t-major, keep [T, m], hm / cm bf16 [T + 1, 2, m, H]
+        with slot 0 filled (the masked state entering step 0), c0m its cell state in float32."""
+        lib, L = self.lib, self.lstm
+        (T, m), O, A = keep.shape, x.shape[2], self.A
+        B, H = T * m, self.policy.lstm_actor.hidden_size
+        dev, bf = x.device, torch.bfloat16
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        G, H4 = 2, 4 * H
         # ---- input projections of both LSTMs, all time steps: [B, O] x [O, 2*4H]
         bsum = (L["bihh"] + L["bhhh"]).view(G * H4)
         gx = torch.addmm(bsum, x[0], L["wihh"].view(G * H4, O).t()).view(T, m, G, H4)      # row (t, n): [actor 4H | critic 4H]

@@ -60,8 +60,22 @@ class PPOConfig:
     # SB3's KL early stop: a minibatch whose approx_kl exceeds 1.5 * target_kl is not applied and ends the update
     target_kl: Optional[float] = None
     clip_range_vf: Optional[float] = None   # value-function clipping is not implemented: anything but None is refused
+    # Recurrent policies: truncated BPTT as sb3-contrib trains (a minibatch = batch_size consecutive transitions, every sequence started
+    # from the LSTM state stored with its first transition [3P-RECALL, sb3-contrib 1.6.2 RecurrentRolloutBuffer]).  None: a minibatch is
+    # batch_size // n_steps whole rollouts from the state of the rollout start.  L: every env's rollout is cut into n_steps // L aligned
+    # chunks of L steps, a minibatch is batch_size // L chunks drawn from one permutation of all of them, each started from the state the
+    # rollout stored as it entered the chunk's first step (DESIGN.md §6 lists the differences from sb3-contrib).  The SB3 zip has no such
+    # field: a resumed run passes seq_len again.
+    seq_len: Optional[int] = None
 
     def __post_init__(self):
+        if self.seq_len is not None:
+            if self.seq_len < 1:
+                raise ValueError(f"seq_len={self.seq_len}: a chunk has at least one step")
+            if self.n_steps % self.seq_len:
+                raise ValueError(f"seq_len={self.seq_len} does not divide n_steps={self.n_steps}: chunks are aligned, none is padded")
+            if self.batch_size % self.seq_len:
+                raise ValueError(f"seq_len={self.seq_len} does not divide batch_size={self.batch_size}: a minibatch is whole chunks")
         if self.clip_range_vf is not None:
             raise NotImplementedError("clip_range_vf (value-function clipping) is not implemented; leave it None")
         if self.lr_schedule is not None:
@@ -107,6 +121,12 @@ class PPO:
         if cfg.target_kl is not None and (cfg.graph_allreduce or os.environ.get("MYO_GRAPH_ALLREDUCE") == "1"):
             raise ValueError("target_kl needs the host between gradient and optimizer step on N > 1 ranks (the all-reduced approx_kl "
                              "decides): it cannot be combined with graph_allreduce")
+        if cfg.seq_len is not None:
+            if not policy.recurrent:
+                raise ValueError("seq_len cuts the sequences of a recurrent policy: this policy has no LSTM")
+            if cfg.batch_size // cfg.seq_len > env.num_envs * cfg.n_steps // cfg.seq_len:
+                raise ValueError(f"batch_size={cfg.batch_size} asks for {cfg.batch_size // cfg.seq_len} chunks of {cfg.seq_len} steps, the "
+                                 f"rollout has {env.num_envs * cfg.n_steps // cfg.seq_len}")
         if not policy.recurrent and (cfg.n_steps * env.num_envs) % min(cfg.batch_size, cfg.n_steps * env.num_envs):
             # SB3 warns here too and then trains on the truncated last minibatch of each epoch; every update path of this
             # class works on fixed-size minibatches (one captured graph) and SKIPS that remainder instead
@@ -165,6 +185,9 @@ class PPO:
         self._last_starts = torch.ones(N, device=d)
         self._state = policy.initial_state(N, d)
         self._rollout_state0 = None
+        # seq_len: the state entering step s * seq_len of the rollout, slot s.  Eager and torch-graph rollouts: four float32
+        # [S, 1, N, H] views (h_pi, c_pi, h_vf, c_vf); HIP-kernel rollout: stacked (actor, critic) bf16 h / float32 c [S, 2, N, H]
+        self._snap_state, self._snap_full, self._snap_spare, self._snap_h, self._snap_c = None, None, None, None, None
         self.num_timesteps = 0
         self.n_updates = 0
         self.ep_returns: list = []
@@ -187,7 +210,7 @@ class PPO:
         # ... and the update: the captured MLP step (_build_graphs) and the captured recurrent step (_build_recurrent_graphs), each
         # with the shape it was captured for, its static tensors and its graphs
         self._graph, self._gs, self._graph_fb, self._graph_ap, self._graph_epoch, self._epoch_chunk = None, None, None, None, None, 0
-        self._rgraph, self._rg, self._rgraph_fb, self._rgraph_ap = None, None, None, None
+        self._rgraph, self._rg, self._rgraph_fb, self._rgraph_ap, self._rgraph_L = None, None, None, None, None
         self._allreduce_in_graph = False
         self._early_stopped, self._last_diag = False, None
 
@@ -201,6 +224,11 @@ class PPO:
 
     @torch.no_grad()
     def _rollout_policy_part(self):
+        if self.cfg.seq_len is not None and self.policy.recurrent:     # the state entering a chunk's first step goes to its slot, any other step's to the spare one
+            L = self.cfg.seq_len
+            slot = torch.where(self._t_idx % L == 0, torch.div(self._t_idx, L, rounding_mode="floor"), self._snap_spare)
+            for dst, src in zip(self._snap_full, self._state_s):
+                dst.index_copy_(0, slot, src.unsqueeze(0))
         with self._autocast():
             if self.policy.recurrent:
                 actions, values, logp, new_state = self.policy.act(self._obs_s, self._state_s, self._starts_s)
@@ -289,6 +317,9 @@ class PPO:
             self._bsum = torch.zeros((2, 1, 4 * H), device=d, dtype=bf)
             self.crit_h_buf, self.crit_c_buf = torch.zeros((T, N, H), device=d, dtype=bf), torch.zeros((T, N, H), device=d, dtype=bf)
             Lw = fused.lstm
+            if cfg.seq_len is not None:      # (allocated once: the update's captured graph reads them by address)
+                S = T // cfg.seq_len
+                self._snap_h, self._snap_c = torch.zeros((S, 2, N, H), device=d, dtype=bf), torch.zeros((S, 2, N, H), device=d)
 
         sde = getattr(self.policy, "use_sde", False)
         if sde:          # gSDE: myo_rollout_sample_sde leaves actions / log pi in step tensors, the rollout buffers take them by index
@@ -315,6 +346,9 @@ class PPO:
         def part_a_recurrent():
             st = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
             lib.check(lib.L.myo_rollout_policy_input(p(self._obs_s), N, O, p(self.obs_buf), p(self._x2), 2, p(self._t_idx), st))
+            if self._snap_h is not None:     # seq_len: the state entering a chunk's first step, before the mask (the device decides)
+                lib.check(lib.L.myo_rollout_state_snapshot(p(self._hs), p(self._cs32), 2, N, H, p(self._t_idx), cfg.seq_len,
+                                                           T // cfg.seq_len, p(self._snap_h), p(self._snap_c), st))
             keep = torch.rsub(self._starts_s, 1.0).view(1, N, 1)            # state zeroed where an episode starts
             torch.mul(self._hs, keep, out=self._hm)
             torch.mul(self._cs32, keep, out=self._cm32)
@@ -428,6 +462,22 @@ class PPO:
         Lw = self._fused_rec.lstm
         torch.add(Lw["bihh"], Lw["bhhh"], out=self._bsum.view(2, -1))
 
+    def _new_snapshots(self, state):
+        """seq_len on the eager and torch-graph rollouts: four [S, 1, N, H] snapshot buffers shaped after `state`, each the first S
+        slots of a buffer with one spare slot (where the captured rollout sends the steps that open no chunk)."""
+        S = self.cfg.n_steps // self.cfg.seq_len
+        self._snap_spare = torch.full((1,), S, dtype=torch.long, device=self.device)
+        self._snap_full = tuple(torch.zeros((S + 1,) + tuple(x.shape), device=self.device, dtype=x.dtype) for x in state)
+        self._snap_state = tuple(x[:S] for x in self._snap_full)
+
+    def rollout_snapshots(self):
+        """seq_len: (h_pi, c_pi, h_vf, c_vf) float32 [S, 1, N, H], the LSTM state that entered step s * seq_len of the last rollout
+        (before the episode-start mask), whichever rollout path stored it.  Slot 0 is _rollout_state0."""
+        if self._snap_h is not None:
+            h, c = self._snap_h, self._snap_c
+            return (h[:, 0:1].float(), c[:, 0:1], h[:, 1:2].float(), c[:, 1:2])
+        return self._snap_state
+
     def _native_state(self):
         """(h_pi, c_pi, h_vf, c_vf) float32 [1,N,H] from the native recurrent rollout's stacked state."""
         f = lambda z, k: z[k:k + 1].float()
@@ -449,6 +499,8 @@ class PPO:
         if self.policy.recurrent:               # static LSTM state (before / after the current step)
             self._state_s = tuple(x.clone() for x in self._state)
             self._state_new = tuple(torch.zeros_like(x) for x in self._state)
+            if self.cfg.seq_len is not None:
+                self._new_snapshots(self._state)
         side = torch.cuda.Stream(device=d)
         side.wait_stream(torch.cuda.current_stream(d))
         with torch.cuda.stream(side):           # eager warm-up (also binds the env's constants)
@@ -594,10 +646,15 @@ class PPO:
             self._last_obs = env.reset_tensor().clone()
         if pol.recurrent:
             self._rollout_state0 = tuple(s.clone() for s in self._state)
+            if cfg.seq_len is not None and self._snap_state is None:
+                self._new_snapshots(self._state)
         if hasattr(env, "begin_rollout"):
             env.begin_rollout()
         for t in range(cfg.n_steps):
             obs, starts = self._last_obs, self._last_starts
+            if cfg.seq_len is not None and t % cfg.seq_len == 0:      # the state entering a chunk's first step
+                for dst, src in zip(self._snap_state, self._state):
+                    dst[t // cfg.seq_len].copy_(src)
             with self._autocast():
                 actions, values, logp, new_state = pol.act(obs, self._state, starts)
             clipped = torch.clamp(actions, -1.0, 1.0)
@@ -764,11 +821,18 @@ class PPO:
     # ---------------------------------------------------------------- eager update (CPU, use_graphs=False, gSDE without stacked trunks)
     def _train_eager(self, adv, ret):
         """Autograd + torch Adam.  MLP policy: minibatches are rows of the flattened buffer; recurrent policy: whole rollouts of a
-        subset of envs, initial LSTM state = state at rollout start.  Returns the last minibatch's losses and the last epoch's
-        diagnostics."""
+        subset of envs, initial LSTM state = state at rollout start, or with seq_len chunks of the rollouts from the stored state
+        that entered them.  Returns the last minibatch's losses and the last epoch's diagnostics."""
         cfg, pol = self.cfg, self.policy
         T, N = cfg.n_steps, self.env.num_envs
-        if pol.recurrent:
+        if pol.recurrent and cfg.seq_len is not None:
+            L = cfg.seq_len
+            n_items, k = N * (T // L), cfg.batch_size // L
+            snaps = self.rollout_snapshots()
+
+            def evaluate(items):
+                return self._chunk_loss(items, snaps, adv, ret)
+        elif pol.recurrent:
             n_items, k = N, max(1, min(N, cfg.batch_size // T))
 
             def evaluate(idx):
@@ -805,6 +869,18 @@ class PPO:
             if self._early_stopped:
                 break
         return pl, vl, diag
+
+    def _chunk_loss(self, items, snaps, adv, ret):
+        """The loss of a minibatch of chunks (seq_len): item c = chunk c // N of env c % N, steps [s L, (s + 1) L), evaluated in one
+        call on [L, m, .] tensors from the snapshot states gathered per item (no host synchronisation: capturable)."""
+        N, L = self.env.num_envs, self.cfg.seq_len
+        s, n = torch.div(items, N, rounding_mode="floor"), items % N
+        tt = (s * L).unsqueeze(0) + torch.arange(L, device=items.device).unsqueeze(1)        # [L, m] rollout steps
+        sel = lambda buf: buf[tt, n]
+        st0 = tuple(x[s, 0, n].unsqueeze(0) for x in snaps)
+        with self._autocast():
+            v, lp, ent = self.policy.evaluate_actions(sel(self.obs_buf), sel(self.act_buf), st0, sel(self.start_buf))
+        return self._loss(v.reshape(-1), lp.reshape(-1), ent, sel(self.logp_buf).reshape(-1), sel(adv).reshape(-1), sel(ret).reshape(-1))
 
     # ---------------------------------------------------------------- hipGraph-captured minibatch step
     def _mb_forward_backward(self):
@@ -880,11 +956,12 @@ class PPO:
         self._flat_adam.restore(snap)
         return fb, ap, epoch, inside
 
-    def _run_captured(self, n_items, k, g, fb, ap, stats=None, epoch=None):
+    def _run_captured(self, n_items, k, g, fb, ap, stats=None, epoch=None, adv_of=None):
         """The epochs and minibatches of a captured update: a permutation of n_items per epoch, k of them per minibatch, staged by
         copying their indices into g["idx"] and run by replaying `fb` (one rank, or the all-reduce inside the graph: the whole step;
         else gradient -> eager all-reduce -> `ap`).  stats: where the moments of the GLOBAL minibatch's advantages go when the step
-        does not compute them itself.  epoch: the graph of _epoch_chunk whole steps, which then runs the epoch (_replay_epoch_chunked)."""
+        does not compute them itself (adv_of(items): those advantages, where the items are not columns of g["adv"]).  epoch: the graph of
+        _epoch_chunk whole steps, which then runs the epoch (_replay_epoch_chunked)."""
         cfg = self.cfg
         tkl = cfg.target_kl is not None
         # one rank with target_kl: the step itself compares approx_kl with the limit in the hyper-parameter block and, past it, raises
@@ -903,7 +980,8 @@ class PPO:
                 for s in range(0, n_items - k + 1, k):
                     g["idx"].copy_(perm[s:s + k])
                     if stats is not None:
-                        mean, std = self._global_adv_moments(g["adv"][..., perm[s:s + k]].double())
+                        items = perm[s:s + k]
+                        mean, std = self._global_adv_moments((adv_of(items) if adv_of is not None else g["adv"][..., items]).double())
                         stats.copy_(torch.stack([mean, std]).float())
                     fb.replay()
                     if ap is not None:
@@ -1008,12 +1086,19 @@ class PPO:
     def _rec_forward_backward(self):
         g = self._rg
         idx = g["idx"]
+        L = self._rgraph_L
         if self._fused_rec is not None:
+            state = (g["h0"], g["c0"]) if L is None else (g["h_snap"], g["c_snap"])
             pl, vl = self._fused_rec.run_sequences(self.obs_buf, self.act_buf, self.start_buf, self.logp_buf, g["adv"], g["ret"],
-                                                   g["h0"], g["c0"], idx)
+                                                   *state, idx, seq_len=L)
             g["pl"], g["vl"] = pl, vl             # views of the loss kernel's accumulator
             return
         self._flat_grad.zero_()
+        if L is not None:
+            loss, pl, vl = self._chunk_loss(idx, g["state0"], g["adv"], g["ret"])
+            loss.backward()
+            g["pl"].copy_(pl); g["vl"].copy_(vl)
+            return
         st0 = tuple(x.index_select(1, idx) for x in g["state0"])
         sel = lambda buf: buf.index_select(1, idx)
         with self._autocast():
@@ -1023,52 +1108,74 @@ class PPO:
         loss.backward()                       # p.grad are views of the flat gradient: accumulated in place
         g["pl"].copy_(pl); g["vl"].copy_(vl)
 
-    def _build_recurrent_graphs(self, T, N, m):
+    def _build_recurrent_graphs(self, T, N, m, L=None):
+        """The static tensors and the captured step for whole rollouts of m envs, or with L for m chunks of L steps: g["idx"] then
+        holds m item ids, and the state inputs are the rollout's snapshots."""
         d = self.device
-        self._rg = {"idx": torch.arange(m, device=d), "state0": tuple(torch.zeros_like(x) for x in self._rollout_state0),
+        state = self._rollout_state0 if L is None else self.rollout_snapshots()
+        if L is not None and self._fused_rec is not None:
+            state = ()                            # (the fused chunk step reads the stacked snapshots below)
+        self._rg = {"idx": torch.arange(m, device=d), "state0": tuple(torch.zeros_like(x) for x in state),
                     "adv": torch.zeros((T, N), device=d), "ret": torch.zeros((T, N), device=d),
                     "pl": torch.zeros((), device=d), "vl": torch.zeros((), device=d)}
-        if self._fused_rec is not None:           # stacked (actor, critic) LSTM state of the rollout start
-            H = self.policy.hidden
+        H = self.policy.hidden
+        if self._fused_rec is not None and L is None:           # stacked (actor, critic) LSTM state of the rollout start
             self._rg["h0"], self._rg["c0"] = torch.zeros((2, N, H), device=d), torch.zeros((2, N, H), device=d)
+        elif self._fused_rec is not None:
+            # stacked snapshots, bf16 h / float32 c [S, 2, N, H]: the HIP-kernel rollout's own buffers (written in place, read by address),
+            # else static copies that _rec_stage fills
+            self._rg["h_snap"], self._rg["c_snap"] = (self._snap_h, self._snap_c) if self._snap_h is not None else \
+                (torch.zeros((T // L, 2, N, H), device=d, dtype=torch.bfloat16), torch.zeros((T // L, 2, N, H), device=d))
+        self._rgraph_L = L
         # (BPTT over n_steps is one graph per minibatch already: no all-reduce inside the graph and no epoch-chunk graph here)
         self._rgraph_fb, self._rgraph_ap, _, _ = self._capture_step(self._rec_forward_backward, self._rg, graph_allreduce=False,
                                                                     epoch_steps=0)
-        self._rgraph = (T, N, m)
+        self._rgraph = (T, N, m, L)
 
-    def _rec_stage(self, adv, ret, T, N, m):
-        """Graphs for this shape (built on first use) and the update's inputs copied into their static tensors."""
+    def _rec_stage(self, adv, ret, T, N, m, L=None):
+        """Graphs for this shape (built on first use) and the update's inputs copied into their static tensors.  L: m chunks of L steps
+        (seq_len) instead of m whole rollouts."""
         cfg = self.cfg
         if self._fused_rec is not None:
             ext = (cfg.sync_adv_moments and self.world > 1) or not cfg.normalize_advantage
             if self._fused_rec.external_adv_stats != ext:
                 self._fused_rec.external_adv_stats = ext
                 self._rgraph = None
-        if self._rgraph != (T, N, m):
-            self._build_recurrent_graphs(T, N, m)
+        if self._rgraph != (T, N, m, L):
+            self._build_recurrent_graphs(T, N, m, L)
             self._hp_write()             # (the capture's warm-up steps have left their marks in the block)
         g = self._rg
         g["adv"].copy_(adv); g["ret"].copy_(ret)
-        for dst, src in zip(g["state0"], self._rollout_state0):
-            dst.copy_(src)
         fr = self._fused_rec
+        state = self._rollout_state0 if L is None else self.rollout_snapshots()
+        if fr is None or L is None:
+            for dst, src in zip(g["state0"], state):
+                dst.copy_(src)
         if fr is not None:
             fr.refresh_shadow()                   # (parameters may have been loaded since the last update)
-            hp, cp, hv, cv = self._rollout_state0
-            g["h0"][0].copy_(hp[0]); g["h0"][1].copy_(hv[0]); g["c0"][0].copy_(cp[0]); g["c0"][1].copy_(cv[0])
+            hp, cp, hv, cv = state
+            if L is None:
+                g["h0"][0].copy_(hp[0]); g["h0"][1].copy_(hv[0]); g["c0"][0].copy_(cp[0]); g["c0"][1].copy_(cv[0])
+            elif g["h_snap"] is not self._snap_h:
+                g["h_snap"][:, 0:1].copy_(hp); g["h_snap"][:, 1:2].copy_(hv); g["c_snap"][:, 0:1].copy_(cp); g["c_snap"][:, 1:2].copy_(cv)
             if not cfg.normalize_advantage:
                 fr.stats.copy_(torch.tensor([0.0, 1.0], device=self.device))
         return g
 
     def _train_recurrent_graphed(self, adv, ret):
         """Same minibatches as the eager recurrent path (whole rollouts of a random subset of envs, LSTM state of
-        the rollout start), replayed from a graph: BPTT over n_steps is thousands of small launches."""
+        the rollout start; with seq_len: chunks from their snapshot states), replayed from a graph: BPTT over n_steps is thousands
+        of small launches."""
         cfg = self.cfg
-        T, N = cfg.n_steps, self.env.num_envs
-        m = max(1, min(N, cfg.batch_size // T))
-        g, fr = self._rec_stage(adv, ret, T, N, m), self._fused_rec
+        T, N, L = cfg.n_steps, self.env.num_envs, cfg.seq_len
+        m = max(1, min(N, cfg.batch_size // T)) if L is None else cfg.batch_size // L
+        g, fr = self._rec_stage(adv, ret, T, N, m, L), self._fused_rec
         global_moments = fr is not None and fr.external_adv_stats and cfg.normalize_advantage
-        self._run_captured(N, m, g, self._rgraph_fb, self._rgraph_ap, stats=fr.stats if global_moments else None)
+        adv_of = None
+        if L is not None:        # the advantages of a minibatch of chunks (item c = chunk c // N of env c % N), for the cross-rank moments
+            adv_of = lambda items: g["adv"].view(T // L, L, N)[torch.div(items, N, rounding_mode="floor"), :, items % N]
+        self._run_captured(N if L is None else N * (T // L), m, g, self._rgraph_fb, self._rgraph_ap,
+                           stats=fr.stats if global_moments else None, adv_of=adv_of)
         return g["pl"], g["vl"]
 
     # ---------------------------------------------------------------- persistence (SB3 zip layout)

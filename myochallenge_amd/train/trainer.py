@@ -7,6 +7,8 @@ calls ``agent.learn(total_timesteps, callback=callbacks, reset_num_timesteps=Tru
 ``final_model.pkl`` (a model zip, despite the suffix) and ``final_env.pkl``.  ``model_config`` keys are SB3's
 constructor keywords; callables (``lambda _: 5e-05``, ``lambda p: 3e-4 * p``) are SB3 schedules of progress_remaining and
 reach the agent as such (``PPOConfig.lr_schedule`` / ``clip_range_schedule``); ``target_kl`` is the agent's KL early stop.
+``model_config["seq_len"]`` (not an SB3 keyword, not stored in a model zip: a resumed run passes it again) is ``PPOConfig.seq_len``,
+the truncated-BPTT length of sb3-contrib's ``batch_size`` consecutive transitions.
 One addition: ``model_config["policy"] = "MlpPolicy"`` selects the MLP actor-critic (the hipGraph fast
 path); the default stays ``"MlpLstmPolicy"``.
 """
@@ -21,7 +23,7 @@ from ..rl.policy import ActorCriticPolicy
 from ..rl.ppo import PPO, PPOConfig
 
 _PPO_KEYS = ("n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "ent_coef", "vf_coef", "max_grad_norm",
-             "normalize_advantage")
+             "normalize_advantage", "seq_len")
 _IGNORED = ("verbose", "tensorboard_log", "device", "sde_sample_freq", "create_eval_env", "_init_setup_model")
 
 
