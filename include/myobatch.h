@@ -310,6 +310,8 @@ typedef struct myo_render_camera {      /* MuJoCo's free camera (mjvCamera, type
 #define MYO_RENDER_SEG 4
 #define MYO_RENDER_SITES 8              /* draw every site, not only the task's targets */
 #define MYO_RENDER_TENDONS 16           /* draw the tendon items of myo_batch_tendon_paths after the geoms and sites */
+#define MYO_RENDER_CONTACTS 32          /* draw the contact items of myo_batch_contact_items (points and forces) after them; bit 64 is
+                                         * reserved and refused */
 #define MYO_RENDER_ITEM_N 24            /* doubles per item of myo_batch_geom_poses / myo_batch_tendon_paths */
 #define MYO_RENDER_MAX_PIXELS (1 << 24) /* width * height */
 
@@ -345,16 +347,55 @@ int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* ou
  * output or k < 0 returns MYO_E_ARG before any device call. */
 int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream);
 
+/* Contact item pass (MuJoCo's mjVIS_CONTACTPOINT / mjVIS_CONTACTFORCE): for envs env_idx[0 .. k) (dev int32; an index outside
+ * [0, N) gets all-zero rows), one wave per env runs the forward pass of myo_batch_sense at the env's present state — the same device
+ * functions, so the contacts are the ones myo_batch_sense reports for that state: same pair order, same slots, same warm-started
+ * solve — and one lane per contact slot writes two items of the pose pass's format into out (dev double[k, 2 * cap,
+ * MYO_RENDER_ITEM_N], cap = myo_batch_contact_capacity).  Slot c owns rows 2c and 2c + 1; rows of slots >= ncon are all zero
+ * (alpha 0 = never drawn).
+ *   row 2c, the contact point: a cylinder (a flat disc) centred at the contact's pos; rotation [3..12) with its third column the
+ *     contact normal and the first two mju_makeFrame's tangents of it, in that order; size [12..15) = disc_radius, disc_half_height,
+ *     0; type [15] = cylinder; rgba [16..20) = point_rgba; bounding radius [20] = sqrt(radius^2 + half height^2); 0 [21];
+ *     slot + 1 [22]; the contact's dist [23].
+ *   row 2c + 1, the contact force: the world force on geom2's body, F = n f0 + t1 f1 + t2 f2 from the first three components of
+ *     con_d's force[6] in that frame (torsional and rolling components are not drawn), as a capsule from pos to pos +
+ *     metres_per_newton * F laid out like a tendon piece: midpoint [0..3), rotation with its third column along F, size =
+ *     force_radius, half length, 0; rgba = force_rgba; bounding radius = radius + half length; 0 [21]; slot + 1 [22]; |F| in
+ *     newtons [23].  |F| == 0 (a contact inside the margin that carries no force): an all-zero row.  No arrow head: a shaft only.
+ * Sizes and colours come from the batch's myo_render_style — this library's own drawing rule, NOT MuJoCo's (whose contact
+ * colouring and meansize / meanmass scaling are not reproduced or claimed here).  Defaults, for a hand-sized scene: disc radius
+ * 0.003 m, half height 0.0005 m; shaft radius 0.001 m; 0.02 m/N; point_rgba (0.9, 0.6, 0.2, 1); force_rgba (0.7, 0.9, 0.9, 1);
+ * geom_alpha 1.  geom_alpha multiplies the alpha of GEOM items (not sites, tendons or contact items) in renders with
+ * MYO_RENDER_CONTACTS only — mjVIS_TRANSPARENT's job: a disc sits inside the penetration of two surfaces and is hidden otherwise.
+ * `size` = sizeof(myo_render_style), first, so that the struct can grow; set / get with another size, a NULL argument, a
+ * non-finite or negative length, or a colour component / geom_alpha outside [0, 1] return MYO_E_ARG.
+ * The pass is read-only exactly as myo_batch_sense is: no record, warm start, draw counter, step generation or wrap order changes; a
+ * pass that has to drop contacts beyond the capacity counts it in myo_batch_health.  A null output or k < 0 returns MYO_E_ARG before
+ * any device call. */
+typedef struct myo_render_style {
+  size_t size;
+  double disc_radius, disc_half_height, force_radius, metres_per_newton;
+  float point_rgba[4], force_rgba[4];
+  double geom_alpha;
+} myo_render_style;
+int myo_batch_set_render_style(myo_batch* b, const myo_render_style* style);
+int myo_batch_get_render_style(const myo_batch* b, myo_render_style* style);
+int myo_batch_contact_items(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream);
+
 /* Pinhole ray casting of the items of envs env_idx[0 .. k): one ray through every pixel centre, row 0 at the top (gym's
  * rgb_array; mjr_readPixels is bottom-up).  cams: HOST array of ncams cameras, ncams = 1 (all envs) or k (one per env).
  * flags: MYO_RENDER_* ; each requested output is a dev buffer owned by the caller:
  *   rgb   uint8 [k, height, width, 3]  headlight Lambert shading rgb * (0.3 + 0.7 |n . d|) over a fixed background; a
  *                                      translucent item (alpha < 1) nearer than the nearest opaque one is blended over it
  *   depth float [k, height, width]     distance along the camera axis, +inf for the background
- *   segid int32 [k, height, width]     geom id, ngeom + site id for sites, ngeom + nsite + tendon id for tendons, -1 for the background
+ *   segid int32 [k, height, width]     geom id, ngeom + site id for sites, ngeom + nsite + tendon id for tendons, ngeom + nsite +
+ *                                      ntendon + contact slot for both items of a contact, -1 for the background
  * With MYO_RENDER_TENDONS the tendon items are drawn after the geoms and sites under the same shading, translucency, depth and
  * tile-culling rules (a second pass of the tile over the same pixels; a model with more than 512 tendon items is refused with
  * MYO_E_ARG, never truncated).  Without the flag nothing about the call changes.
+ * With MYO_RENDER_CONTACTS the contact items of myo_batch_contact_items are drawn after those, under the same rules (one more pass
+ * of the tile over the same pixels), and the geoms' alpha is multiplied by the style's geom_alpha.  Without the flag the call
+ * launches exactly what it launched before the flag existed.
  * Depth and segmentation are those of the nearest drawn surface, translucent ones included.  Invalid arguments return
  * MYO_E_ARG before any device call. */
 int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,

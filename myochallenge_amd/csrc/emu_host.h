@@ -184,11 +184,73 @@ extern "C" int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int 
   emu_tendon_paths(b, env_idx, k, out);
   return MYO_OK;
 }
+static void emu_contact_items(myo_batch* b, const int32_t* env_idx, int k, double* out) {
+  const int ncitem = 2 * sense_capacity(b);
+  std::vector<double> tmp(contact_tmp_doubles(b, k));
+  const SenseDev T = contact_tmp(b, k, tmp.data());
+  with_scratch(b, [&](auto& M, auto& s) {
+    for (int r = 0; r < k; ++r) {
+      const int e = env_idx[r];
+      double* o = out + (size_t)r * ncitem * MYO_RENDER_ITEM_N;
+      if (e < 0 || e >= b->n) memset(o, 0, sizeof(double) * (size_t)ncitem * MYO_RENDER_ITEM_N);
+      else env_contact_items(M, b->K, b->L, env_rec(b, e), s, e, r, T, b->style, o);
+    }
+  });
+}
+extern "C" int myo_batch_contact_items(myo_batch* b, const int32_t* env_idx, int k, double* out, void*) {
+  int empty = 0;
+  int rc = contact_items_check(b, env_idx, k, out, &empty);
+  if (rc || empty) return rc;
+  emu_contact_items(b, env_idx, k, out);
+  return MYO_OK;
+}
+// MYO_RENDER_CONTACTS (k_render_layers): the tables one after the other through one item table into the same hits
+static void emu_render_layers(myo_batch* b, const int32_t* env_idx, int k, const std::vector<double>& cam_tab, int ncams, int width, int height,
+                              int flags, uint8_t* rgb, float* depth, int32_t* segid) {
+  const bool tendons = (flags & MYO_RENDER_TENDONS) && b->ntitem > 0;
+  const int ncitem = 2 * sense_capacity(b), ntitem = tendons ? b->ntitem : 0;
+  std::vector<double> items((size_t)k * b->nitem * MYO_RENDER_ITEM_N), titems((size_t)k * ntitem * MYO_RENDER_ITEM_N), citems((size_t)k * ncitem * MYO_RENDER_ITEM_N);
+  emu_geom_poses(b, env_idx, k, items.data());
+  if (tendons) emu_tendon_paths(b, env_idx, k, titems.data());
+  emu_contact_items(b, env_idx, k, citems.data());
+  std::vector<RItem> lds((size_t)std::max(b->nitem, std::max(ntitem, ncitem)));
+  std::vector<RHit> hits(MYO_RTILE * MYO_RTILE);
+  std::vector<float> dirs(3 * MYO_RTILE * MYO_RTILE);
+  const int tiles_x = (width + MYO_RTILE - 1) / MYO_RTILE, tiles_y = (height + MYO_RTILE - 1) / MYO_RTILE, nt = MYO_RTILE * MYO_RTILE;
+  for (int e = 0; e < k; ++e) {
+    const double* cam = &cam_tab[(size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N];
+    RLayers Y;
+    Y.it = items.data() + (size_t)e * b->nitem * MYO_RENDER_ITEM_N; Y.tn = titems.data() + (size_t)e * ntitem * MYO_RENDER_ITEM_N;
+    Y.cn = citems.data() + (size_t)e * ncitem * MYO_RENDER_ITEM_N;
+    Y.nitem = b->nitem; Y.ngeom = b->ngeom; Y.ntitem = ntitem; Y.ncitem = ncitem; Y.seg_c = b->nitem + b->ntendon; Y.geom_alpha = (float)b->style.geom_alpha;
+    for (int ty = 0; ty < tiles_y; ++ty)
+      for (int tx = 0; tx < tiles_x; ++tx) {
+        const int tx0 = tx * MYO_RTILE, ty0 = ty * MYO_RTILE;
+        auto PX = [&](int t) { return tx0 + t % MYO_RTILE; };
+        auto PY = [&](int t) { return ty0 + t / MYO_RTILE; };
+        auto trace = [&](int n, int base) {
+          for (int t = 0; t < nt; ++t) render_cull(t, lds.data(), n, cam, width, height, tx0, ty0);
+          for (int t = 0; t < nt; ++t) if (PX(t) < width && PY(t) < height) render_trace(lds.data(), n, base, &dirs[3 * t], hits[t]);
+        };
+        for (int t = 0; t < nt; ++t) render_ray(cam, width, height, PX(t), PY(t), &dirs[3 * t], hits[t]);
+        for (int t = 0; t < nt; ++t) render_stage_geoms(t, lds.data(), Y.it, Y.nitem, Y.ngeom, Y.geom_alpha, cam, flags);
+        trace(Y.nitem, 0);
+        if (ntitem > 0) {
+          for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), Y.tn, ntitem, cam, flags);
+          trace(ntitem, Y.nitem);
+        }
+        for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), Y.cn, ncitem, cam, flags);
+        trace(ncitem, Y.nitem + ntitem);
+        for (int t = 0; t < nt; ++t) render_layers_finish(Y, cam, width, height, PX(t), PY(t), flags, (size_t)e, hits[t], &dirs[3 * t], rgb, depth, segid);
+      }
+  }
+}
 extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
                                 int flags, uint8_t* rgb, float* depth, int32_t* segid, void*) {
   std::vector<double> cam_tab;
   int rc = render_check(b, env_idx, k, cams, ncams, width, height, flags, rgb, depth, segid, cam_tab);
   if (rc) return rc;
+  if (flags & MYO_RENDER_CONTACTS) { emu_render_layers(b, env_idx, k, cam_tab, ncams, width, height, flags, rgb, depth, segid); return MYO_OK; }
   std::vector<double> items((size_t)k * b->nitem * MYO_RENDER_ITEM_N);
   emu_geom_poses(b, env_idx, k, items.data());
   const bool tendons = (flags & MYO_RENDER_TENDONS) && b->ntitem > 0;

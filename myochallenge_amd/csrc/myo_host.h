@@ -24,8 +24,8 @@
 #include "../../include/myo_model_blob.h"
 #include "myo_mjb.h"
 #include "myo_task.h"
-#include "myo_render.h"
 #include "myo_sense.h"
+#include "myo_render.h"
 
 
 // ------------------------------------------------------------------------------------------ backend (defined by the including file)
@@ -1027,6 +1027,8 @@ struct myo_batch {
   double* render_ws = nullptr; // dev: item poses and cameras of myo_batch_render, grown on demand (not in allocs)
   size_t render_ws_bytes = 0;
   std::vector<double> cam_host;      // the cameras of the last myo_batch_render (source of its asynchronous upload)
+  // how contact items are drawn (myo_batch_set_render_style; the defaults of include/myobatch.h)
+  myo_render_style style = {sizeof(myo_render_style), 0.003, 0.0005, 0.001, 0.02, {0.9f, 0.6f, 0.2f, 1.f}, {0.7f, 0.9f, 0.9f, 1.f}, 1.0};
   MYO_BACKEND_BATCH_FIELDS     // what the backend keeps per batch (the HIP backend: its timing events)
 };
 
@@ -1424,7 +1426,7 @@ static int render_check(const myo_batch* b, const int32_t* env_idx, int k, const
   if (!cams || (ncams != 1 && ncams != k)) return fail(MYO_E_ARG, "myo_batch_render: ncams must be 1 or k (%d), got %d", k, ncams);
   if (width <= 0 || height <= 0 || (long long)width * height > MYO_RENDER_MAX_PIXELS)
     return fail(MYO_E_ARG, "myo_batch_render: width and height must be >= 1 with width * height <= %d", MYO_RENDER_MAX_PIXELS);
-  if (flags & ~(MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG | MYO_RENDER_SITES | MYO_RENDER_TENDONS)) return fail(MYO_E_ARG, "myo_batch_render: unknown flag bits 0x%x", flags);
+  if (flags & ~(MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG | MYO_RENDER_SITES | MYO_RENDER_TENDONS | MYO_RENDER_CONTACTS)) return fail(MYO_E_ARG, "myo_batch_render: unknown flag bits 0x%x", flags);
   if (!(flags & (MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG))) return fail(MYO_E_ARG, "myo_batch_render: no output requested");
   if ((flags & MYO_RENDER_TENDONS) && b->ntitem > MYO_RTEN_MAX)
     return fail(MYO_E_ARG, "myo_batch_render: MYO_RENDER_TENDONS: %d tendon items, at most %d can be drawn", b->ntitem, MYO_RTEN_MAX);
@@ -1432,6 +1434,34 @@ static int render_check(const myo_batch* b, const int32_t* env_idx, int k, const
     return fail(MYO_E_ARG, "myo_batch_render: a requested output buffer is NULL");
   if ((long long)k * width * height > (1ll << 31)) return fail(MYO_E_ARG, "myo_batch_render: k * width * height exceeds 2^31 pixels");
   return render_cameras(cams, ncams, height, cam_tab);
+}
+// myo_batch_contact_items: as myo_batch_tendon_paths; k = 0 is an empty result (*empty)
+static int contact_items_check(const myo_batch* b, const int32_t* env_idx, int k, const double* out, int* empty) {
+  if (!b) return fail(MYO_E_ARG, "myo_batch_contact_items: null batch");
+  if (k < 0) return fail(MYO_E_ARG, "myo_batch_contact_items: k must be >= 0, got %d", k);
+  if (!out) return fail(MYO_E_ARG, "myo_batch_contact_items: null output");
+  if (k > 0 && !env_idx) return fail(MYO_E_ARG, "myo_batch_contact_items: null env_idx");
+  *empty = k == 0;
+  return MYO_OK;
+}
+// the style of the contact items: held per batch, read by the next contact item pass / render with MYO_RENDER_CONTACTS
+extern "C" int myo_batch_set_render_style(myo_batch* b, const myo_render_style* st) {
+  if (!b || !st) return fail(MYO_E_ARG, "myo_batch_set_render_style: null batch or style");
+  if (st->size != sizeof(myo_render_style)) return fail(MYO_E_ARG, "myo_batch_set_render_style: myo_render_style.size is %zu, this library's struct has %zu bytes", st->size, sizeof(myo_render_style));
+  const double len[4] = {st->disc_radius, st->disc_half_height, st->force_radius, st->metres_per_newton};
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(len[k]) || len[k] < 0) return fail(MYO_E_ARG, "myo_batch_set_render_style: radii, half height and metres_per_newton must be finite and >= 0");
+  bool ok = st->geom_alpha >= 0 && st->geom_alpha <= 1;
+  for (int k = 0; k < 4; ++k) ok = ok && st->point_rgba[k] >= 0.f && st->point_rgba[k] <= 1.f && st->force_rgba[k] >= 0.f && st->force_rgba[k] <= 1.f;
+  if (!ok) return fail(MYO_E_ARG, "myo_batch_set_render_style: colour components and geom_alpha must be in [0, 1]");
+  b->style = *st;
+  return MYO_OK;
+}
+extern "C" int myo_batch_get_render_style(const myo_batch* b, myo_render_style* st) {
+  if (!b || !st) return fail(MYO_E_ARG, "myo_batch_get_render_style: null batch or style");
+  if (st->size != sizeof(myo_render_style)) return fail(MYO_E_ARG, "myo_batch_get_render_style: myo_render_style.size is %zu, this library's struct has %zu bytes", st->size, sizeof(myo_render_style));
+  *st = b->style;
+  return MYO_OK;
 }
 // the render workspace: k item tables then the cameras (doubles); grown on demand
 static int render_workspace(myo_batch* b, size_t doubles) {
@@ -1575,6 +1605,16 @@ static SenseDev sense_dev(const myo_batch* b, const myo_sense_out* o) {
   return d;
 }
 extern "C" int myo_batch_contact_capacity(const myo_batch* b) { return b ? sense_capacity(b) : -1; }
+// the compact temporaries of a contact item pass over k envs (csrc/myo_render.h env_contact_items), in doubles at `base`:
+// con_d [k, cap, 13], then ncon int32 [k]
+static size_t contact_tmp_doubles(const myo_batch* b, int k) { return (size_t)k * sense_capacity(b) * MYO_SENSE_CON_N + ((size_t)k + 1) / 2; }
+static SenseDev contact_tmp(const myo_batch* b, int k, double* base) {
+  SenseDev d = {};
+  d.cap = sense_capacity(b);
+  d.con_d = base;
+  d.ncon = (int*)(base + (size_t)k * d.cap * MYO_SENSE_CON_N);
+  return d;
+}
 // k = 0 is an empty copy (*empty)
 static int copy_envs_check(const myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, int* empty) {
   if (!dst || !src || !dst_idx || !src_idx || k < 0) return fail(MYO_E_ARG, "myo_batch_copy_envs: null argument");

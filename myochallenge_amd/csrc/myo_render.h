@@ -9,6 +9,10 @@
 //   tendons    MYO_RENDER_TENDONS (k_render_tendons): the same tile runs a SECOND LDS pass over the same pixels — the geoms' table is
 //              traced, then the tendon items are staged over it, culled and traced into the same per-pixel hit; the hit items are shaded
 //              from their global rows.  The LDS allocation is max(items, tendon items) * sizeof(RItem), not their sum.
+//   contacts   env_contact_items: one wave per listed env runs env_sense (csrc/myo_sense.h, unchanged) into a compact temporary of the render
+//              workspace, then one lane per contact slot writes the slot's point (a disc) and force (a capsule shaft) items.
+//              MYO_RENDER_CONTACTS (k_render_layers): the tile traces two or three tables in turn — geoms, tendons if asked for, contact
+//              items — through the same LDS table into the same per-pixel hit; the allocation is the largest table's.
 // The per-thread functions take the thread index, so the emulation build (csrc/emu_host.h) runs the same code thread by thread.
 #pragma once
 
@@ -163,6 +167,66 @@ DEV void env_tendon_paths(const DevModel<T>& M_in, const TaskDev& K_in, const En
   }
   SYNC();
   ws_release(K, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- contact item pass
+// the two items of contact slot c from its con_d row (dist, pos[3], normal[3], force[6]): o[0 .. 24) the point, o[24 .. 48) the force
+DEV void contact_slot_items(double* o, const double* cd, int c, const myo_render_style& st) {
+  const HP pos[3] = {cd[1], cd[2], cd[3]}, nrm[3] = {cd[4], cd[5], cd[6]};
+  // the contact frame as the stepper builds it: make_frame on a copy of the normal, the record's six numbers, the second tangent
+  struct { HP nrm[3], tinv; } cf;
+  HP fr[6] = {nrm[0], nrm[1], nrm[2], 0, 0, 0}, t2[3];
+  cf.tinv = make_frame(fr);
+  for (int k = 0; k < 3; ++k) cf.nrm[k] = fr[k];
+  con_frame(cf, fr);
+  con_t2(fr, t2);
+  const HP r = (HP)st.disc_radius, h = (HP)st.disc_half_height;
+  for (int k = 0; k < 3; ++k) {
+    o[k] = pos[k];
+    o[3 + 3 * k] = fr[3 + k]; o[4 + 3 * k] = t2[k]; o[5 + 3 * k] = nrm[k];
+  }
+  o[12] = r; o[13] = h; o[14] = 0;
+  o[15] = MYO_GEOM_CYLINDER;
+  for (int k = 0; k < 4; ++k) o[16 + k] = (HP)st.point_rgba[k];
+  o[20] = sqrt(r * r + h * h); o[21] = 0; o[22] = c + 1; o[23] = cd[0];
+  // the world force on geom2's body and its shaft from the contact point
+  HP F[3], tip[3];
+  for (int k = 0; k < 3; ++k) F[k] = nrm[k] * cd[7] + fr[3 + k] * cd[8] + t2[k] * cd[9];
+  const HP fn = norm3(F);
+  double* o2 = o + MYO_RENDER_ITEM_N;
+  if (fn > 0) {
+    const HP rgba[4] = {(HP)st.force_rgba[0], (HP)st.force_rgba[1], (HP)st.force_rgba[2], (HP)st.force_rgba[3]};
+    for (int k = 0; k < 3; ++k) tip[k] = pos[k] + (HP)st.metres_per_newton * F[k];
+    tendon_item(o2, pos, tip, (HP)st.force_radius, rgba, c, fn);
+  } else {
+    for (int k = 0; k < MYO_RENDER_ITEM_N; ++k) o2[k] = 0;
+  }
+}
+// row `row` of the call (env `env` of the batch): tmp = the call's compact temporaries ncon [k], con_d [k, cap, 13].  env_sense indexes
+// its outputs by batch env, so it is handed pointers offset by (row - env) strides: its stores land in row `row`.
+template <typename T, int NC>
+DEV void env_contact_items(const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s, int env, int row,
+                           const SenseDev& tmp, const myo_render_style& st, double* out) {
+  WAVE_FN_K
+  const int cap = tmp.cap;
+  const long long shift = (long long)row - (long long)env;
+  SenseDev O;
+  O.con_geom = nullptr; O.body_wrench = nullptr; O.qfrc_constraint = nullptr;
+  O.act_length = nullptr; O.act_velocity = nullptr; O.act_force = nullptr; O.activation = nullptr; O.ten_length = nullptr; O.ten_velocity = nullptr;
+  O.cap = cap;
+  O.ncon = tmp.ncon + shift;
+  O.con_d = tmp.con_d + shift * (long long)(cap * MYO_SENSE_CON_N);
+  env_sense(M, K, L, rec, s, env, O);
+  SYNC_G();      // (the rows below are read by other lanes than the ones that stored them)
+  const double* cd = tmp.con_d + (size_t)row * cap * MYO_SENSE_CON_N;
+  PHASE {
+    const int ncon = tmp.ncon[row];
+    for (int c = lane; c < cap; c += 64) {
+      double* o = out + (size_t)c * 2 * MYO_RENDER_ITEM_N;
+      if (c < ncon) contact_slot_items(o, cd + (size_t)c * MYO_SENSE_CON_N, c, st);
+      else for (int k = 0; k < 2 * MYO_RENDER_ITEM_N; ++k) o[k] = 0;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- ray cast
@@ -368,6 +432,39 @@ DEV void render_pixel_finish(const double* it, int nitem, const double* tn, cons
     render_load(rt, o, cam, flags);
     if (h.it >= nitem) st = nitem + (int)o[22] - 1;
   }
+  const size_t pix = (e * (size_t)H + (size_t)py) * (size_t)W + (size_t)px;
+  render_write(&ro, &rt, so, st, h, d, flags, pix, rgb, depth, seg);
+}
+// ... with MYO_RENDER_CONTACTS (k_render_layers).  The geoms' table is staged with the style's geom_alpha on the alpha of the geoms
+// (items < ngeom; the sites keep theirs) ...
+DEV void render_stage_geoms(int tid, RItem* lds, const double* it, int nitem, int ngeom, float geom_alpha, const double* cam, int flags) {
+  for (int i = tid; i < nitem; i += MYO_RTILE * MYO_RTILE) {
+    RItem& r = lds[i];
+    render_load(r, it + (size_t)i * MYO_RENDER_ITEM_N, cam, flags);
+    if (i < ngeom) { r.rgba[3] *= geom_alpha; if (!(r.rgba[3] > 0.f)) r.draw = 0; }
+  }
+}
+// ... and after every table was traced into h the hit items come from their global rows: `it` the env's nitem items, `tn` its ntitem
+// tendon items (0: that table was not traced), `cn` its contact items.  A contact item's id is seg_c + its slot ([22] - 1),
+// seg_c = ngeom + nsite + ntendon.
+struct RLayers { const double *it, *tn, *cn; int nitem, ngeom, ntitem, ncitem, seg_c; float geom_alpha; };
+DEV int render_layer_item(RItem& r, const RLayers& Y, int idx, const double* cam, int flags) {
+  const double* o;
+  int id;
+  if (idx < Y.nitem) { o = Y.it + (size_t)idx * MYO_RENDER_ITEM_N; id = idx; }
+  else if (idx < Y.nitem + Y.ntitem) { o = Y.tn + (size_t)(idx - Y.nitem) * MYO_RENDER_ITEM_N; id = Y.nitem + (int)o[22] - 1; }
+  else { o = Y.cn + (size_t)(idx - Y.nitem - Y.ntitem) * MYO_RENDER_ITEM_N; id = Y.seg_c + (int)o[22] - 1; }
+  render_load(r, o, cam, flags);
+  if (idx < Y.ngeom) r.rgba[3] *= Y.geom_alpha;
+  return id;
+}
+DEV void render_layers_finish(const RLayers& Y, const double* cam, int W, int H, int px, int py, int flags, size_t e, const RHit& h, const float* d,
+                              unsigned char* rgb, float* depth, int* seg) {
+  if (px >= W || py >= H) return;
+  RItem ro, rt;
+  int so = h.io, st = h.it;
+  if (h.io >= 0) so = render_layer_item(ro, Y, h.io, cam, flags);
+  if (h.it >= 0) st = render_layer_item(rt, Y, h.it, cam, flags);
   const size_t pix = (e * (size_t)H + (size_t)py) * (size_t)W + (size_t)px;
   render_write(&ro, &rt, so, st, h, d, flags, pix, rgb, depth, seg);
 }

@@ -425,6 +425,61 @@ __global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render_tendons(const 
   if (inside) render_trace(lds, ntitem, nitem, d, h);
   render_pixel_finish(it, nitem, tn, cam, W, H, px, py, flags, (size_t)e, h, d, rgb, depth, seg);
 }
+// render contact item pass (csrc/myo_render.h): row r of `out` = the 2 * cap contact items of env env_idx[r]; an index outside
+// [0, n_envs): all zero.  Keyed like k_sense: arithmetic x contact capacity.
+template <typename T, int NC>
+__global__ void __launch_bounds__(64, 2) k_contact_items(EnvRecordLayout L, double* rec, const int* __restrict__ env_idx, int n_envs, SenseDev tmp,
+                                                      myo_render_style style, double* out) {
+  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
+  s.rk = nullptr;
+  const DevModel<T>& M = myo_cmodel<T>();
+  const TaskDev& K = c_task;
+  const int env = env_idx[blockIdx.x];
+  double* o = out + (size_t)blockIdx.x * 2 * tmp.cap * MYO_RENDER_ITEM_N;
+  if (env < 0 || env >= n_envs) {
+    for (int i = threadIdx.x; i < 2 * tmp.cap * MYO_RENDER_ITEM_N; i += 64) o[i] = 0.0;
+    return;
+  }
+  env_contact_items<T>(M, K, L, rec + (size_t)env * L.stride, s, env, (int)blockIdx.x, tmp, style, o);
+}
+// ray cast with MYO_RENDER_CONTACTS: the geoms' table (with the style's geom_alpha), the tendon items if there are any (Y.ntitem > 0),
+// then the contact items take turns in LDS and are traced into the same per-pixel hit (an instantiation of its own: k_render and
+// k_render_tendons are what they were)
+__global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render_layers(RLayers Y, const double* __restrict__ cams, int ncams, int W, int H, int flags,
+                                                                         unsigned char* rgb, float* depth, int* seg) {
+  RItem* lds = reinterpret_cast<RItem*>(myo_lds);
+  const int tid = threadIdx.x, tiles_x = (W + MYO_RTILE - 1) / MYO_RTILE, e = blockIdx.y;
+  const int tx0 = (int)(blockIdx.x % tiles_x) * MYO_RTILE, ty0 = (int)(blockIdx.x / tiles_x) * MYO_RTILE;
+  const int px = tx0 + tid % MYO_RTILE, py = ty0 + tid / MYO_RTILE;
+  const double* cam = cams + (size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N;
+  Y.it += (size_t)e * Y.nitem * MYO_RENDER_ITEM_N;
+  Y.tn += (size_t)e * Y.ntitem * MYO_RENDER_ITEM_N;
+  Y.cn += (size_t)e * Y.ncitem * MYO_RENDER_ITEM_N;
+  const bool inside = px < W && py < H;
+  float d[3];
+  RHit h;
+  render_ray(cam, W, H, px, py, d, h);
+  render_stage_geoms(tid, lds, Y.it, Y.nitem, Y.ngeom, Y.geom_alpha, cam, flags);
+  __syncthreads();
+  render_cull(tid, lds, Y.nitem, cam, W, H, tx0, ty0);
+  __syncthreads();
+  if (inside) render_trace(lds, Y.nitem, 0, d, h);
+  __syncthreads();
+  if (Y.ntitem > 0) {
+    render_stage(tid, lds, Y.tn, Y.ntitem, cam, flags);
+    __syncthreads();
+    render_cull(tid, lds, Y.ntitem, cam, W, H, tx0, ty0);
+    __syncthreads();
+    if (inside) render_trace(lds, Y.ntitem, Y.nitem, d, h);
+    __syncthreads();
+  }
+  render_stage(tid, lds, Y.cn, Y.ncitem, cam, flags);
+  __syncthreads();
+  render_cull(tid, lds, Y.ncitem, cam, W, H, tx0, ty0);
+  __syncthreads();
+  if (inside) render_trace(lds, Y.ncitem, Y.nitem + Y.ntitem, d, h);
+  render_layers_finish(Y, cam, W, H, px, py, flags, (size_t)e, h, d, rgb, depth, seg);
+}
 // ... and the order that follows from the census: positions sorted by count, most engaged first (ties keep their order), written back
 // into the batch's own tables — gw_elem[k] = path element of position k, wr_i[8 w + 6] = position of element w — and the counts
 // cleared.  One wave; ngw <= 128 (two positions per lane).  Each wrap's arithmetic is its own: the order changes no result bit.
@@ -789,6 +844,47 @@ extern "C" int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int 
   tendon_paths_launch(b, env_idx, k, out, st);
   return be_launch_status();
 }
+static void contact_items_launch(myo_batch* b, const int32_t* env_idx, int k, const SenseDev& tmp, double* out, hipStream_t st) {
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_contact_items<typename V::T, V::NC>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, tmp, b->style, out);
+  });
+}
+extern "C" int myo_batch_contact_items(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
+  int empty = 0;
+  int rc = contact_items_check(b, env_idx, k, out, &empty);
+  if (rc || empty) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  BIND_OR_RETURN(b, st)
+  if ((rc = render_workspace(b, contact_tmp_doubles(b, k)))) return rc;
+  contact_items_launch(b, env_idx, k, contact_tmp(b, k, b->render_ws), out, st);
+  return be_launch_status();
+}
+// myo_batch_render with MYO_RENDER_CONTACTS (checked, bound): workspace = the geoms' tables, the tendons' (if drawn), the contacts', the
+// cameras, the contact pass's temporaries
+static int render_contacts(myo_batch* b, const int32_t* env_idx, int k, std::vector<double>& cam_tab, int ncams, int width, int height, int flags,
+                           uint8_t* rgb, float* depth, int32_t* segid, hipStream_t st) {
+  const bool tendons = (flags & MYO_RENDER_TENDONS) && b->ntitem > 0;
+  const int ncitem = 2 * sense_capacity(b), ntitem = tendons ? b->ntitem : 0;
+  const size_t geom_n = (size_t)k * b->nitem * MYO_RENDER_ITEM_N, ten_n = (size_t)k * ntitem * MYO_RENDER_ITEM_N;
+  const size_t con_n = (size_t)k * ncitem * MYO_RENDER_ITEM_N, item_n = geom_n + ten_n + con_n, cam_n = cam_tab.size();
+  int rc = render_workspace(b, item_n + cam_n + contact_tmp_doubles(b, k));
+  if (rc) return rc;
+  b->cam_host.swap(cam_tab);      // (kept until the next call: the asynchronous copy reads it)
+  hipError_t e = hipMemcpyAsync(b->render_ws + item_n, b->cam_host.data(), cam_n * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return fail(MYO_E_DEVICE, "myo_batch_render: camera upload failed: %s", hipGetErrorString(e));
+  geom_poses_launch(b, env_idx, k, b->render_ws, st);
+  if (tendons) tendon_paths_launch(b, env_idx, k, b->render_ws + geom_n, st);
+  contact_items_launch(b, env_idx, k, contact_tmp(b, k, b->render_ws + item_n + cam_n), b->render_ws + geom_n + ten_n, st);
+  RLayers Y;
+  Y.it = b->render_ws; Y.tn = b->render_ws + geom_n; Y.cn = b->render_ws + geom_n + ten_n;
+  Y.nitem = b->nitem; Y.ngeom = b->ngeom; Y.ntitem = ntitem; Y.ncitem = ncitem; Y.seg_c = b->nitem + b->ntendon; Y.geom_alpha = (float)b->style.geom_alpha;
+  const int nmax = std::max(b->nitem, std::max(ntitem, ncitem));
+  const unsigned tiles = (unsigned)(((width + MYO_RTILE - 1) / MYO_RTILE) * ((height + MYO_RTILE - 1) / MYO_RTILE));
+  hipLaunchKernelGGL(k_render_layers, dim3(tiles, (unsigned)k), dim3(MYO_RTILE * MYO_RTILE), (unsigned)(nmax * sizeof(RItem)), st,
+                     Y, b->render_ws + item_n, ncams, width, height, flags, rgb, depth, segid);
+  return be_launch_status();
+}
 extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
                                 int flags, uint8_t* rgb, float* depth, int32_t* segid, void* stream) {
   std::vector<double> cam_tab;
@@ -797,6 +893,7 @@ extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, con
   if (k > 65535) return fail(MYO_E_ARG, "myo_batch_render: at most 65535 envs per call");
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
+  if (flags & MYO_RENDER_CONTACTS) return render_contacts(b, env_idx, k, cam_tab, ncams, width, height, flags, rgb, depth, segid, st);
   const bool tendons = (flags & MYO_RENDER_TENDONS) && b->ntitem > 0;
   const size_t geom_n = (size_t)k * b->nitem * MYO_RENDER_ITEM_N;
   const size_t item_n = geom_n + (tendons ? (size_t)k * b->ntitem * MYO_RENDER_ITEM_N : 0);      // the geoms' tables, then the tendons'

@@ -212,15 +212,22 @@ class BaodingVecEnv:
         return self._model.default_camera()
 
     def render_tensor(self, indices=None, width: int = 480, height: int = 480, camera=None, rgb: bool = True, depth: bool = False,
-                      segmentation: bool = False, show_sites: bool = False, tendons: bool = False):
+                      segmentation: bool = False, show_sites: bool = False, tendons: bool = False, contacts: bool = False,
+                      contact_style=None):
         """Draw the present state of envs ``indices`` (default: all) on the GPU; device tensors, no host copy.
 
         camera: None (the default camera), a dict of MuJoCo free-camera keys (lookat, distance, azimuth, elevation, fovy; missing
         keys take the defaults) for every env, or a list of such dicts, one per env.  Returns a dict with the requested outputs:
         ``rgb`` uint8 [k, H, W, 3] (row 0 at the top), ``depth`` float32 [k, H, W] (along the camera axis, inf for the background),
-        ``segmentation`` int32 [k, H, W] (geom id, ngeom + site id, ngeom + nsite + tendon id, -1 for the background).
+        ``segmentation`` int32 [k, H, W] (geom id, ngeom + site id, ngeom + nsite + tendon id, ngeom + nsite + ntendon + contact
+        slot, -1 for the background).
         ``tendons``: also draw the spatial tendons (``tendon_paths``), coloured by muscle activation — this library's own colour
         rule, not MuJoCo's (include/myobatch.h).
+        ``contacts``: also draw every contact's point (a disc) and force (a shaft of ``metres_per_newton`` metres per newton, no
+        arrow head) — ``contact_items``; MuJoCo's mjVIS_CONTACTPOINT / mjVIS_CONTACTFORCE under this library's own sizes and
+        colours.  ``contact_style``: a dict of style fields (disc_radius, disc_half_height, force_radius, metres_per_newton,
+        point_rgba, force_rgba, geom_alpha) set on the batch before the call; they stay set.  ``geom_alpha`` < 1 makes the geoms
+        translucent in renders with ``contacts`` (a disc sits between two touching surfaces and is hidden otherwise).
 
         Differences from MuJoCo's renderer: primitives ray-cast under a headlight (no model lights, shadows or textures; tendon
         arcs around wrap geoms are drawn as chords); model cameras are not available; sites other than the task's targets are drawn only with ``show_sites`` (the synthetic hand
@@ -238,6 +245,9 @@ class BaodingVecEnv:
         flags = (native.RENDER_RGB if rgb else 0) | (native.RENDER_DEPTH if depth else 0) | (native.RENDER_SEG if segmentation else 0)
         flags |= native.RENDER_SITES if show_sites else 0
         flags |= native.RENDER_TENDONS if tendons else 0
+        flags |= native.RENDER_CONTACTS if contacts else 0
+        if contact_style:
+            self.batch.set_render_style(**contact_style)
         out = {}
         if rgb:
             out["rgb"] = t.empty((k, height, width, 3), dtype=t.uint8, device=self.device)
@@ -263,19 +273,34 @@ class BaodingVecEnv:
             self.batch.tendon_paths(t.tensor(idx, dtype=t.int32, device=self.device), out, self._stream())
         return out
 
-    def get_images(self, width: int = 480, height: int = 480, camera=None, tendons: bool = False) -> List[np.ndarray]:
+    def contact_items(self, indices=None):
+        """The contact items of envs ``indices`` (default: all): a device tensor float64 [k, 2 * contact_capacity, 24].  Contact slot c
+        (the order of ``sensors()``'s contact list) owns row 2c, the contact point (a disc at ``pos`` with its axis along the
+        normal, slot + 1 in [22], ``dist`` in [23]), and row 2c + 1, the force on geom2's body (a capsule from ``pos`` to ``pos`` +
+        metres_per_newton * F, slot + 1 in [22], |F| in newtons in [23]; a zero row for a contact without force).  Rows of unused
+        slots are zero (include/myobatch.h myo_batch_contact_items)."""
+        t = self.torch
+        idx = list(range(self.num_envs)) if indices is None else [int(i) for i in indices]
+        if not idx or min(idx) < 0 or max(idx) >= self.num_envs:
+            raise ValueError(f"contact_items indices must be in [0, {self.num_envs})")
+        out = t.zeros((len(idx), 2 * self.batch.contact_capacity, native.RENDER_ITEM_N), dtype=t.float64, device=self.device)
+        self.batch.contact_items(t.tensor(idx, dtype=t.int32, device=self.device), out, self._stream())
+        return out
+
+    def get_images(self, width: int = 480, height: int = 480, camera=None, tendons: bool = False, contacts: bool = False,
+                   contact_style=None) -> List[np.ndarray]:
         """SB3 VecEnv.get_images: one [H, W, 3] uint8 array per env."""
-        rgb = self.render_tensor(None, width, height, camera, tendons=tendons)["rgb"].cpu().numpy()
+        rgb = self.render_tensor(None, width, height, camera, tendons=tendons, contacts=contacts, contact_style=contact_style)["rgb"].cpu().numpy()
         return [rgb[i] for i in range(self.num_envs)]
 
-    def render(self, mode: str = "rgb_array", tendons: bool = False, **kwargs):
+    def render(self, mode: str = "rgb_array", tendons: bool = False, contacts: bool = False, contact_style=None, **kwargs):
         """SB3 VecEnv.render: "rgb_array" returns the envs' images tiled into one grid (stable_baselines3 tile_images)."""
         if mode in ("human", "window"):
             raise NotImplementedError(f"render mode {mode!r} needs a display; this GPU library renders offscreen only: use 'rgb_array'")
         if mode != "rgb_array":
             raise ValueError(f"unknown render mode {mode!r}; supported: {self.metadata['render.modes']}")
         from ..render_io import tile_images
-        return tile_images(self.get_images(tendons=tendons, **kwargs))
+        return tile_images(self.get_images(tendons=tendons, contacts=contacts, contact_style=contact_style, **kwargs))
 
     # ---------------------------------------------------------------- contact and muscle read-out (include/myobatch.h myo_batch_sense)
     # get_attr names (MuJoCo's mjData names and the short ones) -> sensors() keys

@@ -29,12 +29,13 @@ DEFAULT_CONFIG = {
 def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBallsP2", config: dict = None,
              num_episodes: int = 100, num_envs: int = 256, seed: int = 0, deterministic: bool = True, verbose: bool = True,
              render_dir: str = None, render_envs: int = 1, render_size=(480, 480), render_tendons: bool = False,
-             record_dir: str = None, env=None):
+             record_dir: str = None, env=None, render_contacts: bool = False, render_geom_alpha: float = None):
     """record_dir: write ``batch00000.npz`` there — per env step t and env n: ``qpos``, ``qvel``, ``act`` (the state after the step: the
     reset state where the episode ended), ``actuator_length`` / ``actuator_velocity`` / ``actuator_force`` [T, N, nu], ``ncon`` [T, N] and
     ``object_wrench`` [T, N, nobj, 6] (net contact force and torque on the task's objects, ``object_body_ids``), from ``env.sensors``.
     env: an already built env to evaluate on instead of ``EnvironmentFactory.create(env_name, ...)``.
-    render_tendons: draw the tendons, coloured by muscle activation, into the frames.  render_dir: write a PNG of each of the first ``render_envs`` envs after every step (``env{i}_step{t}.png``; the reference
+    render_tendons: draw the tendons, coloured by muscle activation, into the frames.  render_contacts: draw the contact points and
+    contact forces into the frames, with the geoms' alpha multiplied by render_geom_alpha if given (``render_tensor``).  render_dir: write a PNG of each of the first ``render_envs`` envs after every step (``env{i}_step{t}.png``; the reference
     script's ``render`` switch, src/main_eval.py:96-97, shows the frames in a window instead)."""
     from .envs.environment_factory import EnvironmentFactory
     from .metrics.evaluation import evaluate_policy, summarize
@@ -56,9 +57,11 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
         from .render_io import write_png
         os.makedirs(render_dir, exist_ok=True)
         k = max(1, min(int(render_envs), env.num_envs))
+        style = {"geom_alpha": float(render_geom_alpha)} if render_contacts and render_geom_alpha is not None else None
 
         def on_step(t):
-            rgb = env.render_tensor(list(range(k)), int(render_size[0]), int(render_size[1]), tendons=render_tendons)["rgb"].cpu().numpy()
+            rgb = env.render_tensor(list(range(k)), int(render_size[0]), int(render_size[1]), tendons=render_tendons, contacts=render_contacts,
+                                    contact_style=style)["rgb"].cpu().numpy()
             for i in range(k):
                 write_png(os.path.join(render_dir, f"env{i}_step{t:05d}.png"), rgb[i])
     rec = None
@@ -100,15 +103,22 @@ def main(argv=None):
     ap.add_argument("--render-envs", type=int, default=1)
     ap.add_argument("--render-size", type=int, nargs=2, default=(480, 480), metavar=("W", "H"))
     ap.add_argument("--render-tendons", action="store_true", help="with --render-dir: draw the tendons, coloured by muscle activation")
+    ap.add_argument("--render-contacts", action="store_true", help="with --render-dir: draw the contact points and contact forces")
+    ap.add_argument("--render-geom-alpha", type=float, default=None, metavar="A",
+                    help="with --render-contacts: multiply the geoms' alpha by A in [0, 1] (translucent geoms show the contact points between them)")
     ap.add_argument("--record-dir", default=None, help="write per-step qpos / qvel / act, actuator length / velocity / force, ncon and the "
                                                        "objects' contact wrenches of the evaluated batch to batch00000.npz here")
     a = ap.parse_args(argv)
     if a.render_tendons and not a.render_dir:
         ap.error("--render-tendons needs --render-dir")
+    if a.render_contacts and not a.render_dir:
+        ap.error("--render-contacts needs --render-dir")
+    if a.render_geom_alpha is not None and not a.render_contacts:
+        ap.error("--render-geom-alpha needs --render-contacts")
     cfg = json.load(open(a.config)) if a.config else None
     res, _ = evaluate(a.model, a.env_path, a.env_name, cfg, a.num_episodes, a.num_envs, a.seed,
                       render_dir=a.render_dir, render_envs=a.render_envs, render_size=a.render_size, render_tendons=a.render_tendons,
-                      record_dir=a.record_dir)
+                      record_dir=a.record_dir, render_contacts=a.render_contacts, render_geom_alpha=a.render_geom_alpha)
     if a.out:
         np.savez(a.out, **res)
 

@@ -103,8 +103,17 @@ class RenderCamera(C.Structure):
                 ("fovy", C.c_double)]
 
 
-RENDER_RGB, RENDER_DEPTH, RENDER_SEG, RENDER_SITES, RENDER_TENDONS = 1, 2, 4, 8, 16
-RENDER_ITEM_N = 24      # doubles per item of myo_batch_geom_poses / myo_batch_tendon_paths
+RENDER_RGB, RENDER_DEPTH, RENDER_SEG, RENDER_SITES, RENDER_TENDONS, RENDER_CONTACTS = 1, 2, 4, 8, 16, 32      # (bit 64 is reserved)
+RENDER_ITEM_N = 24      # doubles per item of myo_batch_geom_poses / myo_batch_tendon_paths / myo_batch_contact_items
+
+
+class RenderStyle(C.Structure):
+    """myo_render_style of include/myobatch.h: how contact points and contact forces are drawn (this library's own rule)."""
+    _fields_ = [("size", C.c_size_t), ("disc_radius", C.c_double), ("disc_half_height", C.c_double), ("force_radius", C.c_double),
+                ("metres_per_newton", C.c_double), ("point_rgba", C.c_float * 4), ("force_rgba", C.c_float * 4), ("geom_alpha", C.c_double)]
+
+
+RENDER_STYLE_KEYS = tuple(f[0] for f in RenderStyle._fields_[1:])
 
 
 class SenseOut(C.Structure):
@@ -172,6 +181,9 @@ class NativeLib:
         L.myo_batch_geom_poses.argtypes = [vp, vp, i32, vp, vp]
         L.myo_batch_tendon_paths.argtypes = [vp, vp, i32, vp, vp]
         L.myo_batch_render.argtypes = [vp, vp, i32, C.POINTER(RenderCamera), i32, i32, i32, i32, vp, vp, vp, vp]
+        L.myo_batch_contact_items.argtypes = [vp, vp, i32, vp, vp]
+        L.myo_batch_set_render_style.argtypes = [vp, C.POINTER(RenderStyle)]
+        L.myo_batch_get_render_style.argtypes = [vp, C.POINTER(RenderStyle)]
         L.myo_batch_contact_capacity.argtypes = [vp]
         L.myo_batch_sense.argtypes = [vp, C.POINTER(SenseOut), vp]
         if b"MYO_EMU" in L.myo_version():
@@ -256,6 +268,7 @@ EXPORTED_SYMBOLS = [
     "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_clip_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_adam_apply", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_ppo_loss_grad_hp", "myo_adam_clip_step_hp", "myo_adam_apply_hp", "myo_last_error", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
     "myo_batch_contact_capacity", "myo_batch_sense",
+    "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
 ]
 
 # ... of which the lane-serial emulation build (tests/emu/libmyobatch_emu.so: csrc/myobatch_emu.cpp + csrc/emu_host.h, test tooling) has the env
@@ -269,6 +282,7 @@ ENV_PATH_SYMBOLS = [
     "myo_last_error", "myo_model_destroy", "myo_model_from_blob", "myo_model_load_mjb", "myo_model_size", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
     "myo_batch_contact_capacity", "myo_batch_sense",
+    "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
 ]
 
 
@@ -417,6 +431,32 @@ class Batch:
         """path pass of the renderer: env_idx int32[k] -> out float64 [k, ntendon_item, RENDER_ITEM_N], the straight pieces of every
         spatial tendon as capsule items (include/myobatch.h)"""
         self.lib.check(self.lib.L.myo_batch_tendon_paths(self.h, _ptr(env_idx), int(env_idx.shape[0]), _ptr(out), stream))
+
+    def contact_items(self, env_idx, out, stream=None):
+        """contact item pass of the renderer: env_idx int32[k] -> out float64 [k, 2 * contact_capacity, RENDER_ITEM_N]; slot c's rows
+        2c (the contact point, a disc) and 2c + 1 (the contact force, a capsule shaft), zero rows beyond ncon (include/myobatch.h)"""
+        self.lib.check(self.lib.L.myo_batch_contact_items(self.h, _ptr(env_idx), int(env_idx.shape[0]), _ptr(out), stream))
+
+    def get_render_style(self) -> dict:
+        """the batch's contact drawing style (myo_render_style): a dict of RENDER_STYLE_KEYS"""
+        st = RenderStyle()
+        st.size = C.sizeof(RenderStyle)
+        self.lib.check(self.lib.L.myo_batch_get_render_style(self.h, C.byref(st)))
+        return {k: (tuple(getattr(st, k)) if k.endswith("rgba") else float(getattr(st, k))) for k in RENDER_STYLE_KEYS}
+
+    def set_render_style(self, **fields):
+        """change fields of the batch's contact drawing style (keys of RENDER_STYLE_KEYS; the others keep their values)"""
+        st = RenderStyle()
+        st.size = C.sizeof(RenderStyle)
+        self.lib.check(self.lib.L.myo_batch_get_render_style(self.h, C.byref(st)))
+        for k, v in fields.items():
+            if k not in RENDER_STYLE_KEYS:
+                raise KeyError(f"unknown render style field {k!r}; known: {RENDER_STYLE_KEYS}")
+            if k.endswith("rgba"):
+                getattr(st, k)[:] = [float(x) for x in v]
+            else:
+                setattr(st, k, float(v))
+        self.lib.check(self.lib.L.myo_batch_set_render_style(self.h, C.byref(st)))
 
     def render(self, env_idx, cams, width, height, flags, rgb=None, depth=None, segid=None, stream=None):
         """ray cast of envs env_idx int32[k]; cams: a list of 1 or k camera dicts (lookat, distance, azimuth, elevation, fovy)"""

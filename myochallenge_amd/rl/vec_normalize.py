@@ -244,6 +244,9 @@ class VecNormalize:
     def tendon_paths(self, *args, **kwargs):
         return self.venv.tendon_paths(*args, **kwargs)
 
+    def contact_items(self, *args, **kwargs):
+        return self.venv.contact_items(*args, **kwargs)
+
     # contact and muscle read-out: forwarded likewise (raw physical quantities, nothing to normalise)
     def sensors(self, *args, **kwargs):
         return self.venv.sensors(*args, **kwargs)
