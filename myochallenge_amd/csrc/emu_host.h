@@ -2,7 +2,9 @@
 // The kernel SOURCE (wave.h / myo_physics.h / myo_task.h, compiled with -DMYO_EMU: a phase's lanes run one after the other) is stepped
 // env by env on the CPU, through the same records, layouts and task blocks as the product (csrc/myo_host.h), so that the wave-parallel
 // algorithm can be checked against the oracle without a GPU.  It implements the env-path entry points of include/myobatch.h only;
-// the PPO-side kernels have no CPU twin.  Nothing here is compiled into libmyobatch.so.
+// the PPO-side kernels have no CPU twin.  The renderer runs on what the product's runs on: the pass structs and per-thread functions of
+// csrc/myo_render.h, and the plan, workspace layout and RLayers of csrc/myo_host.h (render_plan); only the loops over envs, tiles and
+// threads are its own.  Nothing here is compiled into libmyobatch.so.
 #pragma once
 // ------------------------------------------------------------------------------------------ backend
 static int be_malloc(void** p, size_t n) { *p = calloc(1, n ? n : 1); return *p ? 0 : -1; }
@@ -149,14 +151,15 @@ extern "C" int myo_batch_sense(myo_batch* b, const myo_sense_out* out, void*) {
   return MYO_OK;
 }
 
-// rendering: the pose pass env by env, then the ray cast tile by tile with the kernel's three thread phases one after the other
-static void emu_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out) {
+// rendering: an item pass env by env (k_items) ...
+template <typename Pass>
+static void emu_items(myo_batch* b, const int32_t* env_idx, int k, const Pass& P, double* out) {
   with_scratch(b, [&](auto& M, auto& s) {
     for (int r = 0; r < k; ++r) {
       const int e = env_idx[r];
-      double* o = out + (size_t)r * b->nitem * MYO_RENDER_ITEM_N;
-      if (e < 0 || e >= b->n) memset(o, 0, sizeof(double) * (size_t)b->nitem * MYO_RENDER_ITEM_N);
-      else env_geom_poses(M, b->K, b->L, env_rec(b, e), s, e, b->vis, o);
+      double* o = out + (size_t)r * P.rows * MYO_RENDER_ITEM_N;
+      if (e < 0 || e >= b->n) memset(o, 0, sizeof(double) * (size_t)P.rows * MYO_RENDER_ITEM_N);
+      else pass_run(P, M, b->K, b->L, env_rec(b, e), s, e, r, o);
     }
   });
 }
@@ -164,128 +167,62 @@ extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k,
   int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses");
   if (rc) return rc;
   if (!out) return fail(MYO_E_ARG, "myo_batch_geom_poses: null output");
-  emu_geom_poses(b, env_idx, k, out);
+  emu_items(b, env_idx, k, geom_pass(b), out);
   return MYO_OK;
-}
-static void emu_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out) {
-  with_scratch(b, [&](auto& M, auto& s) {
-    for (int r = 0; r < k; ++r) {
-      const int e = env_idx[r];
-      double* o = out + (size_t)r * b->ntitem * MYO_RENDER_ITEM_N;
-      if (e < 0 || e >= b->n) memset(o, 0, sizeof(double) * (size_t)b->ntitem * MYO_RENDER_ITEM_N);
-      else env_tendon_paths(M, b->K, b->L, env_rec(b, e), s, e, b->tvis, b->titem_adr, o);
-    }
-  });
 }
 extern "C" int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out, void*) {
-  int empty = 0;
-  int rc = tendon_paths_check(b, env_idx, k, out, &empty);
-  if (rc || empty) return rc;
-  emu_tendon_paths(b, env_idx, k, out);
+  int rc = items_check(b, env_idx, k, out, "myo_batch_tendon_paths");
+  if (rc || k == 0 || b->ntitem == 0) return rc;
+  emu_items(b, env_idx, k, tendon_pass(b), out);
   return MYO_OK;
-}
-static void emu_contact_items(myo_batch* b, const int32_t* env_idx, int k, double* out) {
-  const int ncitem = 2 * sense_capacity(b);
-  std::vector<double> tmp(contact_tmp_doubles(b, k));
-  const SenseDev T = contact_tmp(b, k, tmp.data());
-  with_scratch(b, [&](auto& M, auto& s) {
-    for (int r = 0; r < k; ++r) {
-      const int e = env_idx[r];
-      double* o = out + (size_t)r * ncitem * MYO_RENDER_ITEM_N;
-      if (e < 0 || e >= b->n) memset(o, 0, sizeof(double) * (size_t)ncitem * MYO_RENDER_ITEM_N);
-      else env_contact_items(M, b->K, b->L, env_rec(b, e), s, e, r, T, b->style, o);
-    }
-  });
 }
 extern "C" int myo_batch_contact_items(myo_batch* b, const int32_t* env_idx, int k, double* out, void*) {
-  int empty = 0;
-  int rc = contact_items_check(b, env_idx, k, out, &empty);
-  if (rc || empty) return rc;
-  emu_contact_items(b, env_idx, k, out);
+  int rc = items_check(b, env_idx, k, out, "myo_batch_contact_items");
+  if (rc || k == 0) return rc;
+  if ((rc = render_workspace(b, contact_tmp_doubles(b, k)))) return rc;
+  emu_items(b, env_idx, k, contact_pass(b, k, b->render_ws), out);
   return MYO_OK;
 }
-// MYO_RENDER_CONTACTS (k_render_layers): the tables one after the other through one item table into the same hits
-static void emu_render_layers(myo_batch* b, const int32_t* env_idx, int k, const std::vector<double>& cam_tab, int ncams, int width, int height,
-                              int flags, uint8_t* rgb, float* depth, int32_t* segid) {
-  const bool tendons = (flags & MYO_RENDER_TENDONS) && b->ntitem > 0;
-  const int ncitem = 2 * sense_capacity(b), ntitem = tendons ? b->ntitem : 0;
-  std::vector<double> items((size_t)k * b->nitem * MYO_RENDER_ITEM_N), titems((size_t)k * ntitem * MYO_RENDER_ITEM_N), citems((size_t)k * ncitem * MYO_RENDER_ITEM_N);
-  emu_geom_poses(b, env_idx, k, items.data());
-  if (tendons) emu_tendon_paths(b, env_idx, k, titems.data());
-  emu_contact_items(b, env_idx, k, citems.data());
-  std::vector<RItem> lds((size_t)std::max(b->nitem, std::max(ntitem, ncitem)));
-  std::vector<RHit> hits(MYO_RTILE * MYO_RTILE);
-  std::vector<float> dirs(3 * MYO_RTILE * MYO_RTILE);
-  const int tiles_x = (width + MYO_RTILE - 1) / MYO_RTILE, tiles_y = (height + MYO_RTILE - 1) / MYO_RTILE, nt = MYO_RTILE * MYO_RTILE;
-  for (int e = 0; e < k; ++e) {
-    const double* cam = &cam_tab[(size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N];
-    RLayers Y;
-    Y.it = items.data() + (size_t)e * b->nitem * MYO_RENDER_ITEM_N; Y.tn = titems.data() + (size_t)e * ntitem * MYO_RENDER_ITEM_N;
-    Y.cn = citems.data() + (size_t)e * ncitem * MYO_RENDER_ITEM_N;
-    Y.nitem = b->nitem; Y.ngeom = b->ngeom; Y.ntitem = ntitem; Y.ncitem = ncitem; Y.seg_c = b->nitem + b->ntendon; Y.geom_alpha = (float)b->style.geom_alpha;
-    for (int ty = 0; ty < tiles_y; ++ty)
-      for (int tx = 0; tx < tiles_x; ++tx) {
-        const int tx0 = tx * MYO_RTILE, ty0 = ty * MYO_RTILE;
-        auto PX = [&](int t) { return tx0 + t % MYO_RTILE; };
-        auto PY = [&](int t) { return ty0 + t / MYO_RTILE; };
-        auto trace = [&](int n, int base) {
-          for (int t = 0; t < nt; ++t) render_cull(t, lds.data(), n, cam, width, height, tx0, ty0);
-          for (int t = 0; t < nt; ++t) if (PX(t) < width && PY(t) < height) render_trace(lds.data(), n, base, &dirs[3 * t], hits[t]);
-        };
-        for (int t = 0; t < nt; ++t) render_ray(cam, width, height, PX(t), PY(t), &dirs[3 * t], hits[t]);
-        for (int t = 0; t < nt; ++t) render_stage_geoms(t, lds.data(), Y.it, Y.nitem, Y.ngeom, Y.geom_alpha, cam, flags);
-        trace(Y.nitem, 0);
-        if (ntitem > 0) {
-          for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), Y.tn, ntitem, cam, flags);
-          trace(ntitem, Y.nitem);
-        }
-        for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), Y.cn, ncitem, cam, flags);
-        trace(ncitem, Y.nitem + ntitem);
-        for (int t = 0; t < nt; ++t) render_layers_finish(Y, cam, width, height, PX(t), PY(t), flags, (size_t)e, hits[t], &dirs[3 * t], rgb, depth, segid);
-      }
-  }
-}
+// ... and the ray cast tile by tile, a kernel's thread phases (what lies between two barriers) one after the other, in the device's
+// workspace layout (render_plan): the plain arm is k_render, the layered arm k_render_layers
 extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
                                 int flags, uint8_t* rgb, float* depth, int32_t* segid, void*) {
   std::vector<double> cam_tab;
   int rc = render_check(b, env_idx, k, cams, ncams, width, height, flags, rgb, depth, segid, cam_tab);
   if (rc) return rc;
-  if (flags & MYO_RENDER_CONTACTS) { emu_render_layers(b, env_idx, k, cam_tab, ncams, width, height, flags, rgb, depth, segid); return MYO_OK; }
-  std::vector<double> items((size_t)k * b->nitem * MYO_RENDER_ITEM_N);
-  emu_geom_poses(b, env_idx, k, items.data());
-  const bool tendons = (flags & MYO_RENDER_TENDONS) && b->ntitem > 0;
-  std::vector<double> titems(tendons ? (size_t)k * b->ntitem * MYO_RENDER_ITEM_N : 0);
-  if (tendons) emu_tendon_paths(b, env_idx, k, titems.data());
-  std::vector<RItem> lds((size_t)(tendons && b->ntitem > b->nitem ? b->ntitem : b->nitem));
+  const RenderPlan p = render_plan(b, k, flags, cam_tab.size());
+  if ((rc = render_workspace(b, p.total))) return rc;
+  double* ws = b->render_ws;
+  memcpy(ws + p.cams, cam_tab.data(), cam_tab.size() * sizeof(double));
+  emu_items(b, env_idx, k, geom_pass(b), ws);
+  if (p.ntitem > 0) emu_items(b, env_idx, k, tendon_pass(b), ws + p.tendons);
+  if (p.ncitem > 0) emu_items(b, env_idx, k, contact_pass(b, k, ws + p.tmp), ws + p.contacts);
+  const RLayers Y = render_layers(b, p, ws);
+  std::vector<RItem> lds((size_t)p.nmax);
   std::vector<RHit> hits(MYO_RTILE * MYO_RTILE);
   std::vector<float> dirs(3 * MYO_RTILE * MYO_RTILE);
   const int tiles_x = (width + MYO_RTILE - 1) / MYO_RTILE, tiles_y = (height + MYO_RTILE - 1) / MYO_RTILE, nt = MYO_RTILE * MYO_RTILE;
   for (int e = 0; e < k; ++e) {
-    const double* cam = &cam_tab[(size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N];
+    const double* cam = ws + p.cams + (size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N;
     for (int ty = 0; ty < tiles_y; ++ty)
       for (int tx = 0; tx < tiles_x; ++tx) {
-        for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), items.data() + (size_t)e * b->nitem * MYO_RENDER_ITEM_N, b->nitem, cam, flags);
-        for (int t = 0; t < nt; ++t) render_cull(t, lds.data(), b->nitem, cam, width, height, tx * MYO_RTILE, ty * MYO_RTILE);
-        if (!tendons) {
-          for (int t = 0; t < nt; ++t)
-            render_pixel(lds.data(), b->nitem, cam, width, height, tx * MYO_RTILE + t % MYO_RTILE, ty * MYO_RTILE + t / MYO_RTILE, flags, (size_t)e, rgb, depth, segid);
+        const int tx0 = tx * MYO_RTILE, ty0 = ty * MYO_RTILE;
+        auto PX = [&](int t) { return tx0 + t % MYO_RTILE; };
+        auto PY = [&](int t) { return ty0 + t / MYO_RTILE; };
+        if (!p.layered) {
+          for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), ws + (size_t)e * b->nitem * MYO_RENDER_ITEM_N, b->nitem, cam, flags);
+          for (int t = 0; t < nt; ++t) render_cull(t, lds.data(), b->nitem, cam, width, height, tx0, ty0);
+          for (int t = 0; t < nt; ++t) render_pixel(lds.data(), b->nitem, cam, width, height, PX(t), PY(t), flags, (size_t)e, rgb, depth, segid);
           continue;
         }
-        // MYO_RENDER_TENDONS (k_render_tendons): trace the geoms' table, restage the tendon items over it, trace them into the same hits
-        const double* it = items.data() + (size_t)e * b->nitem * MYO_RENDER_ITEM_N;
-        const double* tn = titems.data() + (size_t)e * b->ntitem * MYO_RENDER_ITEM_N;
-        auto PX = [&](int t) { return tx * MYO_RTILE + t % MYO_RTILE; };
-        auto PY = [&](int t) { return ty * MYO_RTILE + t / MYO_RTILE; };
-        for (int t = 0; t < nt; ++t) {
-          render_ray(cam, width, height, PX(t), PY(t), &dirs[3 * t], hits[t]);
-          if (PX(t) < width && PY(t) < height) render_trace(lds.data(), b->nitem, 0, &dirs[3 * t], hits[t]);
+        for (int t = 0; t < nt; ++t) render_ray(cam, width, height, PX(t), PY(t), &dirs[3 * t], hits[t]);
+        for (int j = 0, base = 0; j < Y.nl; base += Y.l[j++].n) {
+          const int n = Y.l[j].n;
+          for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), Y.l[j].rows + (size_t)e * n * MYO_RENDER_ITEM_N, n, cam, flags, j == 0 ? Y.ngeom : 0, Y.geom_alpha);
+          for (int t = 0; t < nt; ++t) render_cull(t, lds.data(), n, cam, width, height, tx0, ty0);
+          for (int t = 0; t < nt; ++t) if (PX(t) < width && PY(t) < height) render_trace(lds.data(), n, base, &dirs[3 * t], hits[t]);
         }
-        for (int t = 0; t < nt; ++t) render_stage(t, lds.data(), tn, b->ntitem, cam, flags);
-        for (int t = 0; t < nt; ++t) render_cull(t, lds.data(), b->ntitem, cam, width, height, tx * MYO_RTILE, ty * MYO_RTILE);
-        for (int t = 0; t < nt; ++t) {
-          if (PX(t) < width && PY(t) < height) render_trace(lds.data(), b->ntitem, b->nitem, &dirs[3 * t], hits[t]);
-          render_pixel_finish(it, b->nitem, tn, cam, width, height, PX(t), PY(t), flags, (size_t)e, hits[t], &dirs[3 * t], rgb, depth, segid);
-        }
+        for (int t = 0; t < nt; ++t) render_layers_finish(Y, cam, width, height, PX(t), PY(t), flags, (size_t)e, hits[t], &dirs[3 * t], rgb, depth, segid);
       }
   }
   return MYO_OK;

@@ -1383,14 +1383,13 @@ extern "C" int myo_model_default_camera(const myo_model* m, myo_render_camera* o
   out->azimuth = 90.0; out->elevation = -45.0; out->fovy = 45.0;      // MuJoCo 2.1's mjVisual.global defaults [3P-RECALL]
   return MYO_OK;
 }
-// myo_batch_tendon_paths: null output / k < 0 / null list are refused before any device call; k = 0 or a model without tendon items
-// is an empty result (*empty)
-static int tendon_paths_check(const myo_batch* b, const int32_t* env_idx, int k, const double* out, int* empty) {
-  if (!b) return fail(MYO_E_ARG, "myo_batch_tendon_paths: null batch");
-  if (k < 0) return fail(MYO_E_ARG, "myo_batch_tendon_paths: k must be >= 0, got %d", k);
-  if (!out) return fail(MYO_E_ARG, "myo_batch_tendon_paths: null output");
-  if (k > 0 && !env_idx) return fail(MYO_E_ARG, "myo_batch_tendon_paths: null env_idx");
-  *empty = (k == 0 || b->ntitem == 0);
+// myo_batch_tendon_paths / _contact_items (`fn`): null output / k < 0 / null list are refused before any device call; k = 0, or a
+// model without tendon items, is then an empty result (the caller's test)
+static int items_check(const myo_batch* b, const int32_t* env_idx, int k, const double* out, const char* fn) {
+  if (!b) return fail(MYO_E_ARG, "%s: null batch", fn);
+  if (k < 0) return fail(MYO_E_ARG, "%s: k must be >= 0, got %d", fn, k);
+  if (!out) return fail(MYO_E_ARG, "%s: null output", fn);
+  if (k > 0 && !env_idx) return fail(MYO_E_ARG, "%s: null env_idx", fn);
   return MYO_OK;
 }
 static int render_check_items(const myo_batch* b, const int32_t* env_idx, int k, const char* fn) {
@@ -1435,15 +1434,6 @@ static int render_check(const myo_batch* b, const int32_t* env_idx, int k, const
   if ((long long)k * width * height > (1ll << 31)) return fail(MYO_E_ARG, "myo_batch_render: k * width * height exceeds 2^31 pixels");
   return render_cameras(cams, ncams, height, cam_tab);
 }
-// myo_batch_contact_items: as myo_batch_tendon_paths; k = 0 is an empty result (*empty)
-static int contact_items_check(const myo_batch* b, const int32_t* env_idx, int k, const double* out, int* empty) {
-  if (!b) return fail(MYO_E_ARG, "myo_batch_contact_items: null batch");
-  if (k < 0) return fail(MYO_E_ARG, "myo_batch_contact_items: k must be >= 0, got %d", k);
-  if (!out) return fail(MYO_E_ARG, "myo_batch_contact_items: null output");
-  if (k > 0 && !env_idx) return fail(MYO_E_ARG, "myo_batch_contact_items: null env_idx");
-  *empty = k == 0;
-  return MYO_OK;
-}
 // the style of the contact items: held per batch, read by the next contact item pass / render with MYO_RENDER_CONTACTS
 extern "C" int myo_batch_set_render_style(myo_batch* b, const myo_render_style* st) {
   if (!b || !st) return fail(MYO_E_ARG, "myo_batch_set_render_style: null batch or style");
@@ -1463,7 +1453,7 @@ extern "C" int myo_batch_get_render_style(const myo_batch* b, myo_render_style* 
   *st = b->style;
   return MYO_OK;
 }
-// the render workspace: k item tables then the cameras (doubles); grown on demand
+// the render workspace (laid out by render_plan below), in doubles; grown on demand
 static int render_workspace(myo_batch* b, size_t doubles) {
   if (b->render_ws_bytes >= doubles * sizeof(double)) return MYO_OK;
   if (b->render_ws) { be_free(b->render_ws); b->render_ws = nullptr; b->render_ws_bytes = 0; }
@@ -1614,6 +1604,39 @@ static SenseDev contact_tmp(const myo_batch* b, int k, double* base) {
   d.con_d = base;
   d.ncon = (int*)(base + (size_t)k * d.cap * MYO_SENSE_CON_N);
   return d;
+}
+// the three item passes of a batch (csrc/myo_render.h); tmp: the contact pass's temporaries, contact_tmp_doubles(b, k) doubles
+static GeomPass geom_pass(const myo_batch* b) { return {b->nitem, b->vis}; }
+static TendonPass tendon_pass(const myo_batch* b) { return {b->ntitem, b->tvis, b->titem_adr}; }
+static ContactPass contact_pass(const myo_batch* b, int k, double* tmp) { return {2 * sense_capacity(b), contact_tmp(b, k, tmp), b->style}; }
+// What a myo_batch_render call of k envs runs, and its workspace (offsets in doubles, the same on both backends): the geoms' table
+// [k, nitem], the tendons' [k, ntitem] (ntitem = 0: not drawn — no flag, or a model without tendon items), the contacts' [k, ncitem]
+// (0: no MYO_RENDER_CONTACTS), the cameras, the contact pass's temporaries.  A table of n > 0 rows has its item pass run.  layered:
+// k_render_layers over the tables that are there (render_layers), else k_render over the geoms'; nmax sizes the cast's LDS table.
+struct RenderPlan { size_t tendons, contacts, cams, tmp, total; int ntitem, ncitem, nmax; bool layered; };
+static RenderPlan render_plan(const myo_batch* b, int k, int flags, size_t ncam_doubles) {
+  RenderPlan p;
+  const bool contacts = (flags & MYO_RENDER_CONTACTS) != 0;
+  p.ntitem = (flags & MYO_RENDER_TENDONS) ? b->ntitem : 0;
+  p.ncitem = contacts ? 2 * sense_capacity(b) : 0;
+  p.nmax = std::max(b->nitem, std::max(p.ntitem, p.ncitem));
+  p.layered = p.ntitem > 0 || contacts;
+  p.tendons = (size_t)k * b->nitem * MYO_RENDER_ITEM_N;
+  p.contacts = p.tendons + (size_t)k * p.ntitem * MYO_RENDER_ITEM_N;
+  p.cams = p.contacts + (size_t)k * p.ncitem * MYO_RENDER_ITEM_N;
+  p.tmp = p.cams + ncam_doubles;
+  p.total = p.tmp + (contacts ? contact_tmp_doubles(b, k) : 0);
+  return p;
+}
+// the layers of a layered plan whose workspace is at `ws`; without contacts the geoms stay opaque (x * 1.0f is exact)
+static RLayers render_layers(const myo_batch* b, const RenderPlan& p, const double* ws) {
+  RLayers Y = {};
+  Y.l[Y.nl++] = {ws, b->nitem, 0};
+  if (p.ntitem > 0) Y.l[Y.nl++] = {ws + p.tendons, p.ntitem, b->nitem};
+  if (p.ncitem > 0) Y.l[Y.nl++] = {ws + p.contacts, p.ncitem, b->nitem + b->ntendon};
+  Y.ngeom = b->ngeom;
+  Y.geom_alpha = p.ncitem > 0 ? (float)b->style.geom_alpha : 1.f;
+  return Y;
 }
 // k = 0 is an empty copy (*empty)
 static int copy_envs_check(const myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, int* empty) {

@@ -1,18 +1,21 @@
-// myo_render.h — rendering of env states (include/myobatch.h: myo_batch_geom_poses, myo_batch_render).
-//   pose pass  env_geom_poses: one wave per listed env; load_env + the stepper's own kinematics, then one lane per item writes its
-//              world pose, the env's geometry (geom_size0_hp / geom_lpos_hp ...), its type and colour.  Reads the record only.
-//   ray cast   render_*: one workgroup of 256 threads per (env, 16x16 tile); the env's items are staged in LDS in fp32 relative to
-//              the camera, a per-tile cull on each item's bounding sphere marks the items the tile can see (the flag is the same for
-//              every thread of the tile: the loop over items stays uniform), then one thread per pixel intersects its ray with them.
-//   path pass  env_tendon_paths: one wave per listed env; load_env + kinematics, then one lane per tendon path element (the host-resolved
-//              te_i walk) runs the stepper's wrap_geom and writes the element's straight pieces as capsule items (include/myobatch.h).
-//   tendons    MYO_RENDER_TENDONS (k_render_tendons): the same tile runs a SECOND LDS pass over the same pixels — the geoms' table is
-//              traced, then the tendon items are staged over it, culled and traced into the same per-pixel hit; the hit items are shaded
-//              from their global rows.  The LDS allocation is max(items, tendon items) * sizeof(RItem), not their sum.
-//   contacts   env_contact_items: one wave per listed env runs env_sense (csrc/myo_sense.h, unchanged) into a compact temporary of the render
-//              workspace, then one lane per contact slot writes the slot's point (a disc) and force (a capsule shaft) items.
-//              MYO_RENDER_CONTACTS (k_render_layers): the tile traces two or three tables in turn — geoms, tendons if asked for, contact
-//              items — through the same LDS table into the same per-pixel hit; the allocation is the largest table's.
+// myo_render.h — rendering of env states (include/myobatch.h: myo_batch_geom_poses / _tendon_paths / _contact_items, myo_batch_render).
+//   item passes  one wave per listed env writes one table of MYO_RENDER_ITEM_N-double rows.  A pass is a small struct (GeomPass,
+//                TendonPass, ContactPass: its host-built tables and its rows per env) with a pass_run that calls the pass's env_* function;
+//                one kernel (k_items, csrc/myobatch.hip) and one emulation loop (emu_items, csrc/emu_host.h) run all three.
+//     env_geom_poses     load_env + the stepper's own kinematics, then one lane per item (geoms, then sites) writes its world pose, the
+//                        env's geometry (geom_size0_hp / geom_lpos_hp ...), its type and colour.  Reads the record only.
+//     env_tendon_paths   load_env + kinematics, then one lane per tendon path element (the host-resolved te_i walk) runs the stepper's
+//                        wrap_geom and writes the element's straight pieces as capsule items.
+//     env_contact_items  env_sense (csrc/myo_sense.h) into a compact temporary of the render workspace, then one lane per contact slot
+//                        writes the slot's point (a disc) and force (a capsule shaft) items.
+//   ray casts    one workgroup of 256 threads per (env, 16x16 tile).  A table's items are staged in LDS in fp32 relative to the camera, a
+//                per-tile cull on each item's bounding sphere marks the items the tile can see (the flag is the same for every thread
+//                of the tile: the loop over items stays uniform), then one thread per pixel intersects its ray with them.
+//     k_render          one table (geoms + sites); the pixel is finished from LDS (render_pixel).
+//     k_render_layers   RLayers: two or three tables — geoms, tendon items if drawn, contact items if drawn — take turns in the same LDS
+//                       table and are traced into the same per-pixel hit; the hit items are then shaded from their global rows
+//                       (render_layers_finish).  The LDS allocation is the largest table's, not the sum.
+// Which passes and which cast a myo_batch_render call runs, and where their tables lie in the workspace: render_plan (csrc/myo_host.h).
 // The per-thread functions take the thread index, so the emulation build (csrc/emu_host.h) runs the same code thread by thread.
 #pragma once
 
@@ -229,6 +232,27 @@ DEV void env_contact_items(const DevModel<T>& M, const TaskDev& K, const EnvReco
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the three passes
+// what k_items / emu_items run for row `row` of a call (env `env` of the batch): `rows` items per env, written at `out`
+struct GeomPass { int rows; const float* vis; };                            // rows = ngeom + nsite
+struct TendonPass { int rows; const float *tvis; const int* tadr; };        // rows = the model's tendon items
+struct ContactPass { int rows; SenseDev tmp; myo_render_style style; };     // rows = 2 * tmp.cap
+template <typename T, int NC>
+DEV void pass_run(const GeomPass& P, const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s, int env, int,
+                  double* out) {
+  env_geom_poses(M, K, L, rec, s, env, P.vis, out);
+}
+template <typename T, int NC>
+DEV void pass_run(const TendonPass& P, const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s, int env, int,
+                  double* out) {
+  env_tendon_paths(M, K, L, rec, s, env, P.tvis, P.tadr, out);
+}
+template <typename T, int NC>
+DEV void pass_run(const ContactPass& P, const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s, int env,
+                  int row, double* out) {
+  env_contact_items(M, K, L, rec, s, env, row, P.tmp, P.style, out);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- ray cast
 struct RItem {      // one item in LDS: fp32, relative to the camera position
   float c[3], R[9], sz[3], rgba[4], rb;
@@ -245,8 +269,13 @@ DEV void render_load(RItem& r, const double* o, const double* cam, int flags) {
   r.type = (int)o[15];
   r.draw = r.rgba[3] > 0.f && (o[21] == 0.0 || (flags & MYO_RENDER_SITES));
 }
-DEV void render_stage(int tid, RItem* lds, const double* it, int nitem, const double* cam, int flags) {
-  for (int i = tid; i < nitem; i += MYO_RTILE * MYO_RTILE) render_load(lds[i], it + (size_t)i * MYO_RENDER_ITEM_N, cam, flags);
+// (ngeom, geom_alpha: the layered cast's translucent geoms — the alpha of items < ngeom is scaled; the sites keep theirs)
+DEV void render_stage(int tid, RItem* lds, const double* it, int nitem, const double* cam, int flags, int ngeom = 0, float geom_alpha = 1.f) {
+  for (int i = tid; i < nitem; i += MYO_RTILE * MYO_RTILE) {
+    RItem& r = lds[i];
+    render_load(r, it + (size_t)i * MYO_RENDER_ITEM_N, cam, flags);
+    if (i < ngeom) { r.rgba[3] *= geom_alpha; if (!(r.rgba[3] > 0.f)) r.draw = 0; }
+  }
 }
 
 // per-tile cull: the item's bounding sphere against the tile's four side planes through the camera and the camera plane
@@ -415,56 +444,28 @@ DEV void render_pixel(const RItem* lds, int nitem, const double* cam, int W, int
   const size_t pix = (e * (size_t)H + (size_t)py) * (size_t)W + (size_t)px;
   render_write(lds + (h.io >= 0 ? h.io : 0), lds + (h.it >= 0 ? h.it : 0), h.io, h.it, h, d, flags, pix, rgb, depth, seg);
 }
-// ... with MYO_RENDER_TENDONS, after both tables were traced into h: the hit items come from their global rows (`it`: the env's nitem
-// items, `tn`: its tendon items; the LDS table holds the tendons by now); a tendon item's id is nitem + its tendon ([22] - 1)
-DEV void render_pixel_finish(const double* it, int nitem, const double* tn, const double* cam, int W, int H, int px, int py, int flags, size_t e,
-                             const RHit& h, const float* d, unsigned char* rgb, float* depth, int* seg) {
-  if (px >= W || py >= H) return;
-  RItem ro, rt;
-  int so = h.io, st = h.it;
-  if (h.io >= 0) {
-    const double* o = h.io < nitem ? it + (size_t)h.io * MYO_RENDER_ITEM_N : tn + (size_t)(h.io - nitem) * MYO_RENDER_ITEM_N;
-    render_load(ro, o, cam, flags);
-    if (h.io >= nitem) so = nitem + (int)o[22] - 1;
-  }
-  if (h.it >= 0) {
-    const double* o = h.it < nitem ? it + (size_t)h.it * MYO_RENDER_ITEM_N : tn + (size_t)(h.it - nitem) * MYO_RENDER_ITEM_N;
-    render_load(rt, o, cam, flags);
-    if (h.it >= nitem) st = nitem + (int)o[22] - 1;
-  }
-  const size_t pix = (e * (size_t)H + (size_t)py) * (size_t)W + (size_t)px;
-  render_write(&ro, &rt, so, st, h, d, flags, pix, rgb, depth, seg);
-}
-// ... with MYO_RENDER_CONTACTS (k_render_layers).  The geoms' table is staged with the style's geom_alpha on the alpha of the geoms
-// (items < ngeom; the sites keep theirs) ...
-DEV void render_stage_geoms(int tid, RItem* lds, const double* it, int nitem, int ngeom, float geom_alpha, const double* cam, int flags) {
-  for (int i = tid; i < nitem; i += MYO_RTILE * MYO_RTILE) {
-    RItem& r = lds[i];
-    render_load(r, it + (size_t)i * MYO_RENDER_ITEM_N, cam, flags);
-    if (i < ngeom) { r.rgba[3] *= geom_alpha; if (!(r.rgba[3] > 0.f)) r.draw = 0; }
-  }
-}
-// ... and after every table was traced into h the hit items come from their global rows: `it` the env's nitem items, `tn` its ntitem
-// tendon items (0: that table was not traced), `cn` its contact items.  A contact item's id is seg_c + its slot ([22] - 1),
-// seg_c = ngeom + nsite + ntendon.
-struct RLayers { const double *it, *tn, *cn; int nitem, ngeom, ntitem, ncitem, seg_c; float geom_alpha; };
-DEV int render_layer_item(RItem& r, const RLayers& Y, int idx, const double* cam, int flags) {
-  const double* o;
-  int id;
-  if (idx < Y.nitem) { o = Y.it + (size_t)idx * MYO_RENDER_ITEM_N; id = idx; }
-  else if (idx < Y.nitem + Y.ntitem) { o = Y.tn + (size_t)(idx - Y.nitem) * MYO_RENDER_ITEM_N; id = Y.nitem + (int)o[22] - 1; }
-  else { o = Y.cn + (size_t)(idx - Y.nitem - Y.ntitem) * MYO_RENDER_ITEM_N; id = Y.seg_c + (int)o[22] - 1; }
+// The layered cast (k_render_layers): l[0] is the geoms' table, staged with geom_alpha on the alpha of the geoms (1: opaque as they
+// are); then the tendon items if drawn, then the contact items if drawn.  rows: the call's [k, n, MYO_RENDER_ITEM_N] table.  Hit indices
+// run on through the layers in order; the id of an item of layer 0 is its index, of a later layer id_base + its [22] - 1 (id_base:
+// ngeom + nsite for tendons, ngeom + nsite + ntendon for contact slots).
+struct RLayer { const double* rows; int n, id_base; };
+struct RLayers { RLayer l[3]; int nl, ngeom; float geom_alpha; };
+// after every layer was traced into h the hit items come from their global rows (the LDS table holds the last layer by now)
+DEV int render_layer_item(RItem& r, const RLayers& Y, size_t e, int idx, const double* cam, int flags) {
+  int j = 0, base = 0;
+  while (j + 1 < Y.nl && idx >= base + Y.l[j].n) base += Y.l[j++].n;
+  const double* o = Y.l[j].rows + (e * (size_t)Y.l[j].n + (size_t)(idx - base)) * MYO_RENDER_ITEM_N;
   render_load(r, o, cam, flags);
   if (idx < Y.ngeom) r.rgba[3] *= Y.geom_alpha;
-  return id;
+  return j == 0 ? idx : Y.l[j].id_base + (int)o[22] - 1;
 }
 DEV void render_layers_finish(const RLayers& Y, const double* cam, int W, int H, int px, int py, int flags, size_t e, const RHit& h, const float* d,
                               unsigned char* rgb, float* depth, int* seg) {
   if (px >= W || py >= H) return;
   RItem ro, rt;
   int so = h.io, st = h.it;
-  if (h.io >= 0) so = render_layer_item(ro, Y, h.io, cam, flags);
-  if (h.it >= 0) st = render_layer_item(rt, Y, h.it, cam, flags);
+  if (h.io >= 0) so = render_layer_item(ro, Y, e, h.io, cam, flags);
+  if (h.it >= 0) st = render_layer_item(rt, Y, e, h.it, cam, flags);
   const size_t pix = (e * (size_t)H + (size_t)py) * (size_t)W + (size_t)px;
   render_write(&ro, &rt, so, st, h, d, flags, pix, rgb, depth, seg);
 }

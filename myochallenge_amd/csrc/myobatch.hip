@@ -350,22 +350,22 @@ __global__ void __launch_bounds__(64, 2) k_wrap_census(EnvRecordLayout L, double
   const int env = blockIdx.x;
   env_wrap_census<T>(M, K, L, rec + (size_t)env * L.stride, s, env, cnt);
 }
-// render pose pass (csrc/myo_render.h): row r of `out` = env env_idx[r]'s items; a listed index outside [0, n_envs) gets an all-zero
-// row (nothing drawn)
-template <typename T, bool RK, int NC>
-__global__ void __launch_bounds__(64, 2) k_geom_poses(EnvRecordLayout L, double* rec, const int* __restrict__ env_idx, int n_envs,
-                                                   const float* vis, int nitem, double* out) {
+// render item pass (csrc/myo_render.h: GeomPass, TendonPass, ContactPass): row r of `out` = the P.rows items of env env_idx[r]; a listed
+// index outside [0, n_envs) gets an all-zero row (nothing drawn).  Keyed like k_sense, arithmetic x contact capacity: no pass integrates
+// (load_env, kinematics and the env_* passes never read s.rk).
+template <typename T, int NC, typename Pass>
+__global__ void __launch_bounds__(64, 2) k_items(EnvRecordLayout L, double* rec, const int* __restrict__ env_idx, int n_envs, Pass P, double* out) {
   Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
-  s.rk = rk_storage<T, RK, NC>();
+  s.rk = nullptr;
   const DevModel<T>& M = myo_cmodel<T>();
   const TaskDev& K = c_task;
-  const int env = env_idx[blockIdx.x];
-  double* o = out + (size_t)blockIdx.x * nitem * MYO_RENDER_ITEM_N;
+  const int env = env_idx[blockIdx.x], n = P.rows * MYO_RENDER_ITEM_N;
+  double* o = out + (size_t)blockIdx.x * n;
   if (env < 0 || env >= n_envs) {
-    for (int i = threadIdx.x; i < nitem * MYO_RENDER_ITEM_N; i += 64) o[i] = 0.0;
+    for (int i = threadIdx.x; i < n; i += 64) o[i] = 0.0;
     return;
   }
-  env_geom_poses<T>(M, K, L, rec + (size_t)env * L.stride, s, env, vis, o);
+  pass_run(P, M, K, L, rec + (size_t)env * L.stride, s, env, (int)blockIdx.x, o);
 }
 // render ray cast: workgroup (tile, env row) of 256 threads, one pixel each; the item table in dynamic LDS
 __global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render(const double* __restrict__ items, int nitem, const double* __restrict__ cams,
@@ -380,71 +380,9 @@ __global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render(const double* 
   __syncthreads();
   render_pixel(lds, nitem, cam, W, H, tx0 + tid % MYO_RTILE, ty0 + tid / MYO_RTILE, flags, (size_t)e, rgb, depth, seg);
 }
-// render path pass (csrc/myo_render.h): row r of `out` = the tendon items of env env_idx[r]; an index outside [0, n_envs): all zero
-template <typename T, bool RK, int NC>
-__global__ void __launch_bounds__(64, 2) k_tendon_paths(EnvRecordLayout L, double* rec, const int* __restrict__ env_idx, int n_envs,
-                                                     const float* tvis, const int* tadr, int ntitem, double* out) {
-  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
-  s.rk = rk_storage<T, RK, NC>();
-  const DevModel<T>& M = myo_cmodel<T>();
-  const TaskDev& K = c_task;
-  const int env = env_idx[blockIdx.x];
-  double* o = out + (size_t)blockIdx.x * ntitem * MYO_RENDER_ITEM_N;
-  if (env < 0 || env >= n_envs) {
-    for (int i = threadIdx.x; i < ntitem * MYO_RENDER_ITEM_N; i += 64) o[i] = 0.0;
-    return;
-  }
-  env_tendon_paths<T>(M, K, L, rec + (size_t)env * L.stride, s, env, tvis, tadr, o);
-}
-// ray cast with MYO_RENDER_TENDONS: the geoms' table is traced, then the tendon items take its place in LDS and are traced into the
-// same per-pixel hit (an instantiation of its own: k_render is what it was)
-__global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render_tendons(const double* __restrict__ items, int nitem, const double* __restrict__ titems,
-                                                                          int ntitem, const double* __restrict__ cams, int ncams, int W, int H, int flags,
-                                                                          unsigned char* rgb, float* depth, int* seg) {
-  RItem* lds = reinterpret_cast<RItem*>(myo_lds);
-  const int tid = threadIdx.x, tiles_x = (W + MYO_RTILE - 1) / MYO_RTILE, e = blockIdx.y;
-  const int tx0 = (int)(blockIdx.x % tiles_x) * MYO_RTILE, ty0 = (int)(blockIdx.x / tiles_x) * MYO_RTILE;
-  const int px = tx0 + tid % MYO_RTILE, py = ty0 + tid / MYO_RTILE;
-  const double* cam = cams + (size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N;
-  const double* it = items + (size_t)e * nitem * MYO_RENDER_ITEM_N;
-  const double* tn = titems + (size_t)e * ntitem * MYO_RENDER_ITEM_N;
-  const bool inside = px < W && py < H;
-  float d[3];
-  RHit h;
-  render_ray(cam, W, H, px, py, d, h);
-  render_stage(tid, lds, it, nitem, cam, flags);
-  __syncthreads();
-  render_cull(tid, lds, nitem, cam, W, H, tx0, ty0);
-  __syncthreads();
-  if (inside) render_trace(lds, nitem, 0, d, h);
-  __syncthreads();
-  render_stage(tid, lds, tn, ntitem, cam, flags);
-  __syncthreads();
-  render_cull(tid, lds, ntitem, cam, W, H, tx0, ty0);
-  __syncthreads();
-  if (inside) render_trace(lds, ntitem, nitem, d, h);
-  render_pixel_finish(it, nitem, tn, cam, W, H, px, py, flags, (size_t)e, h, d, rgb, depth, seg);
-}
-// render contact item pass (csrc/myo_render.h): row r of `out` = the 2 * cap contact items of env env_idx[r]; an index outside
-// [0, n_envs): all zero.  Keyed like k_sense: arithmetic x contact capacity.
-template <typename T, int NC>
-__global__ void __launch_bounds__(64, 2) k_contact_items(EnvRecordLayout L, double* rec, const int* __restrict__ env_idx, int n_envs, SenseDev tmp,
-                                                      myo_render_style style, double* out) {
-  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
-  s.rk = nullptr;
-  const DevModel<T>& M = myo_cmodel<T>();
-  const TaskDev& K = c_task;
-  const int env = env_idx[blockIdx.x];
-  double* o = out + (size_t)blockIdx.x * 2 * tmp.cap * MYO_RENDER_ITEM_N;
-  if (env < 0 || env >= n_envs) {
-    for (int i = threadIdx.x; i < 2 * tmp.cap * MYO_RENDER_ITEM_N; i += 64) o[i] = 0.0;
-    return;
-  }
-  env_contact_items<T>(M, K, L, rec + (size_t)env * L.stride, s, env, (int)blockIdx.x, tmp, style, o);
-}
-// ray cast with MYO_RENDER_CONTACTS: the geoms' table (with the style's geom_alpha), the tendon items if there are any (Y.ntitem > 0),
-// then the contact items take turns in LDS and are traced into the same per-pixel hit (an instantiation of its own: k_render and
-// k_render_tendons are what they were)
+// layered ray cast (RLayers, csrc/myo_render.h): the tables take turns in LDS and are traced into the same per-pixel hit, which is then
+// shaded from the hit items' global rows.  Serves every call that draws tendons or contacts; k_render stays the plain call's kernel
+// (48 VGPRs against 80: folding it in here would cost every plain render occupancy).
 __global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render_layers(RLayers Y, const double* __restrict__ cams, int ncams, int W, int H, int flags,
                                                                          unsigned char* rgb, float* depth, int* seg) {
   RItem* lds = reinterpret_cast<RItem*>(myo_lds);
@@ -452,32 +390,24 @@ __global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render_layers(RLayers
   const int tx0 = (int)(blockIdx.x % tiles_x) * MYO_RTILE, ty0 = (int)(blockIdx.x / tiles_x) * MYO_RTILE;
   const int px = tx0 + tid % MYO_RTILE, py = ty0 + tid / MYO_RTILE;
   const double* cam = cams + (size_t)(ncams == 1 ? 0 : e) * MYO_RCAM_N;
-  Y.it += (size_t)e * Y.nitem * MYO_RENDER_ITEM_N;
-  Y.tn += (size_t)e * Y.ntitem * MYO_RENDER_ITEM_N;
-  Y.cn += (size_t)e * Y.ncitem * MYO_RENDER_ITEM_N;
   const bool inside = px < W && py < H;
   float d[3];
   RHit h;
   render_ray(cam, W, H, px, py, d, h);
-  render_stage_geoms(tid, lds, Y.it, Y.nitem, Y.ngeom, Y.geom_alpha, cam, flags);
-  __syncthreads();
-  render_cull(tid, lds, Y.nitem, cam, W, H, tx0, ty0);
-  __syncthreads();
-  if (inside) render_trace(lds, Y.nitem, 0, d, h);
-  __syncthreads();
-  if (Y.ntitem > 0) {
-    render_stage(tid, lds, Y.tn, Y.ntitem, cam, flags);
+  for (int j = 0, base = 0; j < Y.nl; base += Y.l[j++].n) {
+    const int n = Y.l[j].n;
+    // (the camera through a pointer the compiler takes as new in every turn: hoisted out of the loop, the cull's fp32 camera and tile
+    //  terms — fp64 -> fp32 conversions are vector instructions — stay in VGPRs across all three phases, 94 VGPRs and 5 waves / SIMD;
+    //  rebuilt per layer, as the three written-out blocks did, 66 and 7)
+    const double* camj = cam;
+    asm volatile("" : "+s"(camj));
+    render_stage(tid, lds, Y.l[j].rows + (size_t)e * n * MYO_RENDER_ITEM_N, n, camj, flags, j == 0 ? Y.ngeom : 0, Y.geom_alpha);
     __syncthreads();
-    render_cull(tid, lds, Y.ntitem, cam, W, H, tx0, ty0);
+    render_cull(tid, lds, n, camj, W, H, tx0, ty0);
     __syncthreads();
-    if (inside) render_trace(lds, Y.ntitem, Y.nitem, d, h);
+    if (inside) render_trace(lds, n, base, d, h);
     __syncthreads();
   }
-  render_stage(tid, lds, Y.cn, Y.ncitem, cam, flags);
-  __syncthreads();
-  render_cull(tid, lds, Y.ncitem, cam, W, H, tx0, ty0);
-  __syncthreads();
-  if (inside) render_trace(lds, Y.ncitem, Y.nitem + Y.ntitem, d, h);
   render_layers_finish(Y, cam, W, H, px, py, flags, (size_t)e, h, d, rgb, depth, seg);
 }
 // ... and the order that follows from the census: positions sorted by count, most engaged first (ties keep their order), written back
@@ -814,10 +744,11 @@ extern "C" int myo_batch_sense(myo_batch* b, const myo_sense_out* out, void* str
   return be_launch_status();
 }
 
-static void geom_poses_launch(myo_batch* b, const int32_t* env_idx, int k, double* out, hipStream_t st) {
+template <typename Pass>
+static void items_launch(myo_batch* b, const int32_t* env_idx, int k, const Pass& P, double* out, hipStream_t st) {
   with_variant(b, [&](auto v) {
     using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_geom_poses<typename V::T, V::RK, V::NC>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->vis, b->nitem, out);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_items<typename V::T, V::NC, Pass>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, P, out);
   });
 }
 extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
@@ -826,63 +757,24 @@ extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k,
   if (!out) return fail(MYO_E_ARG, "myo_batch_geom_poses: null output");
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
-  geom_poses_launch(b, env_idx, k, out, st);
+  items_launch(b, env_idx, k, geom_pass(b), out, st);
   return be_launch_status();
-}
-static void tendon_paths_launch(myo_batch* b, const int32_t* env_idx, int k, double* out, hipStream_t st) {
-  with_variant(b, [&](auto v) {
-    using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tendon_paths<typename V::T, V::RK, V::NC>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, b->tvis, b->titem_adr, b->ntitem, out);
-  });
 }
 extern "C" int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
-  int empty = 0;
-  int rc = tendon_paths_check(b, env_idx, k, out, &empty);
-  if (rc || empty) return rc;
+  int rc = items_check(b, env_idx, k, out, "myo_batch_tendon_paths");
+  if (rc || k == 0 || b->ntitem == 0) return rc;
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
-  tendon_paths_launch(b, env_idx, k, out, st);
+  items_launch(b, env_idx, k, tendon_pass(b), out, st);
   return be_launch_status();
 }
-static void contact_items_launch(myo_batch* b, const int32_t* env_idx, int k, const SenseDev& tmp, double* out, hipStream_t st) {
-  with_variant(b, [&](auto v) {
-    using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_contact_items<typename V::T, V::NC>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, tmp, b->style, out);
-  });
-}
 extern "C" int myo_batch_contact_items(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
-  int empty = 0;
-  int rc = contact_items_check(b, env_idx, k, out, &empty);
-  if (rc || empty) return rc;
+  int rc = items_check(b, env_idx, k, out, "myo_batch_contact_items");
+  if (rc || k == 0) return rc;
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
   if ((rc = render_workspace(b, contact_tmp_doubles(b, k)))) return rc;
-  contact_items_launch(b, env_idx, k, contact_tmp(b, k, b->render_ws), out, st);
-  return be_launch_status();
-}
-// myo_batch_render with MYO_RENDER_CONTACTS (checked, bound): workspace = the geoms' tables, the tendons' (if drawn), the contacts', the
-// cameras, the contact pass's temporaries
-static int render_contacts(myo_batch* b, const int32_t* env_idx, int k, std::vector<double>& cam_tab, int ncams, int width, int height, int flags,
-                           uint8_t* rgb, float* depth, int32_t* segid, hipStream_t st) {
-  const bool tendons = (flags & MYO_RENDER_TENDONS) && b->ntitem > 0;
-  const int ncitem = 2 * sense_capacity(b), ntitem = tendons ? b->ntitem : 0;
-  const size_t geom_n = (size_t)k * b->nitem * MYO_RENDER_ITEM_N, ten_n = (size_t)k * ntitem * MYO_RENDER_ITEM_N;
-  const size_t con_n = (size_t)k * ncitem * MYO_RENDER_ITEM_N, item_n = geom_n + ten_n + con_n, cam_n = cam_tab.size();
-  int rc = render_workspace(b, item_n + cam_n + contact_tmp_doubles(b, k));
-  if (rc) return rc;
-  b->cam_host.swap(cam_tab);      // (kept until the next call: the asynchronous copy reads it)
-  hipError_t e = hipMemcpyAsync(b->render_ws + item_n, b->cam_host.data(), cam_n * sizeof(double), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return fail(MYO_E_DEVICE, "myo_batch_render: camera upload failed: %s", hipGetErrorString(e));
-  geom_poses_launch(b, env_idx, k, b->render_ws, st);
-  if (tendons) tendon_paths_launch(b, env_idx, k, b->render_ws + geom_n, st);
-  contact_items_launch(b, env_idx, k, contact_tmp(b, k, b->render_ws + item_n + cam_n), b->render_ws + geom_n + ten_n, st);
-  RLayers Y;
-  Y.it = b->render_ws; Y.tn = b->render_ws + geom_n; Y.cn = b->render_ws + geom_n + ten_n;
-  Y.nitem = b->nitem; Y.ngeom = b->ngeom; Y.ntitem = ntitem; Y.ncitem = ncitem; Y.seg_c = b->nitem + b->ntendon; Y.geom_alpha = (float)b->style.geom_alpha;
-  const int nmax = std::max(b->nitem, std::max(ntitem, ncitem));
-  const unsigned tiles = (unsigned)(((width + MYO_RTILE - 1) / MYO_RTILE) * ((height + MYO_RTILE - 1) / MYO_RTILE));
-  hipLaunchKernelGGL(k_render_layers, dim3(tiles, (unsigned)k), dim3(MYO_RTILE * MYO_RTILE), (unsigned)(nmax * sizeof(RItem)), st,
-                     Y, b->render_ws + item_n, ncams, width, height, flags, rgb, depth, segid);
+  items_launch(b, env_idx, k, contact_pass(b, k, b->render_ws), out, st);
   return be_launch_status();
 }
 extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
@@ -893,24 +785,21 @@ extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, con
   if (k > 65535) return fail(MYO_E_ARG, "myo_batch_render: at most 65535 envs per call");
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
-  if (flags & MYO_RENDER_CONTACTS) return render_contacts(b, env_idx, k, cam_tab, ncams, width, height, flags, rgb, depth, segid, st);
-  const bool tendons = (flags & MYO_RENDER_TENDONS) && b->ntitem > 0;
-  const size_t geom_n = (size_t)k * b->nitem * MYO_RENDER_ITEM_N;
-  const size_t item_n = geom_n + (tendons ? (size_t)k * b->ntitem * MYO_RENDER_ITEM_N : 0);      // the geoms' tables, then the tendons'
-  if ((rc = render_workspace(b, item_n + cam_tab.size()))) return rc;
+  const RenderPlan p = render_plan(b, k, flags, cam_tab.size());
+  if ((rc = render_workspace(b, p.total))) return rc;
+  double* ws = b->render_ws;
   b->cam_host.swap(cam_tab);      // (kept until the next call: the asynchronous copy reads it)
-  hipError_t e = hipMemcpyAsync(b->render_ws + item_n, b->cam_host.data(), b->cam_host.size() * sizeof(double), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(ws + p.cams, b->cam_host.data(), b->cam_host.size() * sizeof(double), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return fail(MYO_E_DEVICE, "myo_batch_render: camera upload failed: %s", hipGetErrorString(e));
-  geom_poses_launch(b, env_idx, k, b->render_ws, st);
-  const unsigned tiles = (unsigned)(((width + MYO_RTILE - 1) / MYO_RTILE) * ((height + MYO_RTILE - 1) / MYO_RTILE));
-  if (tendons) {
-    tendon_paths_launch(b, env_idx, k, b->render_ws + geom_n, st);
-    const int nmax = b->nitem > b->ntitem ? b->nitem : b->ntitem;
-    hipLaunchKernelGGL(k_render_tendons, dim3(tiles, (unsigned)k), dim3(MYO_RTILE * MYO_RTILE), (unsigned)(nmax * sizeof(RItem)), st,
-                       b->render_ws, b->nitem, b->render_ws + geom_n, b->ntitem, b->render_ws + item_n, ncams, width, height, flags, rgb, depth, segid);
+  items_launch(b, env_idx, k, geom_pass(b), ws, st);
+  if (p.ntitem > 0) items_launch(b, env_idx, k, tendon_pass(b), ws + p.tendons, st);
+  if (p.ncitem > 0) items_launch(b, env_idx, k, contact_pass(b, k, ws + p.tmp), ws + p.contacts, st);
+  const dim3 grid((unsigned)(((width + MYO_RTILE - 1) / MYO_RTILE) * ((height + MYO_RTILE - 1) / MYO_RTILE)), (unsigned)k);
+  const unsigned lds = (unsigned)(p.nmax * sizeof(RItem));
+  if (p.layered) {
+    hipLaunchKernelGGL(k_render_layers, grid, dim3(MYO_RTILE * MYO_RTILE), lds, st, render_layers(b, p, ws), ws + p.cams, ncams, width, height, flags, rgb, depth, segid);
   } else {
-    hipLaunchKernelGGL(k_render, dim3(tiles, (unsigned)k), dim3(MYO_RTILE * MYO_RTILE), (unsigned)(b->nitem * sizeof(RItem)), st,
-                       b->render_ws, b->nitem, b->render_ws + item_n, ncams, width, height, flags, rgb, depth, segid);
+    hipLaunchKernelGGL(k_render, grid, dim3(MYO_RTILE * MYO_RTILE), lds, st, ws, b->nitem, ws + p.cams, ncams, width, height, flags, rgb, depth, segid);
   }
   return be_launch_status();
 }

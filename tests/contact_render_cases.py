@@ -250,6 +250,19 @@ def case_off_means_off(lib, dtype):
         assert np.array_equal(before[k], after[k]) and np.array_equal(before[k], after_styled[k]), k
     seg_c = env._model.size("ngeom") + env._model.size("nsite") + env._model.size("ntendon")
     assert not (before["segmentation"] >= seg_c).any() and (with_c["segmentation"] >= seg_c).any()
+    # the pixels that show no contact item are what they are without the flag: opaque items over opaque geoms (geom_alpha back at 1),
+    # the one-table cast and the two-layer cast (tendons) against the casts with the contact layer
+    try:
+        env.batch.set_render_style(**dict(IMAGE_STYLE, geom_alpha=1.0))
+        for tendons in (False, True):
+            without, with_c = shot(tendons=tendons), shot(tendons=tendons, contacts=True)
+            contact = with_c["segmentation"] >= seg_c
+            print("other pixels", dtype, "tendons", tendons, "contact pixels", int(contact.sum()), "of", contact.size)
+            assert contact.any() and contact.mean() <= 0.5
+            for k in without:
+                assert np.array_equal(without[k][~contact], with_c[k][~contact]), (tendons, k)
+    finally:
+        env.batch.set_render_style(**DEFAULT_STYLE)
 
 
 def case_read_only(lib, dtype, n=3, seed=5, nsteps=10):
@@ -325,4 +338,8 @@ def case_pose_batch(lib, dtype):
     assert (off["segmentation"] >= 0).any()
     for k in off:
         assert np.array_equal(off[k], on[k]), k
+    two, three = shot(tendons=True), shot(tendons=True, contacts=True)      # two layers against three with an empty third
+    assert not np.array_equal(two["rgb"], off["rgb"])
+    for k in two:
+        assert np.array_equal(two[k], three[k]), k
     env.close()
