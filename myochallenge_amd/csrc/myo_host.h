@@ -1,11 +1,14 @@
 // myo_host.h — the host side both builds of libmyobatch share: error reporting, the host model (blob -> tables), the batch
 // (records, layouts, task block), myo_batch_create / _destroy, the kernel variant of a batch (with_variant) with its LDS footprint,
-// the entry points that only read or write env records, and the argument checks of the others.  Included by csrc/myobatch.hip (the
-// product: the HIP backend, the kernels and the launching entry points) and by csrc/myobatch_emu.cpp (test tooling: csrc/emu_host.h runs
-// the same kernel SOURCE lane by lane on the CPU).  The including file defines, before the include:
-//   MYO_BACKEND_NAME           "gfx950" | "MYO_EMU lane-serial test build"   (myo_version)
-//   MYO_BACKEND_DENSE_NEWTON   0 | 1: factor the Newton system densely (no block-arrow tables)
-//   MYO_BACKEND_BATCH_FIELDS   members the backend keeps in struct myo_batch
+// and EVERY env-path entry point of include/myobatch.h: argument checks, plans and workspaces are written once, over the few backend
+// primitives declared below (be_run: one job over the blocks of a launch; be_step; the ray cast; ...).  Included by csrc/myobatch.hip
+// (the product: the HIP backend, the kernels, the PPO side) and by csrc/myobatch_emu.cpp (test tooling: csrc/emu_host.h runs the same
+// kernel SOURCE lane by lane on the CPU).  The including file defines, before the include:
+//   MYO_BACKEND_NAME             "gfx950" | "MYO_EMU lane-serial test build"   (myo_version)
+//   MYO_BACKEND_DENSE_NEWTON     0 | 1: factor the Newton system densely (no block-arrow tables)
+//   MYO_BACKEND_BATCH_FIELDS     members the backend keeps in struct myo_batch
+//   MYO_BACKEND_RENDER_ENVS_MAX  envs one myo_batch_render call may list
+//   struct DeviceGuard           DeviceGuard g(device): the device is current while g lives
 // and, after it, the backend functions declared below.
 #pragma once
 #include "../../include/myobatch.h"
@@ -45,6 +48,22 @@ static void be_xfer(myo_batch* b, int off, int cnt, double* ext, int to_ext, voi
 static void be_xfer_i(myo_batch* b, int off, int cnt, int* ext, int to_ext, void* stream);   // ... of a field that holds integers
 static int be_launch_status();                                                             // MYO_OK, or what became of the launches just issued (MYO_E_DEVICE)
 static void be_task_changed(myo_batch* b);                                                 // the host's task block (b->K) changed: what was issued is waited for, the next launch uploads it again
+// the launches of the env path (`stream` as above).  be_run: job J (csrc/myo_task.h) for blocks 0 .. nblocks - 1 of the batch's kernel
+// variant, with the model and task constants bound; timed: between the batch's timing events when timing is on.  Returns the launch status.
+template <typename Job> static int be_run(myo_batch* b, const Job& J, int nblocks, void* stream, int timed = 0);
+static int be_step(myo_batch* b, const float* act, float* obs, float* rew, uint8_t* done, uint8_t* trunc, float* term_obs, float* comps,
+                   float* ep_info, void* stream);                                          // one env step of every env, by the batch's step plan
+static int be_bind(myo_batch* b, void* stream);                                            // the batch's constants become the device's
+static int be_wrap_order(myo_batch* b, void* stream);                                      // census of the wraps, then their new order (a batch without wrap_cnt: nothing)
+struct RenderPlan;
+static int be_camera_upload(myo_batch* b, double* dst, std::vector<double>& cam_tab, void* stream);   // cam_tab -> dst; may keep cam_tab's storage (b->cam_host)
+static int be_cast(myo_batch* b, const RenderPlan& p, int k, int ncams, int width, int height, int flags, uint8_t* rgb, float* depth,
+                   int32_t* segid, void* stream);                                          // the ray cast over the plan's tables in b->render_ws
+static int be_copy_envs(myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, void* stream);
+static int be_health(myo_batch* b, int out[4]);                                            // out <- b->K.health (waits for the device)
+static int be_set_step_generation(myo_batch* b, unsigned int gen);
+static double be_kernel_ms(myo_batch* b);
+static int be_wave_slots(int device, int n_workgroups, int lds_bytes, int32_t out[4]);
 
 static thread_local char g_err[4096] = "";      // (room for a loader report that lists every unsupported feature of a model)
 static int fail(int code, const char* fmt, ...) {
@@ -1015,7 +1034,7 @@ struct myo_batch {
   double ms_sum;
   int ms_cnt;
   int wrap_tune_in = 16;       // steps until the next census of the wraps (myo_batch_step: 16 steps after a reset of all envs, then every 256)
-  int* wrap_cnt = nullptr;     // dev int[ngw]: engagement counts of the wrap census (k_wrap_census / k_wrap_reorder); null = one pass of wraps, nothing to order
+  int* wrap_cnt = nullptr;     // dev int[ngw]: engagement counts of the wrap census (CensusJob / k_wrap_reorder); null = one pass of wraps, nothing to order
   bool has_slot_ws = false;    // K.ctrl_ws is the device's shared wave-slot workspace (slot_workspace_acquire / _release)
   bool has_big_ws = false;     // ... and K.big_ws its block of the 48-slot fp64 scratch's records / wrap results
   float* vis = nullptr;        // dev [nitem, 8]: the model's visual table with this task's targets drawn (myo_batch_geom_poses)
@@ -1375,7 +1394,7 @@ extern "C" void myo_batch_destroy(myo_batch* b) {
   if (b->render_ws) be_free(b->render_ws);
   delete b;
 }
-// ---- rendering (include/myobatch.h; csrc/myo_render.h): what both backends check before their launches
+// ---- rendering (include/myobatch.h; csrc/myo_render.h): checks, cameras, style and workspace; the entry points are further down
 extern "C" int myo_model_default_camera(const myo_model* m, myo_render_camera* out) {
   if (!m || !out) return fail(MYO_E_ARG, "myo_model_default_camera: null argument");
   for (int k = 0; k < 3; ++k) out->lookat[k] = m->cam_lookat[k];
@@ -1417,22 +1436,6 @@ static int render_cameras(const myo_render_camera* cams, int ncams, int height, 
     o[12] = 0.5 * height / tan(0.5 * C.fovy * d2r);
   }
   return MYO_OK;
-}
-static int render_check(const myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
-                        int flags, const uint8_t* rgb, const float* depth, const int32_t* segid, std::vector<double>& cam_tab) {
-  int rc = render_check_items(b, env_idx, k, "myo_batch_render");
-  if (rc) return rc;
-  if (!cams || (ncams != 1 && ncams != k)) return fail(MYO_E_ARG, "myo_batch_render: ncams must be 1 or k (%d), got %d", k, ncams);
-  if (width <= 0 || height <= 0 || (long long)width * height > MYO_RENDER_MAX_PIXELS)
-    return fail(MYO_E_ARG, "myo_batch_render: width and height must be >= 1 with width * height <= %d", MYO_RENDER_MAX_PIXELS);
-  if (flags & ~(MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG | MYO_RENDER_SITES | MYO_RENDER_TENDONS | MYO_RENDER_CONTACTS)) return fail(MYO_E_ARG, "myo_batch_render: unknown flag bits 0x%x", flags);
-  if (!(flags & (MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG))) return fail(MYO_E_ARG, "myo_batch_render: no output requested");
-  if ((flags & MYO_RENDER_TENDONS) && b->ntitem > MYO_RTEN_MAX)
-    return fail(MYO_E_ARG, "myo_batch_render: MYO_RENDER_TENDONS: %d tendon items, at most %d can be drawn", b->ntitem, MYO_RTEN_MAX);
-  if (((flags & MYO_RENDER_RGB) && !rgb) || ((flags & MYO_RENDER_DEPTH) && !depth) || ((flags & MYO_RENDER_SEG) && !segid))
-    return fail(MYO_E_ARG, "myo_batch_render: a requested output buffer is NULL");
-  if ((long long)k * width * height > (1ll << 31)) return fail(MYO_E_ARG, "myo_batch_render: k * width * height exceeds 2^31 pixels");
-  return render_cameras(cams, ncams, height, cam_tab);
 }
 // the style of the contact items: held per batch, read by the next contact item pass / render with MYO_RENDER_CONTACTS
 extern "C" int myo_batch_set_render_style(myo_batch* b, const myo_render_style* st) {
@@ -1554,34 +1557,86 @@ extern "C" int myo_batch_enable_timing(myo_batch* b, int on) {
   return MYO_OK;
 }
 
-// ---- what both backends check before the launches of the other entry points
+// ---- the entry points that launch: each written once, over the backend primitives (be_run and the others declared at the top)
 static int task_layer_check(const myo_batch* b) { return b->K.kind ? MYO_OK : fail(MYO_E_STATE, "batch has no task layer"); }
-static int reset_check(const myo_batch* b) {
+extern "C" int myo_batch_bind_constants(myo_batch* b, void* stream) {
   if (int rc = batch_check(b)) return rc;
-  return task_layer_check(b);
+  return be_bind(b, stream);
 }
-static int step_check(const myo_batch* b, const float* act, const float* obs, const float* rew, const uint8_t* done) {
+// census of the wraps over the envs' present states, then the new order (both on the stream: usable between any two steps, also while
+// a graph of steps exists — the tables are rewritten in place)
+extern "C" int myo_batch_tune_wrap_order(myo_batch* b, void* stream) {
+  if (int rc = batch_check(b)) return rc;
+  return be_wrap_order(b, stream);
+}
+extern "C" int myo_batch_reset(myo_batch* b, const uint8_t* mask, float* obs, void* stream) {
+  if (int rc = batch_check(b)) return rc;
+  if (int rc = task_layer_check(b)) return rc;
+  if (int rc = be_run(b, ResetJob{mask, obs}, b->n, stream)) return rc;
+  if (mask) return MYO_OK;
+  b->wrap_tune_in = 16;                 // a reset of every env: the wrap order from the reset states, again 16 steps on
+  return be_wrap_order(b, stream);
+}
+extern "C" int myo_batch_step(myo_batch* b, const float* act, float* obs, float* rew, uint8_t* done, uint8_t* trunc,
+                              float* term_obs, float* comps, float* ep_info, void* stream) {
   if (!b || !act || !obs || !rew || !done) return fail(MYO_E_ARG, "myo_batch_step: act/obs/rew/done are required");
-  return task_layer_check(b);
+  if (int rc = task_layer_check(b)) return rc;
+  return be_step(b, act, obs, rew, done, trunc, term_obs, comps, ep_info, stream);
 }
-static int step_inner_check(const myo_batch* b, const float* act, const float* obs) {
+// test hook: put the step plan's generation counter (and every env's state, consistently) at `gen` — the counter wraps after
+// 2^28 steps and the protocol's arithmetic is modulo 2^32 (tests/test_step_parts.py steps across the wrap)
+extern "C" int myo_batch_set_step_generation(myo_batch* b, unsigned int gen) {
+  if (int rc = batch_check(b)) return rc;
+  return b->part_state ? be_set_step_generation(b, gen) : MYO_OK;
+}
+// Health counters of a batch (synchronises the device).  out[0]: k_step workgroups that found their env's hand-off state in another
+// generation than the launch's (see the protocol comment at k_step); out[1]: substeps in which an env had more contacts than its
+// scratch holds (the surplus was dropped); out[2]: the same for limit rows; out[3]: the most contact slots such a substep asked for.
+// All 0 in a healthy batch, and in one without counters.
+extern "C" int myo_batch_health(myo_batch* b, int out[4]) {
+  if (!b || !out) return fail(MYO_E_ARG, "null argument");
+  for (int k = 0; k < 4; ++k) out[k] = 0;
+  return b->K.health ? be_health(b, out) : MYO_OK;
+}
+// Device check of what the per-slot workspace rests on (myo_wave_slot, wave.h): `n_workgroups` one-wave workgroups with `lds_bytes` of
+// dynamic LDS (k_step's footprint: the same residency) each take their slot's occupancy counter, stay for ~20 us, and leave.
+// out[0]: workgroups that found their slot occupied (must be 0); out[1]: distinct slots seen; out[2]: largest slot index; out[3]: bit mask of XCC ids.
+extern "C" int myo_debug_wave_slots(int device, int n_workgroups, int lds_bytes, int32_t out[4]) {
+  if (!out || n_workgroups <= 0 || lds_bytes < 0 || lds_bytes > 65536) return fail(MYO_E_ARG, "bad argument");
+  return be_wave_slots(device, n_workgroups, lds_bytes, out);
+}
+extern "C" int myo_batch_step_inner(myo_batch* b, const uint8_t* mask, const float* act, float* obs, uint8_t* done, void* stream) {
   if (!b || !act || !obs) return fail(MYO_E_ARG, "myo_batch_step_inner: act/obs are required");
-  return task_layer_check(b);
+  if (int rc = task_layer_check(b)) return rc;
+  return be_run(b, StepInnerJob{mask, act, obs, done}, b->n, stream);
 }
-static int step_inner_idx_check(const myo_batch* b, const int* idx, int n_idx, const float* act, const float* obs) {
+// Compact form of myo_batch_step_inner: the envs idx[0 .. n_idx) (dev int32; -1 = empty slot) take one unwrapped env step with
+// row r of act [n_idx, nu]; row r of obs [n_idx, obs_dim] and done [n_idx] (may be NULL) receive env idx[r]'s results.  An env
+// must not be listed twice.  MixtureModelBaodingEnv's base phase runs the few envs that were just reset this way.
+extern "C" int myo_batch_step_inner_idx(myo_batch* b, const int* idx, int n_idx, const float* act, float* obs, uint8_t* done, void* stream) {
   if (!b || !idx || !act || !obs || n_idx <= 0) return fail(MYO_E_ARG, "myo_batch_step_inner_idx: idx/act/obs are required");
-  return task_layer_check(b);
+  if (int rc = task_layer_check(b)) return rc;
+  return be_run(b, StepInnerIdxJob{idx, act, obs, done}, n_idx, stream);
 }
-static int physics_step_check(const myo_batch* b, int nsub) { return b && nsub >= 0 ? MYO_OK : fail(MYO_E_ARG, "bad arguments"); }
-static int forward_dump_check(const myo_batch* b, const double* out) { return b && out ? MYO_OK : fail(MYO_E_ARG, "bad arguments"); }
-// myo_batch_sense (csrc/myo_sense.h): the struct's size is its version.  A k_step launch runs every part of an env step, so a call that is
-// stream-ordered behind the steps never meets an env between two parts of one.
-static int sense_check(const myo_batch* b, const myo_sense_out* out) {
-  if (!b || !out) return fail(MYO_E_BADARG, "myo_batch_sense: null batch or output struct");
-  if (out->size != sizeof(myo_sense_out)) return fail(MYO_E_BADARG, "myo_batch_sense: myo_sense_out.size is %zu, this library's struct has %zu bytes", out->size, sizeof(myo_sense_out));
-  return MYO_OK;
+// Whole env records from one batch into another (same model, same task kind): dst env dst_idx[r] <- src env src_idx[r], r < k.
+// The record is everything an env is between two steps (state, warm start, task scalars, per-episode draws, counters), so the
+// destination env continues exactly where the source env stood.  MixtureModelBaodingEnv hands pre-played episodes (reset + base
+// phase, done in bulk on a pool batch) to the envs that have just finished.  k = 0 is an empty copy.
+extern "C" int myo_batch_copy_envs(myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, void* stream) {
+  if (!dst || !src || !dst_idx || !src_idx || k < 0) return fail(MYO_E_ARG, "myo_batch_copy_envs: null argument");
+  if (dst->L.stride != src->L.stride || dst->nq != src->nq || dst->nv != src->nv || dst->na != src->na || dst->K.kind != src->K.kind || dst->device != src->device)
+    return fail(MYO_E_ARG, "myo_batch_copy_envs: the two batches differ in model, task kind or device");
+  return k ? be_copy_envs(dst, dst_idx, src, src_idx, k, stream) : MYO_OK;
 }
-// the sense rows of the variant table: k_sense / env_sense exist per arithmetic and contact capacity, keyed as k_step is (the integrator
+extern "C" int myo_batch_physics_step(myo_batch* b, const double* ctrl, int nsub, void* stream) {
+  if (!b || nsub < 0) return fail(MYO_E_ARG, "bad arguments");
+  return be_run(b, PhysicsJob{ctrl, nsub}, b->n, stream, 1);
+}
+extern "C" int myo_batch_forward_dump(myo_batch* b, const double* ctrl, double* out, void* stream) {
+  if (!b || !out) return fail(MYO_E_ARG, "bad arguments");
+  return be_run(b, DumpJob{ctrl, b->D, out}, b->n, stream);
+}
+// the sense rows of the variant table: SenseJob / env_sense exist per arithmetic and contact capacity, keyed as k_step is (the integrator
 // does not enter: a forward pass integrates nothing); a row's capacity is its scratch's record slots
 static int sense_capacity(const myo_batch* b) {
   return with_variant(b, [](auto v) { using V = decltype(v); return (int)Scratch<typename V::T, V::NC>::NREC; });
@@ -1605,14 +1660,18 @@ static SenseDev contact_tmp(const myo_batch* b, int k, double* base) {
   d.ncon = (int*)(base + (size_t)k * d.cap * MYO_SENSE_CON_N);
   return d;
 }
-// the three item passes of a batch (csrc/myo_render.h); tmp: the contact pass's temporaries, contact_tmp_doubles(b, k) doubles
-static GeomPass geom_pass(const myo_batch* b) { return {b->nitem, b->vis}; }
-static TendonPass tendon_pass(const myo_batch* b) { return {b->ntitem, b->tvis, b->titem_adr}; }
-static ContactPass contact_pass(const myo_batch* b, int k, double* tmp) { return {2 * sense_capacity(b), contact_tmp(b, k, tmp), b->style}; }
+// the three item passes of a batch (csrc/myo_render.h) over the envs idx[0 .. k) into `out`; tmp: the contact pass's temporaries,
+// contact_tmp_doubles(b, k) doubles
+static GeomPass geom_pass(const myo_batch* b, const int* idx, double* out) { return {idx, out, b->nitem, b->vis}; }
+static TendonPass tendon_pass(const myo_batch* b, const int* idx, double* out) { return {idx, out, b->ntitem, b->tvis, b->titem_adr}; }
+static ContactPass contact_pass(const myo_batch* b, const int* idx, int k, double* tmp, double* out) {
+  return {idx, out, 2 * sense_capacity(b), contact_tmp(b, k, tmp), b->style};
+}
 // What a myo_batch_render call of k envs runs, and its workspace (offsets in doubles, the same on both backends): the geoms' table
 // [k, nitem], the tendons' [k, ntitem] (ntitem = 0: not drawn — no flag, or a model without tendon items), the contacts' [k, ncitem]
 // (0: no MYO_RENDER_CONTACTS), the cameras, the contact pass's temporaries.  A table of n > 0 rows has its item pass run.  layered:
-// k_render_layers over the tables that are there (render_layers), else k_render over the geoms'; nmax sizes the cast's LDS table.
+// the cast (be_cast) is the layered one over the tables that are there (render_layers), else the plain one over the geoms'; nmax sizes
+// the cast's LDS table.
 struct RenderPlan { size_t tendons, contacts, cams, tmp, total; int ntitem, ncitem, nmax; bool layered; };
 static RenderPlan render_plan(const myo_batch* b, int k, int flags, size_t ncam_doubles) {
   RenderPlan p;
@@ -1638,18 +1697,55 @@ static RLayers render_layers(const myo_batch* b, const RenderPlan& p, const doub
   Y.geom_alpha = p.ncitem > 0 ? (float)b->style.geom_alpha : 1.f;
   return Y;
 }
-// k = 0 is an empty copy (*empty)
-static int copy_envs_check(const myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, int* empty) {
-  if (!dst || !src || !dst_idx || !src_idx || k < 0) return fail(MYO_E_ARG, "myo_batch_copy_envs: null argument");
-  if (dst->L.stride != src->L.stride || dst->nq != src->nq || dst->nv != src->nv || dst->na != src->na || dst->K.kind != src->K.kind || dst->device != src->device)
-    return fail(MYO_E_ARG, "myo_batch_copy_envs: the two batches differ in model, task kind or device");
-  *empty = k == 0;
-  return MYO_OK;
+// myo_batch_sense (csrc/myo_sense.h): the struct's size is its version.  A k_step launch runs every part of an env step, so a call that is
+// stream-ordered behind the steps never meets an env between two parts of one.
+extern "C" int myo_batch_sense(myo_batch* b, const myo_sense_out* out, void* stream) {
+  if (!b || !out) return fail(MYO_E_BADARG, "myo_batch_sense: null batch or output struct");
+  if (out->size != sizeof(myo_sense_out)) return fail(MYO_E_BADARG, "myo_batch_sense: myo_sense_out.size is %zu, this library's struct has %zu bytes", out->size, sizeof(myo_sense_out));
+  return be_run(b, SenseJob{sense_dev(b, out)}, b->n, stream);
 }
-// out is zeroed; a batch without counters has nothing more to report (*empty)
-static int health_check(const myo_batch* b, int out[4], int* empty) {
-  if (!b || !out) return fail(MYO_E_ARG, "null argument");
-  for (int k = 0; k < 4; ++k) out[k] = 0;
-  *empty = !b->K.health;
-  return MYO_OK;
+extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
+  if (int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses")) return rc;
+  if (!out) return fail(MYO_E_ARG, "myo_batch_geom_poses: null output");
+  return be_run(b, geom_pass(b, env_idx, out), k, stream);
 }
+extern "C" int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
+  int rc = items_check(b, env_idx, k, out, "myo_batch_tendon_paths");
+  if (rc || k == 0 || b->ntitem == 0) return rc;
+  return be_run(b, tendon_pass(b, env_idx, out), k, stream);
+}
+extern "C" int myo_batch_contact_items(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
+  int rc = items_check(b, env_idx, k, out, "myo_batch_contact_items");
+  if (rc || k == 0) return rc;
+  DeviceGuard guard(b->device);
+  if ((rc = render_workspace(b, contact_tmp_doubles(b, k)))) return rc;
+  return be_run(b, contact_pass(b, env_idx, k, b->render_ws, out), k, stream);
+}
+extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
+                                int flags, uint8_t* rgb, float* depth, int32_t* segid, void* stream) {
+  int rc = render_check_items(b, env_idx, k, "myo_batch_render");
+  if (rc) return rc;
+  if (!cams || (ncams != 1 && ncams != k)) return fail(MYO_E_ARG, "myo_batch_render: ncams must be 1 or k (%d), got %d", k, ncams);
+  if (width <= 0 || height <= 0 || (long long)width * height > MYO_RENDER_MAX_PIXELS)
+    return fail(MYO_E_ARG, "myo_batch_render: width and height must be >= 1 with width * height <= %d", MYO_RENDER_MAX_PIXELS);
+  if (flags & ~(MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG | MYO_RENDER_SITES | MYO_RENDER_TENDONS | MYO_RENDER_CONTACTS)) return fail(MYO_E_ARG, "myo_batch_render: unknown flag bits 0x%x", flags);
+  if (!(flags & (MYO_RENDER_RGB | MYO_RENDER_DEPTH | MYO_RENDER_SEG))) return fail(MYO_E_ARG, "myo_batch_render: no output requested");
+  if ((flags & MYO_RENDER_TENDONS) && b->ntitem > MYO_RTEN_MAX)
+    return fail(MYO_E_ARG, "myo_batch_render: MYO_RENDER_TENDONS: %d tendon items, at most %d can be drawn", b->ntitem, MYO_RTEN_MAX);
+  if (((flags & MYO_RENDER_RGB) && !rgb) || ((flags & MYO_RENDER_DEPTH) && !depth) || ((flags & MYO_RENDER_SEG) && !segid))
+    return fail(MYO_E_ARG, "myo_batch_render: a requested output buffer is NULL");
+  if ((long long)k * width * height > (1ll << 31)) return fail(MYO_E_ARG, "myo_batch_render: k * width * height exceeds 2^31 pixels");
+  std::vector<double> cam_tab;
+  if ((rc = render_cameras(cams, ncams, height, cam_tab))) return rc;
+  if (k > MYO_BACKEND_RENDER_ENVS_MAX) return fail(MYO_E_ARG, "myo_batch_render: at most %d envs per call", MYO_BACKEND_RENDER_ENVS_MAX);
+  DeviceGuard guard(b->device);
+  const RenderPlan p = render_plan(b, k, flags, cam_tab.size());
+  if ((rc = render_workspace(b, p.total))) return rc;
+  double* ws = b->render_ws;
+  if ((rc = be_camera_upload(b, ws + p.cams, cam_tab, stream))) return rc;
+  if ((rc = be_run(b, geom_pass(b, env_idx, ws), k, stream))) return rc;
+  if (p.ntitem > 0 && (rc = be_run(b, tendon_pass(b, env_idx, ws + p.tendons), k, stream))) return rc;
+  if (p.ncitem > 0 && (rc = be_run(b, contact_pass(b, env_idx, k, ws + p.tmp, ws + p.contacts), k, stream))) return rc;
+  return be_cast(b, p, k, ncams, width, height, flags, rgb, depth, segid, stream);
+}
+extern "C" double myo_batch_kernel_ms(myo_batch* b) { return b ? be_kernel_ms(b) : -1.0; }

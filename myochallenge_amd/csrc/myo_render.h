@@ -1,7 +1,7 @@
 // myo_render.h — rendering of env states (include/myobatch.h: myo_batch_geom_poses / _tendon_paths / _contact_items, myo_batch_render).
 //   item passes  one wave per listed env writes one table of MYO_RENDER_ITEM_N-double rows.  A pass is a small struct (GeomPass,
-//                TendonPass, ContactPass: its host-built tables and its rows per env) with a pass_run that calls the pass's env_* function;
-//                one kernel (k_items, csrc/myobatch.hip) and one emulation loop (emu_items, csrc/emu_host.h) run all three.
+//                TendonPass, ContactPass: the env list, the output, its host-built tables and its rows per env) with a job_run that calls
+//                the pass's env_* function: a job like every env-path entry point's (csrc/myo_task.h), run by k_env / be_run.
 //     env_geom_poses     load_env + the stepper's own kinematics, then one lane per item (geoms, then sites) writes its world pose, the
 //                        env's geometry (geom_size0_hp / geom_lpos_hp ...), its type and colour.  Reads the record only.
 //     env_tendon_paths   load_env + kinematics, then one lane per tendon path element (the host-resolved te_i walk) runs the stepper's
@@ -233,25 +233,26 @@ DEV void env_contact_items(const DevModel<T>& M, const TaskDev& K, const EnvReco
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the three passes
-// what k_items / emu_items run for row `row` of a call (env `env` of the batch): `rows` items per env, written at `out`
-struct GeomPass { int rows; const float* vis; };                            // rows = ngeom + nsite
-struct TendonPass { int rows; const float *tvis; const int* tadr; };        // rows = the model's tendon items
-struct ContactPass { int rows; SenseDev tmp; myo_render_style style; };     // rows = 2 * tmp.cap
-template <typename T, int NC>
-DEV void pass_run(const GeomPass& P, const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s, int env, int,
-                  double* out) {
-  env_geom_poses(M, K, L, rec, s, env, P.vis, out);
+// Jobs (csrc/myo_task.h) over a LIST of envs: block r writes the `rows` items of env idx[r] to row r of `out` [k, rows, MYO_RENDER_ITEM_N];
+// a listed index outside [0, n_envs) gets an all-zero row (nothing drawn).  Keyed without the integrator: no pass integrates (load_env,
+// kinematics and the env_* passes never read s.rk).
+struct GeomPass { static constexpr bool RK = false; const int* idx; double* out; int rows; const float* vis; };                      // rows = ngeom + nsite
+struct TendonPass { static constexpr bool RK = false; const int* idx; double* out; int rows; const float *tvis; const int* tadr; };  // rows = the model's tendon items
+struct ContactPass { static constexpr bool RK = false; const int* idx; double* out; int rows; SenseDev tmp; myo_render_style style; };   // rows = 2 * tmp.cap
+// row `block` of a pass's table and its env; null, with the row zeroed, for an index outside the batch
+template <typename Pass>
+DEV double* pass_row(const Pass& P, int block, int n_envs, int& env) {
+  WAVE_FN
+  const int n = P.rows * MYO_RENDER_ITEM_N;
+  double* o = P.out + (size_t)block * n;
+  env = P.idx[block];
+  if (env >= 0 && env < n_envs) return o;
+  PHASE { for (int i = lane; i < n; i += 64) o[i] = 0.0; }
+  return nullptr;
 }
-template <typename T, int NC>
-DEV void pass_run(const TendonPass& P, const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s, int env, int,
-                  double* out) {
-  env_tendon_paths(M, K, L, rec, s, env, P.tvis, P.tadr, out);
-}
-template <typename T, int NC>
-DEV void pass_run(const ContactPass& P, const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s, int env,
-                  int row, double* out) {
-  env_contact_items(M, K, L, rec, s, env, row, P.tmp, P.style, out);
-}
+MYO_JOB_RUN(GeomPass) { int env; if (double* o = pass_row(J, block, n_envs, env)) env_geom_poses(M, K, L, MYO_ENV_REC(env), s, env, J.vis, o); }
+MYO_JOB_RUN(TendonPass) { int env; if (double* o = pass_row(J, block, n_envs, env)) env_tendon_paths(M, K, L, MYO_ENV_REC(env), s, env, J.tvis, J.tadr, o); }
+MYO_JOB_RUN(ContactPass) { int env; if (double* o = pass_row(J, block, n_envs, env)) env_contact_items(M, K, L, MYO_ENV_REC(env), s, env, block, J.tmp, J.style, o); }
 
 // ---------------------------------------------------------------------------------------------------------------- ray cast
 struct RItem {      // one item in LDS: fp32, relative to the camera position

@@ -228,3 +228,7 @@ DEV void env_sense(const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout
   SYNC();
   ws_release(K, s);
 }
+
+// the job of myo_batch_sense (jobs: csrc/myo_task.h); keyed without the integrator, a forward pass integrates nothing
+struct SenseJob { static constexpr bool RK = false; SenseDev O; };
+MYO_JOB_RUN(SenseJob) { env_sense(M, K, L, MYO_ENV_REC(block), s, block, J.O); }

@@ -20,6 +20,7 @@
 // Random numbers: the reference mixes gym's np_random, the global np.random and random.choice
 // (SURVEY §7.4-6); seed-for-seed parity is not meaningful, so the device draws from
 // Philox4x32-10 keyed by (seed, env, episode) in the reference's draw ORDER.
+// At the end: the jobs (ResetJob, StepInnerJob, ...), the form in which every env-path entry point but the step reaches its env_* function.
 #pragma once
 #include "myo_physics.h"
 
@@ -651,7 +652,7 @@ DEV void store_env(const DevModel<T>& M_in, const TaskDev& K_in, const EnvRecord
   SYNC();
 }
 
-// ---- the three env-level entry points (one call = one env; the kernels are thin wrappers)
+// ---- the env-level entry points (one call = one env): env_step is k_step's body, the others are called by their jobs' job_run (end of this file)
 template <typename T, int RKM = -1, int NC>
 DEV void env_step(const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s,
                   int env, const float* act, float* obs, float* rew, unsigned char* done, unsigned char* trunc,
@@ -882,3 +883,31 @@ DEV void env_forward_dump(const DevModel<T>& M, const TaskDev& K, const EnvRecor
   SYNC();
   ws_release(K, s);
 }
+
+// ---- jobs.  An env-path entry point's arguments travel as one small trivially-copyable struct, by value: to the one wrapper kernel
+// (k_env, csrc/myobatch.hip), or to the emulation's loop over blocks (be_run, csrc/emu_host.h).  job_run(job, variant, ...) is what block
+// `block` of the launch does: it maps the block to its env and calls the env_* function above; `rec` is the batch's first record, n_envs
+// its env count, V the KernelVariant (csrc/myo_host.h).  A job names its key: RK = false drops the integrator from the variant (the
+// kernel has no RK4 twin and s.rk is null).  The jobs of csrc/myo_sense.h and csrc/myo_render.h follow the same form.
+#define MYO_JOB_RUN(Job)                                                                                                             \
+  template <typename V, typename T, int NC>                                                                                          \
+  DEV void job_run(const Job& J, V, const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout& L, double* rec, Scratch<T, NC>& s, \
+                   int block, int n_envs)
+#define MYO_ENV_REC(env) (rec + (size_t)(env) * L.stride)
+struct ResetJob { static constexpr bool RK = true; const unsigned char* mask; float* obs; };
+MYO_JOB_RUN(ResetJob) { env_reset(M, K, L, MYO_ENV_REC(block), s, block, J.mask, J.obs); }
+struct StepInnerJob { static constexpr bool RK = true; const unsigned char* mask; const float* act; float* obs; unsigned char* done; };
+MYO_JOB_RUN(StepInnerJob) { env_step_inner<T, V::RK ? 1 : 0>(M, K, L, MYO_ENV_REC(block), s, block, J.mask, J.act, J.obs, J.done); }
+// the same for a LIST of envs: block r steps env idx[r] (outside [0, n_envs): an empty slot) with row r of act / obs / done
+struct StepInnerIdxJob { static constexpr bool RK = true; const int* idx; const float* act; float* obs; unsigned char* done; };
+MYO_JOB_RUN(StepInnerIdxJob) {
+  const int env = J.idx[block];
+  if (env < 0 || env >= n_envs) return;
+  env_step_inner<T, V::RK ? 1 : 0>(M, K, L, MYO_ENV_REC(env), s, env, (const unsigned char*)nullptr, J.act, J.obs, J.done, block);
+}
+struct PhysicsJob { static constexpr bool RK = true; const double* ctrl; int nsub; };
+MYO_JOB_RUN(PhysicsJob) { env_physics<T, V::RK ? 1 : 0>(M, K, L, MYO_ENV_REC(block), s, block, J.ctrl, J.nsub); }
+struct CensusJob { static constexpr bool RK = true; int* cnt; };
+MYO_JOB_RUN(CensusJob) { env_wrap_census(M, K, L, MYO_ENV_REC(block), s, block, J.cnt); }
+struct DumpJob { static constexpr bool RK = false; const double* ctrl; DumpLayout D; double* out; };      // forward dynamics integrate nothing
+MYO_JOB_RUN(DumpJob) { env_forward_dump(M, K, L, MYO_ENV_REC(block), s, block, J.ctrl, J.D, J.out); }

@@ -2,7 +2,7 @@
 //   hipcc --offload-arch=gfx950  -> libmyobatch.so   (the product; no CPU path)
 // One workgroup = one wavefront = one environment; grid = number of environments.
 // The host side it shares with the test tooling (model tables, batch records, myo_batch_create, the kernel variant of a batch, the record
-// accessors and the argument checks) is csrc/myo_host.h; the lane-serial
+// accessors and every env-path entry point) is csrc/myo_host.h, written over the backend primitives defined here; the lane-serial
 // emulation of the same kernel SOURCE is another translation unit (csrc/myobatch_emu.cpp + csrc/emu_host.h), not a path of this one.
 #include <hip/hip_runtime.h>
 #include <utility>
@@ -10,6 +10,13 @@
 #define MYO_BACKEND_NAME "gfx950"
 #define MYO_BACKEND_DENSE_NEWTON 0
 #define MYO_BACKEND_BATCH_FIELDS hipEvent_t ev0, ev1; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+#define MYO_BACKEND_RENDER_ENVS_MAX 65535      /* (gridDim.y of the ray cast) */
+// every launch entry point runs on the batch's own device, whatever the caller's current device is
+struct DeviceGuard {
+  int prev = -1; bool switched = false;
+  explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = (hipSetDevice(dev) == hipSuccess); }
+  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
+};
 #include "myo_host.h"
 
 // ------------------------------------------------------------------------------------------ backend
@@ -80,12 +87,6 @@ static void big_workspace_release(int device) {
   SlotWs& w = g_slot_ws[device];
   if (w.big_users > 0 && --w.big_users == 0) { (void)hipFree(w.big); w.big = nullptr; }
 }
-// every launch entry point runs on the batch's own device, whatever the caller's current device is
-struct DeviceGuard {
-  int prev = -1; bool switched = false;
-  explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = (hipSetDevice(dev) == hipSuccess); }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-};
 static void unbind(const myo_batch* b, int device) {
   std::lock_guard<std::mutex> lk(g_bound_mu);
   if (device >= 0 && device < MYO_MAX_DEVICES && g_bound[device].b == b) g_bound[device].b = nullptr;
@@ -279,93 +280,17 @@ __global__ void __launch_bounds__(64, 2) k_step(EnvRecordLayout L, double* rec, 
   if (threadIdx.x < MYO_NPROF) atomicAdd(&g_prof[threadIdx.x], s.prof[threadIdx.x]);
 #endif
 }
-template <typename T, bool RK, int NC>
-__global__ void __launch_bounds__(64, 2) k_reset(EnvRecordLayout L, double* rec,
-                                              const unsigned char* mask, float* obs) {
+// Every other env-path launch: block blockIdx.x runs job J (csrc/myo_task.h, myo_sense.h, myo_render.h: the entry point's arguments and the
+// job_run that maps the block to its env and calls the env_* function).  Keyed like k_step, arithmetic x integrator x contact capacity;
+// a job that never integrates (Job::RK = false) has RK = false whatever the batch's integrator, and a null s.rk.  The job comes before
+// n_envs among the kernel arguments: its fields lie where the separate arguments of a written-out wrapper would.
+template <typename T, bool RK, int NC, typename Job>
+__global__ void __launch_bounds__(64, 2) k_env(EnvRecordLayout L, double* rec, Job J, int n_envs) {
   Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
   s.rk = rk_storage<T, RK, NC>();
   const DevModel<T>& M = myo_cmodel<T>();
   const TaskDev& K = c_task;
-  const int env = blockIdx.x;
-  env_reset<T>(M, K, L, rec + (size_t)env * L.stride, s, env, mask, obs);
-}
-template <typename T, bool RK, int NC>
-__global__ void __launch_bounds__(64, 2) k_step_inner(EnvRecordLayout L, double* rec, const unsigned char* mask, const float* act,
-                                                   float* obs, unsigned char* done) {
-  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
-  s.rk = rk_storage<T, RK, NC>();
-  const DevModel<T>& M = myo_cmodel<T>();
-  const TaskDev& K = c_task;
-  const int env = blockIdx.x;
-  env_step_inner<T, RK ? 1 : 0>(M, K, L, rec + (size_t)env * L.stride, s, env, mask, act, obs, done);
-}
-// the same for a LIST of envs: block r steps env idx[r] (idx[r] < 0: an empty slot) with row r of act / obs / done
-template <typename T, bool RK, int NC>
-__global__ void __launch_bounds__(64, 2) k_step_inner_idx(EnvRecordLayout L, double* rec, const int* __restrict__ idx, int n_envs, const float* act,
-                                                       float* obs, unsigned char* done) {
-  const int env = idx[blockIdx.x];
-  if (env < 0 || env >= n_envs) return;
-  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
-  s.rk = rk_storage<T, RK, NC>();
-  const DevModel<T>& M = myo_cmodel<T>();
-  const TaskDev& K = c_task;
-  env_step_inner<T, RK ? 1 : 0>(M, K, L, rec + (size_t)env * L.stride, s, env, (const unsigned char*)nullptr, act, obs, done, (int)blockIdx.x);
-}
-template <typename T, bool RK, int NC>
-__global__ void __launch_bounds__(64, 2) k_physics(EnvRecordLayout L, double* rec,
-                                                const double* ctrl, int nsub) {
-  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
-  s.rk = rk_storage<T, RK, NC>();
-  const DevModel<T>& M = myo_cmodel<T>();
-  const TaskDev& K = c_task;
-  const int env = blockIdx.x;
-  env_physics<T, RK ? 1 : 0>(M, K, L, rec + (size_t)env * L.stride, s, env, ctrl, nsub);
-}
-template <typename T, bool RK, int NC>
-__global__ void __launch_bounds__(64, 2) k_dump(EnvRecordLayout L, double* rec, const double* ctrl,
-                                             DumpLayout D, double* out) {
-  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
-  s.rk = rk_storage<T, RK, NC>();
-  const DevModel<T>& M = myo_cmodel<T>();
-  const TaskDev& K = c_task;
-  const int env = blockIdx.x;
-  env_forward_dump<T>(M, K, L, rec + (size_t)env * L.stride, s, env, ctrl, D, out);
-}
-// the contact and muscle read-out (csrc/myo_sense.h): one forward pass at the env's present state, nothing written back to the record
-template <typename T, int NC>
-__global__ void __launch_bounds__(64, 2) k_sense(EnvRecordLayout L, double* rec, SenseDev O) {
-  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
-  s.rk = nullptr;
-  const DevModel<T>& M = myo_cmodel<T>();
-  const TaskDev& K = c_task;
-  const int env = blockIdx.x;
-  env_sense<T>(M, K, L, rec + (size_t)env * L.stride, s, env, O);
-}
-template <typename T, bool RK, int NC>
-__global__ void __launch_bounds__(64, 2) k_wrap_census(EnvRecordLayout L, double* rec, int* cnt) {
-  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
-  s.rk = rk_storage<T, RK, NC>();
-  const DevModel<T>& M = myo_cmodel<T>();
-  const TaskDev& K = c_task;
-  const int env = blockIdx.x;
-  env_wrap_census<T>(M, K, L, rec + (size_t)env * L.stride, s, env, cnt);
-}
-// render item pass (csrc/myo_render.h: GeomPass, TendonPass, ContactPass): row r of `out` = the P.rows items of env env_idx[r]; a listed
-// index outside [0, n_envs) gets an all-zero row (nothing drawn).  Keyed like k_sense, arithmetic x contact capacity: no pass integrates
-// (load_env, kinematics and the env_* passes never read s.rk).
-template <typename T, int NC, typename Pass>
-__global__ void __launch_bounds__(64, 2) k_items(EnvRecordLayout L, double* rec, const int* __restrict__ env_idx, int n_envs, Pass P, double* out) {
-  Scratch<T, NC>& s = *reinterpret_cast<Scratch<T, NC>*>(myo_lds);
-  s.rk = nullptr;
-  const DevModel<T>& M = myo_cmodel<T>();
-  const TaskDev& K = c_task;
-  const int env = env_idx[blockIdx.x], n = P.rows * MYO_RENDER_ITEM_N;
-  double* o = out + (size_t)blockIdx.x * n;
-  if (env < 0 || env >= n_envs) {
-    for (int i = threadIdx.x; i < n; i += 64) o[i] = 0.0;
-    return;
-  }
-  pass_run(P, M, K, L, rec + (size_t)env * L.stride, s, env, (int)blockIdx.x, o);
+  job_run(J, KernelVariant<T, RK, NC>{}, M, K, L, rec, s, (int)blockIdx.x, n_envs);
 }
 // render ray cast: workgroup (tile, env row) of 256 threads, one pixel each; the item table in dynamic LDS
 __global__ void __launch_bounds__(MYO_RTILE * MYO_RTILE) k_render(const double* __restrict__ items, int nitem, const double* __restrict__ cams,
@@ -462,7 +387,6 @@ static unsigned lds_dyn(const myo_batch* b) {
 }
 #define BIND_OR_RETURN(b, st) DeviceGuard _guard((b)->device); { int _rc = bind_constants(b, st); if (_rc) return _rc; }
 
-
 // ---- the backend functions myo_host.h declares (myo_batch_create / _destroy call them)
 static int be_batch_workspaces(myo_batch* b, int n_envs, int device) {
   (void)n_envs;
@@ -545,49 +469,44 @@ static void be_task_changed(myo_batch* b) {
   unbind(b, b->device);              // the task block in __constant__ memory is re-uploaded at the next launch
 }
 
-extern "C" int myo_batch_bind_constants(myo_batch* b, void* stream) {
-  if (int rc = batch_check(b)) return rc;
+static int be_bind(myo_batch* b, void* stream) {
   DeviceGuard guard(b->device);
   return bind_constants(b, (hipStream_t)stream);
 }
-
-// census of the wraps over the envs' present states, then the new order (both on the stream: usable between any two steps, also while
-// a graph of steps exists — the tables are rewritten in place)
+// k_env over a job (the device is current and the constants are bound)
+template <typename Job>
+static void env_launch(myo_batch* b, const Job& J, int nblocks, hipStream_t st) {
+  with_variant(b, [&](auto v) {
+    using V = decltype(v);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_env<typename V::T, V::RK && Job::RK, V::NC, Job>), dim3(nblocks), dim3(64), lds_dyn(b), st, b->L, b->rec, J, b->n);
+  });
+}
+template <typename Job>
+static int be_run(myo_batch* b, const Job& J, int nblocks, void* stream, int timed) {
+  hipStream_t st = (hipStream_t)stream;
+  BIND_OR_RETURN(b, st)
+  if (timed) timing_begin(b, st);
+  env_launch(b, J, nblocks, st);
+  if (timed) timing_end(b, st);
+  return be_launch_status();
+}
 static void wrap_order_launch(myo_batch* b, hipStream_t st) {
   if (!b->wrap_cnt) return;
   int* gw = const_cast<int*>(b->dtype == MYO_F64 ? b->Md.gw_elem.p : b->Mf.gw_elem.p);
   int* wr = const_cast<int*>(b->dtype == MYO_F64 ? b->Md.wr_i.p : b->Mf.wr_i.p);
   const int ngw = b->dtype == MYO_F64 ? b->Md.ngw : b->Mf.ngw;
-  with_variant(b, [&](auto v) {
-    using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wrap_census<typename V::T, V::RK, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, b->wrap_cnt);
-  });
+  env_launch(b, CensusJob{b->wrap_cnt}, b->n, st);
   hipLaunchKernelGGL(k_wrap_reorder, dim3(1), dim3(64), 0, st, ngw, b->wrap_cnt, gw, wr);
 }
-extern "C" int myo_batch_tune_wrap_order(myo_batch* b, void* stream) {
-  if (int rc = batch_check(b)) return rc;
+static int be_wrap_order(myo_batch* b, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
   wrap_order_launch(b, st);
   return be_launch_status();
 }
 
-extern "C" int myo_batch_reset(myo_batch* b, const uint8_t* mask, float* obs, void* stream) {
-  if (int rc = reset_check(b)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  BIND_OR_RETURN(b, st)
-  with_variant(b, [&](auto v) {
-    using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reset<typename V::T, V::RK, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, mask, obs);
-  });
-  if (int rc = be_launch_status()) return rc;
-  if (!mask) { wrap_order_launch(b, st); b->wrap_tune_in = 16; }       // a reset of every env: the wrap order from the reset states, again 16 steps on
-  return be_launch_status();
-}
-
-extern "C" int myo_batch_step(myo_batch* b, const float* act, float* obs, float* rew, uint8_t* done, uint8_t* trunc,
-                              float* term_obs, float* comps, float* ep_info, void* stream) {
-  if (int rc = step_check(b, act, obs, rew, done)) return rc;
+static int be_step(myo_batch* b, const float* act, float* obs, float* rew, uint8_t* done, uint8_t* trunc, float* term_obs, float* comps,
+                   float* ep_info, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   BIND_OR_RETURN(b, st)
   timing_begin(b, st);
@@ -607,11 +526,7 @@ extern "C" int myo_batch_step(myo_batch* b, const float* act, float* obs, float*
   return be_launch_status();
 }
 
-// test hook: put the step plan's generation counter (and every env's state, consistently) at `gen` — the counter wraps after
-// 2^28 steps and the protocol's arithmetic is modulo 2^32 (tests/test_step_parts.py steps across the wrap)
-extern "C" int myo_batch_set_step_generation(myo_batch* b, unsigned int gen) {
-  if (int rc = batch_check(b)) return rc;
-  if (!b->part_state) return MYO_OK;
+static int be_set_step_generation(myo_batch* b, unsigned int gen) {
   DeviceGuard guard(b->device);
   std::vector<int> st((size_t)b->n, (int)(16u * gen));
   const int g4[4] = {(int)gen, 0, 0, 0};
@@ -619,23 +534,14 @@ extern "C" int myo_batch_set_step_generation(myo_batch* b, unsigned int gen) {
     return fail(MYO_E_DEVICE, "myo_batch_set_step_generation: copy failed");
   return MYO_OK;
 }
-
-// Health counters of a batch (synchronises the device).  out[0]: k_step workgroups that found their env's hand-off state in another
-// generation than the launch's (see the protocol comment at k_step); out[1]: substeps in which an env had more contacts than its
-// scratch holds (the surplus was dropped); out[2]: the same for limit rows; out[3]: the most contact slots such a substep asked for.  All 0 in a healthy batch.
-extern "C" int myo_batch_health(myo_batch* b, int out[4]) {
-  int empty = 0;
-  int rc = health_check(b, out, &empty);
-  if (rc || empty) return rc;
+static int be_health(myo_batch* b, int out[4]) {
   DeviceGuard guard(b->device);
   if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, b->K.health, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
     return fail(MYO_E_DEVICE, "myo_batch_health: copy failed");
   return MYO_OK;
 }
 
-// Device check of what the per-slot workspace rests on (myo_wave_slot, wave.h): `n_workgroups` one-wave workgroups with `lds_bytes` of
-// dynamic LDS (k_step's footprint: the same residency) each take their slot's occupancy counter, stay for ~20 us, and leave.
-// out[0]: workgroups that found their slot occupied (must be 0); out[1]: distinct slots seen; out[2]: largest slot index; out[3]: bit mask of XCC ids.
+// the probe of myo_debug_wave_slots (csrc/myo_host.h)
 __global__ void __launch_bounds__(64, 2) k_wave_slot_probe(int* occ, int* seen, int* out) {
   if (threadIdx.x != 0) return;
   const unsigned slot = myo_wave_slot(0);
@@ -647,8 +553,7 @@ __global__ void __launch_bounds__(64, 2) k_wave_slot_probe(int* occ, int* seen, 
   while (wall_clock64() - t0 < 2000ull) __builtin_amdgcn_s_sleep(8);
   atomicSub(occ + slot, 1);
 }
-extern "C" int myo_debug_wave_slots(int device, int n_workgroups, int lds_bytes, int32_t out[4]) {
-  if (!out || n_workgroups <= 0 || lds_bytes < 0 || lds_bytes > 65536) return fail(MYO_E_ARG, "bad argument");
+static int be_wave_slots(int device, int n_workgroups, int lds_bytes, int32_t out[4]) {
   DeviceGuard guard(device);
   int *occ = nullptr, *seen = nullptr, *o = nullptr;
   const size_t nb = sizeof(int) * (size_t)MYO_WAVE_SLOTS;
@@ -665,135 +570,26 @@ extern "C" int myo_debug_wave_slots(int device, int n_workgroups, int lds_bytes,
   return MYO_OK;
 }
 
-extern "C" int myo_batch_step_inner(myo_batch* b, const uint8_t* mask, const float* act, float* obs, uint8_t* done, void* stream) {
-  if (int rc = step_inner_check(b, act, obs)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  BIND_OR_RETURN(b, st)
-  with_variant(b, [&](auto v) {
-    using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step_inner<typename V::T, V::RK, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, mask, act, obs, done);
-  });
-  return be_launch_status();
-}
-
-// Compact form of myo_batch_step_inner: the envs idx[0 .. n_idx) (dev int32; -1 = empty slot) take one unwrapped env step with
-// row r of act [n_idx, nu]; row r of obs [n_idx, obs_dim] and done [n_idx] (may be NULL) receive env idx[r]'s results.  An env
-// must not be listed twice.  MixtureModelBaodingEnv's base phase runs the few envs that were just reset this way.
-extern "C" int myo_batch_step_inner_idx(myo_batch* b, const int* idx, int n_idx, const float* act, float* obs, uint8_t* done, void* stream) {
-  if (int rc = step_inner_idx_check(b, idx, n_idx, act, obs)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  BIND_OR_RETURN(b, st)
-  with_variant(b, [&](auto v) {
-    using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step_inner_idx<typename V::T, V::RK, V::NC>), dim3(n_idx), dim3(64), lds_dyn(b), st, b->L, b->rec, idx, b->n, act, obs, done);
-  });
-  return be_launch_status();
-}
-
-// Whole env records from one batch into another (same model, same task kind): dst env dst_idx[r] <- src env src_idx[r], r < k.
-// The record is everything an env is between two steps (state, warm start, task scalars, per-episode draws, counters), so the
-// destination env continues exactly where the source env stood.  MixtureModelBaodingEnv hands pre-played episodes (reset + base
-// phase, done in bulk on a pool batch) to the envs that have just finished.
 __global__ void k_copy_envs(double* dst, const int* __restrict__ dst_idx, int n_dst, const double* src, const int* __restrict__ src_idx, int n_src, int stride) {
   const int d = dst_idx[blockIdx.x], s = src_idx[blockIdx.x];
   if (d < 0 || d >= n_dst || s < 0 || s >= n_src) return;
   for (int i = threadIdx.x; i < stride; i += blockDim.x) dst[(size_t)d * stride + i] = src[(size_t)s * stride + i];
 }
-extern "C" int myo_batch_copy_envs(myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, void* stream) {
-  int empty = 0;
-  int rc = copy_envs_check(dst, dst_idx, src, src_idx, k, &empty);
-  if (rc || empty) return rc;
+static int be_copy_envs(myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, void* stream) {
   DeviceGuard guard(dst->device);
   hipLaunchKernelGGL(k_copy_envs, dim3(k), dim3(64), 0, (hipStream_t)stream, dst->rec, dst_idx, dst->n, src->rec, src_idx, src->n, dst->L.stride);
   return be_launch_status();
 }
 
-extern "C" int myo_batch_physics_step(myo_batch* b, const double* ctrl, int nsub, void* stream) {
-  if (int rc = physics_step_check(b, nsub)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  BIND_OR_RETURN(b, st)
-  timing_begin(b, st);
-  with_variant(b, [&](auto v) {
-    using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_physics<typename V::T, V::RK, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, nsub);
-  });
-  timing_end(b, st);
-  return be_launch_status();
-}
-
-extern "C" int myo_batch_forward_dump(myo_batch* b, const double* ctrl, double* out, void* stream) {
-  if (int rc = forward_dump_check(b, out)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  BIND_OR_RETURN(b, st)
-  with_variant(b, [&](auto v) {      // RK = false whatever the integrator: forward dynamics integrate nothing, so k_dump has no RK4 variants
-    using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dump<typename V::T, false, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, ctrl, b->D, out);
-  });
-  return be_launch_status();
-}
-
-extern "C" int myo_batch_sense(myo_batch* b, const myo_sense_out* out, void* stream) {
-  if (int rc = sense_check(b, out)) return rc;
-  const SenseDev O = sense_dev(b, out);
-  hipStream_t st = (hipStream_t)stream;
-  BIND_OR_RETURN(b, st)
-  with_variant(b, [&](auto v) {
-    using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sense<typename V::T, V::NC>), dim3(b->n), dim3(64), lds_dyn(b), st, b->L, b->rec, O);
-  });
-  return be_launch_status();
-}
-
-template <typename Pass>
-static void items_launch(myo_batch* b, const int32_t* env_idx, int k, const Pass& P, double* out, hipStream_t st) {
-  with_variant(b, [&](auto v) {
-    using V = decltype(v);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_items<typename V::T, V::NC, Pass>), dim3(k), dim3(64), lds_dyn(b), st, b->L, b->rec, env_idx, b->n, P, out);
-  });
-}
-extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
-  int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses");
-  if (rc) return rc;
-  if (!out) return fail(MYO_E_ARG, "myo_batch_geom_poses: null output");
-  hipStream_t st = (hipStream_t)stream;
-  BIND_OR_RETURN(b, st)
-  items_launch(b, env_idx, k, geom_pass(b), out, st);
-  return be_launch_status();
-}
-extern "C" int myo_batch_tendon_paths(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
-  int rc = items_check(b, env_idx, k, out, "myo_batch_tendon_paths");
-  if (rc || k == 0 || b->ntitem == 0) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  BIND_OR_RETURN(b, st)
-  items_launch(b, env_idx, k, tendon_pass(b), out, st);
-  return be_launch_status();
-}
-extern "C" int myo_batch_contact_items(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
-  int rc = items_check(b, env_idx, k, out, "myo_batch_contact_items");
-  if (rc || k == 0) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  BIND_OR_RETURN(b, st)
-  if ((rc = render_workspace(b, contact_tmp_doubles(b, k)))) return rc;
-  items_launch(b, env_idx, k, contact_pass(b, k, b->render_ws), out, st);
-  return be_launch_status();
-}
-extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, const myo_render_camera* cams, int ncams, int width, int height,
-                                int flags, uint8_t* rgb, float* depth, int32_t* segid, void* stream) {
-  std::vector<double> cam_tab;
-  int rc = render_check(b, env_idx, k, cams, ncams, width, height, flags, rgb, depth, segid, cam_tab);
-  if (rc) return rc;
-  if (k > 65535) return fail(MYO_E_ARG, "myo_batch_render: at most 65535 envs per call");
-  hipStream_t st = (hipStream_t)stream;
-  BIND_OR_RETURN(b, st)
-  const RenderPlan p = render_plan(b, k, flags, cam_tab.size());
-  if ((rc = render_workspace(b, p.total))) return rc;
-  double* ws = b->render_ws;
+static int be_camera_upload(myo_batch* b, double* dst, std::vector<double>& cam_tab, void* stream) {
   b->cam_host.swap(cam_tab);      // (kept until the next call: the asynchronous copy reads it)
-  hipError_t e = hipMemcpyAsync(ws + p.cams, b->cam_host.data(), b->cam_host.size() * sizeof(double), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return fail(MYO_E_DEVICE, "myo_batch_render: camera upload failed: %s", hipGetErrorString(e));
-  items_launch(b, env_idx, k, geom_pass(b), ws, st);
-  if (p.ntitem > 0) items_launch(b, env_idx, k, tendon_pass(b), ws + p.tendons, st);
-  if (p.ncitem > 0) items_launch(b, env_idx, k, contact_pass(b, k, ws + p.tmp), ws + p.contacts, st);
+  const hipError_t e = hipMemcpyAsync(dst, b->cam_host.data(), b->cam_host.size() * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream);
+  return e == hipSuccess ? MYO_OK : fail(MYO_E_DEVICE, "myo_batch_render: camera upload failed: %s", hipGetErrorString(e));
+}
+static int be_cast(myo_batch* b, const RenderPlan& p, int k, int ncams, int width, int height, int flags, uint8_t* rgb, float* depth,
+                   int32_t* segid, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const double* ws = b->render_ws;
   const dim3 grid((unsigned)(((width + MYO_RTILE - 1) / MYO_RTILE) * ((height + MYO_RTILE - 1) / MYO_RTILE)), (unsigned)k);
   const unsigned lds = (unsigned)(p.nmax * sizeof(RItem));
   if (p.layered) {
@@ -804,8 +600,7 @@ extern "C" int myo_batch_render(myo_batch* b, const int32_t* env_idx, int k, con
   return be_launch_status();
 }
 
-extern "C" double myo_batch_kernel_ms(myo_batch* b) {
-  if (!b) return -1.0;
+static double be_kernel_ms(myo_batch* b) {
   double sum = 0;
   int cnt = 0;
   for (auto& pr : b->pending) {

@@ -6,5 +6,7 @@
 #define MYO_BACKEND_NAME "MYO_EMU lane-serial test build"
 #define MYO_BACKEND_DENSE_NEWTON 1
 #define MYO_BACKEND_BATCH_FIELDS
+#define MYO_BACKEND_RENDER_ENVS_MAX 0x7fffffff
+struct DeviceGuard { explicit DeviceGuard(int) {} };      // (one device: the host)
 #include "myo_host.h"
 #include "emu_host.h"

@@ -535,6 +535,54 @@ def case_step_inner(lib, mj, dtype, tol, nsteps=12):
     b.close()
 
 
+def case_env_lists(lib, mj, dtype):
+    """Where a block-to-env mapping can go wrong: row against env, the early return before the env is loaded, the all-zero row.
+    Batch A: step_inner(mask = [1, 0, 1]).  Batch B (same seed, same reset): step_inner_idx(idx = [2, -1, 0, 3]) on four rows with obs and
+    done pre-filled with a sentinel.  Rows 0 and 2 of B are A's envs 2 and 0 bit for bit, rows 1 and 3 keep the sentinel, state and warm
+    start of all three envs are bit-equal (env 1 untouched in both), health is all zero.  The same list through geom_poses and
+    contact_items: the rows of -1 and 3 are all zero, the others are the rows of the full list."""
+    mem = Mem(lib)
+    cm, om, _ = oracle_for(mj)
+    n, idx = 3, np.array([2, -1, 0, 3], np.int32)
+    act = np.clip(np.random.RandomState(4).normal(0, 0.3, (n, om.nu)), -1, 1).astype(np.float32)
+    model = native.Model(cm, lib)
+
+    def start():
+        b = native.Batch(model, make_task_cfg("CustomMyoBaodingBallsP1", cm), n, 0, 9, dtype)
+        b.reset(None, mem.zeros((n, b.obs_dim), np.float32))
+        return b
+
+    def state(b):
+        qp, qv, ac, tt, w = mem.zeros((n, om.nq)), mem.zeros((n, om.nv)), mem.zeros((n, om.na)), mem.zeros(n), mem.zeros((n, om.nv))
+        b.get_state(qp, qv, ac, tt); b.warmstart(w, None)
+        return [mem.host(x).copy() for x in (qp, qv, ac, tt, w)]
+
+    a, b = start(), start()
+    nobs = a.obs_dim
+    before = state(a)
+    obs_a, done_a = mem.arr(np.full((n, nobs), 7.0), np.float32), mem.arr(np.full(n, 9), np.uint8)
+    a.step_inner(mem.arr(np.array([1, 0, 1]), np.uint8), mem.arr(act, np.float32), obs_a, done_a)
+    obs_b, done_b = mem.arr(np.full((4, nobs), 7.0), np.float32), mem.arr(np.full(4, 9), np.uint8)
+    rows = np.zeros((4, om.nu), np.float32); rows[0], rows[2] = act[2], act[0]
+    b.step_inner_idx(mem.arr(idx, np.int32), mem.arr(rows, np.float32), obs_b, done_b)
+    oa, da, ob, db = (mem.host(x).copy() for x in (obs_a, done_a, obs_b, done_b))
+    assert np.array_equal(ob[0], oa[2]) and np.array_equal(ob[2], oa[0]) and db[0] == da[2] and db[2] == da[0]
+    assert not (oa[[0, 2]] == 7.0).all(1).any() and da[0] != 9 and da[2] != 9              # (the steps did write)
+    assert (ob[[1, 3]] == 7.0).all() and (db[[1, 3]] == 9).all() and (oa[1] == 7.0).all() and da[1] == 9
+    sa, sb = state(a), state(b)
+    for x, y, z in zip(sa, sb, before):
+        assert np.array_equal(x, y) and np.array_equal(x[1], z[1]) and not np.array_equal(x[0], z[0])
+    assert not any(a.health().values()) and not any(b.health().values())
+    for call, rows_per_env in ((b.geom_poses, model.size("ngeom") + model.size("nsite")), (b.contact_items, 2 * b.contact_capacity)):
+        full, part = mem.zeros((n, rows_per_env, native.RENDER_ITEM_N)), mem.arr(np.full((4, rows_per_env, native.RENDER_ITEM_N), 7.0))
+        call(mem.arr(np.arange(n), np.int32), full)
+        call(mem.arr(idx, np.int32), part)
+        hf, hp = mem.host(full), mem.host(part)
+        assert hf.any() and np.array_equal(hp[0], hf[2]) and np.array_equal(hp[2], hf[0]) and not hp[[1, 3]].any()
+    assert not any(b.health().values())
+    a.close(); b.close()
+
+
 # ---------------------------------------------------------------- die reorient (SURVEY.md §8f-1)
 def reorient_oracle_cfg(cm, tcfg):
     from myochallenge_amd.envs.reorient import reorient_ids

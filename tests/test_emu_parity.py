@@ -103,6 +103,11 @@ def test_step_inner_against_oracle(emu_lib, models):
     pc.case_step_inner(emu_lib, models["hand"], native.MYO_F64, 1e-9)
 
 
+@pytest.mark.parametrize("dtype", ["f64", "mixed"])
+def test_env_lists(emu_lib, models, dtype):
+    pc.case_env_lists(emu_lib, models["hand"], native.MYO_F64 if dtype == "f64" else native.MYO_MIXED)
+
+
 def test_p2_ball_physics_against_oracle(emu_lib, models):
     pc.case_p2_ball_physics(emu_lib, models["hand"], native.MYO_F64, 1e-9, nsteps=25)
 

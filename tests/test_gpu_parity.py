@@ -188,6 +188,11 @@ def test_step_inner_against_oracle(hip_lib, models):
     pc.case_step_inner(hip_lib, models["hand"], native.MYO_MIXED, 1e-4)
 
 
+@pytest.mark.parametrize("dtype", ["f64", "mixed"])
+def test_env_lists(hip_lib, models, dtype):
+    pc.case_env_lists(hip_lib, models["hand"], native.MYO_F64 if dtype == "f64" else native.MYO_MIXED)
+
+
 def test_blown_up_env_is_contained(hip_lib, models):
     pc.case_bad_state(hip_lib, models["hand"], native.MYO_F64)
     pc.case_bad_state(hip_lib, models["hand"], native.MYO_MIXED)
