@@ -95,7 +95,14 @@ typedef struct myo_task_cfg {
   double pose_target_value[MYO_POSE_NQ_MAX];               /* target_type fixed: target_jnt_value */
   double pose_target_range[MYO_POSE_NQ_MAX][2];            /* target_type generate: target_jnt_range (low, high) per joint */
   double pose_reset_range[MYO_POSE_NQ_MAX][2];             /* reset_type random: the model's jnt_range */
+  /* -- every kind: the `muscle_condition` kwarg of MyoSuite's BaseV0._setup [3P-RECALL], MYO_MUSCLE_* below.  0 = none: the step is
+   * what it was before the fields existed.  reaf_src / reaf_dst: the actuators EIP / EPL of 'reafferentation' (ctrl[dst] maps
+   * action[src], ctrl[src] = 0).  fatigue_F / _R / _r: the rates of the 3CC-r model of 'fatigue' (MyoSuite's defaults: 0.00912,
+   * 0.000094, 150).  'sarcopenia' is a model edit made before the model is compiled and has no field here. */
+  int32_t muscle_condition, reaf_src, reaf_dst;
+  double fatigue_F, fatigue_R, fatigue_r;
 } myo_task_cfg;
+enum { MYO_MUSCLE_NONE = 0, MYO_MUSCLE_FATIGUE = 1, MYO_MUSCLE_REAFFERENTATION = 2 };
 
 /* -- model ------------------------------------------------------------------------------
  * replaces gym.make(..., model_path=...) -> mj_loadModel (src/envs/__init__.py:17,63).
@@ -221,6 +228,14 @@ int myo_batch_set_object_group(myo_batch* b, int gid0, int gidn);
  * builds condim-3 contacts only, which read the sliding coefficient [.,.,0]; a MYO_TASK_REORIENT reset draws all three
  * per geom in the reference's order and keeps the sliding one (the other two slots stay at the model's values). */
 int myo_batch_object_friction(myo_batch* b, const double* set_fric, double* get_fric, void* stream);
+
+/* Muscle fatigue state of a batch made with muscle_condition = MYO_MUSCLE_FATIGUE: dev double[N, 3, nu], per env the active, resting
+ * and fatigued fractions MA[nu], MR[nu], MF[nu] of the 3CC-r model (MyoSuite's CumulativeFatigue [3P-RECALL]; the update rule is
+ * fatigue_advance in csrc/myo_task.h).  The state is part of the env's record: always fp64, (0, 1, 0) after every reset of the env
+ * (myo_batch_reset, the auto-reset of myo_batch_step, the recovery of a blown-up env), advanced once per env step by myo_batch_step /
+ * _step_inner / _step_inner_idx from the step's action — ctrl = MA — left alone by myo_batch_physics_step, copied by
+ * myo_batch_copy_envs.  Either pointer may be NULL (set, then get).  A batch without fatigue returns MYO_E_ARG with a message. */
+int myo_batch_fatigue(myo_batch* b, const double* set_state, double* get_state, void* stream);
 
 /* The model / task parameters of ONE batch per device sit in __constant__ memory; every launching entry point
  * re-uploads them (on its stream) when another batch used the device in between.  A caller that REPLAYS a

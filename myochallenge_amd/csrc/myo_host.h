@@ -1162,6 +1162,8 @@ static void make_taskdev(const myo_task_cfg* c, uint64_t seed, TaskDev& K) {
   memcpy(K.beta_ball_mass, c->beta_ball_mass, 16); memcpy(K.obj_size_range, c->obj_size_range, 16);
   memcpy(K.obj_mass_range, c->obj_mass_range, 16); memcpy(K.obj_friction_change, c->obj_friction_change, 24);
   K.init_qpos0 = c->init_qpos0;
+  K.muscle_condition = c->muscle_condition; K.reaf_src = c->reaf_src; K.reaf_dst = c->reaf_dst;
+  K.fatigue_F = c->fatigue_F; K.fatigue_R = c->fatigue_R; K.fatigue_r = c->fatigue_r;
   if (c->kind == MYO_TASK_REORIENT) {
     // the Baoding per-ball overrides (mass / size / friction by body and geom id) must not fire: the die is the object GROUP
     K.ro_obj_bid = c->obj1_bid; K.objg_gid0 = c->obj1_gid; K.objg_gidn = c->obj2_gid;
@@ -1181,6 +1183,26 @@ static void make_taskdev(const myo_task_cfg* c, uint64_t seed, TaskDev& K) {
   }
 }
 static_assert(MYO_TASK_REORIENT == MYO_TASK_REORIENT_K && MYO_TASK_POSE == MYO_TASK_POSE_K, "task kind ids");
+static_assert(MYO_MUSCLE_FATIGUE == MYO_MUSCLE_FATIGUE_K && MYO_MUSCLE_REAFFERENTATION == MYO_MUSCLE_REAF_K, "muscle condition ids");
+// the muscle_condition fields of a task cfg against the model (include/myobatch.h); a cfg without a task layer has no action map to condition
+static int muscle_condition_check(const myo_model* m, const myo_task_cfg* cfg) {
+  const int mc = cfg ? cfg->muscle_condition : MYO_MUSCLE_NONE;
+  if (mc == MYO_MUSCLE_NONE) return MYO_OK;
+  if (mc != MYO_MUSCLE_FATIGUE && mc != MYO_MUSCLE_REAFFERENTATION) return fail(MYO_E_ARG, "unknown muscle_condition %d", mc);
+  if (cfg->kind == MYO_TASK_NONE) return fail(MYO_E_ARG, "muscle_condition needs a task layer (it acts between the action and ctrl)");
+  if (mc == MYO_MUSCLE_REAFFERENTATION) {
+    if (cfg->reaf_src < 0 || cfg->reaf_src >= m->nu || cfg->reaf_dst < 0 || cfg->reaf_dst >= m->nu || cfg->reaf_src == cfg->reaf_dst)
+      return fail(MYO_E_ARG, "reafferentation: reaf_src / reaf_dst must be two different actuators of the model (nu = %d)", m->nu);
+    return MYO_OK;
+  }
+  if (!(std::isfinite(cfg->fatigue_F) && cfg->fatigue_F >= 0 && std::isfinite(cfg->fatigue_R) && cfg->fatigue_R >= 0 && std::isfinite(cfg->fatigue_r) && cfg->fatigue_r >= 0))
+    return fail(MYO_E_ARG, "fatigue: fatigue_F, fatigue_R and fatigue_r must be finite and >= 0");
+  if (m->nu > 64) return fail(MYO_E_UNSUPPORTED, "fatigue: one lane per actuator, at most 64");
+  for (int i = 0; i < m->nu; ++i)
+    if (!(m->actuator_dynprm[10 * (size_t)i] > 0 && m->actuator_dynprm[10 * (size_t)i + 1] > 0))
+      return fail(MYO_E_UNSUPPORTED, "fatigue: actuator %d has no activation / deactivation time constants (dynprm[0], dynprm[1] > 0): not a muscle", i);
+  return MYO_OK;
+}
 static int task_nobs_host(const myo_task_cfg* c, int na) {
   if (c->kind == MYO_TASK_POSE) return 3 * c->n_hand;
   return c->kind == MYO_TASK_REORIENT ? 2 * c->n_hand + 18 + na : c->n_hand + 24 + na;
@@ -1218,6 +1240,7 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
     }
     if (cfg->frame_skip <= 0 || cfg->max_episode_steps <= 0) return fail(MYO_E_ARG, "frame_skip / max_episode_steps");
   }
+  if (int mrc = muscle_condition_check(m, cfg)) return mrc;
   int rc = be_set_device(device);
   if (rc) return fail(MYO_E_DEVICE, "hipSetDevice(%d): %s", device, be_errstr(rc));
   myo_batch* b = new myo_batch();
@@ -1242,6 +1265,8 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
   L.off_time = o; o += 1; L.off_taskd = o; o += MYO_TASKD_N; L.off_balld = o; o += MYO_BALLD_N; L.off_misc = o; o += MYO_MISC_N;
   L.off_objfric = o; o += 3 * MYO_OBJG_MAX;
   L.off_pose = o; if (b->K.kind == MYO_TASK_POSE) o += 2 * m->nq;     // (the other kinds' records keep their size)
+  const bool fatigue = b->K.muscle_condition == MYO_MUSCLE_FATIGUE;
+  b->K.fat_off = o; if (fatigue) o += 3 * m->nu;                      // (a batch without fatigue keeps its record's size)
   // (store_env writes qpos | qvel | act | warm | time as one run: the order above is part of the kernels' contract)
   if (L.off_qvel != L.off_qpos + m->nq || L.off_act != L.off_qvel + m->nv || L.off_warm != L.off_act + m->na || L.off_time != L.off_warm + m->nv) { delete b; return fail(MYO_E_STATE, "record layout"); }
   L.stride = (o + 15) / 16 * 16;      // whole 128-byte lines per env: no line is shared by two workgroups
@@ -1259,6 +1284,7 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
     double* r = &host[(size_t)e * L.stride];
     for (int i = 0; i < m->nq; ++i) r[L.off_qpos + i] = m->qpos0[i];
     double* td = r + L.off_taskd; double* bd = r + L.off_balld; double* mi = r + L.off_misc;
+    if (fatigue) for (int i = 0; i < m->nu; ++i) r[b->K.fat_off + m->nu + i] = 1.0;      // rested muscles: (MA, MR, MF) = (0, 1, 0)
     td[0] = 3.0 * MYO_PI / 4.0; td[1] = -MYO_PI / 4.0; td[2] = 0.025; td[3] = 0.028; td[4] = 5.0;
     mi[0] = MYO_WHICH_CCW;
     if (b->K.kind == MYO_TASK_REORIENT) {
@@ -1293,6 +1319,15 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
   if (!rc) rc |= be_h2d(p, host.data(), host.size() * sizeof(double));
   b->rec = (double*)p;
   b->allocs.push_back(p);
+  if (fatigue) {                   // the muscles' time constants in fp64, whatever the stepper's arithmetic (fatigue_ctrl, csrc/myo_task.h)
+    std::vector<double> tau(2 * (size_t)m->nu);
+    for (int i = 0; i < m->nu; ++i) { tau[2 * i] = m->actuator_dynprm[10 * (size_t)i]; tau[2 * i + 1] = m->actuator_dynprm[10 * (size_t)i + 1]; }
+    void* tp = nullptr;
+    rc |= be_malloc(&tp, tau.size() * sizeof(double));
+    if (!rc) rc |= be_h2d(tp, tau.data(), tau.size() * sizeof(double));
+    b->K.fatigue_tau = (const double*)tp;
+    if (tp) b->allocs.push_back(tp);
+  }
   {                                // health counters (myo_batch_health), zeroed
     void* hc = nullptr;
     const int zero4[4] = {0, 0, 0, 0};
@@ -1551,6 +1586,12 @@ extern "C" int myo_batch_object_friction(myo_batch* b, const double* set_fric, d
   be_xfer(b, b->L.off_objfric, cnt, (double*)set_fric, 0, stream); be_xfer(b, b->L.off_objfric, cnt, get_fric, 1, stream);
   return be_launch_status();
 }
+extern "C" int myo_batch_fatigue(myo_batch* b, const double* set_state, double* get_state, void* stream) {
+  if (int rc = batch_check(b)) return rc;
+  if (b->K.muscle_condition != MYO_MUSCLE_FATIGUE) return fail(MYO_E_ARG, "myo_batch_fatigue: the batch was made without muscle_condition = MYO_MUSCLE_FATIGUE");
+  be_xfer(b, b->K.fat_off, 3 * b->nu, (double*)set_state, 0, stream); be_xfer(b, b->K.fat_off, 3 * b->nu, get_state, 1, stream);
+  return be_launch_status();
+}
 extern "C" int myo_batch_enable_timing(myo_batch* b, int on) {
   if (int rc = batch_check(b)) return rc;
   b->timing = on;
@@ -1624,8 +1665,9 @@ extern "C" int myo_batch_step_inner_idx(myo_batch* b, const int* idx, int n_idx,
 // phase, done in bulk on a pool batch) to the envs that have just finished.  k = 0 is an empty copy.
 extern "C" int myo_batch_copy_envs(myo_batch* dst, const int* dst_idx, const myo_batch* src, const int* src_idx, int k, void* stream) {
   if (!dst || !src || !dst_idx || !src_idx || k < 0) return fail(MYO_E_ARG, "myo_batch_copy_envs: null argument");
-  if (dst->L.stride != src->L.stride || dst->nq != src->nq || dst->nv != src->nv || dst->na != src->na || dst->K.kind != src->K.kind || dst->device != src->device)
-    return fail(MYO_E_ARG, "myo_batch_copy_envs: the two batches differ in model, task kind or device");
+  if (dst->L.stride != src->L.stride || dst->nq != src->nq || dst->nv != src->nv || dst->na != src->na || dst->K.kind != src->K.kind || dst->device != src->device ||
+      dst->K.muscle_condition != src->K.muscle_condition)
+    return fail(MYO_E_ARG, "myo_batch_copy_envs: the two batches differ in model, task kind, muscle condition or device");
   return k ? be_copy_envs(dst, dst_idx, src, src_idx, k, stream) : MYO_OK;
 }
 extern "C" int myo_batch_physics_step(myo_batch* b, const double* ctrl, int nsub, void* stream) {

@@ -139,6 +139,7 @@ struct EnvRecordLayout {
 // objfric: friction[MYO_OBJG_MAX][3] of the object group's geoms (read only by batches that have a group)
 // balld: mass[2], friction[2][3], size[2]  (10)
 // misc : which_task, counter, elapsed_steps, episode_index, ep_return, ep_len (6, stored as double)
+// fatigue (batches made with muscle_condition fatigue only; at TaskDev::fat_off, behind the pose block): MA[nu], MR[nu], MF[nu] of the 3CC-r model
 #define MYO_TASKD_N 9
 #define MYO_BALLD_N 10
 #define MYO_MISC_N 8      // which_task, counter, elapsed, episode, ep_ret, ep_len, bad (mid-step hand-off only), spare

@@ -86,8 +86,11 @@ __device__ __forceinline__ constexpr int myo_hrow(int i) { const int q = i >> 2;
 #define MYO_ENVWS_N ((MYO_WS_WARM + MYO_NV_MAX + 15) / 16 * 16)
 #define MYO_TASK_REORIENT_K 3   // == MYO_TASK_REORIENT of include/myobatch.h (checked in myobatch.hip)
 #define MYO_TASK_POSE_K 4       // == MYO_TASK_POSE
+#define MYO_MUSCLE_FATIGUE_K 1  // == MYO_MUSCLE_FATIGUE
+#define MYO_MUSCLE_REAF_K 2     // == MYO_MUSCLE_REAFFERENTATION
 struct TaskDev {  // device copy of myo_task_cfg (ids = -1 when there is no task layer)
   int kind, frame_skip, max_episode_steps, n_hand;
+  int muscle_condition, reaf_src, reaf_dst;      // (beside `kind`: the step's action-map phase reads both, one scalar load)
   int obj1_sid, obj2_sid, target1_sid, target2_sid, obj1_bid, obj2_bid, obj1_gid, obj2_gid;
   int objg_gid0, objg_gidn;   // geom group with per-env, per-geom friction (objg_fric) and a size delta (ball_size[0]); empty = -1,-1
   int task_choice, enable_rsi, balls_overlap, limit_init_angle_on, beta_init_angle_on,
@@ -105,6 +108,11 @@ struct TaskDev {  // device copy of myo_task_cfg (ids = -1 when there is no task
   double pose_weights[7], pose_thd, pose_far_th, pose_sds_distance, pose_target_distance;
   int pose_reset_type, pose_target_type;
   double pose_init_qpos[MYO_POSE_NQ_MAX], pose_target_value[MYO_POSE_NQ_MAX], pose_target_range[MYO_POSE_NQ_MAX][2], pose_reset_range[MYO_POSE_NQ_MAX][2];
+  // muscle condition (every kind; include/myobatch.h MYO_MUSCLE_*; the condition and reafferentation's actuators are at the top): fatigue's rates and, per actuator, the
+  // activation / deactivation time constants dynprm[0], dynprm[1] in fp64 whatever the stepper's T (fatigue_tau: double[2 nu], else null)
+  double fatigue_F, fatigue_R, fatigue_r;
+  const double* fatigue_tau;
+  int fat_off;                // env record: doubles from its start to the fatigue block MA[nu], MR[nu], MF[nu] (fatigue only; else the record's end)
   void* rk_ws;                // RkScratch<T>[n_envs] in global memory (RK4 models), else null
   int objf_off;               // env record: doubles from the warm start to the object group's friction triples (Scratch::SPILL reads them in place)
   int* slot_map;              // int[MYO_WS_SLOTS]: owner flags of the workspace blocks (myo_ws_acquire / myo_ws_release, wave.h); emulation: null

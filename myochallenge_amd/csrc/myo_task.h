@@ -244,16 +244,94 @@ DEV int task_nobs(const TaskDev& K, int na) {
   return K.kind == MYO_TASK_REORIENT_K ? 2 * K.n_hand + 18 + na : K.n_hand + 24 + na;
 }
 
+// ---- muscle conditions: the `muscle_condition` kwarg of MyoSuite's BaseV0._setup, restated from MyoSuite 1.x / 2.x [3P-RECALL] — THE
+// one place of this layer that holds the rules; a check against MyoSuite changes task_act_map / fatigue_advance and nothing else.
+//   sarcopenia      : a model edit (gainprm[:, 2] *= 0.5), made on the host before the model is compiled: nothing here
+//   reafferentation : ctrl[EPL] = sigmoid(a[EIP]), ctrl[EIP] = 0 — the action map below, K.reaf_src = EIP, K.reaf_dst = EPL
+//   fatigue         : the 3CC-r cumulative-fatigue model between the muscle map and ctrl (fatigue_advance, fatigue_ctrl)
+// BaseV0.step's muscle map: clip to [-1, 1], then float32 sigmoid(5 (a - 0.5)) (normalize_act)
+DEV float task_act_map(float a) {
+  a = a < -1.f ? -1.f : (a > 1.f ? 1.f : a);
+  // every operation but exp is an IEEE float32 operation; exp is the correctly rounded float32 exponential
+  // (a device expf is 1 ulp off glibc's / numpy's on some arguments: a 6e-8 difference in ctrl, 1e-8 in the
+  // trajectory after 20 env steps)
+  return 1.0f / (1.0f + (float)exp((double)(-5.0f * (a - 0.5f))));
+}
+// One env step of the three-compartment controller with recovery (3CC-r) for one muscle: MA active, MR resting, MF fatigued fractions
+// (MA + MR + MF = 1), TL the target load = the muscle map's output, ta / td the muscle's activation / deactivation time constants
+// (dynprm[0], dynprm[1]), dt = frame_skip * timestep, F / R the fatigue / recovery rates, r the recovery multiplier during rest.  All
+// three increments use the values from before the step.  fp64 in every build.
+DEV void fatigue_advance(double F, double R, double r, double dt, double ta, double td, double TL, double& MA, double& MR, double& MF) {
+  const double LD = (0.5 + 1.5 * MA) / ta, LR = (0.5 + 1.5 * MA) / td;
+  const double need = TL - MA;
+  double C;
+  if (MA < TL) C = MR > need ? LD * need : LD * MR;
+  else C = LR * need;
+  const double rR = MA >= TL ? r * R : R;
+  const double lo1 = -MA / dt + F * MA, lo2 = (MR - 1.0) / dt + rR * MF, hi1 = (1.0 - MA) / dt + F * MA, hi2 = MR / dt + rR * MF;
+  const double lo = lo1 > lo2 ? lo1 : lo2, hi = hi1 < hi2 ? hi1 : hi2;
+  C = C < lo ? lo : C;
+  C = C > hi ? hi : C;
+  const double dA = (C - F * MA) * dt, dR = (-C + rR * MF) * dt, dF = (F * MA - rR * MF) * dt;
+  MA += dA; MR += dR; MF += dF;
+}
+// ctrl of an env step under fatigue; lanes = muscles.  The env's fatigue block is IN ITS RECORD, MA[nu], MR[nu], MF[nu] at rec + K.fat_off
+// (the offset sits with the task constants, as objf_off does: the kernels' arguments are what they were).  The part of a step that starts at substep 0 (advance) moves the state on by the step's action and stores it — written
+// through when the part hands the record to another workgroup (st_pub with the part's s.pub, as store_env does), so it is drained and
+// published with the rest of the record; every later part reads the stored MA as its ctrl and advances nothing.  A leaf of its own: the
+// fp64 arithmetic gets its own register allocation and k_step's body holds one call under a wave-uniform test.
+template <typename T, int NC>
+DEVFN void fatigue_ctrl(const DevModel<T>& M_in, const TaskDev& K_in, Scratch<T, NC>& s_in, const float* action /* may be null = zeros */,
+                        double* rec, int advance) {
+  MYO_BIND_M(T) MYO_BIND_K MYO_BIND_S(T)
+  WAVE_FN
+  const int nu = M.nu;
+  const double dt = (double)K.frame_skip * M.h_timestep;
+  PHASE {
+    const int i = lane;
+    if (i < nu) {
+      auto f = (GPTR(double))rec + K.fat_off;
+      double MA = f[i];
+      if (advance) {
+        double MR = f[nu + i], MF = f[2 * nu + i];
+        const double TL = (double)task_act_map(action ? action[i] : 0.0f);
+        fatigue_advance(K.fatigue_F, K.fatigue_R, K.fatigue_r, dt, K.fatigue_tau[2 * i], K.fatigue_tau[2 * i + 1], TL, MA, MR, MF);
+        const int wt = UNI(s.pub);
+        st_pub(f + i, MA, wt); st_pub(f + nu + i, MR, wt); st_pub(f + 2 * nu + i, MF, wt);
+      }
+      ctrl_set(s, i, (T)MA);
+    }
+  }
+  SYNC();
+}
+// BaseV0.reset: every muscle rested (MA, MR, MF) = (0, 1, 0)
+template <typename T, int NC>
+DEV void fatigue_reset(const DevModel<T>& M, const TaskDev& K, Scratch<T, NC>& s, double* rec) {
+  WAVE_FN_K
+  (void)s;
+  if (K.muscle_condition != MYO_MUSCLE_FATIGUE_K) return;
+  const int nu = M.nu;
+  PHASE {
+    auto f = (GPTR(double))rec + K.fat_off;
+    if (lane < nu) { f[lane] = 0.0; f[nu + lane] = 1.0; f[2 * nu + lane] = 0.0; }
+  }
+  SYNC();
+}
+
 // ---- env.step(a) without the VecEnv bookkeeping
 // An env step may be run in parts by several workgroups (the launch's makespan, see k_step): substeps [k_lo, k_hi) of the
-// frame_skip; the part that starts at 0 also moves the targets, every part recomputes ctrl (a pure function of the action), the
+// frame_skip; the part that starts at 0 also moves the targets (and the fatigue state), every part recomputes ctrl (a pure function of
+// the action — under fatigue: of the state the first part stored, fatigue_ctrl), the
 // part that ends at frame_skip also makes observation and reward (k_hi < 0 = frame_skip).  Everything a substep hands to the
-// next one is in the env record (load_env / store_env), so the split is bit-exact.  pose: the env's pose block (MYO_TASK_POSE only).
+// next one is in the env record (load_env / store_env), so the split is bit-exact.  pose: the env's pose block (MYO_TASK_POSE only);
+// fat_rec: the env's record, for its fatigue block (null: no fatigue in this call — the zero-action step inside a reset with RSI, which
+// the reset's own (0, 1, 0) follows).
 template <typename T, int RKM = -1, int NC>
 DEV void task_step_core(const DevModel<T>& M_in, const TaskDev& K_in, Scratch<T, NC>& s_in, const float* action /* may be null = zeros */,
-                        int k_lo = 0, int k_hi = -1, const double* pose = nullptr) {
+                        int k_lo = 0, int k_hi = -1, const double* pose = nullptr, double* fat_rec = nullptr) {
   MYO_BIND_M(T) MYO_BIND_K MYO_BIND_S(T)
   WAVE_FN_K
+  const bool fatigue = K.muscle_condition == MYO_MUSCLE_FATIGUE_K && fat_rec;
   PHASE {
     if (lane == 0 && K.kind != MYO_TASK_REORIENT_K && k_lo == 0) {
       if (s.which_task != 0) {
@@ -269,17 +347,15 @@ DEV void task_step_core(const DevModel<T>& M_in, const TaskDev& K_in, Scratch<T,
       s.counter++;
     }
     const int i = lane;
-    if (i < M.nu) {  // BaseV0.step: clip, then float32 sigmoid(5(a-0.5)) for muscles (normalize_act)
-      float a = action ? action[i] : 0.0f;
-      a = a < -1.f ? -1.f : (a > 1.f ? 1.f : a);
-      // every operation but exp is an IEEE float32 operation; exp is the correctly rounded float32 exponential
-      // (a device expf is 1 ulp off glibc's / numpy's on some arguments: a 6e-8 difference in ctrl, 1e-8 in the
-      // trajectory after 20 env steps)
-      const float c = 1.0f / (1.0f + (float)exp((double)(-5.0f * (a - 0.5f))));
+    if (i < M.nu && !fatigue) {  // BaseV0.step: the muscle map; reafferentation: lane EPL maps EIP's action, lane EIP writes 0
+      const bool reaf = K.muscle_condition == MYO_MUSCLE_REAF_K;
+      const float a = action ? action[(reaf && i == K.reaf_dst) ? K.reaf_src : i] : 0.0f;
+      const float c = (reaf && i == K.reaf_src) ? 0.0f : task_act_map(a);
       ctrl_set(s, i, (T)c);
     }
   }
   SYNC();
+  if (fatigue) fatigue_ctrl(M, K, s, action, fat_rec, k_lo == 0);
   const int k_end = (k_hi < 0 || k_hi > K.frame_skip) ? K.frame_skip : k_hi;
   for (int k = k_lo; k < k_end; ++k) mj_step<T, RKM>(M, K, s);
   if (k_end < K.frame_skip) return;
@@ -530,9 +606,10 @@ DEVFN void pose_reset(const DevModel<T>& M_in, const TaskDev& K_in, Scratch<T, N
 }
 
 template <typename T, int NC>
-DEV void task_reset(const DevModel<T>& M, const TaskDev& K, Scratch<T, NC>& s, int env, double* pose) {
+DEV void task_reset(const DevModel<T>& M, const TaskDev& K, Scratch<T, NC>& s, int env, double* pose, double* rec) {
   if (K.kind == MYO_TASK_POSE_K) pose_reset(M, K, s, env, pose);
   else if (K.kind == MYO_TASK_REORIENT_K) reorient_reset(M, K, s, env); else baoding_reset(M, K, s, env);
+  fatigue_reset(M, K, s, rec);
 }
 
 // ---- HBM record <-> scratch
@@ -661,7 +738,7 @@ DEV void env_step(const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout&
   WAVE_FN_K
   const int nobs = task_nobs(K, M.na);
   load_env(M, K, L, rec, s, env, pub);
-  task_step_core<T, RKM>(M, K, s, act + (size_t)env * M.nu, k_lo, k_hi, rec + L.off_pose);
+  task_step_core<T, RKM>(M, K, s, act + (size_t)env * M.nu, k_lo, k_hi, rec + L.off_pose, rec);
   if (k_hi >= 0 && k_hi < K.frame_skip) { store_env(M, K, L, rec, s, (s.pub ? 3 : 1) | (k_lo > 0 ? 4 : 0)); ws_release(K, s); return; }
   // A numerically blown-up env (mj_checkPos / mj_checkVel / mj_checkAcc: MuJoCo warns and resets the data) is not
   // an error of the batch: the env ends its episode with done = 1, reward 0, zero reward components except `done`,
@@ -690,7 +767,7 @@ DEV void env_step(const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout&
   if (is_done) {
     PHASE { if (lane == 0) s.episode++; }
     SYNC();
-    task_reset(M, K, s, env, rec + L.off_pose);
+    task_reset(M, K, s, env, rec + L.off_pose, rec);
   }
   PHASE {
     for (int i = lane; i < nobs; i += 64) {
@@ -715,12 +792,12 @@ DEV void env_step_inner(const DevModel<T>& M, const TaskDev& K, const EnvRecordL
   const int nobs = task_nobs(K, M.na);
   const int io = row < 0 ? env : row;
   load_env(M, K, L, rec, s, env);
-  task_step_core<T, RKM>(M, K, s, act + (size_t)io * M.nu, 0, -1, rec + L.off_pose);
+  task_step_core<T, RKM>(M, K, s, act + (size_t)io * M.nu, 0, -1, rec + L.off_pose, rec);
   const int bad = s.bad, fall = S_RWD(s)[6] != 0 || bad;
   if (bad) {                        // blown-up env: back to a finite reset state (see env_step)
     PHASE { if (lane == 0) s.episode++; }
     SYNC();
-    task_reset(M, K, s, env, rec + L.off_pose);
+    task_reset(M, K, s, env, rec + L.off_pose, rec);
   }
   PHASE {
     if (lane == 0 && done_out) done_out[io] = (unsigned char)fall;
@@ -740,7 +817,7 @@ DEV void env_reset(const DevModel<T>& M, const TaskDev& K, const EnvRecordLayout
   load_env(M, K, L, rec, s, env);
   PHASE { if (lane == 0) s.episode++; }
   SYNC();
-  task_reset(M, K, s, env, rec + L.off_pose);
+  task_reset(M, K, s, env, rec + L.off_pose, rec);
   if (obs) { PHASE { for (int i = lane; i < nobs; i += 64) obs[(size_t)env * nobs + i] = (float)S_OBS(s)[i]; } SYNC(); }
   store_env(M, K, L, rec, s);
   ws_release(K, s);

@@ -21,8 +21,8 @@ from typing import Any, List, Optional, Sequence
 import numpy as np
 
 from .. import native
-from ..model import CompiledModel, compile_model
-from .config import make_task_cfg, resolve_kwargs
+from ..model import CompiledModel, apply_muscle_condition, compile_model
+from .config import check_muscle_condition, make_task_cfg, resolve_kwargs
 
 
 @dataclass
@@ -54,8 +54,14 @@ class BaodingVecEnv:
         self.env_name = env_name
         self.config = config
         self.params = self._resolve(env_name, config)
+        self.muscle_condition = check_muscle_condition(self.params.get("muscle_condition"))
         if model is None:
             model = self._default_model()
+        if self.muscle_condition == "sarcopenia":       # a model edit (the other conditions are lowered into the task cfg)
+            if isinstance(model, CompiledModel):
+                raise ValueError(f"{env_name}: muscle_condition='sarcopenia' edits the model and model= is already compiled: apply the "
+                                 "condition before compiling (model.apply_muscle_condition), then pass the result without the kwarg")
+            model = apply_muscle_condition(model, "sarcopenia")
         if not isinstance(model, CompiledModel):
             integ = None if integrator is None else {"euler": 0, "rk4": 1}[integrator.lower()]
             model = self._compile(model, integ, unsupported_contacts)
@@ -189,12 +195,37 @@ class BaodingVecEnv:
             self.batch.get_task(t, None, None, self._stream())
             w = t[:, 0].cpu().numpy()
             return [int(w[i]) for i in idx]
+        if attr_name == "muscle_fatigue":              # MyoSuite's env.muscle_fatigue.MF
+            v = self.fatigue_state()["MF"].cpu().numpy()
+            return [v[i].copy() for i in idx]
         if attr_name in self._SENSOR_ATTRS:
             v = self.sensors([self._SENSOR_ATTRS[attr_name]])[self._SENSOR_ATTRS[attr_name]].cpu().numpy()
             return [v[i].copy() for i in idx]
         if attr_name in self.params:
             return [self.params[attr_name] for _ in idx]
         raise AttributeError(attr_name)
+
+    # ---------------------------------------------------------------- muscle fatigue (include/myobatch.h myo_batch_fatigue)
+    def _fatigue_block(self):
+        if self.muscle_condition != "fatigue":
+            raise native.MyoError(f"{self.env_name}: made without muscle_condition='fatigue': there is no fatigue state")
+        return self.torch.zeros((self.num_envs, 3, self.act_dim), dtype=self.torch.float64, device=self.device)
+
+    def fatigue_state(self) -> dict:
+        """The 3CC-r state of every muscle: device tensors ``MA``, ``MR``, ``MF`` (active, resting, fatigued fraction), float64
+        [N, nu] each; ``ctrl`` of the last step was ``MA``.  Needs ``muscle_condition="fatigue"``."""
+        blk = self._fatigue_block()
+        self.batch.fatigue(None, blk, self._stream())
+        return {"MA": blk[:, 0], "MR": blk[:, 1], "MF": blk[:, 2]}
+
+    def set_fatigue_state(self, MA, MR, MF) -> None:
+        """Overwrite the fatigue state of every env ([N, nu] each, or [nu] for all envs): e.g. start an evaluation fatigued."""
+        t, blk = self.torch, self._fatigue_block()
+        for k, v in enumerate((MA, MR, MF)):
+            blk[:, k] = t.as_tensor(v, dtype=t.float64, device=self.device)
+        self.batch.fatigue(blk, None, self._stream())
+        if self.device.type == "cuda":
+            t.cuda.synchronize(self.device)       # (the block is a temporary: the copy must have read it)
 
     def set_attr(self, attr_name: str, value, indices=None) -> None:
         raise AttributeError("task parameters are fixed at construction; build a new BaodingVecEnv")

@@ -11,8 +11,8 @@ from __future__ import annotations
 
 from typing import Dict
 
-from ..native import (CHOICE_CCW, CHOICE_CW, CHOICE_FIXED, CHOICE_RANDOM, TASK_BAODING_P1,
-                      TASK_BAODING_P2, TaskCfg)
+from ..native import (CHOICE_CCW, CHOICE_CW, CHOICE_FIXED, CHOICE_RANDOM, MUSCLE_FATIGUE, MUSCLE_NONE,
+                      MUSCLE_REAFFERENTATION, TASK_BAODING_P1, TASK_BAODING_P2, TaskCfg)
 
 REWARD_KEYS = ("pos_dist_1", "pos_dist_2", "act_reg", "alive", "sparse", "solved", "done")
 
@@ -36,12 +36,54 @@ REGISTRATION = {
                 "task_choice": "random"}),
 }
 
+# ---- [3P-RECALL] MyoSuite 1.x / 2.x BaseV0._setup(muscle_condition=...) and its CumulativeFatigue — not in the reference, restated
+# here in ONE place for the Python layer (the device's rule: csrc/myo_task.h fatigue_advance / task_act_map).  Every env of the
+# reference ends in BaseV0._setup(**kwargs), so every env family takes the two kwargs below.
+MYOSUITE_MUSCLE = dict(
+    conditions=(None, "", "sarcopenia", "fatigue", "reafferentation"),
+    sarcopenia_gain_scale=0.5,                        # actuator_gainprm[:, 2] *= 0.5 (peak force); biasprm untouched
+    reafferentation=("EIP", "EPL"),                   # tendon transfer: ctrl[EPL] = sigmoid(a[EIP]), ctrl[EIP] = 0
+    fatigue_params=dict(F=0.00912, R=0.000094, r=150.0),      # 3CC-r: fatigue rate, recovery rate, recovery multiplier during rest
+)
+MUSCLE_DEFAULTS = dict(muscle_condition=None, fatigue_params=None)
+
+
+def check_muscle_condition(condition):
+    """None, "", "sarcopenia", "fatigue" or "reafferentation" -> the condition ("" -> None); anything else: ValueError"""
+    if condition not in MYOSUITE_MUSCLE["conditions"]:
+        raise ValueError(f"unknown muscle_condition {condition!r}; known: {MYOSUITE_MUSCLE['conditions']}")
+    return condition or None
+
+
+def lower_muscle_condition(c: TaskCfg, compiled, p: dict) -> None:
+    """muscle_condition / fatigue_params of the resolved kwargs `p` -> the muscle fields of the task cfg.  Sarcopenia leaves no
+    trace here: it is a model edit made before the model was compiled (model.apply_muscle_condition)."""
+    cond = check_muscle_condition(p.get("muscle_condition"))
+    prm = dict(MYOSUITE_MUSCLE["fatigue_params"])
+    given = p.get("fatigue_params") or {}
+    for k in given:
+        if k not in prm:
+            raise ValueError(f"fatigue_params: unknown key {k!r}; known: {sorted(prm)}")
+    prm.update({k: float(v) for k, v in given.items()})
+    c.muscle_condition, c.reaf_src, c.reaf_dst = MUSCLE_NONE, -1, -1
+    c.fatigue_F, c.fatigue_R, c.fatigue_r = prm["F"], prm["R"], prm["r"]
+    if cond == "fatigue":
+        c.muscle_condition = MUSCLE_FATIGUE
+    elif cond == "reafferentation":
+        src, dst = MYOSUITE_MUSCLE["reafferentation"]
+        try:
+            c.reaf_src, c.reaf_dst = compiled.name2id("actuator", src), compiled.name2id("actuator", dst)
+        except KeyError as exc:
+            raise ValueError(f"muscle_condition 'reafferentation' needs actuators named {src} and {dst}: {exc}") from exc
+        c.muscle_condition = MUSCLE_REAFFERENTATION
+
+
 # _setup defaults
 P1_DEFAULTS = dict(
     frame_skip=10, drop_th=1.25, proximity_th=0.015, goal_time_period=(5, 5), goal_xrange=(0.025, 0.025),
     goal_yrange=(0.028, 0.028),
     weighted_reward_keys={"pos_dist_1": 5.0, "pos_dist_2": 5.0, "alive": 0.0, "act_reg": 0.0},
-    task=None, enable_rsi=False, noise_palm=0, noise_fingers=0, noise_balls=0, rsi_probability=1)
+    task=None, enable_rsi=False, noise_palm=0, noise_fingers=0, noise_balls=0, rsi_probability=1, **MUSCLE_DEFAULTS)
 P2_DEFAULTS = dict(
     frame_skip=10, drop_th=1.25, proximity_th=0.015, goal_time_period=(5, 5), goal_xrange=(0.025, 0.025),
     goal_yrange=(0.028, 0.028), obj_size_range=(0.018, 0.024), obj_mass_range=(0.030, 0.300),
@@ -49,7 +91,7 @@ P2_DEFAULTS = dict(
     # BaodingEnvV1.DEFAULT_RWD_KEYS_AND_WEIGHTS [3P-RECALL MyoSuite 1.2.3]
     weighted_reward_keys={"pos_dist_1": 5.0, "pos_dist_2": 5.0},
     enable_rsi=False, rsi_probability=1, balls_overlap=False, overlap_probability=0, limit_init_angle=False,
-    beta_init_angle=None, beta_ball_size=None, beta_ball_mass=None, noise_fingers=0)
+    beta_init_angle=None, beta_ball_size=None, beta_ball_mass=None, noise_fingers=0, **MUSCLE_DEFAULTS)
 IGNORED = {"normalize_act", "model_path", "obs_keys", "seed"}
 
 
@@ -136,4 +178,5 @@ def make_task_cfg(env_name: str, compiled, **kwargs) -> TaskCfg:
         for i in range(3):
             c.obj_friction_change[i] = float(p["obj_friction_change"][i])
     c.init_qpos0 = -1.57                                         # baoding.py:283,401
+    lower_muscle_condition(c, compiled, p)
     return c

@@ -55,6 +55,8 @@ class MixtureModelBaodingVecEnv(BaodingVecEnv):
             kw = dict(batch_kw)
             kw["seed"] = int(kw.get("seed", 0)) + 7919
             kw["model"] = self.compiled                         # the same compiled model
+            if self.muscle_condition == "sarcopenia":           # (... which already carries that edit; fatigue and reafferentation
+                config = dict(config, muscle_condition=None)    #  travel in the task cfg: pool envs are stepped under them too)
             pool_cls = BaodingVecEnv if type(self)._select_device is BaodingVecEnv._select_device else \
                 type("_PoolVecEnv", (BaodingVecEnv,), {"_select_device": type(self)._select_device})      # (test builds: the env's own device rule)
             self._pool = pool_cls(env_name, self.pool_size, config, **kw)

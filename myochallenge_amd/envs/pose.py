@@ -28,6 +28,7 @@ import numpy as np
 from .. import native
 from ..synth_hand import JNT_NAMES_HAND
 from .baoding import BaodingVecEnv
+from .config import MUSCLE_DEFAULTS, lower_muscle_condition
 
 # ---- [3P-RECALL] MyoSuite 1.x PoseEnvV0 / BaseV0 — not in the reference, restated here in ONE place
 MYOSUITE_POSE = dict(
@@ -78,7 +79,7 @@ SETUP_DEFAULTS = dict(   # CustomPoseEnv._setup (pose.py:7-22) + BaseV0's frame_
     viz_site_targets=None, target_jnt_range=None, target_jnt_value=None, reset_type="init", target_type="generate",
     obs_keys=MYOSUITE_POSE["obs_keys"], weighted_reward_keys=MYOSUITE_POSE["weighted_reward_keys"], pose_thd=0.35,
     weight_bodyname=None, weight_range=None, sds_distance=0, target_distance=1, frame_skip=MYOSUITE_POSE["frame_skip"],
-    normalize_act=True)
+    normalize_act=True, **MUSCLE_DEFAULTS)
 _RESET = {"init": native.POSE_RESET_INIT, "random": native.POSE_RESET_RANDOM, "sds": native.POSE_RESET_SDS}
 _TARGET = {"generate": native.POSE_TARGET_GENERATE, "fixed": native.POSE_TARGET_FIXED}
 
@@ -156,6 +157,7 @@ def make_pose_cfg(env_name: str, compiled, **kwargs) -> native.TaskCfg:
             c.pose_target_value[i] = 0.5 * (float(lo) + float(hi))
     elif p["target_type"] == "generate":
         raise ValueError("target_type 'generate' needs target_jnt_range")
+    lower_muscle_condition(c, compiled, p)
     return c
 
 

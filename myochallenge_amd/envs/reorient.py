@@ -30,6 +30,7 @@ import torch
 from .. import native
 from ..model import compile_model
 from .baoding import BaodingVecEnv
+from .config import MUSCLE_DEFAULTS, lower_muscle_condition
 
 REGISTRATION = {      # src/envs/__init__.py:24-55
     "CustomMyoReorientP1": dict(max_episode_steps=150, kwargs=dict(normalize_act=True, frame_skip=5, goal_pos=(-0.010, 0.010),
@@ -41,7 +42,7 @@ REGISTRATION = {      # src/envs/__init__.py:24-55
 SETUP_DEFAULTS = dict(   # reorient.py:58-76; DEFAULT_RWD_KEYS_AND_WEIGHTS of ReorientEnvV0 [3P-RECALL]
     weighted_reward_keys={"pos_dist": 100.0, "rot_dist": 1.0}, goal_pos=(0.0, 0.0), goal_rot=(0.785, 0.785), obj_size_change=0,
     obj_friction_change=(0, 0, 0), pos_th=0.025, rot_th=0.262, drop_th=0.200, enable_rsi=False, rsi_distance_pos=0,
-    rsi_distance_rot=0, goal_rot_x=None, goal_rot_y=None, goal_rot_z=None, frame_skip=5, normalize_act=True)
+    rsi_distance_rot=0, goal_rot_x=None, goal_rot_y=None, goal_rot_z=None, frame_skip=5, normalize_act=True, **MUSCLE_DEFAULTS)
 RWD_KEYS = ("pos_dist", "rot_dist", "pos_dist_diff", "rot_dist_diff", "alive", "act_reg", "sparse", "solved", "done", "dense")
 
 
@@ -170,6 +171,7 @@ def make_reorient_cfg(env_name: str, compiled, **kwargs) -> native.TaskCfg:
         c.ro_goal_init_pos[i] = float(goal0[i])
         c.ro_goal_obj_offset[i] = float(goal0[i] - obj0[i])
     c.init_qpos0 = -1.5                                                   # reorient.py:120-121
+    lower_muscle_condition(c, compiled, p)
     return c
 
 

@@ -29,8 +29,12 @@ DEFAULT_CONFIG = {
 def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBallsP2", config: dict = None,
              num_episodes: int = 100, num_envs: int = 256, seed: int = 0, deterministic: bool = True, verbose: bool = True,
              render_dir: str = None, render_envs: int = 1, render_size=(480, 480), render_tendons: bool = False,
-             record_dir: str = None, env=None, render_contacts: bool = False, render_geom_alpha: float = None):
-    """record_dir: write ``batch00000.npz`` there — per env step t and env n: ``qpos``, ``qvel``, ``act`` (the state after the step: the
+             record_dir: str = None, env=None, render_contacts: bool = False, render_geom_alpha: float = None,
+             muscle_condition: str = None, fatigue_params: dict = None):
+    """muscle_condition / fatigue_params: evaluate under MyoSuite's ``muscle_condition`` ("sarcopenia", "fatigue", "reafferentation";
+    fatigue_params: a dict with any of F, R, r) — they override the config's; with fatigue, record_dir also gets ``fatigue_MA`` /
+    ``fatigue_MR`` / ``fatigue_MF`` [T, N, nu].
+    record_dir: write ``batch00000.npz`` there — per env step t and env n: ``qpos``, ``qvel``, ``act`` (the state after the step: the
     reset state where the episode ended), ``actuator_length`` / ``actuator_velocity`` / ``actuator_force`` [T, N, nu], ``ncon`` [T, N] and
     ``object_wrench`` [T, N, nobj, 6] (net contact force and torque on the task's objects, ``object_body_ids``), from ``env.sensors``.
     env: an already built env to evaluate on instead of ``EnvironmentFactory.create(env_name, ...)``.
@@ -44,6 +48,10 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
     if config is None:             # the reference script's Baoding config; other envs: their registration defaults
         config = DEFAULT_CONFIG if env_name.startswith("CustomMyoBaoding") or env_name == "MixtureModelBaodingEnv" else {}
     config = dict(config)
+    if muscle_condition is not None:
+        config["muscle_condition"] = muscle_condition
+    if fatigue_params:
+        config["fatigue_params"] = dict(config.get("fatigue_params") or {}, **fatigue_params)
     if env is None:
         env = EnvironmentFactory.create(env_name, num_envs=min(num_envs, num_episodes), seed=seed, **config)
     venv = VecNormalize.load(env_path, env)
@@ -69,6 +77,9 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
         os.makedirs(record_dir, exist_ok=True)
         rec = {k: [] for k in ("qpos", "qvel", "act", "actuator_length", "actuator_velocity", "actuator_force", "ncon", "object_wrench")}
         obj, draw = env.object_body_ids(), on_step
+        fatigue = getattr(env, "muscle_condition", None) == "fatigue"
+        if fatigue:
+            rec.update(fatigue_MA=[], fatigue_MR=[], fatigue_MF=[])
 
         def on_step(t):
             if draw is not None:
@@ -78,6 +89,9 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
             for k, v in (("qpos", qp), ("qvel", qv), ("act", ac), ("actuator_length", s["act_length"]), ("actuator_velocity", s["act_velocity"]),
                          ("actuator_force", s["act_force"]), ("ncon", s["ncon"]), ("object_wrench", s["body_wrench"][:, obj])):
                 rec[k].append(v.cpu().numpy())
+            if fatigue:
+                for k, v in env.fatigue_state().items():
+                    rec["fatigue_" + k].append(v.cpu().numpy())
     res = evaluate_policy(policy, env, venv, n_eval_episodes=num_episodes, deterministic=deterministic, on_step=on_step)
     if rec is not None:
         np.savez(os.path.join(record_dir, "batch00000.npz"), object_body_ids=np.asarray(obj, np.int64), **{k: np.stack(v) for k, v in rec.items()})
@@ -108,6 +122,11 @@ def main(argv=None):
                     help="with --render-contacts: multiply the geoms' alpha by A in [0, 1] (translucent geoms show the contact points between them)")
     ap.add_argument("--record-dir", default=None, help="write per-step qpos / qvel / act, actuator length / velocity / force, ncon and the "
                                                        "objects' contact wrenches of the evaluated batch to batch00000.npz here")
+    ap.add_argument("--muscle-condition", default=None, choices=("sarcopenia", "fatigue", "reafferentation"),
+                    help="evaluate under MyoSuite's muscle_condition (overrides the config's)")
+    ap.add_argument("--fatigue-F", type=float, default=None, help="with --muscle-condition fatigue: fatigue rate F (default 0.00912)")
+    ap.add_argument("--fatigue-R", type=float, default=None, help="... recovery rate R (default 0.000094)")
+    ap.add_argument("--fatigue-r", type=float, default=None, help="... recovery multiplier during rest r (default 150)")
     a = ap.parse_args(argv)
     if a.render_tendons and not a.render_dir:
         ap.error("--render-tendons needs --render-dir")
@@ -115,10 +134,14 @@ def main(argv=None):
         ap.error("--render-contacts needs --render-dir")
     if a.render_geom_alpha is not None and not a.render_contacts:
         ap.error("--render-geom-alpha needs --render-contacts")
+    fat = {k: v for k, v in (("F", a.fatigue_F), ("R", a.fatigue_R), ("r", a.fatigue_r)) if v is not None}
+    if fat and a.muscle_condition != "fatigue":
+        ap.error("--fatigue-F / --fatigue-R / --fatigue-r need --muscle-condition fatigue")
     cfg = json.load(open(a.config)) if a.config else None
     res, _ = evaluate(a.model, a.env_path, a.env_name, cfg, a.num_episodes, a.num_envs, a.seed,
                       render_dir=a.render_dir, render_envs=a.render_envs, render_size=a.render_size, render_tendons=a.render_tendons,
-                      record_dir=a.record_dir, render_contacts=a.render_contacts, render_geom_alpha=a.render_geom_alpha)
+                      record_dir=a.record_dir, render_contacts=a.render_contacts, render_geom_alpha=a.render_geom_alpha,
+                      muscle_condition=a.muscle_condition, fatigue_params=fat or None)
     if a.out:
         np.savez(a.out, **res)
 

@@ -118,6 +118,30 @@ class CompiledModel:
         return out + bytes(payload)
 
 
+def apply_muscle_condition(m: MjbModel, condition) -> MjbModel:
+    """The model edit of MyoSuite's ``BaseV0._setup(muscle_condition=...)`` [3P-RECALL: envs/config.py MYOSUITE_MUSCLE], on a copy
+    of the decoded model ``m`` — BEFORE ``compile_model``: the compiled tables carry constants derived from the peak force.
+
+    ``"sarcopenia"`` halves every actuator's peak force, ``actuator_gainprm[:, 2]``; ``actuator_biasprm`` stays, so passive force
+    keeps its scale.  A negative entry is MuJoCo's unresolved "auto" force (the compiler computes it from ``scale / acc0``): halving
+    it would change nothing, so such a model is refused.  The other conditions (None, "", "fatigue", "reafferentation") act on
+    the controls, not on the model: the copy is returned unedited."""
+    from .envs.config import MYOSUITE_MUSCLE, check_muscle_condition
+    if isinstance(m, CompiledModel):
+        raise ValueError("apply_muscle_condition edits a decoded model (mjb.load_mjb, synth_hand): apply the condition before compiling")
+    condition = check_muscle_condition(condition)
+    out = MjbModel(sizes=dict(m.sizes), opt=dict(m.opt), arrays={k: np.array(v, copy=True) for k, v in m.arrays.items()},
+                   names={k: list(v) for k, v in m.names.items()}, model_name=m.model_name, stat=dict(m.stat))
+    if condition == "sarcopenia":
+        gp = np.asarray(out.arrays["actuator_gainprm"], float).reshape(int(m.nu), -1).copy()
+        if np.any(gp[:, 2] < 0):
+            raise ValueError("sarcopenia: actuator_gainprm[:, 2] (peak force) is negative for actuator(s) "
+                             f"{np.nonzero(gp[:, 2] < 0)[0].tolist()}: an unresolved 'auto' force cannot be halved")
+        gp[:, 2] *= MYOSUITE_MUSCLE["sarcopenia_gain_scale"]
+        out.arrays["actuator_gainprm"] = gp.reshape(np.asarray(m.arrays["actuator_gainprm"]).shape)
+    return out
+
+
 def _depths(parent: np.ndarray) -> np.ndarray:
     d = np.zeros(len(parent), np.int32)
     for i in range(1, len(parent)):

@@ -22,6 +22,7 @@ TASK_NONE, TASK_BAODING_P1, TASK_BAODING_P2, TASK_REORIENT, TASK_POSE = 0, 1, 2,
 POSE_RESET_INIT, POSE_RESET_RANDOM, POSE_RESET_SDS = 0, 1, 2
 POSE_TARGET_GENERATE, POSE_TARGET_FIXED = 0, 1
 CHOICE_FIXED, CHOICE_CW, CHOICE_CCW, CHOICE_RANDOM = 0, 1, 2, 3
+MUSCLE_NONE, MUSCLE_FATIGUE, MUSCLE_REAFFERENTATION = 0, 1, 2      # myo_task_cfg.muscle_condition
 N_RWD = 8
 RWD_KEYS = ("pos_dist_1", "pos_dist_2", "act_reg", "alive", "sparse", "solved", "done", "dense")
 
@@ -63,6 +64,9 @@ class TaskCfg(C.Structure):
         ("pose_reset_type", C.c_int32), ("pose_target_type", C.c_int32),
         ("pose_init_qpos", C.c_double * POSE_NQ_MAX), ("pose_target_value", C.c_double * POSE_NQ_MAX),
         ("pose_target_range", C.c_double * 2 * POSE_NQ_MAX), ("pose_reset_range", C.c_double * 2 * POSE_NQ_MAX),
+        # muscle condition (every kind): MUSCLE_*; reafferentation's actuators; fatigue's rates
+        ("muscle_condition", C.c_int32), ("reaf_src", C.c_int32), ("reaf_dst", C.c_int32),
+        ("fatigue_F", C.c_double), ("fatigue_R", C.c_double), ("fatigue_r", C.c_double),
     ]
 
 
@@ -171,6 +175,7 @@ class NativeLib:
         L.myo_batch_tune_wrap_order.argtypes = [vp, vp]
         L.myo_batch_set_object_group.argtypes = [vp, i32, i32]
         L.myo_batch_object_friction.argtypes = [vp, vp, vp, vp]
+        L.myo_batch_fatigue.argtypes = [vp, vp, vp, vp]
         L.myo_batch_forward_dump.argtypes = [vp, vp, vp, vp]
         L.myo_batch_dump_size.argtypes = [vp]
         L.myo_batch_dump_offset.argtypes = [vp, C.c_char_p]
@@ -269,6 +274,7 @@ EXPORTED_SYMBOLS = [
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
     "myo_batch_contact_capacity", "myo_batch_sense",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
+    "myo_batch_fatigue",
 ]
 
 # ... of which the lane-serial emulation build (tests/emu/libmyobatch_emu.so: csrc/myobatch_emu.cpp + csrc/emu_host.h, test tooling) has the env
@@ -283,6 +289,7 @@ ENV_PATH_SYMBOLS = [
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
     "myo_batch_contact_capacity", "myo_batch_sense",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
+    "myo_batch_fatigue",
 ]
 
 
@@ -406,6 +413,10 @@ class Batch:
     def object_friction(self, set_fric=None, get_fric=None, stream=None):
         """friction triples of the object group's geoms, float64 [N, ngeom_group, 3] (set, then get; either may be None)"""
         self.lib.check(self.lib.L.myo_batch_object_friction(self.h, _ptr(set_fric), _ptr(get_fric), stream))
+
+    def fatigue(self, set_state=None, get_state=None, stream=None):
+        """fatigue state of a batch made with muscle_condition fatigue, float64 [N, 3, nu] = MA, MR, MF (set, then get; either may be None)"""
+        self.lib.check(self.lib.L.myo_batch_fatigue(self.h, _ptr(set_state), _ptr(get_state), stream))
 
     def bind_constants(self, stream=None):
         """Make this batch the one whose model / task sit in __constant__ memory (needed before replaying a

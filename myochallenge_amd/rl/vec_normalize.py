@@ -254,6 +254,17 @@ class VecNormalize:
     def contact_table(self, *args, **kwargs):
         return self.venv.contact_table(*args, **kwargs)
 
+    # muscle fatigue state (muscle_condition="fatigue"): forwarded likewise
+    def fatigue_state(self):
+        return self.venv.fatigue_state()
+
+    def set_fatigue_state(self, MA, MR, MF):
+        return self.venv.set_fatigue_state(MA, MR, MF)
+
+    def get_attr(self, attr_name: str, indices=None):
+        """SB3 VecEnvWrapper.get_attr: the wrapped env's (e.g. ``muscle_fatigue``, the sensor names, the task kwargs)"""
+        return self.venv.get_attr(attr_name, indices)
+
     def close(self):
         if self.venv is not None:
             self.venv.close()
