@@ -303,6 +303,43 @@ typedef struct myo_sense_out {
 int myo_batch_contact_capacity(const myo_batch* b);
 int myo_batch_sense(myo_batch* b, const myo_sense_out* out, void* stream);
 
+/* ---- per-env kinematics and dynamics read-out (MuJoCo's sim.data by name: data.xpos, data.site_xpos, data.qM, data.actuator_moment,
+ * data.qfrc_actuator, data.qacc ... — what custom rewards, fingertip / object tracking and moment-arm curves are made of).
+ * One wave per env runs the stepper's forward pass at the env's PRESENT state, seeded like myo_batch_sense (the env's qacc_warmstart,
+ * its own ball / die parameters), and publishes the arrays below.  ctrl: dev double[N, nu] or NULL (= 0); it enters act_dot and the
+ * forces of actuators without an activation state.  The pass ENDS after the last stage a non-NULL pointer needs — position, inertia,
+ * velocity, actuation, smooth acceleration, constrained acceleration, in this order: a call for poses or moment arms runs no
+ * composite-inertia pass, no collision and no solver; only qacc runs the collision passes, the constraint rows and the Newton solve.
+ * Reads the env records only: no record, warm start, draw counter, step generation or wrap order changes; a qacc pass that has to
+ * drop contacts beyond the capacity counts it in myo_batch_health like a substep.
+ *
+ * myo_data_out: caller-owned DEVICE arrays of doubles, any of them NULL (not wanted); `size` = sizeof(myo_data_out), first, so that
+ * the struct can grow.  World frame, MuJoCo's conventions; N = envs; [stage]:
+ *   xpos, xipos, subtree_com  [N, nbody, 3]   body frame origin, inertial frame origin, centre of mass of the body's subtree  [position]
+ *   xquat                     [N, nbody, 4]   unit quaternion (w, x, y, z)                                                    [position]
+ *   xmat                      [N, nbody, 9]   row-major rotation matrix                                                       [position]
+ *   geom_xpos, geom_xmat      [N, ngeom, 3 / 9]  with the env's own geometry (the die's size delta moves its geoms)            [position]
+ *   site_xpos                 [N, nsite, 3]   the Baoding target sites where the task puts them                              [position]
+ *   ten_J                     [N, ntendon, nv]  tendon moment arms, dense                                                     [position]
+ *   actuator_moment           [N, nu, nv]     gear times the actuator's tendon's row of ten_J                                 [position]
+ *   qM                        [N, nv, nv]     joint-space inertia, dense and symmetric (data.qM expanded by mj_fullM)         [inertia]
+ *   cvel                      [N, nbody, 6]   com-based body velocity: rotation [0..3), translation [3..6) at subtree_com of the
+ *                                             body's tree root                                                                [velocity]
+ *   qfrc_bias, qfrc_passive   [N, nv]                                                                                         [velocity]
+ *   qfrc_actuator             [N, nv]                                                                                         [actuation]
+ *   act_dot                   [N, na]                                                                                         [actuation]
+ *   qacc_smooth               [N, nv]         unconstrained acceleration                                                      [smooth acceleration]
+ *   qacc                      [N, nv]                                                                                         [constrained acceleration]
+ * The die's `target` body, its geoms and sites are at the episode's goal_pos / goal_quat (the reference writes them into the model).
+ * A NULL batch / struct or another `size` returns MYO_E_BADARG (= MYO_E_ARG) before any device call; a struct whose pointers are all
+ * NULL launches nothing. */
+typedef struct myo_data_out {
+  size_t size;
+  double *xpos, *xquat, *xmat, *xipos, *subtree_com, *geom_xpos, *geom_xmat, *site_xpos,
+      *cvel, *qM, *ten_J, *actuator_moment, *qfrc_bias, *qfrc_passive, *qfrc_actuator, *qacc_smooth, *qacc, *act_dot;
+} myo_data_out;
+int myo_batch_data(myo_batch* b, const double* ctrl, const myo_data_out* out, void* stream);
+
 /* ---- rendering of env states (MuJoCo's mjr_render / mjr_readPixels seam: CustomPenEnv.render -> self.sim.render,
  * /root/reference/src/main_eval.py:96-97).  Draws what the stepper holds: every geom at the pose of the env's present state
  * and with the env's own geometry (Baoding P2 ball radius, die size delta), the Baoding target sites where the task puts

@@ -28,6 +28,7 @@
 #include "myo_mjb.h"
 #include "myo_task.h"
 #include "myo_sense.h"
+#include "myo_data.h"
 #include "myo_render.h"
 
 
@@ -1745,6 +1746,21 @@ extern "C" int myo_batch_sense(myo_batch* b, const myo_sense_out* out, void* str
   if (!b || !out) return fail(MYO_E_BADARG, "myo_batch_sense: null batch or output struct");
   if (out->size != sizeof(myo_sense_out)) return fail(MYO_E_BADARG, "myo_batch_sense: myo_sense_out.size is %zu, this library's struct has %zu bytes", out->size, sizeof(myo_sense_out));
   return be_run(b, SenseJob{sense_dev(b, out)}, b->n, stream);
+}
+// myo_batch_data (csrc/myo_data.h): the last stage a non-null pointer needs travels in the job; a struct without one launches nothing
+extern "C" int myo_batch_data(myo_batch* b, const double* ctrl, const myo_data_out* out, void* stream) {
+  if (!b || !out) return fail(MYO_E_BADARG, "myo_batch_data: null batch or output struct");
+  if (out->size != sizeof(myo_data_out)) return fail(MYO_E_BADARG, "myo_batch_data: myo_data_out.size is %zu, this library's struct has %zu bytes", out->size, sizeof(myo_data_out));
+  DataDev d = {out->xpos, out->xquat, out->xmat, out->xipos, out->subtree_com, out->geom_xpos, out->geom_xmat, out->site_xpos, out->cvel, out->qM,
+               out->ten_J, out->actuator_moment, out->qfrc_bias, out->qfrc_passive, out->qfrc_actuator, out->qacc_smooth, out->qacc, out->act_dot, ctrl, -1};
+  if (d.xpos || d.xquat || d.xmat || d.xipos || d.subtree_com || d.geom_xpos || d.geom_xmat || d.site_xpos || d.ten_J || d.actuator_moment) d.stage = MYO_DATA_POS;
+  if (d.qM) d.stage = MYO_DATA_INERTIA;
+  if (d.cvel || d.qfrc_bias || d.qfrc_passive) d.stage = MYO_DATA_VEL;
+  if (d.qfrc_actuator || d.act_dot) d.stage = MYO_DATA_ACT;
+  if (d.qacc_smooth) d.stage = MYO_DATA_SMOOTH;
+  if (d.qacc) d.stage = MYO_DATA_CONSTRAINED;
+  if (d.stage < 0) return MYO_OK;
+  return be_run(b, DataJob{d}, b->n, stream);
 }
 extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
   if (int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses")) return rc;

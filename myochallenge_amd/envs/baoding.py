@@ -201,6 +201,9 @@ class BaodingVecEnv:
         if attr_name in self._SENSOR_ATTRS:
             v = self.sensors([self._SENSOR_ATTRS[attr_name]])[self._SENSOR_ATTRS[attr_name]].cpu().numpy()
             return [v[i].copy() for i in idx]
+        if attr_name in native.DATA_KEYS:              # MuJoCo's sim.data.<name> (names sensors() serves keep that route, above)
+            v = self.data([attr_name])[attr_name].cpu().numpy()
+            return [v[i].copy() for i in idx]
         if attr_name in self.params:
             return [self.params[attr_name] for _ in idx]
         raise AttributeError(attr_name)
@@ -363,6 +366,41 @@ class BaodingVecEnv:
             idx = t.as_tensor([int(i) for i in indices], dtype=t.long, device=self.device)
             out = {k: v[idx] for k, v in out.items()}
         return out
+
+    # ---------------------------------------------------------------- kinematics and dynamics read-out (include/myobatch.h myo_batch_data)
+    def data(self, keys=None, indices=None, ctrl=None) -> dict:
+        """MuJoCo's ``sim.data`` by name for the envs' PRESENT states: one forward pass on the GPU that ends after the last stage
+        the asked keys need, nothing about the envs changes.  Device tensors (float64, world frame), no host copy.
+
+        keys (default: all).  Position stage: ``xpos`` / ``xipos`` / ``subtree_com`` [k, nbody, 3], ``xquat`` [k, nbody, 4] (w, x, y,
+        z), ``xmat`` [k, nbody, 9], ``geom_xpos`` / ``geom_xmat`` [k, ngeom, 3 / 9], ``site_xpos`` [k, nsite, 3] (``site_names``),
+        ``ten_J`` [k, ntendon, nv], ``actuator_moment`` [k, nu, nv].  Inertia: ``qM`` [k, nv, nv] (dense).  Velocity: ``cvel``
+        [k, nbody, 6] (rotation, translation), ``qfrc_bias`` / ``qfrc_passive`` [k, nv].  Actuation: ``qfrc_actuator`` [k, nv],
+        ``act_dot`` [k, na].  Acceleration: ``qacc_smooth`` [k, nv]; ``qacc`` [k, nv] — the only key that runs collision and the
+        constraint solver.  indices: the envs' rows to return (default: all; the pass itself always runs the whole batch).
+        ctrl: [N, nu] tensor or array (default 0): enters ``act_dot`` and the forces of actuators without an activation state."""
+        t = self.torch
+        shapes = self.batch.data_shapes()
+        keys = list(shapes) if keys is None else list(keys)
+        for k in keys:
+            if k not in shapes:
+                raise KeyError(f"unknown data key {k!r}; known: {sorted(shapes)}")
+        out = {k: t.zeros((self.num_envs,) + shapes[k], dtype=t.float64, device=self.device) for k in keys}
+        if ctrl is not None:
+            ctrl = t.as_tensor(ctrl, dtype=t.float64, device=self.device).contiguous()
+            if tuple(ctrl.shape) != (self.num_envs, self.act_dim):
+                raise ValueError(f"ctrl must have shape {(self.num_envs, self.act_dim)}")
+        self.batch.data(self._stream(), ctrl, **out)
+        if ctrl is not None and self.device.type == "cuda":
+            t.cuda.synchronize(self.device)       # (ctrl may be a temporary: the pass must have read it)
+        if indices is not None:
+            idx = t.as_tensor([int(i) for i in indices], dtype=t.long, device=self.device)
+            out = {k: v[idx] for k, v in out.items()}
+        return out
+
+    def site_names(self) -> List[str]:
+        """names of the model's sites: rows of ``data()``'s ``site_xpos``"""
+        return list(self.compiled.names.get("site", []))
 
     @property
     def geom_names(self) -> List[str]:

@@ -131,6 +131,16 @@ SENSE_KEYS = tuple(f[0] for f in SenseOut._fields_[1:])
 SENSE_CON_N = 13        # doubles per contact of con_d: dist, pos[3], normal[3], force[6]
 
 
+class DataOut(C.Structure):
+    """myo_data_out of include/myobatch.h: caller-owned device arrays (doubles) of myo_batch_data, any of them NULL."""
+    _fields_ = [("size", C.c_size_t)] + [(k, C.c_void_p) for k in (
+        "xpos", "xquat", "xmat", "xipos", "subtree_com", "geom_xpos", "geom_xmat", "site_xpos", "cvel", "qM", "ten_J", "actuator_moment",
+        "qfrc_bias", "qfrc_passive", "qfrc_actuator", "qacc_smooth", "qacc", "act_dot")]
+
+
+DATA_KEYS = tuple(f[0] for f in DataOut._fields_[1:])
+
+
 class MyoError(RuntimeError):
     pass
 
@@ -191,6 +201,7 @@ class NativeLib:
         L.myo_batch_get_render_style.argtypes = [vp, C.POINTER(RenderStyle)]
         L.myo_batch_contact_capacity.argtypes = [vp]
         L.myo_batch_sense.argtypes = [vp, C.POINTER(SenseOut), vp]
+        L.myo_batch_data.argtypes = [vp, vp, C.POINTER(DataOut), vp]
         if b"MYO_EMU" in L.myo_version():
             return      # the emulation build (test tooling, csrc/emu_host.h) implements the env path only: ENV_PATH_SYMBOLS
         L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp]
@@ -272,7 +283,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_ppo_gather_seq", "myo_rollout_state_snapshot", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
     "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_clip_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_adam_apply", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_ppo_loss_grad_hp", "myo_adam_clip_step_hp", "myo_adam_apply_hp", "myo_last_error", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
-    "myo_batch_contact_capacity", "myo_batch_sense",
+    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
 ]
@@ -287,7 +298,7 @@ ENV_PATH_SYMBOLS = [
     "myo_batch_step", "myo_batch_step_inner", "myo_batch_step_inner_idx", "myo_batch_tune_wrap_order", "myo_batch_warmstart", "myo_debug_wave_slots",
     "myo_last_error", "myo_model_destroy", "myo_model_from_blob", "myo_model_load_mjb", "myo_model_size", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
-    "myo_batch_contact_capacity", "myo_batch_sense",
+    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
 ]
@@ -502,6 +513,27 @@ class Batch:
                 raise KeyError(k)
             setattr(out, k, _ptr(v))
         self.lib.check(self.lib.L.myo_batch_sense(self.h, C.byref(out), stream))
+
+    def data_shapes(self) -> dict:
+        """key -> per-env shape of the float64 arrays of data()"""
+        m = self.model
+        nb, nv, nu, ng = m.size("nbody"), m.size("nv"), m.size("nu"), m.size("ngeom")
+        return {"xpos": (nb, 3), "xquat": (nb, 4), "xmat": (nb, 9), "xipos": (nb, 3), "subtree_com": (nb, 3), "geom_xpos": (ng, 3),
+                "geom_xmat": (ng, 9), "site_xpos": (m.size("nsite"), 3), "cvel": (nb, 6), "qM": (nv, nv), "ten_J": (m.size("ntendon"), nv),
+                "actuator_moment": (nu, nv), "qfrc_bias": (nv,), "qfrc_passive": (nv,), "qfrc_actuator": (nv,), "qacc_smooth": (nv,),
+                "qacc": (nv,), "act_dot": (m.size("na"),)}
+
+    def data(self, stream=None, ctrl=None, **arrays):
+        """kinematics and dynamics read-out of the envs' present states (myo_batch_data): keyword = a key of DATA_KEYS, value = the
+        float64 device array that receives it ([N, *data_shapes()[key]]); ctrl: float64 [N, nu] or None (0).  Keys not given are not
+        computed, and the pass ends after the last stage a given key needs."""
+        out = DataOut()
+        out.size = C.sizeof(DataOut)
+        for k, v in arrays.items():
+            if k not in DATA_KEYS:
+                raise KeyError(k)
+            setattr(out, k, _ptr(v))
+        self.lib.check(self.lib.L.myo_batch_data(self.h, _ptr(ctrl), C.byref(out), stream))
 
     @property
     def dump_size(self) -> int:

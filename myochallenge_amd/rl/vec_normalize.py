@@ -254,6 +254,13 @@ class VecNormalize:
     def contact_table(self, *args, **kwargs):
         return self.venv.contact_table(*args, **kwargs)
 
+    # kinematics and dynamics read-out (MuJoCo's sim.data by name): forwarded likewise
+    def data(self, *args, **kwargs):
+        return self.venv.data(*args, **kwargs)
+
+    def site_names(self):
+        return self.venv.site_names()
+
     # muscle fatigue state (muscle_condition="fatigue"): forwarded likewise
     def fatigue_state(self):
         return self.venv.fatigue_state()
