@@ -255,8 +255,10 @@ def test_fused_ppo_step_matches_fp32_reference(hip_lib, merged):
     step (ppo_mlp_step_grads, itself checked against autograd on CPU).  `merged`: flat parameter vector,
     actor/critic trunks as one batched GEMM per layer.  Tolerance: the policy-gradient terms
     sum_i adv_i * dlogp_i cancel heavily, so bf16 rounding of the activations shows up as 6-7 % relative
-    gradient noise on the actor (measured, identical for both paths; the critic side is < 2 %); the HIP
-    kernels themselves are checked exactly in test_ppo_elementwise_kernels_exact."""
+    gradient noise on the actor (measured, identical for both paths; the critic side is < 2 %).  The kernels
+    themselves are pinned elsewhere: the element-wise kernels of the GEMM path in test_ppo_elementwise_kernels_exact,
+    the matrix-core kernels of csrc/myo_ppo_mlp.h (what `merged` runs through here) against a float64 reference
+    that rounds where they round, at every shape they branch on, in tests/test_ppo_mlp_kernels.py."""
     import copy
     import torch
     from myochallenge_amd.rl.fused_mlp import FusedPPOStep, flatten_parameters, ppo_mlp_step_grads
