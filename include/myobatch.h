@@ -712,6 +712,19 @@ typedef struct myo_ppo_mlp_desc {
 int myo_ppo_mlp_sqnorm_parts(int act_dim);
 long long myo_ppo_mlp_workspace_bytes(int B, int obs_dim, int act_dim, int hidden, long long G);
 int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream);
+/* The same step with RESIDENT operand images, four launches instead of six: the bf16 weight images at the front of `workspace`
+ * are taken as current and the advantage moments as the caller's (compute_adv_stats must be 0), so neither the image pass nor
+ * the moments pass runs.  The images are current after myo_ppo_mlp_images (once, whenever `params` may have been written from
+ * outside: a load, the start of an update) and stay so while every change of `params` is an optimizer step through
+ * myo_adam_clip_step_images / myo_adam_apply_images on the same descriptor.  Same results as myo_ppo_mlp_step, bit for bit. */
+int myo_ppo_mlp_step_resident(const myo_ppo_mlp_desc* d, void* stream);
+/* The image pass alone: the operand images of `params` into `workspace`, zero padding included (reads B, O, A, hidden, params, G,
+ * the twelve offsets, workspace, workspace_bytes of `d`). */
+int myo_ppo_mlp_images(const myo_ppo_mlp_desc* d, void* stream);
+/* {mean, unbiased std} of the advantages of n_mb minibatches in two launches: idx int64[n_mb * B] are their rows one minibatch
+ * after the other (an epoch's permutation), stats f32[n_mb][2] <- what myo_ppo_mlp_step with compute_adv_stats = 1 leaves in
+ * adv_stats for idx[k B .. (k + 1) B), bit for bit.  scratch: f32[192 * n_mb]. */
+int myo_ppo_adv_moments_epoch(const float* adv, const int64_t* idx, int B, int n_mb, float* stats, float* scratch, void* stream);
 
 /* One env step's policy call of the rollout for the same MLP actor-critic (collect_rollouts: ActorCriticPolicy.forward,
  * DiagGaussianDistribution.sample / log_prob, RolloutBuffer.add; /root/reference/src/train/trainer.py:66-71 -> agent.learn) in one
@@ -760,6 +773,15 @@ int myo_adam_clip_step_hp(float* p, const float* g, float* m, float* v, int n, f
 int myo_adam_apply_hp(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
                       float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
                       uint16_t* p_bf16, float* hp, void* stream);
+/* Both again (hp may be NULL), and every parameter the step updates is also stored into the operand images of the fused MLP step
+ * that `images` describes (its workspace, shapes and offsets; images->G must be n): the weights as bf16 in the layouts of
+ * myo_ppo_mlp_images, the biases as fp32.  With the stop flag up the images stay untouched too. */
+int myo_adam_clip_step_images(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                              float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
+                              float* hp, const myo_ppo_mlp_desc* images, void* stream);
+int myo_adam_apply_images(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                          float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
+                          uint16_t* p_bf16, float* hp, const myo_ppo_mlp_desc* images, void* stream);
 
 const char* myo_last_error(void);
 const char* myo_version(void);

@@ -64,6 +64,20 @@ struct MlpPrepArgs {
 };
 
 #define MLP_ADV_BLOCKS 64
+// {mean, unbiased std} of B advantages from their nb slices (n, mean, M2): Chan's update in slice order, by ONE thread
+__device__ __forceinline__ void mlp_adv_merge(const float* sp, int nb, int B, float* __restrict__ stats) {
+  float cn = 0.f, cm = 0.f, c2 = 0.f;
+  for (int b = 0; b < nb; ++b) {
+    const float bn = sp[3 * b], bm = sp[3 * b + 1], b2 = sp[3 * b + 2];
+    if (bn > 0.f) {
+      const float tot = cn + bn, dl = bm - cm;
+      cm += dl * (bn / tot);
+      c2 += b2 + dl * dl * (cn * bn / tot);
+      cn = tot;
+    }
+  }
+  stats[0] = cm; stats[1] = sqrtf(c2 / (B > 1 ? B - 1 : 1));
+}
 __global__ void __launch_bounds__(256) k_mlp_prep(MlpPrepArgs P) {
   // the last block first merges the slices of the advantage moments in slice order (Chan's update, a fixed order: deterministic)
   // — here, behind a kernel boundary, instead of by the last block of k_adv_moments behind a device-scope fence (an L2 write-back:
@@ -73,19 +87,7 @@ __global__ void __launch_bounds__(256) k_mlp_prep(MlpPrepArgs P) {
     const int t = threadIdx.x;
     if (t < 3 * P.adv_nb) sp[t] = P.adv_part[t];
     __syncthreads();
-    if (t == 0) {
-      float cn = 0.f, cm = 0.f, c2 = 0.f;
-      for (int b = 0; b < P.adv_nb; ++b) {
-        const float bn = sp[3 * b], bm = sp[3 * b + 1], b2 = sp[3 * b + 2];
-        if (bn > 0.f) {
-          const float tot = cn + bn, dl = bm - cm;
-          cm += dl * (bn / tot);
-          c2 += b2 + dl * dl * (cn * bn / tot);
-          cn = tot;
-        }
-      }
-      P.adv_stats[0] = cm; P.adv_stats[1] = sqrtf(c2 / (P.B > 1 ? P.B - 1 : 1));
-    }
+    if (t == 0) mlp_adv_merge(sp, P.adv_nb, P.B, P.adv_stats);
   }
   constexpr int H = MLP_H;
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
@@ -120,11 +122,15 @@ __global__ void __launch_bounds__(256) k_mlp_prep(MlpPrepArgs P) {
 // mean and unbiased std of adv[idx[0..B)), first half: MLP_ADV_BLOCKS blocks (a minibatch drawn from a shuffled rollout touches one
 // 128 B line per row — 2 MB through ONE CU's L1 was 23 us of a 150 us optimizer step), each reducing its contiguous slice of the
 // index list to (n, mean, M2) with the values kept in registers (one memory pass) -> part[3 * block]; k_mlp_prep merges them.
-__global__ void __launch_bounds__(256) k_adv_moments(const float* __restrict__ adv, const long long* __restrict__ idx, int B,
-                                                     float* __restrict__ part) {
+// A grid of (MLP_ADV_BLOCKS, n_mb) does this for n_mb index lists of B rows that lie one after the other (the minibatches of an
+// epoch's permutation): blockIdx.y = the list, its slices -> part_all[3 * MLP_ADV_BLOCKS * y ..), merged by k_adv_merge.
+__global__ void __launch_bounds__(256) k_adv_moments(const float* __restrict__ adv, const long long* __restrict__ idx_all, int B,
+                                                     float* __restrict__ part_all) {
   __shared__ float red[4];
   __shared__ float s_mean;
   const int t = threadIdx.x, nb = gridDim.x;
+  const long long* __restrict__ idx = idx_all + (size_t)blockIdx.y * B;
+  float* __restrict__ part = part_all + (size_t)blockIdx.y * 3 * nb;
   const int chunk = (B + nb - 1) / nb, lo = blockIdx.x * chunk, hi = min(B, lo + chunk), n = max(hi - lo, 0);
   constexpr int PER = 4;                  // slices up to 1024 rows in registers; longer ones re-read (second loops below)
   float v[PER];
@@ -147,6 +153,55 @@ __global__ void __launch_bounds__(256) k_adv_moments(const float* __restrict__ a
   if ((t & 63) == 0) red[t >> 6] = m2;
   __syncthreads();
   if (t == 0) { part[3 * blockIdx.x] = (float)n; part[3 * blockIdx.x + 1] = mean; part[3 * blockIdx.x + 2] = (red[0] + red[1]) + (red[2] + red[3]); }
+}
+// second half for an epoch's lists: block y runs k_mlp_prep's merge on list y's slices -> stats[2 y ..) — behind the kernel boundary
+// like there, so no device-scope fence is needed
+__global__ void __launch_bounds__(256) k_adv_merge(const float* __restrict__ part_all, int nb, int B, float* __restrict__ stats) {
+  __shared__ float sp[3 * MLP_ADV_BLOCKS];
+  const int t = threadIdx.x;
+  if (t < 3 * nb) sp[t] = part_all[(size_t)blockIdx.x * 3 * nb + t];
+  __syncthreads();
+  if (t == 0) mlp_adv_merge(sp, nb, B, stats + 2 * blockIdx.x);
+}
+
+// Where k_adam mirrors every parameter it updates (W1p == nullptr: nowhere): the operand images k_mlp_prep builds, which then
+// stay current from one optimizer step to the next without a prep launch.  Padding entries are k_mlp_prep's alone.
+struct MlpImgTarget {
+  unsigned short *W1p, *W2, *W2T, *Whp, *WhT;
+  float* bias;
+  int off_W1[2], off_b1[2], off_W2[2], off_b2[2], off_Wh[2], off_bh[2];     // (k_adam indexes the flat vector with an int)
+  int O, OP, A;
+};
+// parameter i of the flat vector has become x: the image entries k_mlp_prep would derive from it (its layout arithmetic, inverted;
+// unsigned differences: one compare per tensor, the large W2 first)
+__device__ __forceinline__ void mlp_img_store(const MlpImgTarget& T, int i, float x) {
+  constexpr unsigned H = MLP_H;
+#pragma unroll
+  for (int net = 0; net < 2; ++net) {
+    const unsigned Ah = net == 0 ? (unsigned)T.A : 1u;
+    unsigned j = (unsigned)(i - T.off_W2[net]);
+    if (j < H * H) {
+      const unsigned short v = mlp_f2bf(x);
+      T.W2[net * H * H + j] = v;
+      T.W2T[net * H * H + (j % H) * H + j / H] = v;
+      return;
+    }
+    j = (unsigned)(i - T.off_W1[net]);
+    if (j < H * (unsigned)T.O) { const unsigned o = j / (unsigned)T.O; T.W1p[net * H * T.OP + o * T.OP + (j - o * T.O)] = mlp_f2bf(x); return; }
+    j = (unsigned)(i - T.off_Wh[net]);
+    if (j < Ah * H) {
+      const unsigned short v = mlp_f2bf(x);
+      T.Whp[net * MLP_APM * H + j] = v;
+      T.WhT[net * H * MLP_AKP + (j % H) * MLP_AKP + j / H] = v;
+      return;
+    }
+    j = (unsigned)(i - T.off_b1[net]);
+    if (j < H) { T.bias[net * H + j] = x; return; }
+    j = (unsigned)(i - T.off_b2[net]);
+    if (j < H) { T.bias[2 * H + net * H + j] = x; return; }
+    j = (unsigned)(i - T.off_bh[net]);
+    if (j < Ah) { T.bias[4 * H + net * MLP_APM + j] = x; return; }
+  }
 }
 
 // One wave's slab of a layer: BM rows x 64 columns, acc[mt][nt] += A(LDS rows, K-contiguous) * W(global rows, K-contiguous)'.
@@ -189,7 +244,10 @@ __device__ __forceinline__ void mlp_mma_slab(myo_f32x4 (&acc)[MT][4], const unsi
 
 #ifdef MLP_PROF
 __device__ unsigned long long g_mlp_prof[16];
-#define MLP_STAMP(k) { __syncthreads(); if (threadIdx.x == 0 && blockIdx.x == 3 && blockIdx.y == 0) g_mlp_prof[k] = wall_clock64(); }
+#ifndef MLP_PROF_NET
+#define MLP_PROF_NET 0     // the stamped workgroup: row block 3 of the actor (0) or the critic (1)
+#endif
+#define MLP_STAMP(k) { __syncthreads(); if (threadIdx.x == 0 && blockIdx.x == 3 && blockIdx.y == MLP_PROF_NET) g_mlp_prof[k] = wall_clock64(); }
 extern "C" int myo_debug_mlp_prof(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mlp_prof), sizeof g_mlp_prof); }
 #else
 #define MLP_STAMP(k)
@@ -698,6 +756,12 @@ __global__ void __launch_bounds__(256) k_mlp_reduce_finish(MlpRfArgs P) {
   __shared__ float red[4];
   const int t = threadIdx.x, A = P.A;
   if ((int)blockIdx.x < MLP_RF_BLOCKS) {
+    // block 0 records the minibatch in the hyper-parameter block: it was the launch's long pole (16 us against 6 for the slab
+    // blocks) with five column sums one after the other and then the block's words read one dependent load at a time; the words
+    // are requested here, ahead of everything, and the five columns' loads go out together
+    const bool rec = P.hp && blockIdx.x == 0;
+    MyoHpWords hw = {};
+    if (rec && t == 0) hw = myo_hp_load(P.hp);
     float sq = 0.f;
     for (long long e = (long long)blockIdx.x * 256 + t; e < P.G; e += (long long)MLP_RF_BLOCKS * 256) {
       float s = 0.f;
@@ -709,16 +773,20 @@ __global__ void __launch_bounds__(256) k_mlp_reduce_finish(MlpRfArgs P) {
     for (int off = 32; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
     if ((t & 63) == 0) red[t >> 6] = sq;
     float pl = 0.f, vl = 0.f, kl = 0.f, cf = 0.f, el = 0.f;
-    if (P.hp && blockIdx.x == 0 && t < 64) {       // the loss columns this decision needs, in the column blocks' order
-      pl = myo_col_sum(P.part, A, P.NB, t); vl = myo_col_sum(P.part, A + 1, P.NB, t);
-      kl = myo_col_sum(P.part, 2 * A + 3, P.NB, t); cf = myo_col_sum(P.part, 2 * A + 4, P.NB, t); el = myo_col_sum(P.part, 2 * A + 5, P.NB, t);
+    if (rec && t < 64) {       // the loss columns this decision needs, each in the column blocks' order (myo_col_sum's)
+      const float* c0 = P.part + (size_t)A * P.NB; const float* c2 = P.part + (size_t)(2 * A + 3) * P.NB;
+      for (int b = t; b < P.NB; b += 64) { pl += c0[b]; vl += c0[P.NB + b]; kl += c2[b]; cf += c2[P.NB + b]; el += c2[2 * P.NB + b]; }
+      for (int off = 32; off >= 1; off >>= 1) {
+        pl += __shfl_xor(pl, off, 64); vl += __shfl_xor(vl, off, 64); kl += __shfl_xor(kl, off, 64);
+        cf += __shfl_xor(cf, off, 64); el += __shfl_xor(el, off, 64);
+      }
     }
     __syncthreads();
     if (t == 0) {
       P.sq_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
       if (blockIdx.x == 0) {
         // the stop flag has one reader and one writer in this launch (this thread); k_adam reads it after the kernel boundary
-        const bool stopped = P.hp ? myo_hp_record(P.hp, pl, vl, kl, cf, el) : false;
+        const bool stopped = P.hp ? myo_hp_apply(P.hp, hw, pl, vl, kl, cf, el) : false;
         if (!stopped) { const int done = P.adam_step[1]; P.adam_step[0] = done; P.adam_step[1] = done + 1; }
       }
     }

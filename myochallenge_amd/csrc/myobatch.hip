@@ -721,15 +721,27 @@ __global__ void __launch_bounds__(64) k_ppo_loss(const float* __restrict__ mean,
 // finishes the loss sums.  Returns true when the optimizer step that follows must not be applied: the stop flag was already up
 // (sticky: nothing is recorded, the flag and the diagnostics of the minibatch that raised it stay), or this minibatch's
 // approx_kl exceeds the limit (its diagnostics are recorded, as SB3 appends them before it breaks).
-__device__ __forceinline__ bool myo_hp_record(float* __restrict__ hp, float pl, float vl, float kl, float cf, float el) {
+// (in two halves: the six words it reads, requested together — a kernel may ask for them long before its sums are ready, the
+// recording thread being the block's only reader and writer in the launch — and the update from them)
+struct MyoHpWords { int stop, count; float sum_kl, sum_cf, sum_el, lim; };
+__device__ __forceinline__ MyoHpWords myo_hp_load(const float* hp) {
+  const int* hi = reinterpret_cast<const int*>(hp);
+  MyoHpWords w;
+  w.stop = hi[MYO_HP_STOP]; w.count = hi[MYO_HP_COUNT];
+  w.sum_kl = hp[MYO_HP_SUM_KL]; w.sum_cf = hp[MYO_HP_SUM_CLIPFRAC]; w.sum_el = hp[MYO_HP_SUM_ENTLOSS]; w.lim = hp[MYO_HP_KL_LIMIT];
+  return w;
+}
+__device__ __forceinline__ bool myo_hp_apply(float* hp, const MyoHpWords& w, float pl, float vl, float kl, float cf, float el) {
   int* hi = reinterpret_cast<int*>(hp);
-  if (hi[MYO_HP_STOP]) return true;
-  hp[MYO_HP_SUM_KL] += kl; hp[MYO_HP_SUM_CLIPFRAC] += cf; hp[MYO_HP_SUM_ENTLOSS] += el;
-  hi[MYO_HP_COUNT] += 1;
+  if (w.stop) return true;
+  hp[MYO_HP_SUM_KL] = w.sum_kl + kl; hp[MYO_HP_SUM_CLIPFRAC] = w.sum_cf + cf; hp[MYO_HP_SUM_ENTLOSS] = w.sum_el + el;
+  hi[MYO_HP_COUNT] = w.count + 1;
   hp[MYO_HP_LAST_KL] = kl; hp[MYO_HP_LAST_PL] = pl; hp[MYO_HP_LAST_VL] = vl;
-  const float lim = hp[MYO_HP_KL_LIMIT];
-  if (lim > 0.f && kl > lim) { hi[MYO_HP_STOP] = 1; return true; }
+  if (w.lim > 0.f && kl > w.lim) { hi[MYO_HP_STOP] = 1; return true; }
   return false;
+}
+__device__ __forceinline__ bool myo_hp_record(float* hp, float pl, float vl, float kl, float cf, float el) {
+  return myo_hp_apply(hp, myo_hp_load(hp), pl, vl, kl, cf, el);
 }
 // sum over blocks of column c of the loss partials, by one wave: the order k_colmajor_finish adds them in
 __device__ __forceinline__ float myo_col_sum(const float* __restrict__ part, int c, int NB, int lane) {
@@ -1669,6 +1681,8 @@ extern "C" int myo_gae(const float* rew, const float* val, const float* starts, 
   return MYO_OK;
 }
 
+#include "myo_ppo_mlp.h"      // (ahead of Adam: k_adam mirrors the parameters into the fused MLP step's operand images)
+
 // ------------------------------------------------------------------------------------------ Adam
 // clip_grad_norm_(max_norm) + torch.optim.Adam step (no weight decay / amsgrad) over ONE flat fp32
 // parameter vector: 2 launches instead of ~12 multi-tensor ones.  scratch[0] = sum g^2 (after
@@ -1694,8 +1708,8 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float
                                               float* __restrict__ v, int n, float lr, float b1, float b2, float eps,
                                               float max_norm, float gs, const int* __restrict__ step,
                                               const float* __restrict__ part, unsigned short* __restrict__ p_bf16, int nparts,
-                                              float* __restrict__ hp) {
-  if (hp) {       // lr from the hyper-parameter block; stop flag up: p, m, v and the bf16 shadow stay as they are
+                                              float* __restrict__ hp, MlpImgTarget img) {
+  if (hp) {       // lr from the hyper-parameter block; stop flag up: p, m, v, the bf16 shadow and the images stay as they are
     if (reinterpret_cast<const int*>(hp)[MYO_HP_STOP]) return;
     lr = hp[MYO_HP_LR];
   }
@@ -1723,18 +1737,20 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float
     const float pn = p[i] - step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
     p[i] = pn;
     if (p_bf16) p_bf16[i] = myo_f2bf(pn);          // the bf16 shadow the GEMMs read: no separate cast pass
+    if (img.W1p) mlp_img_store(img, i, pn);        // and the fused MLP step's operand images: no prep launch per step
   }
   if (hp && blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<int*>(hp)[MYO_HP_APPLIED] += 1;
 }
+static const MlpImgTarget kNoImages = {};
 static int adam_clip_step(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
                           float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
-                          float* hp, void* stream) {
+                          float* hp, void* stream, const MlpImgTarget& img = kNoImages) {
   if (!p || !g || !m || !v || !step || !scratch || n <= 0) return fail(MYO_E_ARG, "myo_adam_clip_step: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
   hipLaunchKernelGGL(k_grad_sqnorm, dim3(MYO_SQN_BLOCKS), dim3(256), 0, st, g, n, grad_scale, scratch, step, (const float*)hp);
   hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch,
-                     (unsigned short*)p_bf16, MYO_SQN_BLOCKS, hp);
+                     (unsigned short*)p_bf16, MYO_SQN_BLOCKS, hp, img);
   LAUNCH_CHECK(0)
   return MYO_OK;
 }
@@ -1750,11 +1766,11 @@ extern "C" int myo_adam_clip_step_hp(float* p, const float* g, float* m, float* 
 }
 static int adam_apply(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
                       float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
-                      uint16_t* p_bf16, float* hp, void* stream) {
+                      uint16_t* p_bf16, float* hp, void* stream, const MlpImgTarget& img = kNoImages) {
   if (!p || !g || !m || !v || !step || !scratch || n <= 0 || nparts <= 0) return fail(MYO_E_ARG, "myo_adam_apply: bad arguments");
   const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
   hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch,
-                     (unsigned short*)p_bf16, nparts, hp);
+                     (unsigned short*)p_bf16, nparts, hp, img);
   LAUNCH_CHECK(0)
   return MYO_OK;
 }
@@ -1770,7 +1786,6 @@ extern "C" int myo_adam_apply_hp(float* p, const float* g, float* m, float* v, i
 }
 
 // ------------------------------------------------------------------------------------------ fused MLP PPO step
-#include "myo_ppo_mlp.h"
 struct MlpWs { unsigned short *W1p, *W2, *W2T, *Whp, *WhT; float* bias; unsigned short *XT, *H1T, *H2T, *dH1T, *dH2T, *dOT; float *part, *slab, *advpart; size_t bytes; };
 static MlpWs mlp_carve(unsigned char* base, int B, int OP, int A, long long G) {
   MlpWs w;
@@ -1800,31 +1815,42 @@ extern "C" long long myo_ppo_mlp_workspace_bytes(int B, int obs_dim, int act_dim
 extern "C" int myo_ppo_mlp_sqnorm_parts(int act_dim) {
   return MLP_RF_BLOCKS + 2 * act_dim + 3;
 }
-extern "C" int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream) {
-  if (!d || !d->obs || !d->act || !d->oldlp || !d->adv || !d->ret || !d->idx || !d->params || !d->grads || !d->adv_stats || !d->acc ||
-      !d->workspace)
-    return fail(MYO_E_ARG, "myo_ppo_mlp_step: null argument");
-  const int B = d->B, O = d->O, A = d->A, OP = (O + 31) / 32 * 32;
-  if (!mlp_shape_ok(B, O, A, d->hidden)) return fail(MYO_E_UNSUPPORTED, "myo_ppo_mlp_step: needs hidden = %d, obs <= %d, act <= %d, batch a multiple of %d", MLP_H, MLP_OPMAX, MLP_APM, 64 * MLP_SPLITK);
-  const MlpWs w = mlp_carve((unsigned char*)d->workspace, B, OP, A, d->G);
-  if ((long long)w.bytes > d->workspace_bytes) return fail(MYO_E_ARG, "myo_ppo_mlp_step: workspace too small (%zu bytes needed)", w.bytes);
-  hipStream_t st = (hipStream_t)stream;
-  static bool lds_set = false;
-  if (!lds_set) {
-    if (hipFuncSetAttribute((const void*)k_mlp_fwdbwd, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_FWDBWD_LDS) != hipSuccess)
-      return fail(MYO_E_DEVICE, "myo_ppo_mlp_step: cannot reserve %d bytes of LDS", (int)MLP_FWDBWD_LDS);
-    lds_set = true;
-  }
-  if (d->compute_adv_stats) hipLaunchKernelGGL(k_adv_moments, dim3(MLP_ADV_BLOCKS), dim3(256), 0, st, d->adv, (const long long*)d->idx, B, w.advpart);
+static MlpPrepArgs mlp_prep_args(const myo_ppo_mlp_desc* d, const MlpWs& w, int OP) {
   MlpPrepArgs pp;
-  pp.p = d->params; pp.O = O; pp.OP = OP; pp.Ah[0] = A; pp.Ah[1] = 1;
+  pp.p = d->params; pp.O = d->O; pp.OP = OP; pp.Ah[0] = d->A; pp.Ah[1] = 1;
   for (int k = 0; k < 2; ++k) {
     pp.off_W1[k] = d->off_W1[k]; pp.off_b1[k] = d->off_b1[k]; pp.off_W2[k] = d->off_W2[k]; pp.off_b2[k] = d->off_b2[k];
     pp.off_Wh[k] = d->off_Wh[k]; pp.off_bh[k] = d->off_bh[k];
   }
-  pp.adv_part = w.advpart; pp.adv_stats = d->adv_stats; pp.adv_nb = d->compute_adv_stats ? MLP_ADV_BLOCKS : 0; pp.B = B;
+  pp.adv_part = nullptr; pp.adv_stats = nullptr; pp.adv_nb = 0; pp.B = d->B;
   pp.W1p = w.W1p; pp.W2 = w.W2; pp.W2T = w.W2T; pp.Whp = w.Whp; pp.WhT = w.WhT; pp.bias = w.bias;
-  hipLaunchKernelGGL(k_mlp_prep, dim3(256), dim3(256), 0, st, pp);
+  return pp;
+}
+// resident: the operand images at the front of the workspace are current (myo_ppo_mlp_images once, then the Adam kernel of
+// myo_adam_*_images after every step) and the advantage moments are the caller's: neither k_adv_moments nor k_mlp_prep runs
+static int mlp_step(const myo_ppo_mlp_desc* d, void* stream, bool resident) {
+  const char* who = resident ? "myo_ppo_mlp_step_resident" : "myo_ppo_mlp_step";
+  if (!d || !d->obs || !d->act || !d->oldlp || !d->adv || !d->ret || !d->idx || !d->params || !d->grads || !d->adv_stats || !d->acc ||
+      !d->workspace)
+    return fail(MYO_E_ARG, "%s: null argument", who);
+  const int B = d->B, O = d->O, A = d->A, OP = (O + 31) / 32 * 32;
+  if (!mlp_shape_ok(B, O, A, d->hidden)) return fail(MYO_E_UNSUPPORTED, "%s: needs hidden = %d, obs <= %d, act <= %d, batch a multiple of %d", who, MLP_H, MLP_OPMAX, MLP_APM, 64 * MLP_SPLITK);
+  if (resident && d->compute_adv_stats) return fail(MYO_E_ARG, "%s: the advantage moments are the caller's (compute_adv_stats = 0)", who);
+  const MlpWs w = mlp_carve((unsigned char*)d->workspace, B, OP, A, d->G);
+  if ((long long)w.bytes > d->workspace_bytes) return fail(MYO_E_ARG, "%s: workspace too small (%zu bytes needed)", who, w.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  static bool lds_set = false;
+  if (!lds_set) {
+    if (hipFuncSetAttribute((const void*)k_mlp_fwdbwd, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_FWDBWD_LDS) != hipSuccess)
+      return fail(MYO_E_DEVICE, "%s: cannot reserve %d bytes of LDS", who, (int)MLP_FWDBWD_LDS);
+    lds_set = true;
+  }
+  if (!resident) {
+    if (d->compute_adv_stats) hipLaunchKernelGGL(k_adv_moments, dim3(MLP_ADV_BLOCKS), dim3(256), 0, st, d->adv, (const long long*)d->idx, B, w.advpart);
+    MlpPrepArgs pp = mlp_prep_args(d, w, OP);
+    pp.adv_part = w.advpart; pp.adv_stats = d->adv_stats; pp.adv_nb = d->compute_adv_stats ? MLP_ADV_BLOCKS : 0;
+    hipLaunchKernelGGL(k_mlp_prep, dim3(256), dim3(256), 0, st, pp);
+  }
   MlpArgs a;
   a.obs = d->obs; a.act = d->act; a.oldlp = d->oldlp; a.adv = d->adv; a.ret = d->ret; a.idx = (const long long*)d->idx;
   a.log_std = d->params + d->off_log_std; a.adv_stats = d->adv_stats;
@@ -1856,6 +1882,60 @@ extern "C" int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream) {
     hipLaunchKernelGGL(k_colmajor_finish, dim3(2 * A + 3 + (d->hp ? 1 : 0)), dim3(64), 0, st, (const float*)w.part, d->acc, B / MLP_BM, A, d->ent_coef,
                        d->grads + d->off_log_std, d->grads + d->off_bh[0], d->grads + d->off_bh[1], d->hp);
   }
+  LAUNCH_CHECK(0)
+  return MYO_OK;
+}
+extern "C" int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream) { return mlp_step(d, stream, false); }
+extern "C" int myo_ppo_mlp_step_resident(const myo_ppo_mlp_desc* d, void* stream) { return mlp_step(d, stream, true); }
+// the checks the image calls share: the fields of `d` that place the images
+static int mlp_images_ok(const myo_ppo_mlp_desc* d, const char* who, MlpWs* w) {
+  if (!d || !d->params || !d->workspace) return fail(MYO_E_ARG, "%s: null argument", who);
+  if (!mlp_shape_ok(d->B, d->O, d->A, d->hidden)) return fail(MYO_E_UNSUPPORTED, "%s: needs hidden = %d, obs <= %d, act <= %d, batch a multiple of %d", who, MLP_H, MLP_OPMAX, MLP_APM, 64 * MLP_SPLITK);
+  *w = mlp_carve((unsigned char*)d->workspace, d->B, (d->O + 31) / 32 * 32, d->A, d->G);
+  if ((long long)w->bytes > d->workspace_bytes) return fail(MYO_E_ARG, "%s: workspace too small (%zu bytes needed)", who, w->bytes);
+  return MYO_OK;
+}
+extern "C" int myo_ppo_mlp_images(const myo_ppo_mlp_desc* d, void* stream) {
+  MlpWs w;
+  if (int rc = mlp_images_ok(d, "myo_ppo_mlp_images", &w)) return rc;
+  hipLaunchKernelGGL(k_mlp_prep, dim3(256), dim3(256), 0, (hipStream_t)stream, mlp_prep_args(d, w, (d->O + 31) / 32 * 32));
+  LAUNCH_CHECK(0)
+  return MYO_OK;
+}
+static int mlp_img_target(const myo_ppo_mlp_desc* d, int n, const char* who, MlpImgTarget* T) {
+  MlpWs w;
+  if (int rc = mlp_images_ok(d, who, &w)) return rc;
+  if (d->G != n) return fail(MYO_E_ARG, "%s: the descriptor's parameter vector has %lld elements, this one %d", who, (long long)d->G, n);
+  T->W1p = w.W1p; T->W2 = w.W2; T->W2T = w.W2T; T->Whp = w.Whp; T->WhT = w.WhT; T->bias = w.bias;
+  for (int k = 0; k < 2; ++k) {
+    const int64_t off[6] = {d->off_W1[k], d->off_b1[k], d->off_W2[k], d->off_b2[k], d->off_Wh[k], d->off_bh[k]};
+    for (int q = 0; q < 6; ++q)
+      if (off[q] < 0 || off[q] >= n) return fail(MYO_E_ARG, "%s: a tensor offset lies outside the %d parameters", who, n);
+    T->off_W1[k] = (int)off[0]; T->off_b1[k] = (int)off[1]; T->off_W2[k] = (int)off[2]; T->off_b2[k] = (int)off[3];
+    T->off_Wh[k] = (int)off[4]; T->off_bh[k] = (int)off[5];
+  }
+  T->O = d->O; T->OP = (d->O + 31) / 32 * 32; T->A = d->A;
+  return MYO_OK;
+}
+extern "C" int myo_adam_clip_step_images(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                                         float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
+                                         float* hp, const myo_ppo_mlp_desc* images, void* stream) {
+  MlpImgTarget T;
+  if (int rc = mlp_img_target(images, n, "myo_adam_clip_step_images", &T)) return rc;
+  return adam_clip_step(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, p_bf16, hp, stream, T);
+}
+extern "C" int myo_adam_apply_images(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                                     float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
+                                     uint16_t* p_bf16, float* hp, const myo_ppo_mlp_desc* images, void* stream) {
+  MlpImgTarget T;
+  if (int rc = mlp_img_target(images, n, "myo_adam_apply_images", &T)) return rc;
+  return adam_apply(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, nparts, p_bf16, hp, stream, T);
+}
+extern "C" int myo_ppo_adv_moments_epoch(const float* adv, const int64_t* idx, int B, int n_mb, float* stats, float* scratch, void* stream) {
+  if (!adv || !idx || !stats || !scratch || B <= 0 || n_mb <= 0 || n_mb > 65535) return fail(MYO_E_ARG, "myo_ppo_adv_moments_epoch: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_adv_moments, dim3(MLP_ADV_BLOCKS, n_mb), dim3(256), 0, st, adv, (const long long*)idx, B, scratch);
+  hipLaunchKernelGGL(k_adv_merge, dim3(n_mb), dim3(256), 0, st, (const float*)scratch, MLP_ADV_BLOCKS, B, stats);
   LAUNCH_CHECK(0)
   return MYO_OK;
 }

@@ -237,6 +237,11 @@ class NativeLib:
         L.myo_ppo_mlp_workspace_bytes.argtypes = [i32, i32, i32, i32, C.c_longlong]
         L.myo_ppo_mlp_step.argtypes = [C.POINTER(PpoMlpDesc), vp]
         L.myo_ppo_mlp_sqnorm_parts.argtypes = [i32]
+        L.myo_ppo_mlp_step_resident.argtypes = [C.POINTER(PpoMlpDesc), vp]
+        L.myo_ppo_mlp_images.argtypes = [C.POINTER(PpoMlpDesc), vp]
+        L.myo_ppo_adv_moments_epoch.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+        L.myo_adam_clip_step_images.argtypes = L.myo_adam_clip_step_hp.argtypes[:-1] + [C.POINTER(PpoMlpDesc), vp]
+        L.myo_adam_apply_images.argtypes = L.myo_adam_apply_hp.argtypes[:-1] + [C.POINTER(PpoMlpDesc), vp]
         L.myo_ppo_mlp_rollout_workspace_bytes.restype = C.c_longlong
         L.myo_ppo_mlp_rollout_workspace_bytes.argtypes = [i32, i32, i32]
         L.myo_ppo_mlp_rollout_refresh.argtypes = [C.POINTER(PpoMlpRolloutDesc), vp]
@@ -286,6 +291,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
+    "myo_ppo_mlp_step_resident", "myo_ppo_mlp_images", "myo_ppo_adv_moments_epoch", "myo_adam_clip_step_images", "myo_adam_apply_images",
 ]
 
 # ... of which the lane-serial emulation build (tests/emu/libmyobatch_emu.so: csrc/myobatch_emu.cpp + csrc/emu_host.h, test tooling) has the env

@@ -166,6 +166,7 @@ class FlatAdam:
         self.presummed = 0        # > 0: the gradient's producer has left that many partial sums in `sq` and advanced the step counter
         self.shadow = None        # bf16 copy of the flat parameters kept in step by the Adam kernel (FusedPPOStep sets it)
         self.hp = None            # PPO hyper-parameter block (include/myobatch.h): lr and the stop flag are read from it at run time
+        self.images = None        # descriptor of a fused MLP step with resident operand images: the Adam kernel keeps them current
 
     @property
     def step_count(self):
@@ -179,6 +180,20 @@ class FlatAdam:
         f = self.flat
         stream = torch.cuda.current_stream(f["p"].device).cuda_stream
         p = lambda t: C.c_void_p(t.data_ptr())
+        if self.images is not None:
+            sh = p(self.shadow) if self.shadow is not None else None
+            hp = p(self.hp) if self.hp is not None else None
+            if self.presummed > 0:
+                self.lib.check(self.lib.L.myo_adam_apply_images(
+                    p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
+                    self.eps, self.max_norm, float(grad_scale), p(self._step), p(self.sq), int(self.presummed), sh, hp,
+                    C.byref(self.images), C.c_void_p(stream)))
+            else:
+                self.lib.check(self.lib.L.myo_adam_clip_step_images(
+                    p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
+                    self.eps, self.max_norm, float(grad_scale), p(self._step), p(self.sq), sh, hp, C.byref(self.images),
+                    C.c_void_p(stream)))
+            return
         if self.hp is not None:
             sh = p(self.shadow) if self.shadow is not None else None
             if self.presummed > 0:
@@ -210,6 +225,9 @@ class FlatAdam:
             t.copy_(s)
         if self.shadow is not None:
             self.shadow.copy_(self.flat["p"])
+        if self.images is not None:       # resident operand images: they mirror the parameters like the shadow
+            stream = torch.cuda.current_stream(self.flat["p"].device).cuda_stream
+            self.lib.check(self.lib.L.myo_ppo_mlp_images(C.byref(self.images), C.c_void_p(stream)))
 
 
 class FusedPPOStep:
@@ -255,6 +273,13 @@ class FusedPPOStep:
         self.use_mfma_step = True            # the one-launch-per-stage path (csrc/myo_ppo_mlp.h) whenever the shapes fit
         self.adam = None                     # FlatAdam whose |g|^2 partials / step counter the fused step fills (single rank; PPO sets it)
         self.hp = None                       # PPO hyper-parameter block (include/myobatch.h): clip_range read at run time, diagnostics, KL stop
+        # Resident operand images (myo_ppo_mlp_step_resident): the step runs neither the image pass nor the moments pass.  Only for a
+        # driver that (i) calls refresh_images() whenever the parameters may have been written from outside and (ii) takes every
+        # optimizer step through this FlatAdam, whose kernel then mirrors the parameters into the images (one rank: the same object as
+        # self.adam).  None: the stateless step.  PPO sets it (MYO_PPO_RESIDENT=0: off).
+        self.resident_adam = None
+        self.adv_slot = None                 # resident step: where its advantage moments are (a row of epoch_moments' output); None: self.stats
+        self._moments = {}                   # per n_mb: (stats [n_mb, 2], scratch) of epoch_moments
 
     # ---- fused forward / loss / backward on the matrix cores (libmyobatch: myo_ppo_mlp_step)
     def _mfma_desc(self, B, obs_all, act_all, oldlp_all, adv_all, ret_all, idx):
@@ -306,7 +331,34 @@ class FusedPPOStep:
         if self.adam is not None and self.lib.L.myo_ppo_mlp_sqnorm_parts(self.A) <= self.adam.sq.numel():
             d.sqnorm_part, d.adam_step = self.adam.sq.data_ptr(), self.adam._step.data_ptr()
         self._mfma[key] = (d, ws)
+        if self.resident_adam is not None:   # (a new workspace: its images have never been written)
+            stream = torch.cuda.current_stream(obs_all.device).cuda_stream
+            self.lib.check(self.lib.L.myo_ppo_mlp_images(C.byref(d), C.c_void_p(stream)))
         return d
+
+    def refresh_images(self):
+        """Resident operand images of every fused-step workspace from the current parameters (one launch each, padding included)."""
+        stream = torch.cuda.current_stream(self.acc.device).cuda_stream
+        for d, _ in self._mfma.values():
+            if d is not None:
+                self.lib.check(self.lib.L.myo_ppo_mlp_images(C.byref(d), C.c_void_p(stream)))
+
+    def moments_buffers(self, n_mb):
+        hit = self._moments.get(n_mb)
+        if hit is None:
+            dev = self.acc.device
+            hit = self._moments[n_mb] = (torch.zeros((n_mb, 2), device=dev), torch.zeros(192 * n_mb, device=dev))
+        return hit
+
+    def epoch_moments(self, adv_all, idx, B, n_mb):
+        """{mean, unbiased std} of adv_all[idx[k B : (k + 1) B]] for the n_mb minibatches of an index list, [n_mb, 2], in two launches
+        (myo_ppo_adv_moments_epoch) — each row is what the stateless step computes for that minibatch.  The output tensor is cached
+        per n_mb (moments_buffers: call that once outside a capture): hipGraph-safe."""
+        hit = self.moments_buffers(n_mb)
+        stream = torch.cuda.current_stream(adv_all.device).cuda_stream
+        self.lib.check(self.lib.L.myo_ppo_adv_moments_epoch(C.c_void_p(adv_all.data_ptr()), C.c_void_p(idx.data_ptr()), B, n_mb,
+                                                            C.c_void_p(hit[0].data_ptr()), C.c_void_p(hit[1].data_ptr()), C.c_void_p(stream)))
+        return hit[0]
 
     # ---- rollout inference + sampling on the matrix cores (libmyobatch: myo_ppo_mlp_rollout)
     def rollout_desc(self, obs, seed, draw, t_idx, obs_buf, act_buf, val_buf, logp_buf, clipped):
@@ -356,9 +408,20 @@ class FusedPPOStep:
         self.lib.check(self.lib.L.myo_ppo_mlp_rollout(C.byref(d), C.c_void_p(stream)))
 
     def _mfma_step(self, d):
-        d.compute_adv_stats = 0 if self.external_adv_stats else 1
         stream = torch.cuda.current_stream(self.acc.device).cuda_stream
-        self.lib.check(self.lib.L.myo_ppo_mlp_step(C.byref(d), C.c_void_p(stream)))
+        if self.resident_adam is not None:
+            slot = self.adv_slot if self.adv_slot is not None else self.stats
+            if self.adv_slot is None and not self.external_adv_stats:      # no epoch's moments at hand: this minibatch's, into self.stats
+                self.lib.check(self.lib.L.myo_ppo_adv_moments_epoch(C.c_void_p(d.adv), C.c_void_p(d.idx), d.B, 1, C.c_void_p(slot.data_ptr()),
+                                                                    C.c_void_p(self.moments_buffers(1)[1].data_ptr()), C.c_void_p(stream)))
+            d.compute_adv_stats, d.adv_stats = 0, slot.data_ptr()
+            self.lib.check(self.lib.L.myo_ppo_mlp_step_resident(C.byref(d), C.c_void_p(stream)))
+            self.resident_adam.images = d
+        else:
+            d.compute_adv_stats, d.adv_stats = (0 if self.external_adv_stats else 1), self.stats.data_ptr()
+            self.lib.check(self.lib.L.myo_ppo_mlp_step(C.byref(d), C.c_void_p(stream)))
+            if self.adam is not None:
+                self.adam.images = None
         if self.adam is not None:           # the Adam call that follows takes the partial sums this step left (or does its own)
             self.adam.presummed = self.lib.L.myo_ppo_mlp_sqnorm_parts(self.A) if d.sqnorm_part else 0
         return self.acc[self.A], self.acc[self.A + 1]

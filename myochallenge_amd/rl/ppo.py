@@ -172,6 +172,9 @@ class PPO:
         self._hp_write()                 # (a minibatch step run before the first train(), as the tests do, reads the block too)
         if self._fused is not None and self.world == 1 and os.environ.get("MYO_ADAM_SEPARATE") != "1":
             self._fused.adam = self._flat_adam   # nothing is exchanged between gradient and clip: the fused step also squares the gradient
+        if self._fused is not None and os.environ.get("MYO_PPO_RESIDENT") != "0":
+            # the fused step's operand images stay resident: rebuilt once per train(), kept current by the Adam kernel (any world size)
+            self._fused.resident_adam = self._flat_adam
         self.rank = dist.get_rank() if self.world > 1 else 0
         N, T, O, A = env.num_envs, cfg.n_steps, env.obs_dim, env.act_dim
         d = self.device
@@ -892,13 +895,14 @@ class PPO:
     def _mb_apply(self):
         self._flat_adam.step(1.0 / self.world)    # all-reduce SUM ran in place on the flat gradient
 
-    def _capture_step(self, forward_backward, g, graph_allreduce=False, epoch_steps=0):
+    def _capture_step(self, forward_backward, g, graph_allreduce=False, epoch_steps=0, epoch_begin=None, step_begin=None):
         """Capture one minibatch step — forward_backward() on the static tensors `g`, then _mb_apply() — and return
         (fb, ap, epoch, allreduce_inside).  One rank: `fb` is the whole step.  N > 1 ranks: `fb` ends with the gradient, the RCCL
         all-reduce runs eagerly, and `ap` is clip + Adam; or, with graph_allreduce on the nccl backend, `fb` is the whole step with the
         collective inside it (ap None, allreduce_inside True).  epoch_steps = k > 0 also captures `epoch`: k minibatch steps, each
-        with its index copy out of g["perm"] (allocated here), in one graph.  The parameters and the Adam state come out as they
-        went in."""
+        with its index copy out of g["perm"] (allocated here), in one graph; epoch_begin() is captured ahead of the k steps (work on
+        the whole window g["perm"]) and step_begin(j) is called before step j is captured, step_begin(None) after the last.  The
+        parameters and the Adam state come out as they went in."""
         d = self.device
         side = torch.cuda.Stream(device=d)
         # warm-up and capture must not move the parameters.  The snapshot is taken BEFORE the side stream is told to wait: its copies run
@@ -948,11 +952,19 @@ class PPO:
             g["perm"].copy_(torch.arange(epoch_steps * bs, device=d))
             torch.cuda.synchronize(d)
             epoch = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(epoch, capture_error_mode="thread_local"):
-                for s in range(0, epoch_steps * bs, bs):
-                    g["idx"].copy_(g["perm"][s:s + bs])
-                    forward_backward()
-                    self._mb_apply()
+            try:
+                with torch.cuda.graph(epoch, capture_error_mode="thread_local"):
+                    if epoch_begin is not None:
+                        epoch_begin()
+                    for s in range(0, epoch_steps * bs, bs):
+                        if step_begin is not None:
+                            step_begin(s // bs)
+                        g["idx"].copy_(g["perm"][s:s + bs])
+                        forward_backward()
+                        self._mb_apply()
+            finally:
+                if step_begin is not None:
+                    step_begin(None)
         self._flat_adam.restore(snap)
         return fb, ap, epoch, inside
 
@@ -1055,8 +1067,21 @@ class PPO:
         if self.world == 1 and os.environ.get("MYO_EPOCH_GRAPH") != "0" and n_mb > 1:
             self._epoch_chunk = max(1, min(n_mb, int(os.environ.get("MYO_EPOCH_GRAPH_STEPS", "64"))))
         asked = self.world > 1 and (self.cfg.graph_allreduce or os.environ.get("MYO_GRAPH_ALLREDUCE") == "1")
+        fused, hooks = self._fused, {}
+        if fused.resident_adam is not None and self._epoch_chunk and not fused.external_adv_stats:
+            # resident step: the advantage moments of the chunk's minibatches in two launches ahead of its steps, each step reading its
+            # row, instead of one moments pass per step (the per-step graph computes its own minibatch's: _mfma_step)
+            k = self._epoch_chunk
+            fused.moments_buffers(k)         # (allocated here, not inside the capture)
+
+            def epoch_begin():
+                self._chunk_moments = fused.epoch_moments(self._gs["adv"], self._gs["perm"], bs, k)
+
+            def step_begin(j):
+                fused.adv_slot = None if j is None else self._chunk_moments[j]
+            hooks = dict(epoch_begin=epoch_begin, step_begin=step_begin)
         self._graph_fb, self._graph_ap, self._graph_epoch, self._allreduce_in_graph = self._capture_step(
-            self._mb_forward_backward, self._gs, graph_allreduce=asked, epoch_steps=self._epoch_chunk)
+            self._mb_forward_backward, self._gs, graph_allreduce=asked, epoch_steps=self._epoch_chunk, **hooks)
         self._graph = (B, bs)
 
     def _train_graphed(self, adv, ret):
@@ -1074,6 +1099,8 @@ class PPO:
             self._hp_write()             # (the capture's warm-up steps have left their marks in the block)
         g = self._gs
         g["adv"].copy_(adv.view(B)); g["ret"].copy_(ret.view(B))
+        if self._fused.resident_adam is not None:
+            self._fused.refresh_images()      # (parameters may have been loaded or edited since the last update)
         if not cfg.normalize_advantage:
             self._fused.stats.copy_(torch.tensor([0.0, 1.0], device=self.device))
         self._run_captured(B, bs, g, self._graph_fb, self._graph_ap,
