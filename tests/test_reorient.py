@@ -357,20 +357,16 @@ def test_reorient_ppo_lstm_on_gpu(hip_lib):
     assert float((qp[:, -4:].norm(dim=-1) - 1).abs().max()) < 1e-3 and torch.isfinite(qp).all()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("arch,hidden,sde", [((64, 64), 32, False), ((), 32, False), ((64, 64), 48, False), ((), 32, True), ((64,), 32, True)],
-                         ids=["lstm+mlp", "lstm-only", "gemm+cell-kernels", "lstm-only-gsde", "lstm+mlp-gsde"])
-def test_fused_recurrent_step_matches_autograd(hip_lib, monkeypatch, arch, hidden, sde):
-    """rl/fused_lstm.py (hand-derived LSTM + trunk + loss forward / backward in bf16) against autograd under bf16
-    autocast on the same minibatch of sequences: losses and every parameter's gradient, with episode starts inside
-    the sequences and a non-zero LSTM state at the rollout start."""
+def fused_recurrent_pair(monkeypatch, arch, hidden, sde, N=128, T=8, m=64):
+    """Set-up shared by test_fused_recurrent_step_matches_autograd and tests/test_lstm_kernels.py: two PPO instances on copies of one
+    policy — `a` with the fused recurrent step, `b` with autograd — holding the same second rollout (non-zero LSTM state at its start,
+    episode starts inside it), its advantages / returns and one minibatch of m envs.  Returns (a, b, adv, ret, idx, pol)."""
     import copy
     from myochallenge_amd.envs.environment_factory import EnvironmentFactory
     from myochallenge_amd.rl.policy import ActorCriticPolicy
     from myochallenge_amd.rl.ppo import PPO, PPOConfig, compute_gae
     from myochallenge_amd.rl.vec_normalize import VecNormalize
     torch.manual_seed(0)
-    N, T, m = 128, 8, 64
     env = EnvironmentFactory.create("CustomMyoReorientP1", num_envs=N, seed=3)
     # () = the reference's phase-1 policy shape; with gSDE: the FIRST_TASK branch of the archived curriculum scripts (LSTM-128, net_arch=[], use_sde)
     pol = ActorCriticPolicy(env.obs_dim, env.act_dim, arch, arch, lstm_hidden_size=hidden, use_sde=sde)
@@ -393,6 +389,18 @@ def test_fused_recurrent_step_matches_autograd(hip_lib, monkeypatch, arch, hidde
     assert float(a._rollout_state0[0].abs().max()) > 0
     adv, ret = compute_gae(a.rew_buf, a.val_buf, a.start_buf, a._last_values, a._last_starts, 0.99, 0.95)
     idx = torch.randperm(N, device=a.device)[:m]
+    return a, b, adv, ret, idx, pol
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("arch,hidden,sde", [((64, 64), 32, False), ((), 32, False), ((64, 64), 48, False), ((), 32, True), ((64,), 32, True)],
+                         ids=["lstm+mlp", "lstm-only", "gemm+cell-kernels", "lstm-only-gsde", "lstm+mlp-gsde"])
+def test_fused_recurrent_step_matches_autograd(hip_lib, monkeypatch, arch, hidden, sde):
+    """rl/fused_lstm.py (hand-derived LSTM + trunk + loss forward / backward in bf16) against autograd under bf16
+    autocast on the same minibatch of sequences: losses and every parameter's gradient, with episode starts inside
+    the sequences and a non-zero LSTM state at the rollout start."""
+    N, T, m = 128, 8, 64
+    a, b, adv, ret, idx, pol = fused_recurrent_pair(monkeypatch, arch, hidden, sde, N, T, m)
     grads, losses = [], []
     for algo in (a, b):
         g = algo._rec_stage(adv, ret, T, N, m)
