@@ -470,22 +470,16 @@ int myo_batch_enable_timing(myo_batch* b, int on);
  * block order by a second small launch (deterministic, no float atomics).
  * in_bf16 != 0: `mean` and `values` point to bfloat16 data (the GEMM outputs) instead of float32.
  * Optional direct gradient outputs (NULL to skip): g_log_std[A] = acc[0..A) - ent_coef,
- * g_bias_pi[A] = acc[A+2..2A+2), g_bias_vf[1] = acc[2A+2]. */
+ * g_bias_pi[A] = acc[A+2..2A+2), g_bias_vf[1] = acc[2A+2].
+ * hp: the PPO hyper-parameter block (layout below, beside myo_ppo_mlp_desc) or NULL = all of the above.  With it clip_range is
+ * hp[MYO_HP_CLIP] (`clip` is ignored), `work` has ceil(B/64) * (2A+6) floats (three more columns: approx_kl, clip fraction,
+ * entropy loss) and the second launch records the minibatch in the block and raises its stop flag when approx_kl >
+ * hp[MYO_HP_KL_LIMIT]. */
 int myo_ppo_loss_grad(const float* mean, const float* values, const float* actions, const float* old_logp,
                       const float* adv, const float* returns, const float* log_std, const float* adv_stats,
                       int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
                       uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
-                      float* g_log_std, float* g_bias_pi, float* g_bias_vf, void* stream);
-
-/* myo_ppo_loss_grad with the PPO hyper-parameter block `hp` (layout below, beside myo_ppo_mlp_desc).  hp == NULL: exactly
- * myo_ppo_loss_grad.  Otherwise clip_range is hp[MYO_HP_CLIP] (`clip` is ignored), `work` has ceil(B/64) * (2A+6) floats (three
- * more columns: approx_kl, clip fraction, entropy loss) and the second launch records the minibatch in the block and raises its
- * stop flag when approx_kl > hp[MYO_HP_KL_LIMIT]. */
-int myo_ppo_loss_grad_hp(const float* mean, const float* values, const float* actions, const float* old_logp,
-                         const float* adv, const float* returns, const float* log_std, const float* adv_stats,
-                         int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
-                         uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
-                         float* g_log_std, float* g_bias_pi, float* g_bias_vf, float* hp, void* stream);
+                      float* g_log_std, float* g_bias_pi, float* g_bias_vf, float* hp, void* stream);
 
 /* Minibatch gather of one optimiser step (SB3 RolloutBuffer.get + the per-minibatch advantage
  * normalisation statistics of PPO.train): rows idx[0..bs) (dev int64) of obs[N,obs_dim] act[N,act_dim]
@@ -686,6 +680,12 @@ int myo_gae(const float* rew, const float* val, const float* starts, const float
 #define MYO_HP_LAST_PL 10
 #define MYO_HP_LAST_VL 11
 #define MYO_HP_WORDS 16
+/* Where the MLP actor-critic's tensors lie in its flat fp32 parameter (and gradient) vector: offsets in ELEMENTS, [0] actor /
+ * [1] critic; W1 [hidden, obs], W2 [hidden, hidden], Wh [act, hidden] (actor) and [1, hidden] (critic), row-major, their biases,
+ * log_std [act]. */
+typedef struct myo_mlp_layout {
+  int64_t off_W1[2], off_b1[2], off_W2[2], off_b2[2], off_Wh[2], off_bh[2], off_log_std;
+} myo_mlp_layout;
 typedef struct myo_ppo_mlp_desc {
   const float *obs, *act, *oldlp, *adv, *ret;
   const int64_t* idx;
@@ -693,7 +693,7 @@ typedef struct myo_ppo_mlp_desc {
   const float* params;
   float* grads;
   int64_t G;
-  int64_t off_W1[2], off_b1[2], off_W2[2], off_b2[2], off_Wh[2], off_bh[2], off_log_std;
+  myo_mlp_layout layout;
   float clip, vf_coef, ent_coef;
   int32_t compute_adv_stats;
   float* adv_stats;
@@ -701,8 +701,8 @@ typedef struct myo_ppo_mlp_desc {
   void* workspace;
   int64_t workspace_bytes;
   /* single-rank tail (both NULL: off): the squares of the finished gradient, in myo_ppo_mlp_sqnorm_parts(act_dim) partial sums
-   * -> sqnorm_part, and Adam's step counter advanced (adam_step: the int32[2] of myo_adam_clip_step) — then myo_adam_apply
-   * instead of myo_adam_clip_step.  Not for N > 1 ranks: there the gradient changes (all-reduce) before it is clipped. */
+   * -> sqnorm_part, and Adam's step counter advanced (adam_step: the int32[2] `step` of myo_adam_desc) — then myo_adam_step
+   * with nparts = that many.  Not for N > 1 ranks: there the gradient changes (all-reduce) before it is clipped. */
   float* sqnorm_part;
   int32_t* adam_step;
   /* hyper-parameter block (above) or NULL = as without it: clip_range comes from it instead of `clip`, and the launch that
@@ -716,10 +716,10 @@ int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream);
  * are taken as current and the advantage moments as the caller's (compute_adv_stats must be 0), so neither the image pass nor
  * the moments pass runs.  The images are current after myo_ppo_mlp_images (once, whenever `params` may have been written from
  * outside: a load, the start of an update) and stay so while every change of `params` is an optimizer step through
- * myo_adam_clip_step_images / myo_adam_apply_images on the same descriptor.  Same results as myo_ppo_mlp_step, bit for bit. */
+ * myo_adam_step with `images` = the same descriptor.  Same results as myo_ppo_mlp_step, bit for bit. */
 int myo_ppo_mlp_step_resident(const myo_ppo_mlp_desc* d, void* stream);
 /* The image pass alone: the operand images of `params` into `workspace`, zero padding included (reads B, O, A, hidden, params, G,
- * the twelve offsets, workspace, workspace_bytes of `d`). */
+ * layout, workspace, workspace_bytes of `d`). */
 int myo_ppo_mlp_images(const myo_ppo_mlp_desc* d, void* stream);
 /* {mean, unbiased std} of the advantages of n_mb minibatches in two launches: idx int64[n_mb * B] are their rows one minibatch
  * after the other (an epoch's permutation), stats f32[n_mb][2] <- what myo_ppo_mlp_step with compute_adv_stats = 1 leaves in
@@ -738,7 +738,7 @@ typedef struct myo_ppo_mlp_rollout_desc {
   const float* obs;
   int32_t N, O, A, hidden;
   const float* params;
-  int64_t off_W1[2], off_b1[2], off_W2[2], off_b2[2], off_Wh[2], off_bh[2], off_log_std;
+  myo_mlp_layout layout;
   uint64_t seed;
   uint64_t* draw_counter;
   const int32_t* t_idx;
@@ -754,34 +754,30 @@ int myo_ppo_mlp_rollout(const myo_ppo_mlp_rollout_desc* d, void* stream);
 /* clip_grad_norm_(max_norm) followed by one torch.optim.Adam step over a flat fp32 parameter vector
  * (what RecurrentPPO.train does per minibatch; /root/reference/src/train/trainer.py:66-71, SB3 Adam
  * eps 1e-5).  g is multiplied by grad_scale first (1/world after an all-reduce SUM).  step: dev
- * int32[2], zero-initialised ([1] = number of steps taken); scratch: dev float[64] (per-block sums
- * of g^2, added in a fixed order: deterministic).  p_bf16 (may be NULL): bfloat16 copy of p, rewritten with
- * the new parameters in the same pass (the operand the bf16 GEMMs read). */
-int myo_adam_clip_step(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                       float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
-                       void* stream);
-/* The second half of myo_adam_clip_step alone: |g|^2 = the sum of scratch[0 .. nparts) (left there by myo_ppo_mlp_step with
- * sqnorm_part set, which has also advanced `step`), then clip + Adam as above. */
-int myo_adam_apply(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                   float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
-                   uint16_t* p_bf16, void* stream);
-/* Both with the hyper-parameter block (NULL: exactly the calls above): lr is hp[MYO_HP_LR] (`lr` is ignored); with the stop
- * flag up p, m, v, p_bf16 and `step` stay untouched; otherwise hp[MYO_HP_APPLIED] advances by one. */
-int myo_adam_clip_step_hp(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                          float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
-                          float* hp, void* stream);
-int myo_adam_apply_hp(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                      float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
-                      uint16_t* p_bf16, float* hp, void* stream);
-/* Both again (hp may be NULL), and every parameter the step updates is also stored into the operand images of the fused MLP step
- * that `images` describes (its workspace, shapes and offsets; images->G must be n): the weights as bf16 in the layouts of
- * myo_ppo_mlp_images, the biases as fp32.  With the stop flag up the images stay untouched too. */
-int myo_adam_clip_step_images(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                              float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
-                              float* hp, const myo_ppo_mlp_desc* images, void* stream);
-int myo_adam_apply_images(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                          float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
-                          uint16_t* p_bf16, float* hp, const myo_ppo_mlp_desc* images, void* stream);
+ * int32[2], zero-initialised ([1] = number of steps taken); scratch: dev float[max(64, nparts)] (partial sums
+ * of g^2, added in a fixed order: deterministic).  The descriptor is read at call time; its values go to the kernels by value.
+ *   nparts   0: the squares of g are taken here (64 per-block sums -> scratch) and `step` advances.  > 0: |g|^2 = the sum of
+ *            scratch[0 .. nparts), left there by myo_ppo_mlp_step with sqnorm_part set, which has also advanced `step`.
+ *   p_bf16   NULL, or a bfloat16 copy of p, rewritten with the new parameters in the same pass (the operand the bf16 GEMMs read).
+ *   hp       NULL, or the hyper-parameter block: lr is hp[MYO_HP_LR] (`lr` is ignored); with the stop flag up p, m, v, p_bf16,
+ *            the images and `step` stay untouched; otherwise hp[MYO_HP_APPLIED] advances by one.
+ *   images   NULL, or the descriptor of a fused MLP step (its workspace, shapes and layout; images->G must be n): every parameter
+ *            the step updates is also stored into that step's operand images, the weights as bf16 in the layouts of
+ *            myo_ppo_mlp_images, the biases as fp32. */
+typedef struct myo_adam_desc {
+  float* p;
+  const float* g;
+  float *m, *v;
+  int32_t n;
+  float lr, b1, b2, eps, max_norm, grad_scale;
+  int32_t* step;
+  float* scratch;
+  int32_t nparts;
+  uint16_t* p_bf16;
+  float* hp;
+  const myo_ppo_mlp_desc* images;
+} myo_adam_desc;
+int myo_adam_step(const myo_adam_desc* a, void* stream);
 
 const char* myo_last_error(void);
 const char* myo_version(void);

@@ -11,7 +11,7 @@
 //   k_mlp_wgrad    dW = dY' X for the six weight matrices and the four hidden bias vectors: 128 x 128 output tiles,
 //                  split over the batch (split-K) into per-split slabs — plain stores, no float atomics
 //   k_mlp_reduce   flat gradient = sum of the slabs in split order (deterministic)
-// followed by the existing k_colmajor_finish (loss sums, log_std and head-bias gradients) and myo_adam_clip_step.
+// followed by the existing k_colmajor_finish (loss sums, log_std and head-bias gradients) and myo_adam_step.
 //
 // v_mfma_f32_16x16x32_bf16 fragment maps (cdna_hip_programming.md §3): lane l holds A[row l&15][k = 8(l>>4) + j] and
 // B[k = 8(l>>4) + j][col l&15], j = 0..7; C/D: col = l&15, row = 4(l>>4) + reg.  Both operands are therefore read as
@@ -32,12 +32,28 @@ typedef __attribute__((ext_vector_type(4))) float myo_f32x4;
 #define MLP_SOS 49
 #define MLP_SPLITK 16
 
+// The operand images of the weights, [0] actor / [1] critic: bf16 W1p [2][H][OP], W2 [2][H][H], W2T [2][H][H] (transposed),
+// Whp [2][APM][H], WhT [2][H][AKP] (transposed), zero-padded; bias fp32 [2][H] b1, [2][H] b2, [2][APM] bh.  The one record of them:
+// every kernel argument block and both workspaces (the optimizer step's, the rollout's) hold it.
+struct MlpImages { unsigned short *W1p, *W2, *W2T, *Whp, *WhT; float* bias; };
+// the images at the front of a workspace (base == nullptr: the size alone), each on a 256-byte boundary; *bytes <- what they take
+static inline MlpImages mlp_images_carve(unsigned char* base, int OP, size_t* bytes) {
+  size_t o = 0;
+  auto take = [&](size_t n) { unsigned char* p = base ? base + o : nullptr; o += (n + 255) / 256 * 256; return p; };
+  const size_t H = MLP_H;
+  MlpImages w;
+  w.W1p = (unsigned short*)take(2 * H * OP * 2); w.W2 = (unsigned short*)take(2 * H * H * 2); w.W2T = (unsigned short*)take(2 * H * H * 2);
+  w.Whp = (unsigned short*)take(2 * MLP_APM * H * 2); w.WhT = (unsigned short*)take(2 * H * MLP_AKP * 2);
+  w.bias = (float*)take((4 * H + 2 * MLP_APM) * 4);
+  *bytes = o;
+  return w;
+}
+
 struct MlpArgs {
   const float *obs, *act, *oldlp, *adv, *ret;      // rollout arrays [N, .]
   const long long* idx;                            // minibatch rows [B]
   const float *log_std, *adv_stats;
-  const unsigned short *W1p, *W2, *W2T, *Whp, *WhT;  // bf16 images: [2][H][OP], [2][H][H], [2][H][H], [2][APM][H], [2][H][AKP]
-  const float* bias;                               // fp32 [2][H] b1, [2][H] b2, [2][APM] bh
+  MlpImages img;
   unsigned short *XT, *H1T, *H2T, *dH1T, *dH2T, *dOT;   // feature-major bf16 [rows][B]: 128, 2H, 2H, 2H, 2H, 2*128
   float* part;                                     // loss partials, column-major [(2A+3)][NB]
   int B, O, A, OP, NB;
@@ -56,8 +72,7 @@ struct MlpPrepArgs {
   const float* p;                                  // flat fp32 parameters
   long long off_W1[2], off_b1[2], off_W2[2], off_b2[2], off_Wh[2], off_bh[2];
   int O, OP, Ah[2];                                // head widths: A (actor), 1 (critic)
-  unsigned short *W1p, *W2, *W2T, *Whp, *WhT;
-  float* bias;
+  MlpImages img;
   const float* adv_part;       // [3 * adv_nb] slices (n, mean, M2) of the advantage moments left by k_adv_moments, or adv_nb = 0
   float* adv_stats;
   int adv_nb, B;
@@ -95,27 +110,27 @@ __global__ void __launch_bounds__(256) k_mlp_prep(MlpPrepArgs P) {
     const float* W1 = P.p + P.off_W1[net]; const float* W2 = P.p + P.off_W2[net]; const float* Wh = P.p + P.off_Wh[net];
     for (long long e = tid; e < (long long)H * P.OP; e += nth) {
       const int o = (int)(e / P.OP), i = (int)(e % P.OP);
-      P.W1p[(size_t)net * H * P.OP + e] = i < P.O ? mlp_f2bf(W1[(size_t)o * P.O + i]) : (unsigned short)0;
+      P.img.W1p[(size_t)net * H * P.OP + e] = i < P.O ? mlp_f2bf(W1[(size_t)o * P.O + i]) : (unsigned short)0;
     }
     for (long long e = tid; e < (long long)H * H; e += nth) {
       const int o = (int)(e / H), i = (int)(e % H);
       const unsigned short v = mlp_f2bf(W2[e]);
-      P.W2[(size_t)net * H * H + e] = v;
-      P.W2T[(size_t)net * H * H + (size_t)i * H + o] = v;
+      P.img.W2[(size_t)net * H * H + e] = v;
+      P.img.W2T[(size_t)net * H * H + (size_t)i * H + o] = v;
     }
     for (long long e = tid; e < (long long)MLP_APM * H; e += nth) {
       const int a = (int)(e / H), h = (int)(e % H);
-      P.Whp[(size_t)net * MLP_APM * H + e] = a < P.Ah[net] ? mlp_f2bf(Wh[(size_t)a * H + h]) : (unsigned short)0;
+      P.img.Whp[(size_t)net * MLP_APM * H + e] = a < P.Ah[net] ? mlp_f2bf(Wh[(size_t)a * H + h]) : (unsigned short)0;
     }
     for (long long e = tid; e < (long long)H * MLP_AKP; e += nth) {
       const int h = (int)(e / MLP_AKP), a = (int)(e % MLP_AKP);
-      P.WhT[(size_t)net * H * MLP_AKP + e] = a < P.Ah[net] ? mlp_f2bf(Wh[(size_t)a * H + h]) : (unsigned short)0;
+      P.img.WhT[(size_t)net * H * MLP_AKP + e] = a < P.Ah[net] ? mlp_f2bf(Wh[(size_t)a * H + h]) : (unsigned short)0;
     }
     for (long long e = tid; e < H; e += nth) {
-      P.bias[net * H + e] = P.p[P.off_b1[net] + e];
-      P.bias[2 * H + net * H + e] = P.p[P.off_b2[net] + e];
+      P.img.bias[net * H + e] = P.p[P.off_b1[net] + e];
+      P.img.bias[2 * H + net * H + e] = P.p[P.off_b2[net] + e];
     }
-    for (long long e = tid; e < MLP_APM; e += nth) P.bias[4 * H + net * MLP_APM + e] = e < P.Ah[net] ? P.p[P.off_bh[net] + e] : 0.f;
+    for (long long e = tid; e < MLP_APM; e += nth) P.img.bias[4 * H + net * MLP_APM + e] = e < P.Ah[net] ? P.p[P.off_bh[net] + e] : 0.f;
   }
 }
 
@@ -164,11 +179,10 @@ __global__ void __launch_bounds__(256) k_adv_merge(const float* __restrict__ par
   if (t == 0) mlp_adv_merge(sp, nb, B, stats + 2 * blockIdx.x);
 }
 
-// Where k_adam mirrors every parameter it updates (W1p == nullptr: nowhere): the operand images k_mlp_prep builds, which then
+// Where k_adam mirrors every parameter it updates (img.W1p == nullptr: nowhere): the operand images k_mlp_prep builds, which then
 // stay current from one optimizer step to the next without a prep launch.  Padding entries are k_mlp_prep's alone.
 struct MlpImgTarget {
-  unsigned short *W1p, *W2, *W2T, *Whp, *WhT;
-  float* bias;
+  MlpImages img;
   int off_W1[2], off_b1[2], off_W2[2], off_b2[2], off_Wh[2], off_bh[2];     // (k_adam indexes the flat vector with an int)
   int O, OP, A;
 };
@@ -182,25 +196,25 @@ __device__ __forceinline__ void mlp_img_store(const MlpImgTarget& T, int i, floa
     unsigned j = (unsigned)(i - T.off_W2[net]);
     if (j < H * H) {
       const unsigned short v = mlp_f2bf(x);
-      T.W2[net * H * H + j] = v;
-      T.W2T[net * H * H + (j % H) * H + j / H] = v;
+      T.img.W2[net * H * H + j] = v;
+      T.img.W2T[net * H * H + (j % H) * H + j / H] = v;
       return;
     }
     j = (unsigned)(i - T.off_W1[net]);
-    if (j < H * (unsigned)T.O) { const unsigned o = j / (unsigned)T.O; T.W1p[net * H * T.OP + o * T.OP + (j - o * T.O)] = mlp_f2bf(x); return; }
+    if (j < H * (unsigned)T.O) { const unsigned o = j / (unsigned)T.O; T.img.W1p[net * H * T.OP + o * T.OP + (j - o * T.O)] = mlp_f2bf(x); return; }
     j = (unsigned)(i - T.off_Wh[net]);
     if (j < Ah * H) {
       const unsigned short v = mlp_f2bf(x);
-      T.Whp[net * MLP_APM * H + j] = v;
-      T.WhT[net * H * MLP_AKP + (j % H) * MLP_AKP + j / H] = v;
+      T.img.Whp[net * MLP_APM * H + j] = v;
+      T.img.WhT[net * H * MLP_AKP + (j % H) * MLP_AKP + j / H] = v;
       return;
     }
     j = (unsigned)(i - T.off_b1[net]);
-    if (j < H) { T.bias[net * H + j] = x; return; }
+    if (j < H) { T.img.bias[net * H + j] = x; return; }
     j = (unsigned)(i - T.off_b2[net]);
-    if (j < H) { T.bias[2 * H + net * H + j] = x; return; }
+    if (j < H) { T.img.bias[2 * H + net * H + j] = x; return; }
     j = (unsigned)(i - T.off_bh[net]);
-    if (j < Ah) { T.bias[4 * H + net * MLP_APM + j] = x; return; }
+    if (j < Ah) { T.img.bias[4 * H + net * MLP_APM + j] = x; return; }
   }
 }
 
@@ -328,13 +342,13 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
   MLP_STAMP(0)
   if (t < BM) s_idx[t] = P.idx[r0 + t];
   if (t < A) { const float ls = P.log_std[t]; s_ls[t] = ls; s_ls[64 + t] = __expf(-ls); }
-  const float* b1 = P.bias + net * H; const float* b2 = P.bias + 2 * H + net * H; const float* bh = P.bias + 4 * H + net * MLP_APM;
+  const float* b1 = P.img.bias + net * H; const float* b2 = P.img.bias + 2 * H + net * H; const float* bh = P.img.bias + 4 * H + net * MLP_APM;
   float bb1[4], bb2[4];
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) { bb1[nt] = b1[n0 + 16 * nt + lm]; bb2[nt] = b2[n0 + 16 * nt + lm]; }
   myo_bf16x8 bw[8][4];                   // the weight fragments of the NEXT MFMA slab (see mlp_load_w)
   {
-    const unsigned short* W1 = P.W1p + (size_t)net * H * OP;
+    const unsigned short* W1 = P.img.W1p + (size_t)net * H * OP;
     if (OP == 96) mlp_load_w<3>(bw, W1, OP, n0, lm, lq);
     else if (OP == 128) mlp_load_w<4>(bw, W1, OP, n0, lm, lq);
     else if (OP == 64) mlp_load_w<2>(bw, W1, OP, n0, lm, lq);
@@ -385,7 +399,7 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
   else if (OP == 128) mlp_mma_slab<4, MT>(acc, Xs, XS, bw, lm, lq);
   else if (OP == 64) mlp_mma_slab<2, MT>(acc, Xs, XS, bw, lm, lq);
   else mlp_mma_slab<1, MT>(acc, Xs, XS, bw, lm, lq);
-  mlp_load_w<H / 32>(bw, P.W2 + (size_t)net * H * H, H, n0, lm, lq);
+  mlp_load_w<H / 32>(bw, P.img.W2 + (size_t)net * H * H, H, n0, lm, lq);
   const unsigned long long mask1 = mlp_store_act<MT>(acc, bb1, Hs, P.H1T + (size_t)net * H * B, B, r0, n0, lm, lq);
   __syncthreads();
   MLP_STAMP(2)
@@ -393,7 +407,7 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
   mlp_mma_slab<H / 32, MT>(acc, Hs, HS, bw, lm, lq);
   // the head's tiles (16 rows x 16 outputs, MT x 3 of them): wave w < 3 takes output tile w of every row tile (one set of
   // weight fragments, 32 VGPRs, reused MT times)
-  const unsigned short* Wh = P.Whp + (size_t)net * MLP_APM * H;
+  const unsigned short* Wh = P.img.Whp + (size_t)net * MLP_APM * H;
   myo_bf16x8 bh2[H / 32];
   if (w < 3) {
 #pragma unroll
@@ -419,7 +433,7 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
       for (int r = 0; r < 4; ++r) So[(16 * mt + 4 * lq + r) * SOS + 16 * w + lm] = ah[r] + bv;
     }
   }
-  mlp_load_w<MLP_AKP / 32>(bw, P.WhT + (size_t)net * H * MLP_AKP, MLP_AKP, n0, lm, lq);      // d hidden 2's weights fly during the loss phase
+  mlp_load_w<MLP_AKP / 32>(bw, P.img.WhT + (size_t)net * H * MLP_AKP, MLP_AKP, n0, lm, lq);      // d hidden 2's weights fly during the loss phase
   __syncthreads();
   MLP_STAMP(4)
   // ---- loss gradient w.r.t. the head output (k_ppo_loss's arithmetic), one row per lane of wave 0
@@ -500,7 +514,7 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
   MLP_STAMP(6)
   // ---- d hidden 2 = (dOut Wh) * (H2 > 0), written over H2's LDS image (its A-operand role ended with the head)
   mlp_mma_slab<MLP_AKP / 32, MT>(acc, dOs, DS, bw, lm, lq);
-  mlp_load_w<H / 32>(bw, P.W2T + (size_t)net * H * H, H, n0, lm, lq);
+  mlp_load_w<H / 32>(bw, P.img.W2T + (size_t)net * H * H, H, n0, lm, lq);
   mlp_store_grad<MT, true>(acc, mask2, Hs, P.dH2T + (size_t)net * H * B, B, r0, n0, lm, lq);
   __syncthreads();
   MLP_STAMP(7)
@@ -519,8 +533,7 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
 struct MlpPolicyArgs {
   const float* obs;                                 // [N][O] policy input (normalised observation)
   const float* log_std;
-  const unsigned short *W1p, *W2, *Whp;             // bf16 images of k_mlp_prep
-  const float* bias;
+  MlpImages img;                                    // images of k_mlp_prep (W1p, W2, Whp and bias are read)
   float* obs_buf;                                   // [T][N][O] rollout buffer (row t_idx written) or null
   float *act_buf, *val_buf, *logp_buf, *clipped;    // [T][N][A], [T][N], [T][N], [N][A]
   const int* t_idx;
@@ -556,13 +569,13 @@ __global__ void __launch_bounds__(256, 2) k_mlp_policy(MlpPolicyArgs P) {
   const int n0 = 64 * w;
   const size_t tt = (size_t)(*P.t_idx);
   if (t < A) { const float ls = P.log_std[t]; s_ls[t] = ls; s_ls[64 + t] = __expf(ls); }
-  const float* b1 = P.bias + net * H; const float* b2 = P.bias + 2 * H + net * H; const float* bh = P.bias + 4 * H + net * MLP_APM;
+  const float* b1 = P.img.bias + net * H; const float* b2 = P.img.bias + 2 * H + net * H; const float* bh = P.img.bias + 4 * H + net * MLP_APM;
   float bb1[4], bb2[4];
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) { bb1[nt] = b1[n0 + 16 * nt + lm]; bb2[nt] = b2[n0 + 16 * nt + lm]; }
   myo_bf16x8 bw[8][4];
   {
-    const unsigned short* W1 = P.W1p + (size_t)net * H * OP;
+    const unsigned short* W1 = P.img.W1p + (size_t)net * H * OP;
     if (OP == 96) mlp_load_w<3>(bw, W1, OP, n0, lm, lq);
     else if (OP == 128) mlp_load_w<4>(bw, W1, OP, n0, lm, lq);
     else if (OP == 64) mlp_load_w<2>(bw, W1, OP, n0, lm, lq);
@@ -593,11 +606,11 @@ __global__ void __launch_bounds__(256, 2) k_mlp_policy(MlpPolicyArgs P) {
   else if (OP == 128) mlp_mma_slab<4, MT>(acc, Xs, XS, bw, lm, lq);
   else if (OP == 64) mlp_mma_slab<2, MT>(acc, Xs, XS, bw, lm, lq);
   else mlp_mma_slab<1, MT>(acc, Xs, XS, bw, lm, lq);
-  mlp_load_w<H / 32>(bw, P.W2 + (size_t)net * H * H, H, n0, lm, lq);
+  mlp_load_w<H / 32>(bw, P.img.W2 + (size_t)net * H * H, H, n0, lm, lq);
   mlp_store_act_lds<MT>(acc, bb1, Hs, n0, lm, lq);
   __syncthreads();
   mlp_mma_slab<H / 32, MT>(acc, Hs, HS, bw, lm, lq);
-  const unsigned short* Wh = P.Whp + (size_t)net * MLP_APM * H;
+  const unsigned short* Wh = P.img.Whp + (size_t)net * MLP_APM * H;
   myo_bf16x8 bh2[H / 32];
   if (w < 3) {
 #pragma unroll
@@ -741,7 +754,7 @@ __global__ void __launch_bounds__(256) k_mlp_wgrad(MlpWgradArgs P) {
 // The tail of the optimizer step's gradient in ONE launch (single-rank path: nothing is exchanged between the gradient and
 // the clip): blocks 0 .. MLP_RF_BLOCKS-1 sum the split-K slabs into the flat gradient (split order) and their share of
 // |g|^2; block MLP_RF_BLOCKS + c finishes column c of the loss partials (k_colmajor_finish's arithmetic: loss sums, d log_std,
-// head-bias gradients) and the squares of what it wrote; sq_part[0 .. MLP_RF_BLOCKS + ncol) is what myo_adam_apply adds up in
+// head-bias gradients) and the squares of what it wrote; sq_part[0 .. MLP_RF_BLOCKS + ncol) is what myo_adam_step adds up in
 // a fixed order; block 0 also advances Adam's step counter (k_grad_sqnorm's other job).  Instead of k_mlp_reduce +
 // k_colmajor_finish + k_grad_sqnorm.
 #define MLP_RF_BLOCKS 256

@@ -774,11 +774,11 @@ __global__ void __launch_bounds__(64) k_colmajor_finish(const float* __restrict_
     if (g_bias_vf && c == 2 * A + 2) g_bias_vf[0] = a;
   }
 }
-static int ppo_loss_grad(const float* mean, const float* values, const float* actions, const float* old_logp,
-                         const float* adv, const float* returns, const float* log_std, const float* adv_stats,
-                         int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
-                         uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
-                         float* g_log_std, float* g_bias_pi, float* g_bias_vf, float* hp, void* stream) {
+extern "C" int myo_ppo_loss_grad(const float* mean, const float* values, const float* actions, const float* old_logp,
+                                 const float* adv, const float* returns, const float* log_std, const float* adv_stats,
+                                 int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
+                                 uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
+                                 float* g_log_std, float* g_bias_pi, float* g_bias_vf, float* hp, void* stream) {
   if (!mean || !values || !actions || !old_logp || !adv || !returns || !log_std || !adv_stats || !dmean || !dvalue || !acc ||
       !work || B <= 0 || A <= 0 || A > 64)
     return fail(MYO_E_ARG, "myo_ppo_loss_grad: bad arguments");
@@ -794,22 +794,6 @@ static int ppo_loss_grad(const float* mean, const float* values, const float* ac
                      g_bias_vf, hp);
   LAUNCH_CHECK(0)
   return MYO_OK;
-}
-extern "C" int myo_ppo_loss_grad(const float* mean, const float* values, const float* actions, const float* old_logp,
-                                 const float* adv, const float* returns, const float* log_std, const float* adv_stats,
-                                 int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
-                                 uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
-                                 float* g_log_std, float* g_bias_pi, float* g_bias_vf, void* stream) {
-  return ppo_loss_grad(mean, values, actions, old_logp, adv, returns, log_std, adv_stats, B, A, clip, vf_coef, dmean, dvalue, acc,
-                       dmean_bf16, dvalue_bf16, work, in_bf16, ent_coef, g_log_std, g_bias_pi, g_bias_vf, nullptr, stream);
-}
-extern "C" int myo_ppo_loss_grad_hp(const float* mean, const float* values, const float* actions, const float* old_logp,
-                                    const float* adv, const float* returns, const float* log_std, const float* adv_stats,
-                                    int B, int A, float clip, float vf_coef, float* dmean, float* dvalue, float* acc,
-                                    uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
-                                    float* g_log_std, float* g_bias_pi, float* g_bias_vf, float* hp, void* stream) {
-  return ppo_loss_grad(mean, values, actions, old_logp, adv, returns, log_std, adv_stats, B, A, clip, vf_coef, dmean, dvalue, acc,
-                       dmean_bf16, dvalue_bf16, work, in_bf16, ent_coef, g_log_std, g_bias_pi, g_bias_vf, hp, stream);
 }
 
 // ------------------------------------------------------------------------------------------ split-K
@@ -1708,7 +1692,7 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float
                                               float* __restrict__ v, int n, float lr, float b1, float b2, float eps,
                                               float max_norm, float gs, const int* __restrict__ step,
                                               const float* __restrict__ part, unsigned short* __restrict__ p_bf16, int nparts,
-                                              float* __restrict__ hp, MlpImgTarget img) {
+                                              float* __restrict__ hp, MlpImgTarget tgt) {
   if (hp) {       // lr from the hyper-parameter block; stop flag up: p, m, v, the bf16 shadow and the images stay as they are
     if (reinterpret_cast<const int*>(hp)[MYO_HP_STOP]) return;
     lr = hp[MYO_HP_LR];
@@ -1737,64 +1721,20 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float
     const float pn = p[i] - step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
     p[i] = pn;
     if (p_bf16) p_bf16[i] = myo_f2bf(pn);          // the bf16 shadow the GEMMs read: no separate cast pass
-    if (img.W1p) mlp_img_store(img, i, pn);        // and the fused MLP step's operand images: no prep launch per step
+    if (tgt.img.W1p) mlp_img_store(tgt, i, pn);    // and the fused MLP step's operand images: no prep launch per step
   }
   if (hp && blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<int*>(hp)[MYO_HP_APPLIED] += 1;
 }
-static const MlpImgTarget kNoImages = {};
-static int adam_clip_step(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                          float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
-                          float* hp, void* stream, const MlpImgTarget& img = kNoImages) {
-  if (!p || !g || !m || !v || !step || !scratch || n <= 0) return fail(MYO_E_ARG, "myo_adam_clip_step: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
-  hipLaunchKernelGGL(k_grad_sqnorm, dim3(MYO_SQN_BLOCKS), dim3(256), 0, st, g, n, grad_scale, scratch, step, (const float*)hp);
-  hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch,
-                     (unsigned short*)p_bf16, MYO_SQN_BLOCKS, hp, img);
-  LAUNCH_CHECK(0)
-  return MYO_OK;
-}
-extern "C" int myo_adam_clip_step(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                                  float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
-                                  void* stream) {
-  return adam_clip_step(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, p_bf16, nullptr, stream);
-}
-extern "C" int myo_adam_clip_step_hp(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                                     float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
-                                     float* hp, void* stream) {
-  return adam_clip_step(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, p_bf16, hp, stream);
-}
-static int adam_apply(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                      float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
-                      uint16_t* p_bf16, float* hp, void* stream, const MlpImgTarget& img = kNoImages) {
-  if (!p || !g || !m || !v || !step || !scratch || n <= 0 || nparts <= 0) return fail(MYO_E_ARG, "myo_adam_apply: bad arguments");
-  const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
-  hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch,
-                     (unsigned short*)p_bf16, nparts, hp, img);
-  LAUNCH_CHECK(0)
-  return MYO_OK;
-}
-extern "C" int myo_adam_apply(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                              float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
-                              uint16_t* p_bf16, void* stream) {
-  return adam_apply(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, nparts, p_bf16, nullptr, stream);
-}
-extern "C" int myo_adam_apply_hp(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                                 float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
-                                 uint16_t* p_bf16, float* hp, void* stream) {
-  return adam_apply(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, nparts, p_bf16, hp, stream);
-}
+// (the host side, myo_adam_step, stands below the fused MLP step: it places the images from that step's descriptor)
 
 // ------------------------------------------------------------------------------------------ fused MLP PPO step
-struct MlpWs { unsigned short *W1p, *W2, *W2T, *Whp, *WhT; float* bias; unsigned short *XT, *H1T, *H2T, *dH1T, *dH2T, *dOT; float *part, *slab, *advpart; size_t bytes; };
+struct MlpWs { MlpImages img; unsigned short *XT, *H1T, *H2T, *dH1T, *dH2T, *dOT; float *part, *slab, *advpart; size_t bytes; };
 static MlpWs mlp_carve(unsigned char* base, int B, int OP, int A, long long G) {
   MlpWs w;
   size_t o = 0;
+  w.img = mlp_images_carve(base, OP, &o);
   auto take = [&](size_t n) { unsigned char* p = base ? base + o : nullptr; o += (n + 255) / 256 * 256; return p; };
   const size_t H = MLP_H;
-  w.W1p = (unsigned short*)take(2 * H * OP * 2); w.W2 = (unsigned short*)take(2 * H * H * 2); w.W2T = (unsigned short*)take(2 * H * H * 2);
-  w.Whp = (unsigned short*)take(2 * MLP_APM * H * 2); w.WhT = (unsigned short*)take(2 * H * MLP_AKP * 2);
-  w.bias = (float*)take((4 * H + 2 * MLP_APM) * 4);
   w.XT = (unsigned short*)take((size_t)128 * B * 2);
   w.H1T = (unsigned short*)take(2 * H * (size_t)B * 2); w.H2T = (unsigned short*)take(2 * H * (size_t)B * 2);
   w.dH1T = (unsigned short*)take(2 * H * (size_t)B * 2); w.dH2T = (unsigned short*)take(2 * H * (size_t)B * 2);
@@ -1808,6 +1748,10 @@ static MlpWs mlp_carve(unsigned char* base, int B, int OP, int A, long long G) {
 static int mlp_shape_ok(int B, int O, int A, int hidden) {
   return hidden == MLP_H && O >= 1 && O <= MLP_OPMAX && A >= 1 && A <= MLP_APM && B >= 64 * MLP_SPLITK && B % (64 * MLP_SPLITK) == 0;
 }
+static int mlp_shape_check(const myo_ppo_mlp_desc* d, const char* who) {
+  if (mlp_shape_ok(d->B, d->O, d->A, d->hidden)) return MYO_OK;
+  return fail(MYO_E_UNSUPPORTED, "%s: needs hidden = %d, obs <= %d, act <= %d, batch a multiple of %d", who, MLP_H, MLP_OPMAX, MLP_APM, 64 * MLP_SPLITK);
+}
 extern "C" long long myo_ppo_mlp_workspace_bytes(int B, int obs_dim, int act_dim, int hidden, long long G) {
   if (!mlp_shape_ok(B, obs_dim, act_dim, hidden) || G <= 0) return -1;
   return (long long)mlp_carve(nullptr, B, (obs_dim + 31) / 32 * 32, act_dim, G).bytes;
@@ -1815,26 +1759,29 @@ extern "C" long long myo_ppo_mlp_workspace_bytes(int B, int obs_dim, int act_dim
 extern "C" int myo_ppo_mlp_sqnorm_parts(int act_dim) {
   return MLP_RF_BLOCKS + 2 * act_dim + 3;
 }
-static MlpPrepArgs mlp_prep_args(const myo_ppo_mlp_desc* d, const MlpWs& w, int OP) {
+// The image pass: the images of the flat parameters `p` laid out by `lay`; adv_nb > 0: and the merge of that many slices of the
+// advantage moments of B rows (k_mlp_prep's last block)
+static void mlp_launch_prep(const float* p, const myo_mlp_layout& lay, int O, int A, const MlpImages& img, const float* adv_part, float* adv_stats,
+                            int adv_nb, int B, hipStream_t st) {
   MlpPrepArgs pp;
-  pp.p = d->params; pp.O = d->O; pp.OP = OP; pp.Ah[0] = d->A; pp.Ah[1] = 1;
+  pp.p = p; pp.O = O; pp.OP = (O + 31) / 32 * 32; pp.Ah[0] = A; pp.Ah[1] = 1; pp.img = img;
   for (int k = 0; k < 2; ++k) {
-    pp.off_W1[k] = d->off_W1[k]; pp.off_b1[k] = d->off_b1[k]; pp.off_W2[k] = d->off_W2[k]; pp.off_b2[k] = d->off_b2[k];
-    pp.off_Wh[k] = d->off_Wh[k]; pp.off_bh[k] = d->off_bh[k];
+    pp.off_W1[k] = lay.off_W1[k]; pp.off_b1[k] = lay.off_b1[k]; pp.off_W2[k] = lay.off_W2[k]; pp.off_b2[k] = lay.off_b2[k];
+    pp.off_Wh[k] = lay.off_Wh[k]; pp.off_bh[k] = lay.off_bh[k];
   }
-  pp.adv_part = nullptr; pp.adv_stats = nullptr; pp.adv_nb = 0; pp.B = d->B;
-  pp.W1p = w.W1p; pp.W2 = w.W2; pp.W2T = w.W2T; pp.Whp = w.Whp; pp.WhT = w.WhT; pp.bias = w.bias;
-  return pp;
+  pp.adv_part = adv_part; pp.adv_stats = adv_stats; pp.adv_nb = adv_nb; pp.B = B;
+  hipLaunchKernelGGL(k_mlp_prep, dim3(256), dim3(256), 0, st, pp);
 }
 // resident: the operand images at the front of the workspace are current (myo_ppo_mlp_images once, then the Adam kernel of
-// myo_adam_*_images after every step) and the advantage moments are the caller's: neither k_adv_moments nor k_mlp_prep runs
+// myo_adam_step with `images` after every step) and the advantage moments are the caller's: neither k_adv_moments nor k_mlp_prep runs
 static int mlp_step(const myo_ppo_mlp_desc* d, void* stream, bool resident) {
   const char* who = resident ? "myo_ppo_mlp_step_resident" : "myo_ppo_mlp_step";
   if (!d || !d->obs || !d->act || !d->oldlp || !d->adv || !d->ret || !d->idx || !d->params || !d->grads || !d->adv_stats || !d->acc ||
       !d->workspace)
     return fail(MYO_E_ARG, "%s: null argument", who);
   const int B = d->B, O = d->O, A = d->A, OP = (O + 31) / 32 * 32;
-  if (!mlp_shape_ok(B, O, A, d->hidden)) return fail(MYO_E_UNSUPPORTED, "%s: needs hidden = %d, obs <= %d, act <= %d, batch a multiple of %d", who, MLP_H, MLP_OPMAX, MLP_APM, 64 * MLP_SPLITK);
+  const myo_mlp_layout& lay = d->layout;
+  if (int rc = mlp_shape_check(d, who)) return rc;
   if (resident && d->compute_adv_stats) return fail(MYO_E_ARG, "%s: the advantage moments are the caller's (compute_adv_stats = 0)", who);
   const MlpWs w = mlp_carve((unsigned char*)d->workspace, B, OP, A, d->G);
   if ((long long)w.bytes > d->workspace_bytes) return fail(MYO_E_ARG, "%s: workspace too small (%zu bytes needed)", who, w.bytes);
@@ -1847,14 +1794,11 @@ static int mlp_step(const myo_ppo_mlp_desc* d, void* stream, bool resident) {
   }
   if (!resident) {
     if (d->compute_adv_stats) hipLaunchKernelGGL(k_adv_moments, dim3(MLP_ADV_BLOCKS), dim3(256), 0, st, d->adv, (const long long*)d->idx, B, w.advpart);
-    MlpPrepArgs pp = mlp_prep_args(d, w, OP);
-    pp.adv_part = w.advpart; pp.adv_stats = d->adv_stats; pp.adv_nb = d->compute_adv_stats ? MLP_ADV_BLOCKS : 0;
-    hipLaunchKernelGGL(k_mlp_prep, dim3(256), dim3(256), 0, st, pp);
+    mlp_launch_prep(d->params, lay, O, A, w.img, w.advpart, d->adv_stats, d->compute_adv_stats ? MLP_ADV_BLOCKS : 0, B, st);
   }
   MlpArgs a;
   a.obs = d->obs; a.act = d->act; a.oldlp = d->oldlp; a.adv = d->adv; a.ret = d->ret; a.idx = (const long long*)d->idx;
-  a.log_std = d->params + d->off_log_std; a.adv_stats = d->adv_stats;
-  a.W1p = w.W1p; a.W2 = w.W2; a.W2T = w.W2T; a.Whp = w.Whp; a.WhT = w.WhT; a.bias = w.bias;
+  a.log_std = d->params + lay.off_log_std; a.adv_stats = d->adv_stats; a.img = w.img;
   a.XT = w.XT; a.H1T = w.H1T; a.H2T = w.H2T; a.dH1T = w.dH1T; a.dH2T = w.dH2T; a.dOT = w.dOT; a.part = w.part;
   a.B = B; a.O = O; a.A = A; a.OP = OP; a.NB = B / MLP_BM; a.clip = d->clip; a.vf_coef = d->vf_coef; a.hp = d->hp;
   hipLaunchKernelGGL(k_mlp_fwdbwd, dim3(B / MLP_BM, 2), dim3(256), MLP_FWDBWD_LDS, st, a);
@@ -1864,72 +1808,78 @@ static int mlp_step(const myo_ppo_mlp_desc* d, void* stream, bool resident) {
   for (int net = 0; net < 2; ++net) {
     for (int m0 = 0; m0 < MLP_H; m0 += 128) {
       for (int n0 = 0; n0 < MLP_H; n0 += 128)
-        g.job[g.njobs++] = MlpWgradJob{w.dH2T + net * HB, w.H1T + net * HB, MLP_H, MLP_H, MLP_H, m0, n0, d->off_W2[net], n0 == 0 ? d->off_b2[net] : -1};
-      g.job[g.njobs++] = MlpWgradJob{w.dH1T + net * HB, w.XT, MLP_H, O, O, m0, 0, d->off_W1[net], d->off_b1[net]};
+        g.job[g.njobs++] = MlpWgradJob{w.dH2T + net * HB, w.H1T + net * HB, MLP_H, MLP_H, MLP_H, m0, n0, lay.off_W2[net], n0 == 0 ? lay.off_b2[net] : -1};
+      g.job[g.njobs++] = MlpWgradJob{w.dH1T + net * HB, w.XT, MLP_H, O, O, m0, 0, lay.off_W1[net], lay.off_b1[net]};
     }
     for (int n0 = 0; n0 < MLP_H; n0 += 128)
-      g.job[g.njobs++] = MlpWgradJob{w.dOT + (size_t)net * 128 * B, w.H2T + net * HB, net == 0 ? A : 1, MLP_H, MLP_H, 0, n0, d->off_Wh[net], -1};
+      g.job[g.njobs++] = MlpWgradJob{w.dOT + (size_t)net * 128 * B, w.H2T + net * HB, net == 0 ? A : 1, MLP_H, MLP_H, 0, n0, lay.off_Wh[net], -1};
   }
   hipLaunchKernelGGL(k_mlp_wgrad, dim3(g.njobs * MLP_SPLITK), dim3(256), 0, st, g);
   if (d->sqnorm_part && d->adam_step) {
     MlpRfArgs rf;
     rf.slab = w.slab; rf.g = d->grads; rf.G = d->G; rf.splits = MLP_SPLITK; rf.part = w.part; rf.acc = d->acc; rf.NB = B / MLP_BM; rf.A = A;
-    rf.ent_coef = d->ent_coef; rf.off_log_std = d->off_log_std; rf.off_bh0 = d->off_bh[0]; rf.off_bh1 = d->off_bh[1];
+    rf.ent_coef = d->ent_coef; rf.off_log_std = lay.off_log_std; rf.off_bh0 = lay.off_bh[0]; rf.off_bh1 = lay.off_bh[1];
     rf.sq_part = d->sqnorm_part; rf.adam_step = d->adam_step; rf.hp = d->hp;
     hipLaunchKernelGGL(k_mlp_reduce_finish, dim3(MLP_RF_BLOCKS + 2 * A + 3), dim3(256), 0, st, rf);
   } else {
     hipLaunchKernelGGL(k_mlp_reduce, dim3((unsigned)((d->G + 255) / 256)), dim3(256), 0, st, (const float*)w.slab, d->grads, d->G, MLP_SPLITK);
     hipLaunchKernelGGL(k_colmajor_finish, dim3(2 * A + 3 + (d->hp ? 1 : 0)), dim3(64), 0, st, (const float*)w.part, d->acc, B / MLP_BM, A, d->ent_coef,
-                       d->grads + d->off_log_std, d->grads + d->off_bh[0], d->grads + d->off_bh[1], d->hp);
+                       d->grads + lay.off_log_std, d->grads + lay.off_bh[0], d->grads + lay.off_bh[1], d->hp);
   }
   LAUNCH_CHECK(0)
   return MYO_OK;
 }
 extern "C" int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream) { return mlp_step(d, stream, false); }
 extern "C" int myo_ppo_mlp_step_resident(const myo_ppo_mlp_desc* d, void* stream) { return mlp_step(d, stream, true); }
-// the checks the image calls share: the fields of `d` that place the images
-static int mlp_images_ok(const myo_ppo_mlp_desc* d, const char* who, MlpWs* w) {
+// the checks the image calls share (the fields of `d` that place the images); *img <- the images in d's workspace
+static int mlp_images_ok(const myo_ppo_mlp_desc* d, const char* who, MlpImages* img) {
   if (!d || !d->params || !d->workspace) return fail(MYO_E_ARG, "%s: null argument", who);
-  if (!mlp_shape_ok(d->B, d->O, d->A, d->hidden)) return fail(MYO_E_UNSUPPORTED, "%s: needs hidden = %d, obs <= %d, act <= %d, batch a multiple of %d", who, MLP_H, MLP_OPMAX, MLP_APM, 64 * MLP_SPLITK);
-  *w = mlp_carve((unsigned char*)d->workspace, d->B, (d->O + 31) / 32 * 32, d->A, d->G);
-  if ((long long)w->bytes > d->workspace_bytes) return fail(MYO_E_ARG, "%s: workspace too small (%zu bytes needed)", who, w->bytes);
+  if (int rc = mlp_shape_check(d, who)) return rc;
+  const MlpWs w = mlp_carve((unsigned char*)d->workspace, d->B, (d->O + 31) / 32 * 32, d->A, d->G);
+  if ((long long)w.bytes > d->workspace_bytes) return fail(MYO_E_ARG, "%s: workspace too small (%zu bytes needed)", who, w.bytes);
+  *img = w.img;
   return MYO_OK;
 }
 extern "C" int myo_ppo_mlp_images(const myo_ppo_mlp_desc* d, void* stream) {
-  MlpWs w;
-  if (int rc = mlp_images_ok(d, "myo_ppo_mlp_images", &w)) return rc;
-  hipLaunchKernelGGL(k_mlp_prep, dim3(256), dim3(256), 0, (hipStream_t)stream, mlp_prep_args(d, w, (d->O + 31) / 32 * 32));
+  MlpImages img;
+  if (int rc = mlp_images_ok(d, "myo_ppo_mlp_images", &img)) return rc;
+  mlp_launch_prep(d->params, d->layout, d->O, d->A, img, nullptr, nullptr, 0, d->B, (hipStream_t)stream);
   LAUNCH_CHECK(0)
   return MYO_OK;
 }
+
+// k_adam's image target from the fused step's descriptor (k_adam indexes the flat vector with an int: every tensor offset has to
+// lie inside its n elements)
 static int mlp_img_target(const myo_ppo_mlp_desc* d, int n, const char* who, MlpImgTarget* T) {
-  MlpWs w;
-  if (int rc = mlp_images_ok(d, who, &w)) return rc;
+  if (int rc = mlp_images_ok(d, who, &T->img)) return rc;
   if (d->G != n) return fail(MYO_E_ARG, "%s: the descriptor's parameter vector has %lld elements, this one %d", who, (long long)d->G, n);
-  T->W1p = w.W1p; T->W2 = w.W2; T->W2T = w.W2T; T->Whp = w.Whp; T->WhT = w.WhT; T->bias = w.bias;
-  for (int k = 0; k < 2; ++k) {
-    const int64_t off[6] = {d->off_W1[k], d->off_b1[k], d->off_W2[k], d->off_b2[k], d->off_Wh[k], d->off_bh[k]};
-    for (int q = 0; q < 6; ++q)
-      if (off[q] < 0 || off[q] >= n) return fail(MYO_E_ARG, "%s: a tensor offset lies outside the %d parameters", who, n);
-    T->off_W1[k] = (int)off[0]; T->off_b1[k] = (int)off[1]; T->off_W2[k] = (int)off[2]; T->off_b2[k] = (int)off[3];
-    T->off_Wh[k] = (int)off[4]; T->off_bh[k] = (int)off[5];
-  }
+  bool inside = true;
+  auto put = [&](int (&dst)[2], const int64_t (&src)[2]) {
+    for (int k = 0; k < 2; ++k) { inside = inside && src[k] >= 0 && src[k] < n; dst[k] = (int)src[k]; }
+  };
+  const myo_mlp_layout& lay = d->layout;
+  put(T->off_W1, lay.off_W1); put(T->off_b1, lay.off_b1); put(T->off_W2, lay.off_W2); put(T->off_b2, lay.off_b2);
+  put(T->off_Wh, lay.off_Wh); put(T->off_bh, lay.off_bh);
+  if (!inside) return fail(MYO_E_ARG, "%s: a tensor offset lies outside the %d parameters", who, n);
   T->O = d->O; T->OP = (d->O + 31) / 32 * 32; T->A = d->A;
   return MYO_OK;
 }
-extern "C" int myo_adam_clip_step_images(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                                         float eps, float max_norm, float grad_scale, int* step, float* scratch, uint16_t* p_bf16,
-                                         float* hp, const myo_ppo_mlp_desc* images, void* stream) {
-  MlpImgTarget T;
-  if (int rc = mlp_img_target(images, n, "myo_adam_clip_step_images", &T)) return rc;
-  return adam_clip_step(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, p_bf16, hp, stream, T);
-}
-extern "C" int myo_adam_apply_images(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                                     float eps, float max_norm, float grad_scale, const int* step, const float* scratch, int nparts,
-                                     uint16_t* p_bf16, float* hp, const myo_ppo_mlp_desc* images, void* stream) {
-  MlpImgTarget T;
-  if (int rc = mlp_img_target(images, n, "myo_adam_apply_images", &T)) return rc;
-  return adam_apply(p, g, m, v, n, lr, b1, b2, eps, max_norm, grad_scale, step, scratch, nparts, p_bf16, hp, stream, T);
+// clip_grad_norm_ + Adam over the flat vector (k_grad_sqnorm, k_adam above), one entry point: a->nparts == 0 takes the squares
+// of g here (MYO_SQN_BLOCKS partial sums) and advances `step`; > 0 finds both done.  a->images: k_adam mirrors into its images.
+extern "C" int myo_adam_step(const myo_adam_desc* a, void* stream) {
+  if (!a || !a->p || !a->g || !a->m || !a->v || !a->step || !a->scratch || a->n <= 0 || a->nparts < 0) return fail(MYO_E_ARG, "myo_adam_step: bad arguments");
+  const int n = a->n;
+  MlpImgTarget T = {};
+  if (a->images)
+    if (int rc = mlp_img_target(a->images, n, "myo_adam_step", &T)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
+  if (a->nparts == 0)
+    hipLaunchKernelGGL(k_grad_sqnorm, dim3(MYO_SQN_BLOCKS), dim3(256), 0, st, a->g, n, a->grad_scale, a->scratch, (int*)a->step, (const float*)a->hp);
+  hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, st, a->p, a->g, a->m, a->v, n, a->lr, a->b1, a->b2, a->eps, a->max_norm, a->grad_scale,
+                     (const int*)a->step, (const float*)a->scratch, (unsigned short*)a->p_bf16, a->nparts ? a->nparts : MYO_SQN_BLOCKS, a->hp, T);
+  LAUNCH_CHECK(0)
+  return MYO_OK;
 }
 extern "C" int myo_ppo_adv_moments_epoch(const float* adv, const int64_t* idx, int B, int n_mb, float* stats, float* scratch, void* stream) {
   if (!adv || !idx || !stats || !scratch || B <= 0 || n_mb <= 0 || n_mb > 65535) return fail(MYO_E_ARG, "myo_ppo_adv_moments_epoch: bad arguments");
@@ -1940,55 +1890,38 @@ extern "C" int myo_ppo_adv_moments_epoch(const float* adv, const int64_t* idx, i
   return MYO_OK;
 }
 
-struct MlpImg { unsigned short *W1p, *W2, *W2T, *Whp, *WhT; float* bias; size_t bytes; };
-static MlpImg mlp_carve_images(unsigned char* base, int OP) {
-  MlpImg w;
-  size_t o = 0;
-  auto take = [&](size_t n) { unsigned char* p = base ? base + o : nullptr; o += (n + 255) / 256 * 256; return p; };
-  const size_t H = MLP_H;
-  w.W1p = (unsigned short*)take(2 * H * OP * 2); w.W2 = (unsigned short*)take(2 * H * H * 2); w.W2T = (unsigned short*)take(2 * H * H * 2);
-  w.Whp = (unsigned short*)take(2 * MLP_APM * H * 2); w.WhT = (unsigned short*)take(2 * H * MLP_AKP * 2);
-  w.bias = (float*)take((4 * H + 2 * MLP_APM) * 4);
-  w.bytes = o;
-  return w;
-}
-static int mlp_rollout_ok(const myo_ppo_mlp_rollout_desc* d) {
-  return d->hidden == MLP_H && d->O >= 1 && d->O <= MLP_OPMAX && d->A >= 1 && d->A <= MLP_APM && d->N >= MLP_BM && d->N % MLP_BM == 0;
-}
 extern "C" long long myo_ppo_mlp_rollout_workspace_bytes(int obs_dim, int act_dim, int hidden) {
   if (hidden != MLP_H || obs_dim < 1 || obs_dim > MLP_OPMAX || act_dim < 1 || act_dim > MLP_APM) return -1;
-  return (long long)mlp_carve_images(nullptr, (obs_dim + 31) / 32 * 32).bytes;
+  size_t bytes;
+  mlp_images_carve(nullptr, (obs_dim + 31) / 32 * 32, &bytes);
+  return (long long)bytes;
+}
+// the checks the rollout calls share; *img <- the rollout's own images in d's workspace
+static int mlp_rollout_images(const myo_ppo_mlp_rollout_desc* d, const char* who, MlpImages* img) {
+  if (!(d->hidden == MLP_H && d->O >= 1 && d->O <= MLP_OPMAX && d->A >= 1 && d->A <= MLP_APM && d->N >= MLP_BM && d->N % MLP_BM == 0))
+    return fail(MYO_E_UNSUPPORTED, "myo_ppo_mlp_rollout: needs hidden = %d, obs <= %d, act <= %d, envs a multiple of %d", MLP_H, MLP_OPMAX, MLP_APM, MLP_BM);
+  size_t bytes;
+  *img = mlp_images_carve((unsigned char*)d->workspace, (d->O + 31) / 32 * 32, &bytes);
+  if ((long long)bytes > d->workspace_bytes) return fail(MYO_E_ARG, "%s: workspace too small (%zu bytes needed)", who, bytes);
+  return MYO_OK;
 }
 extern "C" int myo_ppo_mlp_rollout_refresh(const myo_ppo_mlp_rollout_desc* d, void* stream) {
   if (!d || !d->params || !d->workspace) return fail(MYO_E_ARG, "myo_ppo_mlp_rollout_refresh: null argument");
-  if (!mlp_rollout_ok(d)) return fail(MYO_E_UNSUPPORTED, "myo_ppo_mlp_rollout: needs hidden = %d, obs <= %d, act <= %d, envs a multiple of %d", MLP_H, MLP_OPMAX, MLP_APM, MLP_BM);
-  const int OP = (d->O + 31) / 32 * 32;
-  const MlpImg w = mlp_carve_images((unsigned char*)d->workspace, OP);
-  if ((long long)w.bytes > d->workspace_bytes) return fail(MYO_E_ARG, "myo_ppo_mlp_rollout_refresh: workspace too small (%zu bytes needed)", w.bytes);
-  MlpPrepArgs pp;
-  pp.p = d->params; pp.O = d->O; pp.OP = OP; pp.Ah[0] = d->A; pp.Ah[1] = 1;
-  for (int k = 0; k < 2; ++k) {
-    pp.off_W1[k] = d->off_W1[k]; pp.off_b1[k] = d->off_b1[k]; pp.off_W2[k] = d->off_W2[k]; pp.off_b2[k] = d->off_b2[k];
-    pp.off_Wh[k] = d->off_Wh[k]; pp.off_bh[k] = d->off_bh[k];
-  }
-  pp.adv_part = nullptr; pp.adv_stats = nullptr; pp.adv_nb = 0; pp.B = 0;
-  pp.W1p = w.W1p; pp.W2 = w.W2; pp.W2T = w.W2T; pp.Whp = w.Whp; pp.WhT = w.WhT; pp.bias = w.bias;
-  hipLaunchKernelGGL(k_mlp_prep, dim3(256), dim3(256), 0, (hipStream_t)stream, pp);
+  MlpImages img;
+  if (int rc = mlp_rollout_images(d, "myo_ppo_mlp_rollout_refresh", &img)) return rc;
+  mlp_launch_prep(d->params, d->layout, d->O, d->A, img, nullptr, nullptr, 0, 0, (hipStream_t)stream);
   LAUNCH_CHECK(0)
   return MYO_OK;
 }
 extern "C" int myo_ppo_mlp_rollout(const myo_ppo_mlp_rollout_desc* d, void* stream) {
   if (!d || !d->obs || !d->params || !d->draw_counter || !d->t_idx || !d->act_buf || !d->val_buf || !d->logp_buf || !d->clipped || !d->workspace)
     return fail(MYO_E_ARG, "myo_ppo_mlp_rollout: null argument");
-  if (!mlp_rollout_ok(d)) return fail(MYO_E_UNSUPPORTED, "myo_ppo_mlp_rollout: needs hidden = %d, obs <= %d, act <= %d, envs a multiple of %d", MLP_H, MLP_OPMAX, MLP_APM, MLP_BM);
-  const int OP = (d->O + 31) / 32 * 32;
-  const MlpImg w = mlp_carve_images((unsigned char*)d->workspace, OP);
-  if ((long long)w.bytes > d->workspace_bytes) return fail(MYO_E_ARG, "myo_ppo_mlp_rollout: workspace too small (%zu bytes needed)", w.bytes);
   MlpPolicyArgs a;
-  a.obs = d->obs; a.log_std = d->params + d->off_log_std; a.W1p = w.W1p; a.W2 = w.W2; a.Whp = w.Whp; a.bias = w.bias;
+  if (int rc = mlp_rollout_images(d, "myo_ppo_mlp_rollout", &a.img)) return rc;
+  a.obs = d->obs; a.log_std = d->params + d->layout.off_log_std;
   a.obs_buf = d->obs_buf; a.act_buf = d->act_buf; a.val_buf = d->val_buf; a.logp_buf = d->logp_buf; a.clipped = d->clipped;
   a.t_idx = d->t_idx; a.draw_counter = (unsigned long long*)d->draw_counter; a.seed = d->seed;
-  a.N = d->N; a.O = d->O; a.A = d->A; a.OP = OP; a.deterministic = d->deterministic;
+  a.N = d->N; a.O = d->O; a.A = d->A; a.OP = (d->O + 31) / 32 * 32; a.deterministic = d->deterministic;
   hipLaunchKernelGGL(k_mlp_policy, dim3(d->N / MLP_BM, 2), dim3(256), MLP_POLICY_LDS, (hipStream_t)stream, a);
   LAUNCH_CHECK(0)
   return MYO_OK;

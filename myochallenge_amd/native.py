@@ -70,14 +70,20 @@ class TaskCfg(C.Structure):
     ]
 
 
+class MlpLayout(C.Structure):
+    """myo_mlp_layout of include/myobatch.h: element offsets of the MLP actor-critic's tensors in the flat vector, [0] actor / [1] critic."""
+    _fields_ = [
+        ("off_W1", C.c_int64 * 2), ("off_b1", C.c_int64 * 2), ("off_W2", C.c_int64 * 2), ("off_b2", C.c_int64 * 2),
+        ("off_Wh", C.c_int64 * 2), ("off_bh", C.c_int64 * 2), ("off_log_std", C.c_int64),
+    ]
+
+
 class PpoMlpDesc(C.Structure):
     """myo_ppo_mlp_desc of include/myobatch.h (one fused PPO minibatch step of the MLP actor-critic)."""
     _fields_ = [
         ("obs", C.c_void_p), ("act", C.c_void_p), ("oldlp", C.c_void_p), ("adv", C.c_void_p), ("ret", C.c_void_p), ("idx", C.c_void_p),
         ("B", C.c_int32), ("O", C.c_int32), ("A", C.c_int32), ("hidden", C.c_int32),
-        ("params", C.c_void_p), ("grads", C.c_void_p), ("G", C.c_int64),
-        ("off_W1", C.c_int64 * 2), ("off_b1", C.c_int64 * 2), ("off_W2", C.c_int64 * 2), ("off_b2", C.c_int64 * 2),
-        ("off_Wh", C.c_int64 * 2), ("off_bh", C.c_int64 * 2), ("off_log_std", C.c_int64),
+        ("params", C.c_void_p), ("grads", C.c_void_p), ("G", C.c_int64), ("layout", MlpLayout),
         ("clip", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("compute_adv_stats", C.c_int32),
         ("adv_stats", C.c_void_p), ("acc", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
         ("sqnorm_part", C.c_void_p), ("adam_step", C.c_void_p), ("hp", C.c_void_p),
@@ -93,11 +99,20 @@ class PpoMlpRolloutDesc(C.Structure):
     """myo_ppo_mlp_rollout_desc of include/myobatch.h (one env step's policy call of the rollout, MLP actor-critic)."""
     _fields_ = [
         ("obs", C.c_void_p), ("N", C.c_int32), ("O", C.c_int32), ("A", C.c_int32), ("hidden", C.c_int32), ("params", C.c_void_p),
-        ("off_W1", C.c_int64 * 2), ("off_b1", C.c_int64 * 2), ("off_W2", C.c_int64 * 2), ("off_b2", C.c_int64 * 2),
-        ("off_Wh", C.c_int64 * 2), ("off_bh", C.c_int64 * 2), ("off_log_std", C.c_int64),
+        ("layout", MlpLayout),
         ("seed", C.c_uint64), ("draw_counter", C.c_void_p), ("t_idx", C.c_void_p),
         ("obs_buf", C.c_void_p), ("act_buf", C.c_void_p), ("val_buf", C.c_void_p), ("logp_buf", C.c_void_p), ("clipped", C.c_void_p),
         ("deterministic", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class AdamDesc(C.Structure):
+    """myo_adam_desc of include/myobatch.h (clip_grad_norm_ + one Adam step over a flat fp32 vector)."""
+    _fields_ = [
+        ("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int32),
+        ("lr", C.c_float), ("b1", C.c_float), ("b2", C.c_float), ("eps", C.c_float), ("max_norm", C.c_float), ("grad_scale", C.c_float),
+        ("step", C.c_void_p), ("scratch", C.c_void_p), ("nparts", C.c_int32),
+        ("p_bf16", C.c_void_p), ("hp", C.c_void_p), ("images", C.POINTER(PpoMlpDesc)),
     ]
 
 
@@ -204,8 +219,7 @@ class NativeLib:
         L.myo_batch_data.argtypes = [vp, vp, C.POINTER(DataOut), vp]
         if b"MYO_EMU" in L.myo_version():
             return      # the emulation build (test tooling, csrc/emu_host.h) implements the env path only: ENV_PATH_SYMBOLS
-        L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp]
-        L.myo_ppo_loss_grad_hp.argtypes = L.myo_ppo_loss_grad.argtypes[:-1] + [vp, vp]
+        L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp, vp]
         L.myo_ppo_gather.argtypes = [vp] * 6 + [i32, i32, i32, vp, i32] + [vp] * 7
         L.myo_ppo_gather_seq.argtypes = [vp] * 9 + [i32] * 8 + [vp, i32] + [vp] * 11
         L.myo_rollout_state_snapshot.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
@@ -229,10 +243,7 @@ class NativeLib:
         L.myo_lstm_seq_supported.argtypes = [i32]
         L.myo_lstm_seq_fwd.argtypes = [vp] + [C.c_longlong] * 3 + [vp] * 4 + [i32] * 5 + [vp, C.c_longlong, C.c_longlong] + [vp] * 4
         L.myo_lstm_seq_bwd.argtypes = [vp, C.c_longlong, C.c_longlong] + [vp] * 5 + [i32] * 5 + [vp] * 2
-        L.myo_adam_clip_step.argtypes = [vp] * 4 + [i32] + [C.c_float] * 6 + [vp, vp, vp, vp]
-        L.myo_adam_apply.argtypes = [vp] * 4 + [i32] + [C.c_float] * 6 + [vp, vp, i32, vp, vp]
-        L.myo_adam_clip_step_hp.argtypes = L.myo_adam_clip_step.argtypes[:-1] + [vp, vp]
-        L.myo_adam_apply_hp.argtypes = L.myo_adam_apply.argtypes[:-1] + [vp, vp]
+        L.myo_adam_step.argtypes = [C.POINTER(AdamDesc), vp]
         L.myo_ppo_mlp_workspace_bytes.restype = C.c_longlong
         L.myo_ppo_mlp_workspace_bytes.argtypes = [i32, i32, i32, i32, C.c_longlong]
         L.myo_ppo_mlp_step.argtypes = [C.POINTER(PpoMlpDesc), vp]
@@ -240,8 +251,6 @@ class NativeLib:
         L.myo_ppo_mlp_step_resident.argtypes = [C.POINTER(PpoMlpDesc), vp]
         L.myo_ppo_mlp_images.argtypes = [C.POINTER(PpoMlpDesc), vp]
         L.myo_ppo_adv_moments_epoch.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-        L.myo_adam_clip_step_images.argtypes = L.myo_adam_clip_step_hp.argtypes[:-1] + [C.POINTER(PpoMlpDesc), vp]
-        L.myo_adam_apply_images.argtypes = L.myo_adam_apply_hp.argtypes[:-1] + [C.POINTER(PpoMlpDesc), vp]
         L.myo_ppo_mlp_rollout_workspace_bytes.restype = C.c_longlong
         L.myo_ppo_mlp_rollout_workspace_bytes.argtypes = [i32, i32, i32]
         L.myo_ppo_mlp_rollout_refresh.argtypes = [C.POINTER(PpoMlpRolloutDesc), vp]
@@ -286,12 +295,12 @@ EXPORTED_SYMBOLS = [
     "myo_batch_set_state", "myo_batch_warmstart", "myo_batch_set_bad_state_buffer", "myo_batch_set_task", "myo_batch_get_task", "myo_batch_set_object_group", "myo_batch_object_friction", "myo_batch_bind_constants", "myo_batch_tune_wrap_order", "myo_batch_forward_dump",
     "myo_batch_dump_size", "myo_batch_dump_offset", "myo_batch_kernel_ms",
     "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_ppo_gather_seq", "myo_rollout_state_snapshot", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
-    "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_clip_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_adam_apply", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_ppo_loss_grad_hp", "myo_adam_clip_step_hp", "myo_adam_apply_hp", "myo_last_error", "myo_version",
+    "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_last_error", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
     "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
-    "myo_ppo_mlp_step_resident", "myo_ppo_mlp_images", "myo_ppo_adv_moments_epoch", "myo_adam_clip_step_images", "myo_adam_apply_images",
+    "myo_ppo_mlp_step_resident", "myo_ppo_mlp_images", "myo_ppo_adv_moments_epoch",
 ]
 
 # ... of which the lane-serial emulation build (tests/emu/libmyobatch_emu.so: csrc/myobatch_emu.cpp + csrc/emu_host.h, test tooling) has the env

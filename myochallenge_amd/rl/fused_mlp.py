@@ -107,7 +107,7 @@ def _colsum(x):
 def flatten_parameters(policy, pad: int = 64):
     """Re-home every parameter (and its .grad) as a view into ONE flat fp32 vector, each slot padded to
     `pad` elements (keeps bf16 GEMM operands 128-byte aligned).  Lets the optimiser be one kernel
-    (``myo_adam_clip_step``) and the data-parallel all-reduce run in place on one buffer.  Must run
+    (``myo_adam_step``) and the data-parallel all-reduce run in place on one buffer.  Must run
     before any hipGraph captures the parameters' addresses."""
     if getattr(policy, "_flat", None) is not None:
         return policy._flat
@@ -162,11 +162,16 @@ class FlatAdam:
         dev = flat["p"].device
         self.m, self.v = torch.zeros_like(flat["p"]), torch.zeros_like(flat["p"])
         self._step = torch.zeros(2, dtype=torch.int32, device=dev)    # [committed, taken]
-        self.sq = torch.zeros(512, device=dev)   # partial sums of |g|^2 (64 of myo_adam_clip_step, or those myo_ppo_mlp_step leaves)
+        self.sq = torch.zeros(512, device=dev)   # partial sums of |g|^2 (64 of myo_adam_step, or those myo_ppo_mlp_step leaves)
         self.presummed = 0        # > 0: the gradient's producer has left that many partial sums in `sq` and advanced the step counter
         self.shadow = None        # bf16 copy of the flat parameters kept in step by the Adam kernel (FusedPPOStep sets it)
         self.hp = None            # PPO hyper-parameter block (include/myobatch.h): lr and the stop flag are read from it at run time
         self.images = None        # descriptor of a fused MLP step with resident operand images: the Adam kernel keeps them current
+        from ..native import AdamDesc
+        # built once: the library reads it at call time and hands the values to the kernels by value (hipGraph-safe, as PpoMlpDesc)
+        d = self._desc = AdamDesc()
+        d.p, d.g, d.m, d.v, d.n = flat["p"].data_ptr(), flat["g"].data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat["p"].numel()
+        d.step, d.scratch = self._step.data_ptr(), self.sq.data_ptr()
 
     @property
     def step_count(self):
@@ -177,45 +182,15 @@ class FlatAdam:
         self._step.fill_(int(step))
 
     def step(self, grad_scale: float = 1.0):
-        f = self.flat
-        stream = torch.cuda.current_stream(f["p"].device).cuda_stream
-        p = lambda t: C.c_void_p(t.data_ptr())
-        if self.images is not None:
-            sh = p(self.shadow) if self.shadow is not None else None
-            hp = p(self.hp) if self.hp is not None else None
-            if self.presummed > 0:
-                self.lib.check(self.lib.L.myo_adam_apply_images(
-                    p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
-                    self.eps, self.max_norm, float(grad_scale), p(self._step), p(self.sq), int(self.presummed), sh, hp,
-                    C.byref(self.images), C.c_void_p(stream)))
-            else:
-                self.lib.check(self.lib.L.myo_adam_clip_step_images(
-                    p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
-                    self.eps, self.max_norm, float(grad_scale), p(self._step), p(self.sq), sh, hp, C.byref(self.images),
-                    C.c_void_p(stream)))
-            return
-        if self.hp is not None:
-            sh = p(self.shadow) if self.shadow is not None else None
-            if self.presummed > 0:
-                self.lib.check(self.lib.L.myo_adam_apply_hp(
-                    p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
-                    self.eps, self.max_norm, float(grad_scale), p(self._step), p(self.sq), int(self.presummed), sh, p(self.hp),
-                    C.c_void_p(stream)))
-            else:
-                self.lib.check(self.lib.L.myo_adam_clip_step_hp(
-                    p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
-                    self.eps, self.max_norm, float(grad_scale), p(self._step), p(self.sq), sh, p(self.hp), C.c_void_p(stream)))
-            return
-        if self.presummed > 0:      # single-rank fused step: myo_ppo_mlp_step has done the squares and the step counter
-            self.lib.check(self.lib.L.myo_adam_apply(
-                p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
-                self.eps, self.max_norm, float(grad_scale), p(self._step), p(self.sq), int(self.presummed),
-                p(self.shadow) if self.shadow is not None else None, C.c_void_p(stream)))
-            return
-        self.lib.check(self.lib.L.myo_adam_clip_step(
-            p(f["p"]), p(f["g"]), p(self.m), p(self.v), f["p"].numel(), self.lr, self.betas[0], self.betas[1],
-            self.eps, self.max_norm, float(grad_scale), p(self._step), p(self.sq),
-            p(self.shadow) if self.shadow is not None else None, C.c_void_p(stream)))
+        """One step (myo_adam_step).  presummed > 0: the gradient's producer has done the squares and the step counter."""
+        d = self._desc
+        d.lr, d.b1, d.b2, d.eps, d.max_norm, d.grad_scale = self.lr, self.betas[0], self.betas[1], self.eps, self.max_norm, float(grad_scale)
+        d.nparts = int(self.presummed)
+        d.p_bf16 = self.shadow.data_ptr() if self.shadow is not None else None
+        d.hp = self.hp.data_ptr() if self.hp is not None else None
+        d.images = C.pointer(self.images) if self.images is not None else None
+        stream = torch.cuda.current_stream(self.flat["p"].device).cuda_stream
+        self.lib.check(self.lib.L.myo_adam_step(C.byref(d), C.c_void_p(stream)))
 
     def snapshot(self):
         return [t.clone() for t in (self.flat["p"], self.m, self.v, self._step)]
@@ -281,22 +256,38 @@ class FusedPPOStep:
         self.adv_slot = None                 # resident step: where its advantage moments are (a row of epoch_moments' output); None: self.stats
         self._moments = {}                   # per n_mb: (stats [n_mb, 2], scratch) of epoch_moments
 
-    # ---- fused forward / loss / backward on the matrix cores (libmyobatch: myo_ppo_mlp_step)
-    def _mfma_desc(self, B, obs_all, act_all, oldlp_all, adv_all, ret_all, idx):
-        """Descriptor of myo_ppo_mlp_step for minibatch size B, or None when the architecture / batch size has no fused path
-        (then the GEMM-per-layer path below runs).  The descriptor and its workspace are cached: hipGraph-safe."""
+    def _fused_layout(self, obs):
+        """Where the fused MLP kernels (myo_ppo_mlp_step, myo_ppo_mlp_rollout) find the policy's tensors in the flat vector
+        (native.MlpLayout), or None when the policy does not fit them: flat parameters with stacked actor / critic trunk views,
+        obs -> hid -> hid -> head in both nets, a 1-D log_std and fp32 observations `obs` [., O]."""
         from .. import native
         flat = getattr(self.policy, "_flat", None)
         if not self.use_mfma_step or flat is None or self.merged is None or len(self.merged) != 2 or self.policy.recurrent:
             return None
         pi, vf = self.nets["pi"], self.nets["vf"]
-        O = obs_all.shape[1]
-        hid = pi[0].weight.shape[0]
+        O, hid = obs.shape[1], pi[0].weight.shape[0]
         shapes_ok = all(tuple(l.weight.shape) == s for l, s in ((pi[0], (hid, O)), (vf[0], (hid, O)), (pi[1], (hid, hid)), (vf[1], (hid, hid)),
                                                                (pi[2], (self.A, hid)), (vf[2], (1, hid))))
-        if not shapes_ok or self.policy.log_std.dim() != 1 or obs_all.dtype != torch.float32:
+        if not shapes_ok or self.policy.log_std.dim() != 1 or obs.dtype != torch.float32:
             return None
-        G = flat["p"].numel()
+        slot = {id(p): sl[0] for p, sl in zip(flat["params"], flat["slots"])}
+        lay = native.MlpLayout()
+        for net, layers in enumerate((pi, vf)):
+            for lin, off_w, off_b in zip(layers, (lay.off_W1, lay.off_W2, lay.off_Wh), (lay.off_b1, lay.off_b2, lay.off_bh)):
+                off_w[net], off_b[net] = slot[id(lin.weight)], slot[id(lin.bias)]
+        lay.off_log_std = slot[id(self.policy.log_std)]
+        return lay
+
+    # ---- fused forward / loss / backward on the matrix cores (libmyobatch: myo_ppo_mlp_step)
+    def _mfma_desc(self, B, obs_all, act_all, oldlp_all, adv_all, ret_all, idx):
+        """Descriptor of myo_ppo_mlp_step for minibatch size B, or None when the architecture / batch size has no fused path
+        (then the GEMM-per-layer path below runs).  The descriptor and its workspace are cached: hipGraph-safe."""
+        from .. import native
+        lay = self._fused_layout(obs_all)
+        if lay is None:
+            return None
+        flat = self.policy._flat
+        O, hid, G = obs_all.shape[1], self.nets["pi"][0].weight.shape[0], flat["p"].numel()
         # one descriptor + workspace per SHAPE (the workspace is ~90 MB at B = 16384); the six data pointers are rewritten on every
         # call — the library reads the descriptor at call time, so a captured graph keeps the pointers it was captured with and an
         # eager caller may pass fresh tensors per minibatch without growing the cache
@@ -313,17 +304,10 @@ class FusedPPOStep:
             self._mfma[key] = (None, None)
             return None
         ws = torch.zeros(nbytes, dtype=torch.uint8, device=obs_all.device)
-        slot = {id(p): sl[0] for p, sl in zip(flat["params"], flat["slots"])}
         d = native.PpoMlpDesc()
         d.obs, d.act, d.oldlp, d.adv, d.ret, d.idx = (t.data_ptr() for t in (obs_all, act_all, oldlp_all, adv_all, ret_all, idx))
         d.B, d.O, d.A, d.hidden = B, O, self.A, hid
-        d.params, d.grads, d.G = flat["p"].data_ptr(), flat["g"].data_ptr(), G
-        for k, (a, b) in enumerate(zip(pi, vf)):
-            for net, lin in enumerate((a, b)):
-                wname, bname = (("off_W1", "off_b1"), ("off_W2", "off_b2"), ("off_Wh", "off_bh"))[k]
-                getattr(d, wname)[net] = slot[id(lin.weight)]
-                getattr(d, bname)[net] = slot[id(lin.bias)]
-        d.off_log_std = slot[id(self.policy.log_std)]
+        d.params, d.grads, d.G, d.layout = flat["p"].data_ptr(), flat["g"].data_ptr(), G, lay
         d.clip, d.vf_coef, d.ent_coef = self.clip, self.vf, self.ent
         d.adv_stats, d.acc = self.stats.data_ptr(), self.acc.data_ptr()
         d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
@@ -366,29 +350,16 @@ class FusedPPOStep:
         when the architecture / number of envs has no fused path.  Cached; `refresh_rollout_images` rebuilds the weight
         images it reads and has to run after every parameter change."""
         from .. import native
-        flat = getattr(self.policy, "_flat", None)
-        if not self.use_mfma_step or flat is None or self.merged is None or len(self.merged) != 2 or self.policy.recurrent:
-            return None
-        pi, vf = self.nets["pi"], self.nets["vf"]
-        N, O = obs.shape
-        hid = pi[0].weight.shape[0]
-        shapes_ok = all(tuple(l.weight.shape) == s for l, s in ((pi[0], (hid, O)), (vf[0], (hid, O)), (pi[1], (hid, hid)), (vf[1], (hid, hid)),
-                                                               (pi[2], (self.A, hid)), (vf[2], (1, hid))))
-        if not shapes_ok or self.policy.log_std.dim() != 1 or obs.dtype != torch.float32 or N % 32:
+        lay = self._fused_layout(obs)
+        (N, O), hid = obs.shape, self.nets["pi"][0].weight.shape[0]
+        if lay is None or N % 32:
             return None
         nbytes = self.lib.L.myo_ppo_mlp_rollout_workspace_bytes(O, self.A, hid)
         if nbytes <= 0:
             return None
         ws = torch.zeros(nbytes, dtype=torch.uint8, device=obs.device)
-        slot = {id(p): sl[0] for p, sl in zip(flat["params"], flat["slots"])}
         d = native.PpoMlpRolloutDesc()
-        d.obs, d.N, d.O, d.A, d.hidden, d.params = obs.data_ptr(), N, O, self.A, hid, flat["p"].data_ptr()
-        for k, (a, b) in enumerate(zip(pi, vf)):
-            for net, lin in enumerate((a, b)):
-                wname, bname = (("off_W1", "off_b1"), ("off_W2", "off_b2"), ("off_Wh", "off_bh"))[k]
-                getattr(d, wname)[net] = slot[id(lin.weight)]
-                getattr(d, bname)[net] = slot[id(lin.bias)]
-        d.off_log_std = slot[id(self.policy.log_std)]
+        d.obs, d.N, d.O, d.A, d.hidden, d.params, d.layout = obs.data_ptr(), N, O, self.A, hid, self.policy._flat["p"].data_ptr(), lay
         d.seed, d.draw_counter, d.t_idx = seed, draw.data_ptr(), t_idx.data_ptr()
         d.obs_buf, d.act_buf, d.val_buf, d.logp_buf, d.clipped = (t.data_ptr() for t in (obs_buf, act_buf, val_buf, logp_buf, clipped))
         d.deterministic, d.workspace, d.workspace_bytes = 0, ws.data_ptr(), nbytes
@@ -505,16 +476,10 @@ class FusedPPOStep:
         work = self._workbuf("loss", ((B + 63) // 64) * (2 * A + 6))
         stream = torch.cuda.current_stream(dev).cuda_stream
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        if self.hp is not None:
-            self.lib.check(self.lib.L.myo_ppo_loss_grad_hp(
-                p(mean), p(values), p(actions), p(old_logp), p(adv), p(returns), p(pol.log_std.data), p(self.stats),
-                B, A, self.clip, self.vf, p(dmean), p(dvalue), p(self.acc), p(dmean_h), p(dvalue_h), p(work), in_bf16, self.ent,
-                p(d[0]), p(d[1]), p(d[2]), p(self.hp), C.c_void_p(stream)))
-            return dmean, dvalue
         self.lib.check(self.lib.L.myo_ppo_loss_grad(
             p(mean), p(values), p(actions), p(old_logp), p(adv), p(returns), p(pol.log_std.data), p(self.stats),
             B, A, self.clip, self.vf, p(dmean), p(dvalue), p(self.acc), p(dmean_h), p(dvalue_h), p(work), in_bf16, self.ent,
-            p(d[0]), p(d[1]), p(d[2]), C.c_void_p(stream)))
+            p(d[0]), p(d[1]), p(d[2]), p(self.hp), C.c_void_p(stream)))
         return dmean, dvalue
 
     def _sde_loss(self, mean_h, value_h, lat_h, actions, old_logp, adv, returns):

@@ -1,4 +1,4 @@
-"""Seeded runs of the fused PPO MLP optimizer step (myo_ppo_mlp_step + myo_adam_apply_hp through FusedPPOStep.run_indexed, the
+"""Seeded runs of the fused PPO MLP optimizer step (myo_ppo_mlp_step + myo_adam_step through FusedPPOStep.run_indexed, the
 stateless path) whose outputs are reduced to SHA-256 digests: what tools/mlp_step_digests.py prints and
 tests/test_ppo_mlp_resident.py compares with tests/golden/mlp_step_digests.json.  The golden file was printed by that tool on an
 MI355X with the library built from the commit BEFORE the resident-image step (same inputs, same torch): a build whose kernels

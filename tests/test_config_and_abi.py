@@ -111,6 +111,31 @@ def test_task_cfg_struct_matches_header():
     assert names == [f[0] for f in native.TaskCfg._fields_]
 
 
+def _header_struct_fields(name):
+    """Field names of `typedef struct <name> { ... } <name>;` in the header, in declaration order."""
+    src = open(os.path.join(ROOT, "include", "myobatch.h")).read()
+    head = "typedef struct %s {" % name
+    body = src[src.index(head) + len(head):src.index("} %s;" % name)]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = []
+    for decl in body.split(";"):
+        m = re.match(r"(?:const\s+)?(?:struct\s+)?\w+\s*(.*)", decl.strip(), flags=re.S)      # a type, then the declarators
+        if m and m.group(1):
+            names += [re.sub(r"\[.*?\]|\*", "", n).strip() for n in m.group(1).split(",")]
+    return names
+
+
+def test_ppo_descriptor_structs_match_header():
+    """Field names and order of the ctypes mirrors of the PPO MLP path == those of the header's structs, and the two MLP
+    descriptors keep the byte size they had with the thirteen offsets as members of their own (before myo_mlp_layout)."""
+    for cname, mirror in (("myo_mlp_layout", native.MlpLayout), ("myo_ppo_mlp_desc", native.PpoMlpDesc),
+                          ("myo_ppo_mlp_rollout_desc", native.PpoMlpRolloutDesc), ("myo_adam_desc", native.AdamDesc)):
+        assert _header_struct_fields(cname) == [f[0] for f in mirror._fields_], cname
+    assert ctypes.sizeof(native.PpoMlpDesc) == 264 and ctypes.sizeof(native.PpoMlpRolloutDesc) == 224
+    assert native.PpoMlpDesc.layout.offset == 88 and native.PpoMlpRolloutDesc.layout.offset == 32
+    assert ctypes.sizeof(native.MlpLayout) == 13 * 8
+
+
 @pytest.mark.parametrize("which", ["emu", "hip"])
 def test_c_abi_argument_checks(which, emu_lib):
     """Every entry point validates its arguments before touching a device: NULL handles / pointers and
@@ -140,14 +165,27 @@ def test_c_abi_argument_checks(which, emu_lib):
         (L.myo_batch_tune_wrap_order, (null, null)),
     ]
     if which == "hip":
+        somewhere = 4096          # stands for a device address: an argument error returns before anything is read through it
+
+        def adam_desc(**changed):
+            d = native.AdamDesc(p=somewhere, g=somewhere, m=somewhere, v=somewhere, n=10, lr=0.1, b1=0.1, b2=0.1, eps=0.1, max_norm=0.1,
+                                grad_scale=0.1, step=somewhere, scratch=somewhere)
+            for k, v in changed.items():
+                setattr(d, k, v)
+            return d
+        # a fused-step descriptor that places its images properly, over a parameter vector of 11 elements where Adam's has 10
+        other_vector = native.PpoMlpDesc(B=1024, O=33, A=17, hidden=256, params=somewhere, G=11, workspace=somewhere, workspace_bytes=1 << 40)
         checks += [
-            (L.myo_ppo_loss_grad, (null,) * 8 + (16, 39, f(0.2), f(0.5)) + (null,) * 6 + (0, f(0.0)) + (null,) * 4),
+            (L.myo_ppo_loss_grad, (null,) * 8 + (16, 39, f(0.2), f(0.5)) + (null,) * 6 + (0, f(0.0)) + (null,) * 5),
             (L.myo_ppo_gather, (null,) * 6 + (16, 86, 39, null, 2) + (null,) * 7),
             (L.myo_bias_relu_bf16, (null, null, 2, 16, 256, null)),
             (L.myo_relu_bwd_colsum_bf16, (null, null, 64, 256, null, null)),
             (L.myo_splitk_reduce, (null, 1, null, 2, 32, 256, null)),
             (L.myo_splitk_reduce2, (null, 1, null, 2, 32, 256, null, 0, null, 2, 64, 256, null)),
-            (L.myo_adam_clip_step, (null,) * 4 + (10,) + (f(0.1),) * 6 + (null,) * 4),
+            (L.myo_adam_step, (null, null)),
+            (L.myo_adam_step, (C.byref(adam_desc(p=None)), null)),
+            (L.myo_adam_step, (C.byref(adam_desc(n=0)), null)),
+            (L.myo_adam_step, (C.byref(adam_desc(images=C.pointer(other_vector))), null)),
             (L.myo_gae, (null,) * 5 + (4, 4, f(0.99), f(0.95), null, null, null)),
             (L.myo_rollout_policy_input, (null, 4, 86, null, null, 2, null, null)),
             (L.myo_rollout_sample, (null, null, null, 4, 39, 1, null, null, null, null, null, null, 0, null)),
@@ -166,6 +204,8 @@ def test_c_abi_argument_checks(which, emu_lib):
         assert len(L.myo_last_error()) > 0
     assert L.myo_batch_num_envs(null) <= 0 and L.myo_batch_obs_dim(null) <= 0
     if which == "hip":
+        assert L.myo_adam_step(C.byref(adam_desc(images=C.pointer(other_vector))), null) == -1
+        assert b"parameter vector has 11 elements, this one 10" in L.myo_last_error()       # (that check, not one ahead of it)
         buf = (C.c_float * 64)()
         assert L.myo_splitk_reduce(buf, 0, buf, 1, 2, 15, None) == -1          # odd n
 

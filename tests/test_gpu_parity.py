@@ -378,7 +378,7 @@ def test_ppo_elementwise_kernels_exact(hip_lib):
     g_ls, g_bpi, g_bvf = torch.zeros(A, device=dev), torch.zeros(A, device=dev), torch.zeros(1, device=dev)
     hip_lib.check(L.myo_ppo_loss_grad(p(mean), p(values), p(act), p(oldlp), p(adv), p(ret), p(log_std), p(stats), B, A, clip, vf,
                                       p(dmean), p(dval), p(acc), p(dmean_h), p(dval_h), p(work), 0, 0.01, p(g_ls), p(g_bpi),
-                                      p(g_bvf), None))
+                                      p(g_bvf), None, None))
     torch.cuda.synchronize()
     tol = lambda a, b, r: float((a - b).abs().max()) <= r * float(b.abs().max()) + 1e-12
     assert tol(dmean, dmean_ref, 2e-5) and tol(dval, dval_ref, 1e-6) and tol(acc, acc_ref, 2e-5)
@@ -388,9 +388,9 @@ def test_ppo_elementwise_kernels_exact(hip_lib):
     mean_b, val_b = mean.bfloat16(), values.bfloat16()
     acc2, dmean2, dval2 = torch.zeros_like(acc), torch.zeros_like(dmean), torch.zeros_like(dval)
     hip_lib.check(L.myo_ppo_loss_grad(p(mean_b.float()), p(val_b.float()), p(act), p(oldlp), p(adv), p(ret), p(log_std), p(stats), B, A,
-                                      clip, vf, p(dmean), p(dval), p(acc), None, None, p(work), 0, 0.0, None, None, None, None))
+                                      clip, vf, p(dmean), p(dval), p(acc), None, None, p(work), 0, 0.0, None, None, None, None, None))
     hip_lib.check(L.myo_ppo_loss_grad(p(mean_b), p(val_b), p(act), p(oldlp), p(adv), p(ret), p(log_std), p(stats), B, A,
-                                      clip, vf, p(dmean2), p(dval2), p(acc2), None, None, p(work), 1, 0.0, None, None, None, None))
+                                      clip, vf, p(dmean2), p(dval2), p(acc2), None, None, p(work), 1, 0.0, None, None, None, None, None))
     torch.cuda.synchronize()
     assert torch.equal(acc, acc2) and torch.equal(dmean, dmean2) and torch.equal(dval, dval2)
 
@@ -450,7 +450,7 @@ def test_gae_kernel_matches_torch_scan(hip_lib):
 
 
 def test_flat_adam_matches_torch_clip_and_adam(hip_lib):
-    """myo_adam_clip_step == clip_grad_norm_(0.5) + torch.optim.Adam(eps=1e-5) over several steps."""
+    """myo_adam_step == clip_grad_norm_(0.5) + torch.optim.Adam(eps=1e-5) over several steps."""
     import torch
     from myochallenge_amd.rl.fused_mlp import FlatAdam, flatten_parameters
     from myochallenge_amd.rl.policy import ActorCriticPolicy
@@ -1316,8 +1316,8 @@ def test_fused_rollout_policy_matches_gemm_path(hip_lib, monkeypatch):
 
 
 def test_single_rank_gradient_tail_matches_the_separate_kernels(hip_lib, monkeypatch):
-    """k_mlp_reduce_finish + myo_adam_apply (slab reduction, loss columns, gradient squares and step counter in one launch; the
-    single-rank path) against k_mlp_reduce + k_colmajor_finish + myo_adam_clip_step (what N > 1 ranks run around their
+    """k_mlp_reduce_finish + myo_adam_step on its partial sums (slab reduction, loss columns, gradient squares and step counter in one launch; the
+    single-rank path) against k_mlp_reduce + k_colmajor_finish + myo_adam_step with nparts = 0 (what N > 1 ranks run around their
     all-reduce): same rollout, same minibatches — the parameters after a PPO update agree to the rounding of the differently
     ordered sum of squares."""
     import torch

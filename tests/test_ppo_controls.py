@@ -214,7 +214,7 @@ def _adam_state(fa):
 
 @pytest.mark.gpu
 def test_stop_flag_fused_mlp_step(hip_lib):
-    """Kernel level, fused MLP step (myo_ppo_mlp_step + myo_adam_apply_hp) at its smallest batch: old_logp = logp - 0.5 makes
+    """Kernel level, fused MLP step (myo_ppo_mlp_step + myo_adam_step) at its smallest batch: old_logp = logp - 0.5 makes
     approx_kl = e^0.5 - 1.5 for every row.  Limit at half of it: two steps change nothing (parameters, m, v, bf16 shadow, step
     counter bit-identical), stop is up, applied == 0.  Limit at twice it: bit-identical to the step without a block, stop down,
     applied == 2.  approx_kl vs the fp32 torch value: the bound the fused-step test uses for policy_loss (2e-3)."""
@@ -358,7 +358,7 @@ def test_schedules_through_captured_recurrent_graph(hip_lib):
 
 @pytest.mark.gpu
 def test_stop_flag_fused_recurrent_step(hip_lib):
-    """Kernel level, fused recurrent minibatch step (run_sequences: myo_ppo_loss_grad_hp, then myo_adam_clip_step_hp) on a window
+    """Kernel level, fused recurrent minibatch step (run_sequences: myo_ppo_loss_grad, then myo_adam_step, both with the block) on a window
     with episode starts inside it: old_logp = (the fp32 policy's log pi) - 0.5, so the fp32 approx_kl over the entries (all
     unmasked: the sequences are whole rollouts, nothing is padded) is e^0.5 - 1.5.  Same three cases as the MLP step."""
     env, algo = _gpu_lstm_algo(schedules=False)

@@ -1,5 +1,5 @@
 """The fused PPO MLP optimizer step with RESIDENT operand images (myo_ppo_mlp_step_resident, myo_ppo_mlp_images,
-myo_adam_*_images, myo_ppo_adv_moments_epoch: four launches per step instead of six) against the stateless step it replaces.
+myo_adam_step with images, myo_ppo_adv_moments_epoch: four launches per step instead of six) against the stateless step it replaces.
 Every comparison is torch.equal: the resident path removes passes, it does not reorder a sum.
 
 Shapes (tests/mlp_digest_cases.CASES): B = 1024 with (O, A) = (1, 1), (33, 17), (97, 48) — OP = 32 / 64 / 128, one to three head
@@ -94,7 +94,7 @@ def test_resident_step_equals_stateless_step(hip_lib, case, stop_before_step_two
 
 @pytest.mark.parametrize("case", mdc.CASES, ids=mdc.case_id)
 def test_resident_step_with_the_multi_rank_tail(hip_lib, case):
-    """The tail N > 1 ranks run — k_mlp_reduce + k_colmajor_finish, then (after the all-reduce) myo_adam_clip_step_images, which
+    """The tail N > 1 ranks run — k_mlp_reduce + k_colmajor_finish, then (after the all-reduce) myo_adam_step with nparts = 0 and images, which
     squares the gradient itself — resident against stateless over three steps: same state, same images."""
     lib = hip_lib
     _, fa_s, st_s, hp_s, data = mdc.make_run(lib, case)
@@ -114,6 +114,50 @@ def test_resident_step_with_the_multi_rank_tail(hip_lib, case):
     lib.check(lib.L.myo_ppo_mlp_images(C.byref(d_s), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
     assert torch.equal(img_s, _image_bytes(lib, st_r, case)[1]) and int(fa_r._step[1]) == 3
+
+
+def test_adam_step_is_one_step_whatever_it_is_handed(hip_lib):
+    """One optimizer step through myo_adam_step on the gradient of the smallest digest case with OP != O and two head tiles
+    (B = 1024, O = 33, A = 17), from the same state, in the eight combinations nparts in {0, the fused step's partial sums} x
+    hp in {NULL, block holding the same lr} x images in {NULL, the fused step's descriptor}.  Within one nparts setting p, m, v
+    and the bf16 shadow are bit-equal across hp and images (the two settings add |g|^2 in different orders); where images is set,
+    the six images are afterwards what a fresh myo_ppo_mlp_images pass writes for the updated parameters."""
+    lib, case = hip_lib, mdc.CASES[1]
+    assert case[:3] == (33, 17, 1024)
+    _, fa, step, hp, data = mdc.make_run(lib, case)
+    before = {k: t.clone() for k, t in (("p", fa.flat["p"]), ("m", fa.m), ("v", fa.v), ("shadow", fa.shadow), ("hp", hp))}
+    step.run_indexed(*data)        # leaves the gradient, its partial sums of squares in fa.sq and the step counter advanced
+    torch.cuda.synchronize()
+    assert fa.presummed == lib.L.myo_ppo_mlp_sqnorm_parts(case[1]) and fa._step.tolist() == [0, 1]
+    sq = fa.sq.clone()
+    desc, img = _image_bytes(lib, step, case)
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    a = native.AdamDesc(p=fa.flat["p"].data_ptr(), g=fa.flat["g"].data_ptr(), m=fa.m.data_ptr(), v=fa.v.data_ptr(), n=fa.flat["p"].numel(),
+                        lr=mdc.LR, b1=0.9, b2=0.999, eps=1e-5, max_norm=mdc.MAX_NORM, grad_scale=1.0, step=fa._step.data_ptr(),
+                        scratch=fa.sq.data_ptr(), p_bf16=fa.shadow.data_ptr())
+    got = {}
+    for nparts in (0, fa.presummed):
+        for with_hp in (False, True):
+            for with_images in (False, True):
+                for k, t in (("p", fa.flat["p"]), ("m", fa.m), ("v", fa.v), ("shadow", fa.shadow), ("hp", hp)):
+                    t.copy_(before[k])
+                fa.sq.copy_(sq)
+                fa._step.copy_(torch.tensor([0, 1 if nparts else 0], dtype=torch.int32))
+                lib.check(lib.L.myo_ppo_mlp_images(C.byref(desc), stream()))          # the images of the parameters before the step
+                a.nparts, a.hp, a.images = nparts, (hp.data_ptr() if with_hp else None), (C.pointer(desc) if with_images else None)
+                lib.check(lib.L.myo_adam_step(C.byref(a), stream()))
+                torch.cuda.synchronize()
+                assert fa._step.tolist() == [0, 1] and int(hp.view(torch.int32)[native.HP_APPLIED]) == int(with_hp)
+                got[nparts, with_hp, with_images] = {k: t.clone() for k, t in (("p", fa.flat["p"]), ("m", fa.m), ("v", fa.v), ("shadow", fa.shadow))}
+                if with_images:
+                    mirrored = img.clone()
+                    lib.check(lib.L.myo_ppo_mlp_images(C.byref(desc), stream()))
+                    torch.cuda.synchronize()
+                    assert torch.equal(mirrored, img), ("operand images", nparts, with_hp)
+        plain = got[nparts, False, False]
+        assert not torch.equal(plain["p"], before["p"]), "no step was taken"
+        for with_hp, with_images in ((False, True), (True, False), (True, True)):
+            _assert_same(plain, got[nparts, with_hp, with_images], "nparts = %d, hp %s, images %s" % (nparts, with_hp, with_images))
 
 
 @pytest.mark.parametrize("n_mb", [1, 3, 16])
