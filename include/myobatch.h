@@ -506,7 +506,16 @@ int myo_ppo_gather_seq(const float* obs, const float* act, const float* oldlp, c
                        float* adv_mb, float* ret_mb, float* keep, uint16_t* hm0, uint16_t* cm0, float* c0_32,
                        float* adv_stats /* NULL: not computed */, float* work, void* stream);
 
-/* h <- max(h + bias, 0) in place: bfloat16 h[groups, rows, cols], bias[groups, cols] (cols even). */
+/* Activation of the hidden MLP layers (torch.nn.ReLU, torch.nn.Tanh: SB3's default) of every fused PPO path.  It is an argument
+ * of the *_act entry points below, not a descriptor field (the descriptors keep their size); any other code: MYO_E_ARG.  tanh is
+ * ONE formula in every kernel, 1 - 2 / (e^2x + 1), evaluated in double from the fp32 pre-activation (saturates to exactly +-1),
+ * rounded to bfloat16 once; its backward is
+ * bf16(dy) * (1 - h * h) on the STORED bfloat16 output h, the product rounded once (autograd under bf16 autocast). */
+#define MYO_ACT_RELU 0
+#define MYO_ACT_TANH 1
+/* h <- activation(h + bias) in place: bfloat16 h[groups, rows, cols], bias[groups, cols] (cols even). */
+int myo_bias_act_bf16(uint16_t* h, const uint16_t* bias, int groups, int rows, int cols, int activation, void* stream);
+/* ... with MYO_ACT_RELU: h <- max(h + bias, 0). */
 int myo_bias_relu_bf16(uint16_t* h, const uint16_t* bias, int groups, int rows, int cols, void* stream);
 
 /* Finishes a split-K product: out[g, j] = sum_k part[g, k, j]; part dev [groups, splits, n] of
@@ -517,9 +526,11 @@ int myo_splitk_reduce(const void* part, int part_is_bf16, float* out, int groups
 int myo_splitk_reduce2(const void* part_a, int a_is_bf16, float* out_a, int groups_a, int splits_a, int n_a,
                        const void* part_b, int b_is_bf16, float* out_b, int groups_b, int splits_b, int n_b, void* stream);
 
-/* ReLU backward in place on bfloat16 dy[rows, cols] (dy *= act > 0) plus column sums of the result
- * over blocks of 32 rows: partial dev float32 [rows/32, cols] (finish with myo_splitk_reduce: the
- * bias gradient).  rows % 32 == 0, cols/2 divides 256. */
+/* Activation backward in place on bfloat16 dy[rows, cols] from the layer's OUTPUT act (ReLU: dy *= act > 0; tanh: dy <-
+ * bf16(dy * (1 - act * act))) plus column sums of the result over blocks of 32 rows: partial dev float32 [rows/32, cols]
+ * (finish with myo_splitk_reduce: the bias gradient).  rows % 32 == 0, cols/2 divides 256. */
+int myo_act_bwd_colsum_bf16(uint16_t* dy, const uint16_t* act, int rows, int cols, float* partial, int activation, void* stream);
+/* ... with MYO_ACT_RELU. */
 int myo_relu_bwd_colsum_bf16(uint16_t* dy, const uint16_t* act, int rows, int cols, float* partial, void* stream);
 
 /* ---- per-step rollout plumbing (between two myo_batch_step launches) ------------------------------
@@ -642,7 +653,7 @@ int myo_gae(const float* rew, const float* val, const float* starts, const float
             const float* last_done, int T, int N, float gamma, float lam, float* adv, float* ret,
             void* stream);
 
-/* One PPO minibatch step of the MLP actor-critic (two hidden layers of 256 per net, ReLU) on the matrix cores: what SB3's
+/* One PPO minibatch step of the MLP actor-critic (two hidden layers of 256 per net, ReLU or tanh) on the matrix cores: what SB3's
  * PPO.train runs per minibatch through autograd (evaluate_actions -> clipped surrogate + vf_coef * MSE - ent_coef * entropy ->
  * backward; /root/reference/src/train/trainer.py:57-71 hands that loop to sb3-contrib).  Gathers rows
  * idx[0..B) of the rollout arrays, runs forward, loss gradient and backward, and leaves d(loss)/d(param) in `grads` (same flat
@@ -711,13 +722,18 @@ typedef struct myo_ppo_mlp_desc {
 } myo_ppo_mlp_desc;
 int myo_ppo_mlp_sqnorm_parts(int act_dim);
 long long myo_ppo_mlp_workspace_bytes(int B, int obs_dim, int act_dim, int hidden, long long G);
+/* The step for hidden activation `activation` (MYO_ACT_*); resident != 0: with resident operand images (below).  The image pass,
+ * the workspace and its size do not depend on the activation.  The tanh step reads each hidden activation back from the
+ * feature-major copy in the workspace where the ReLU step keeps one mask bit in a register. */
+int myo_ppo_mlp_step_act(const myo_ppo_mlp_desc* d, int resident, int activation, void* stream);
+/* ... with MYO_ACT_RELU, resident = 0. */
 int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream);
 /* The same step with RESIDENT operand images, four launches instead of six: the bf16 weight images at the front of `workspace`
  * are taken as current and the advantage moments as the caller's (compute_adv_stats must be 0), so neither the image pass nor
  * the moments pass runs.  The images are current after myo_ppo_mlp_images (once, whenever `params` may have been written from
  * outside: a load, the start of an update) and stay so while every change of `params` is an optimizer step through
  * myo_adam_step with `images` = the same descriptor.  Same results as myo_ppo_mlp_step, bit for bit. */
-int myo_ppo_mlp_step_resident(const myo_ppo_mlp_desc* d, void* stream);
+int myo_ppo_mlp_step_resident(const myo_ppo_mlp_desc* d, void* stream);      /* MYO_ACT_RELU, resident = 1 */
 /* The image pass alone: the operand images of `params` into `workspace`, zero padding included (reads B, O, A, hidden, params, G,
  * layout, workspace, workspace_bytes of `d`). */
 int myo_ppo_mlp_images(const myo_ppo_mlp_desc* d, void* stream);
@@ -749,7 +765,8 @@ typedef struct myo_ppo_mlp_rollout_desc {
 } myo_ppo_mlp_rollout_desc;
 long long myo_ppo_mlp_rollout_workspace_bytes(int obs_dim, int act_dim, int hidden);
 int myo_ppo_mlp_rollout_refresh(const myo_ppo_mlp_rollout_desc* d, void* stream);
-int myo_ppo_mlp_rollout(const myo_ppo_mlp_rollout_desc* d, void* stream);
+int myo_ppo_mlp_rollout_act(const myo_ppo_mlp_rollout_desc* d, int activation, void* stream);      /* hidden activation MYO_ACT_* */
+int myo_ppo_mlp_rollout(const myo_ppo_mlp_rollout_desc* d, void* stream);                           /* ... with MYO_ACT_RELU */
 
 /* clip_grad_norm_(max_norm) followed by one torch.optim.Adam step over a flat fp32 parameter vector
  * (what RecurrentPPO.train does per minibatch; /root/reference/src/train/trainer.py:66-71, SB3 Adam

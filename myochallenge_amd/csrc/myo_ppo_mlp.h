@@ -1,4 +1,4 @@
-// myo_ppo_mlp.h — one PPO minibatch step of the MLP actor-critic (obs -> H -> H -> head, ReLU; both nets) on the
+// myo_ppo_mlp.h — one PPO minibatch step of the MLP actor-critic (obs -> H -> H -> head, ReLU or tanh; both nets) on the
 // matrix cores: what SB3's PPO.train does per minibatch through autograd (evaluate_actions, clipped surrogate + value
 // loss, backward; /root/reference/src/train/trainer.py:57-71 -> sb3 PPO.train) as FOUR launches
 // instead of ~25 (hipBLASLt GEMMs + elementwise kernels, each 8-20 us for microseconds of work):
@@ -18,6 +18,7 @@
 // 16 contiguous bytes per lane from a K-contiguous image (rows of X / H in LDS, rows of W in global memory).
 #pragma once
 #ifndef MYO_EMU
+#include "myo_act.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 myo_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float myo_f32x4;
@@ -269,9 +270,10 @@ extern "C" int myo_debug_mlp_prof(unsigned long long* out) { return (int)hipMemc
 
 // LDS of one workgroup (BM rows): row ids, X (later the head output), ONE hidden image (H1, then H2, then dH2 — each is only
 // needed as the A operand of the next GEMM; the ReLU masks the two gradient epilogues need stay in registers, one bit per
-// accumulator element of the lane, because the wave that applies a mask is the wave that produced the activation),
+// accumulator element of the lane, because the wave that applies a mask is the wave that produced the activation; the tanh
+// instantiation reads its activations back instead, see mlp_load_act),
 // actions (later d log_std terms), d(head output), log_std / exp(-log_std), adv / old log-prob / return.
-// BM = 32: 38 KB, 241 VGPRs -> two workgroups per CU (the register budget decides), whose phases (gather, MFMA slabs, the
+// BM = 32: 38 KB, 232 VGPRs -> two workgroups per CU (the register budget decides), whose phases (gather, MFMA slabs, the
 // one-wave loss phase, feature-major stores) overlap each other's latencies.  BM = 64 (75 KB, also two per CU, every weight
 // fragment fetched from L2 feeding four row tiles instead of two) was measured at the SAME time per row — 54 us per 64-row
 // workgroup against 2 x 28 us, k_mlp_fwdbwd 71.0 vs 69.8 us at B = 16384 — with 33 spilled registers: the phases scale with
@@ -281,7 +283,60 @@ extern "C" int myo_debug_mlp_prof(unsigned long long* out) { return (int)hipMemc
 #endif
 #define MLP_FWDBWD_LDS (512 + MLP_BM * MLP_XS * 2 + MLP_BM * MLP_HS * 2 + MLP_BM * MLP_SOS * 4 + MLP_BM * MLP_DS * 2 + 128 * 4 + 192 * 4)
 
-// activation epilogue of one slab: bias + ReLU -> bf16 -> row-major LDS image (next layer's A operand) + feature-major global copy
+// The hidden activation is a template parameter of k_mlp_fwdbwd / k_mlp_policy (MYO_ACT_RELU, MYO_ACT_TANH: the host picks the
+// instantiation).  ReLU's derivative is one bit per element and stays in registers (mlp_store_act's mask); tanh's is 1 - h^2 of the
+// STORED bf16 activation h (what autograd under bf16 autocast differentiates through), and 2 x 32 of them per lane held across the
+// loss phase do not fit beside its 232 VGPRs: the lane reads them back from the feature-major copy it wrote for k_mlp_wgrad — its own
+// stores, the same addresses, the same uint2 shape (mlp_load_act) — a GEMM ahead of the epilogue that scales with them.
+template <int ACT>
+__device__ __forceinline__ float mlp_act(float x) { return ACT == MYO_ACT_TANH ? myo_act_tanh(x) : fmaxf(x, 0.f); }
+
+// tanh instantiation: activation epilogue of one slab, as mlp_store_act without the mask
+template <int MT>
+__device__ __forceinline__ void mlp_store_act_tanh(const myo_f32x4 (&acc)[MT][4], const float (&bb)[4], unsigned short* Hs, unsigned short* HT,
+                                                   size_t B, int r0, int n0, int lm, int lq) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const int n = n0 + 16 * nt + lm, m = 16 * mt + 4 * lq;
+      unsigned short h[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { h[r] = mlp_f2bf(mlp_act<MYO_ACT_TANH>(acc[mt][nt][r] + bb[nt])); Hs[(m + r) * MLP_HS + n] = h[r]; }
+      *reinterpret_cast<uint2*>(HT + (size_t)n * B + r0 + m) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
+    }
+}
+// the lane's own activations of a slab back from the feature-major copy (what mlp_store_act_tanh stored there): 2 VGPRs per tile
+template <int MT>
+__device__ __forceinline__ void mlp_load_act(uint2 (&hv)[MT][4], const unsigned short* HT, size_t B, int r0, int n0, int lm, int lq) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) hv[mt][nt] = *reinterpret_cast<const uint2*>(HT + (size_t)(n0 + 16 * nt + lm) * B + r0 + 16 * mt + 4 * lq);
+  __builtin_amdgcn_sched_barrier(0);      // (requested here, ahead of the GEMM, not next to their use behind it)
+}
+// tanh gradient epilogue: bf16(acc) * (1 - h^2), the product rounded to bf16 once -> optional LDS image + feature-major global copy
+template <int MT, bool TO_LDS>
+__device__ __forceinline__ void mlp_store_grad_tanh(const myo_f32x4 (&acc)[MT][4], const uint2 (&hv)[MT][4], unsigned short* Hs, unsigned short* HT,
+                                                    size_t B, int r0, int n0, int lm, int lq) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const int n = n0 + 16 * nt + lm, m = 16 * mt + 4 * lq;
+      const float hf[4] = {__uint_as_float(hv[mt][nt].x << 16), __uint_as_float(hv[mt][nt].x & 0xffff0000u),
+                           __uint_as_float(hv[mt][nt].y << 16), __uint_as_float(hv[mt][nt].y & 0xffff0000u)};
+      unsigned short h[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        h[r] = mlp_f2bf(mlp_bf2f(mlp_f2bf(acc[mt][nt][r])) * fmaf(-hf[r], hf[r], 1.f));
+        if (TO_LDS) Hs[(m + r) * MLP_HS + n] = h[r];
+      }
+      *reinterpret_cast<uint2*>(HT + (size_t)n * B + r0 + m) = make_uint2((unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16));
+    }
+}
+
+// ReLU instantiation: activation epilogue of one slab: bias + ReLU -> bf16 -> row-major LDS image (next layer's A operand) + feature-major global copy
 // returns the lane's ReLU mask: bit 16 mt + 4 nt + r = (activation != 0)
 template <int MT>
 __device__ __forceinline__ unsigned long long mlp_store_act(const myo_f32x4 (&acc)[MT][4], const float (&bb)[4], unsigned short* Hs, unsigned short* HT,
@@ -323,6 +378,7 @@ __device__ __forceinline__ void mlp_store_grad(const myo_f32x4 (&acc)[MT][4], un
     }
 }
 
+template <int ACT>
 __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
   constexpr int H = MLP_H, XS = MLP_XS, HS = MLP_HS, DS = MLP_DS, SOS = MLP_SOS, BM = MLP_BM, MT = BM / 16, RW = BM / 4;
   extern __shared__ __align__(16) unsigned char mlp_smem[];
@@ -400,7 +456,9 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
   else if (OP == 64) mlp_mma_slab<2, MT>(acc, Xs, XS, bw, lm, lq);
   else mlp_mma_slab<1, MT>(acc, Xs, XS, bw, lm, lq);
   mlp_load_w<H / 32>(bw, P.img.W2 + (size_t)net * H * H, H, n0, lm, lq);
-  const unsigned long long mask1 = mlp_store_act<MT>(acc, bb1, Hs, P.H1T + (size_t)net * H * B, B, r0, n0, lm, lq);
+  unsigned long long mask1 = 0, mask2 = 0;       // (ReLU instantiation only)
+  if (ACT == MYO_ACT_TANH) mlp_store_act_tanh<MT>(acc, bb1, Hs, P.H1T + (size_t)net * H * B, B, r0, n0, lm, lq);
+  else mask1 = mlp_store_act<MT>(acc, bb1, Hs, P.H1T + (size_t)net * H * B, B, r0, n0, lm, lq);
   __syncthreads();
   MLP_STAMP(2)
   // ---- layer 2
@@ -415,7 +473,8 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
   }
   __builtin_amdgcn_sched_barrier(0);
   __syncthreads();                       // every wave has read H1 out of the hidden image: H2 takes its place
-  const unsigned long long mask2 = mlp_store_act<MT>(acc, bb2, Hs, P.H2T + (size_t)net * H * B, B, r0, n0, lm, lq);
+  if (ACT == MYO_ACT_TANH) mlp_store_act_tanh<MT>(acc, bb2, Hs, P.H2T + (size_t)net * H * B, B, r0, n0, lm, lq);
+  else mask2 = mlp_store_act<MT>(acc, bb2, Hs, P.H2T + (size_t)net * H * B, B, r0, n0, lm, lq);
   __syncthreads();
   MLP_STAMP(3)
   // ---- head (fp32 into So, which reuses X's storage)
@@ -512,15 +571,23 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwdbwd(MlpArgs P) {
     }
   }
   MLP_STAMP(6)
-  // ---- d hidden 2 = (dOut Wh) * (H2 > 0), written over H2's LDS image (its A-operand role ended with the head)
+  // ---- d hidden 2 = (dOut Wh) * act'(H2), written over H2's LDS image (its A-operand role ended with the head)
+  uint2 hv[MT][4];                       // (tanh instantiation only: the lane's stored activations, see mlp_load_act)
+  if (ACT == MYO_ACT_TANH) mlp_load_act<MT>(hv, P.H2T + (size_t)net * H * B, B, r0, n0, lm, lq);
   mlp_mma_slab<MLP_AKP / 32, MT>(acc, dOs, DS, bw, lm, lq);
   mlp_load_w<H / 32>(bw, P.img.W2T + (size_t)net * H * H, H, n0, lm, lq);
-  mlp_store_grad<MT, true>(acc, mask2, Hs, P.dH2T + (size_t)net * H * B, B, r0, n0, lm, lq);
+  if (ACT == MYO_ACT_TANH) {
+    mlp_store_grad_tanh<MT, true>(acc, hv, Hs, P.dH2T + (size_t)net * H * B, B, r0, n0, lm, lq);
+    mlp_load_act<MT>(hv, P.H1T + (size_t)net * H * B, B, r0, n0, lm, lq);      // d hidden 1's, in flight across the barrier and the GEMM
+  } else {
+    mlp_store_grad<MT, true>(acc, mask2, Hs, P.dH2T + (size_t)net * H * B, B, r0, n0, lm, lq);
+  }
   __syncthreads();
   MLP_STAMP(7)
-  // ---- d hidden 1 = (dH2 W2) * (H1 > 0)
+  // ---- d hidden 1 = (dH2 W2) * act'(H1)
   mlp_mma_slab<H / 32, MT>(acc, Hs, HS, bw, lm, lq);
-  mlp_store_grad<MT, false>(acc, mask1, Hs, P.dH1T + (size_t)net * H * B, B, r0, n0, lm, lq);
+  if (ACT == MYO_ACT_TANH) mlp_store_grad_tanh<MT, false>(acc, hv, Hs, P.dH1T + (size_t)net * H * B, B, r0, n0, lm, lq);
+  else mlp_store_grad<MT, false>(acc, mask1, Hs, P.dH1T + (size_t)net * H * B, B, r0, n0, lm, lq);
   MLP_STAMP(8)
 }
 
@@ -543,8 +610,8 @@ struct MlpPolicyArgs {
 };
 #define MLP_POLICY_LDS (MLP_BM * MLP_XS * 2 + MLP_BM * MLP_HS * 2 + 128 * 4)
 
-// forward epilogue: bias + ReLU -> bf16 -> row-major LDS image (the next layer's A operand)
-template <int MT>
+// forward epilogue: bias + activation -> bf16 -> row-major LDS image (the next layer's A operand)
+template <int ACT, int MT>
 __device__ __forceinline__ void mlp_store_act_lds(const myo_f32x4 (&acc)[MT][4], const float (&bb)[4], unsigned short* Hs, int n0, int lm, int lq) {
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
@@ -552,10 +619,11 @@ __device__ __forceinline__ void mlp_store_act_lds(const myo_f32x4 (&acc)[MT][4],
     for (int nt = 0; nt < 4; ++nt) {
       const int n = n0 + 16 * nt + lm, m = 16 * mt + 4 * lq;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) Hs[(m + r) * MLP_HS + n] = mlp_f2bf(fmaxf(acc[mt][nt][r] + bb[nt], 0.f));
+      for (int r = 0; r < 4; ++r) Hs[(m + r) * MLP_HS + n] = mlp_f2bf(mlp_act<ACT>(acc[mt][nt][r] + bb[nt]));
     }
 }
 
+template <int ACT>
 __global__ void __launch_bounds__(256, 2) k_mlp_policy(MlpPolicyArgs P) {
   constexpr int H = MLP_H, XS = MLP_XS, HS = MLP_HS, SOS = MLP_SOS, BM = MLP_BM, MT = BM / 16, RW = BM / 4;
   extern __shared__ __align__(16) unsigned char mlp_smem[];
@@ -607,7 +675,7 @@ __global__ void __launch_bounds__(256, 2) k_mlp_policy(MlpPolicyArgs P) {
   else if (OP == 64) mlp_mma_slab<2, MT>(acc, Xs, XS, bw, lm, lq);
   else mlp_mma_slab<1, MT>(acc, Xs, XS, bw, lm, lq);
   mlp_load_w<H / 32>(bw, P.img.W2 + (size_t)net * H * H, H, n0, lm, lq);
-  mlp_store_act_lds<MT>(acc, bb1, Hs, n0, lm, lq);
+  mlp_store_act_lds<ACT, MT>(acc, bb1, Hs, n0, lm, lq);
   __syncthreads();
   mlp_mma_slab<H / 32, MT>(acc, Hs, HS, bw, lm, lq);
   const unsigned short* Wh = P.img.Whp + (size_t)net * MLP_APM * H;
@@ -618,7 +686,7 @@ __global__ void __launch_bounds__(256, 2) k_mlp_policy(MlpPolicyArgs P) {
   }
   __builtin_amdgcn_sched_barrier(0);
   __syncthreads();                       // every wave has read H1 out of the hidden image: H2 takes its place
-  mlp_store_act_lds<MT>(acc, bb2, Hs, n0, lm, lq);
+  mlp_store_act_lds<ACT, MT>(acc, bb2, Hs, n0, lm, lq);
   __syncthreads();
   if (w < 3) {
     const float bv = bh[16 * w + lm];

@@ -627,6 +627,7 @@ __device__ __forceinline__ unsigned short myo_f2bf(float x) {   // round-to-near
   u += 0x7fffu + ((u >> 16) & 1u);
   return (unsigned short)(u >> 16);
 }
+#include "myo_act.h"          // myo_act_tanh: the one tanh statement of the MLP paths
 template <bool IN_BF16>
 __global__ void __launch_bounds__(64) k_ppo_loss(const float* __restrict__ mean, const float* __restrict__ values,
                                                  const float* __restrict__ actions, const float* __restrict__ old_logp,
@@ -822,11 +823,12 @@ __global__ void __launch_bounds__(256) k_splitk_reduce(const unsigned* __restric
   }
   out[j] = make_float2(a0, a1);
 }
-// dy <- dy * (act > 0) (ReLU backward, bf16 in place) and per-block column sums of the result:
-// partial[blk, c] over the block's 32 rows.  cols/2 must divide 256 (cols = 256: one column pair
-// per thread, two row phases).  Followed by k_splitk_reduce<false> for the bias gradient.
-__global__ void __launch_bounds__(256) k_relu_bwd_colsum(unsigned* __restrict__ dy, const unsigned* __restrict__ act, int P,
-                                                         float2* __restrict__ partial) {
+// dy <- dy * act'(.) from the layer's OUTPUT act (bf16 in place) and per-block column sums of the result: partial[blk, c] over the
+// block's 32 rows.  ReLU: dy * (act > 0); tanh: bf16(dy * (1 - act^2)), one rounding of the product.  cols/2 must divide 256
+// (cols = 256: one column pair per thread, two row phases).  Followed by k_splitk_reduce<false> for the bias gradient.
+template <int ACT>
+__global__ void __launch_bounds__(256) k_act_bwd_colsum(unsigned* __restrict__ dy, const unsigned* __restrict__ act, int P,
+                                                        float2* __restrict__ partial) {
   __shared__ float2 red[256];
   const int t = threadIdx.x, cp = t % P, rph = t / P, nph = 256 / P;
   const size_t row0 = (size_t)blockIdx.x * 32;
@@ -834,9 +836,16 @@ __global__ void __launch_bounds__(256) k_relu_bwd_colsum(unsigned* __restrict__ 
   for (int r = rph; r < 32; r += nph) {
     const size_t i = (row0 + r) * P + cp;
     const unsigned g = dy[i], a = act[i];
-    // bf16 > 0  <=>  sign bit clear and magnitude non-zero
-    const unsigned lo = ((a & 0x8000u) == 0 && (a & 0x7fffu) != 0) ? (g & 0xffffu) : 0u;
-    const unsigned hi = ((a & 0x80000000u) == 0 && (a & 0x7fff0000u) != 0) ? (g & 0xffff0000u) : 0u;
+    unsigned lo, hi;
+    if (ACT == MYO_ACT_TANH) {
+      const float h0 = __uint_as_float(a << 16), h1 = __uint_as_float(a & 0xffff0000u);
+      lo = (unsigned)myo_f2bf(__uint_as_float(g << 16) * fmaf(-h0, h0, 1.f));
+      hi = (unsigned)myo_f2bf(__uint_as_float(g & 0xffff0000u) * fmaf(-h1, h1, 1.f)) << 16;
+    } else {
+      // bf16 > 0  <=>  sign bit clear and magnitude non-zero
+      lo = ((a & 0x8000u) == 0 && (a & 0x7fffu) != 0) ? (g & 0xffffu) : 0u;
+      hi = ((a & 0x80000000u) == 0 && (a & 0x7fff0000u) != 0) ? (g & 0xffff0000u) : 0u;
+    }
     dy[i] = lo | hi;
     a0 += __uint_as_float(lo << 16);
     a1 += __uint_as_float(hi);
@@ -849,16 +858,18 @@ __global__ void __launch_bounds__(256) k_relu_bwd_colsum(unsigned* __restrict__ 
     partial[(size_t)blockIdx.x * P + t] = v;
   }
 }
-// h <- max(h + bias, 0) in place, bf16 [G, R, C] with bias [G, C] (the epilogue of a batched GEMM).
-__global__ void __launch_bounds__(256) k_bias_relu(unsigned* __restrict__ h, const unsigned* __restrict__ bias, int P, size_t RP,
-                                                   size_t total) {
+// h <- act(h + bias) in place (ReLU or tanh, one rounding), bf16 [G, R, C] with bias [G, C] (the epilogue of a batched GEMM).
+template <int ACT>
+__global__ void __launch_bounds__(256) k_bias_act(unsigned* __restrict__ h, const unsigned* __restrict__ bias, int P, size_t RP,
+                                                  size_t total) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const size_t g = i / RP;
   const int cp = (int)(i % P);
   const unsigned x = h[i], b = bias[g * P + cp];
-  const float lo = fmaxf(__uint_as_float(x << 16) + __uint_as_float(b << 16), 0.f);
-  const float hi = fmaxf(__uint_as_float(x & 0xffff0000u) + __uint_as_float(b & 0xffff0000u), 0.f);
+  const float slo = __uint_as_float(x << 16) + __uint_as_float(b << 16), shi = __uint_as_float(x & 0xffff0000u) + __uint_as_float(b & 0xffff0000u);
+  const float lo = ACT == MYO_ACT_TANH ? myo_act_tanh(slo) : fmaxf(slo, 0.f);
+  const float hi = ACT == MYO_ACT_TANH ? myo_act_tanh(shi) : fmaxf(shi, 0.f);
   h[i] = (unsigned)myo_f2bf(lo) | ((unsigned)myo_f2bf(hi) << 16);
 }
 // Minibatch gather of one PPO optimiser step: rows idx[0..bs) of the rollout arrays -> contiguous
@@ -1078,13 +1089,18 @@ __global__ void __launch_bounds__(256) k_reduce_pair(ReduceJob A, ReduceJob B) {
   if ((int)blockIdx.x < A.nblocks) myo_reduce_job(A, blockIdx.x, red);      // block-uniform branch
   else myo_reduce_job(B, blockIdx.x - A.nblocks, red);
 }
-extern "C" int myo_bias_relu_bf16(uint16_t* h, const uint16_t* bias, int groups, int rows, int cols, void* stream) {
-  if (!h || !bias || groups <= 0 || rows <= 0 || cols <= 0 || (cols & 1)) return fail(MYO_E_ARG, "myo_bias_relu_bf16: bad arguments");
+static bool myo_act_known(int activation) { return activation == MYO_ACT_RELU || activation == MYO_ACT_TANH; }
+extern "C" int myo_bias_act_bf16(uint16_t* h, const uint16_t* bias, int groups, int rows, int cols, int activation, void* stream) {
+  if (!h || !bias || groups <= 0 || rows <= 0 || cols <= 0 || (cols & 1)) return fail(MYO_E_ARG, "myo_bias_act_bf16: bad arguments");
+  if (!myo_act_known(activation)) return fail(MYO_E_ARG, "myo_bias_act_bf16: unknown activation code %d", activation);
   const size_t P = cols / 2, RP = (size_t)rows * P, total = RP * groups;
-  hipLaunchKernelGGL(k_bias_relu, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned*)h,
-                     (const unsigned*)bias, (int)P, RP, total);
+  hipLaunchKernelGGL(activation == MYO_ACT_TANH ? k_bias_act<MYO_ACT_TANH> : k_bias_act<MYO_ACT_RELU>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (unsigned*)h, (const unsigned*)bias, (int)P, RP, total);
   LAUNCH_CHECK(0)
   return MYO_OK;
+}
+extern "C" int myo_bias_relu_bf16(uint16_t* h, const uint16_t* bias, int groups, int rows, int cols, void* stream) {
+  return myo_bias_act_bf16(h, bias, groups, rows, cols, MYO_ACT_RELU, stream);
 }
 extern "C" int myo_ppo_gather(const float* obs, const float* act, const float* oldlp, const float* adv, const float* ret,
                               const int64_t* idx, int bs, int obs_dim, int act_dim, uint16_t* obs_bf16, int copies,
@@ -1171,13 +1187,17 @@ extern "C" int myo_splitk_reduce(const void* part, int part_is_bf16, float* out,
   LAUNCH_CHECK(0)
   return MYO_OK;
 }
-extern "C" int myo_relu_bwd_colsum_bf16(uint16_t* dy, const uint16_t* act, int rows, int cols, float* partial, void* stream) {
+extern "C" int myo_act_bwd_colsum_bf16(uint16_t* dy, const uint16_t* act, int rows, int cols, float* partial, int activation, void* stream) {
   if (!dy || !act || !partial || rows <= 0 || cols <= 0 || (rows % 32) || (cols & 1) || (256 % (cols / 2)) || cols / 2 < 8)
-    return fail(MYO_E_ARG, "myo_relu_bwd_colsum_bf16: rows must be a multiple of 32 and cols/2 a divisor of 256 (>= 8)");
-  hipLaunchKernelGGL(k_relu_bwd_colsum, dim3(rows / 32), dim3(256), 0, (hipStream_t)stream, (unsigned*)dy, (const unsigned*)act,
-                     cols / 2, (float2*)partial);
+    return fail(MYO_E_ARG, "myo_act_bwd_colsum_bf16: rows must be a multiple of 32 and cols/2 a divisor of 256 (>= 8)");
+  if (!myo_act_known(activation)) return fail(MYO_E_ARG, "myo_act_bwd_colsum_bf16: unknown activation code %d", activation);
+  hipLaunchKernelGGL(activation == MYO_ACT_TANH ? k_act_bwd_colsum<MYO_ACT_TANH> : k_act_bwd_colsum<MYO_ACT_RELU>, dim3(rows / 32), dim3(256), 0,
+                     (hipStream_t)stream, (unsigned*)dy, (const unsigned*)act, cols / 2, (float2*)partial);
   LAUNCH_CHECK(0)
   return MYO_OK;
+}
+extern "C" int myo_relu_bwd_colsum_bf16(uint16_t* dy, const uint16_t* act, int rows, int cols, float* partial, void* stream) {
+  return myo_act_bwd_colsum_bf16(dy, act, rows, cols, partial, MYO_ACT_RELU, stream);
 }
 
 // ------------------------------------------------------------------------------------------ rollout
@@ -1774,11 +1794,11 @@ static void mlp_launch_prep(const float* p, const myo_mlp_layout& lay, int O, in
 }
 // resident: the operand images at the front of the workspace are current (myo_ppo_mlp_images once, then the Adam kernel of
 // myo_adam_step with `images` after every step) and the advantage moments are the caller's: neither k_adv_moments nor k_mlp_prep runs
-static int mlp_step(const myo_ppo_mlp_desc* d, void* stream, bool resident) {
-  const char* who = resident ? "myo_ppo_mlp_step_resident" : "myo_ppo_mlp_step";
+static int mlp_step(const myo_ppo_mlp_desc* d, void* stream, bool resident, int activation, const char* who) {
   if (!d || !d->obs || !d->act || !d->oldlp || !d->adv || !d->ret || !d->idx || !d->params || !d->grads || !d->adv_stats || !d->acc ||
       !d->workspace)
     return fail(MYO_E_ARG, "%s: null argument", who);
+  if (!myo_act_known(activation)) return fail(MYO_E_ARG, "%s: unknown activation code %d", who, activation);
   const int B = d->B, O = d->O, A = d->A, OP = (O + 31) / 32 * 32;
   const myo_mlp_layout& lay = d->layout;
   if (int rc = mlp_shape_check(d, who)) return rc;
@@ -1786,11 +1806,13 @@ static int mlp_step(const myo_ppo_mlp_desc* d, void* stream, bool resident) {
   const MlpWs w = mlp_carve((unsigned char*)d->workspace, B, OP, A, d->G);
   if ((long long)w.bytes > d->workspace_bytes) return fail(MYO_E_ARG, "%s: workspace too small (%zu bytes needed)", who, w.bytes);
   hipStream_t st = (hipStream_t)stream;
-  static bool lds_set = false;
-  if (!lds_set) {
-    if (hipFuncSetAttribute((const void*)k_mlp_fwdbwd, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_FWDBWD_LDS) != hipSuccess)
+  const bool tanh_act = activation == MYO_ACT_TANH;
+  void (*const fwdbwd)(MlpArgs) = tanh_act ? k_mlp_fwdbwd<MYO_ACT_TANH> : k_mlp_fwdbwd<MYO_ACT_RELU>;
+  static bool lds_set[2] = {false, false};
+  if (!lds_set[tanh_act]) {
+    if (hipFuncSetAttribute((const void*)fwdbwd, hipFuncAttributeMaxDynamicSharedMemorySize, MLP_FWDBWD_LDS) != hipSuccess)
       return fail(MYO_E_DEVICE, "%s: cannot reserve %d bytes of LDS", who, (int)MLP_FWDBWD_LDS);
-    lds_set = true;
+    lds_set[tanh_act] = true;
   }
   if (!resident) {
     if (d->compute_adv_stats) hipLaunchKernelGGL(k_adv_moments, dim3(MLP_ADV_BLOCKS), dim3(256), 0, st, d->adv, (const long long*)d->idx, B, w.advpart);
@@ -1801,7 +1823,7 @@ static int mlp_step(const myo_ppo_mlp_desc* d, void* stream, bool resident) {
   a.log_std = d->params + lay.off_log_std; a.adv_stats = d->adv_stats; a.img = w.img;
   a.XT = w.XT; a.H1T = w.H1T; a.H2T = w.H2T; a.dH1T = w.dH1T; a.dH2T = w.dH2T; a.dOT = w.dOT; a.part = w.part;
   a.B = B; a.O = O; a.A = A; a.OP = OP; a.NB = B / MLP_BM; a.clip = d->clip; a.vf_coef = d->vf_coef; a.hp = d->hp;
-  hipLaunchKernelGGL(k_mlp_fwdbwd, dim3(B / MLP_BM, 2), dim3(256), MLP_FWDBWD_LDS, st, a);
+  hipLaunchKernelGGL(fwdbwd, dim3(B / MLP_BM, 2), dim3(256), MLP_FWDBWD_LDS, st, a);
   MlpWgradArgs g;
   g.njobs = 0; g.B = B; g.rows_per_split = B / MLP_SPLITK; g.G = d->G; g.slab = w.slab;
   const size_t HB = (size_t)MLP_H * B;
@@ -1829,8 +1851,11 @@ static int mlp_step(const myo_ppo_mlp_desc* d, void* stream, bool resident) {
   LAUNCH_CHECK(0)
   return MYO_OK;
 }
-extern "C" int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream) { return mlp_step(d, stream, false); }
-extern "C" int myo_ppo_mlp_step_resident(const myo_ppo_mlp_desc* d, void* stream) { return mlp_step(d, stream, true); }
+extern "C" int myo_ppo_mlp_step_act(const myo_ppo_mlp_desc* d, int resident, int activation, void* stream) {
+  return mlp_step(d, stream, resident != 0, activation, "myo_ppo_mlp_step_act");
+}
+extern "C" int myo_ppo_mlp_step(const myo_ppo_mlp_desc* d, void* stream) { return mlp_step(d, stream, false, MYO_ACT_RELU, "myo_ppo_mlp_step"); }
+extern "C" int myo_ppo_mlp_step_resident(const myo_ppo_mlp_desc* d, void* stream) { return mlp_step(d, stream, true, MYO_ACT_RELU, "myo_ppo_mlp_step_resident"); }
 // the checks the image calls share (the fields of `d` that place the images); *img <- the images in d's workspace
 static int mlp_images_ok(const myo_ppo_mlp_desc* d, const char* who, MlpImages* img) {
   if (!d || !d->params || !d->workspace) return fail(MYO_E_ARG, "%s: null argument", who);
@@ -1913,19 +1938,25 @@ extern "C" int myo_ppo_mlp_rollout_refresh(const myo_ppo_mlp_rollout_desc* d, vo
   LAUNCH_CHECK(0)
   return MYO_OK;
 }
-extern "C" int myo_ppo_mlp_rollout(const myo_ppo_mlp_rollout_desc* d, void* stream) {
+static int mlp_rollout(const myo_ppo_mlp_rollout_desc* d, int activation, void* stream, const char* who) {
   if (!d || !d->obs || !d->params || !d->draw_counter || !d->t_idx || !d->act_buf || !d->val_buf || !d->logp_buf || !d->clipped || !d->workspace)
-    return fail(MYO_E_ARG, "myo_ppo_mlp_rollout: null argument");
+    return fail(MYO_E_ARG, "%s: null argument", who);
+  if (!myo_act_known(activation)) return fail(MYO_E_ARG, "%s: unknown activation code %d", who, activation);
   MlpPolicyArgs a;
-  if (int rc = mlp_rollout_images(d, "myo_ppo_mlp_rollout", &a.img)) return rc;
+  if (int rc = mlp_rollout_images(d, who, &a.img)) return rc;
   a.obs = d->obs; a.log_std = d->params + d->layout.off_log_std;
   a.obs_buf = d->obs_buf; a.act_buf = d->act_buf; a.val_buf = d->val_buf; a.logp_buf = d->logp_buf; a.clipped = d->clipped;
   a.t_idx = d->t_idx; a.draw_counter = (unsigned long long*)d->draw_counter; a.seed = d->seed;
   a.N = d->N; a.O = d->O; a.A = d->A; a.OP = (d->O + 31) / 32 * 32; a.deterministic = d->deterministic;
-  hipLaunchKernelGGL(k_mlp_policy, dim3(d->N / MLP_BM, 2), dim3(256), MLP_POLICY_LDS, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(activation == MYO_ACT_TANH ? k_mlp_policy<MYO_ACT_TANH> : k_mlp_policy<MYO_ACT_RELU>, dim3(d->N / MLP_BM, 2), dim3(256), MLP_POLICY_LDS,
+                     (hipStream_t)stream, a);
   LAUNCH_CHECK(0)
   return MYO_OK;
 }
+extern "C" int myo_ppo_mlp_rollout_act(const myo_ppo_mlp_rollout_desc* d, int activation, void* stream) {
+  return mlp_rollout(d, activation, stream, "myo_ppo_mlp_rollout_act");
+}
+extern "C" int myo_ppo_mlp_rollout(const myo_ppo_mlp_rollout_desc* d, void* stream) { return mlp_rollout(d, MYO_ACT_RELU, stream, "myo_ppo_mlp_rollout"); }
 
 // ------------------------------------------------------------------------------------------ fused LSTM time step
 #include "myo_lstm_step.h"

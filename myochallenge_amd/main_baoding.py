@@ -13,6 +13,8 @@ import json
 import os
 from datetime import datetime
 
+import torch.nn as nn
+
 ENV_NAME = "CustomMyoBaodingBallsP2"
 
 # reward structure and task parameters of the reference script (src/main_baoding.py:27-52)
@@ -64,7 +66,7 @@ def main(argv=None):
     trainer = MyoTrainer(envs=envs, env_config=cfg, load_model_path=a.load_model, log_dir=log_dir,
                          model_config={"policy": a.policy, "learning_rate": lambda _: a.learning_rate, "clip_range": lambda _: 0.2,
                                        "n_steps": a.n_steps, "batch_size": a.batch_size,
-                                       "policy_kwargs": {"net_arch": [{"pi": [256, 256], "vf": [256, 256]}], "log_std_init": -2.0}},
+                                       "policy_kwargs": {"activation_fn": nn.ReLU, "net_arch": [{"pi": [256, 256], "vf": [256, 256]}], "log_std_init": -2.0}},
                          callbacks=[eval_callback, checkpoint_callback], timesteps=a.timesteps)
     trainer.train(total_timesteps=trainer.timesteps)
     trainer.save()

@@ -12,6 +12,8 @@ import json
 import os
 from datetime import datetime
 
+import torch.nn as nn
+
 ENV_NAME = "CustomMyoHandPoseRandom"
 
 # reward structure and task parameters of the reference script (src/main_pose_hand.py:24-40)
@@ -28,7 +30,7 @@ model_config = dict(
     policy="MlpPolicy",
     learning_rate=2.55673e-05, ent_coef=3.62109e-06, clip_range=0.3, gamma=0.99, gae_lambda=0.9, max_grad_norm=0.7,
     vf_coef=0.835671, n_epochs=10,
-    policy_kwargs=dict(log_std_init=-2.0, net_arch=[dict(pi=[256, 256], vf=[256, 256])]),
+    policy_kwargs=dict(log_std_init=-2.0, activation_fn=nn.ReLU, net_arch=[dict(pi=[256, 256], vf=[256, 256])]),
 )
 
 

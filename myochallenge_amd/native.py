@@ -93,6 +93,8 @@ class PpoMlpDesc(C.Structure):
 # word indices of the PPO hyper-parameter block (MYO_HP_* of include/myobatch.h)
 HP_LR, HP_CLIP, HP_KL_LIMIT, HP_STOP, HP_APPLIED, HP_COUNT, HP_SUM_KL, HP_SUM_CLIPFRAC, HP_SUM_ENTLOSS, HP_LAST_KL, HP_LAST_PL, HP_LAST_VL = range(12)
 HP_WORDS = 16
+# activation codes of the hidden MLP layers (MYO_ACT_* of include/myobatch.h)
+ACT_RELU, ACT_TANH = 0, 1
 
 
 class PpoMlpRolloutDesc(C.Structure):
@@ -224,9 +226,11 @@ class NativeLib:
         L.myo_ppo_gather_seq.argtypes = [vp] * 9 + [i32] * 8 + [vp, i32] + [vp] * 11
         L.myo_rollout_state_snapshot.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
         L.myo_bias_relu_bf16.argtypes = [vp, vp, i32, i32, i32, vp]
+        L.myo_bias_act_bf16.argtypes = [vp, vp, i32, i32, i32, i32, vp]
         L.myo_splitk_reduce.argtypes = [vp, i32, vp, i32, i32, i32, vp]
         L.myo_splitk_reduce2.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp]
         L.myo_relu_bwd_colsum_bf16.argtypes = [vp, vp, i32, i32, vp, vp]
+        L.myo_act_bwd_colsum_bf16.argtypes = [vp, vp, i32, i32, vp, i32, vp]
         L.myo_rollout_policy_input.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp]
         L.myo_rollout_sample.argtypes = [vp, vp, vp, i32, i32, u64, vp, vp, vp, vp, vp, vp, i32, vp]
         L.myo_vecnorm_step.argtypes = [vp] * 5 + [i32, i32] + [vp] * 5 + [dbl] * 4 + [i32] * 3 + [vp] * 9
@@ -247,6 +251,7 @@ class NativeLib:
         L.myo_ppo_mlp_workspace_bytes.restype = C.c_longlong
         L.myo_ppo_mlp_workspace_bytes.argtypes = [i32, i32, i32, i32, C.c_longlong]
         L.myo_ppo_mlp_step.argtypes = [C.POINTER(PpoMlpDesc), vp]
+        L.myo_ppo_mlp_step_act.argtypes = [C.POINTER(PpoMlpDesc), i32, i32, vp]
         L.myo_ppo_mlp_sqnorm_parts.argtypes = [i32]
         L.myo_ppo_mlp_step_resident.argtypes = [C.POINTER(PpoMlpDesc), vp]
         L.myo_ppo_mlp_images.argtypes = [C.POINTER(PpoMlpDesc), vp]
@@ -255,6 +260,7 @@ class NativeLib:
         L.myo_ppo_mlp_rollout_workspace_bytes.argtypes = [i32, i32, i32]
         L.myo_ppo_mlp_rollout_refresh.argtypes = [C.POINTER(PpoMlpRolloutDesc), vp]
         L.myo_ppo_mlp_rollout.argtypes = [C.POINTER(PpoMlpRolloutDesc), vp]
+        L.myo_ppo_mlp_rollout_act.argtypes = [C.POINTER(PpoMlpRolloutDesc), i32, vp]
 
     def check(self, rc: int):
         if rc != 0:
@@ -301,6 +307,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
     "myo_ppo_mlp_step_resident", "myo_ppo_mlp_images", "myo_ppo_adv_moments_epoch",
+    "myo_ppo_mlp_step_act", "myo_ppo_mlp_rollout_act", "myo_bias_act_bf16", "myo_act_bwd_colsum_bf16",
 ]
 
 # ... of which the lane-serial emulation build (tests/emu/libmyobatch_emu.so: csrc/myobatch_emu.cpp + csrc/emu_host.h, test tooling) has the env

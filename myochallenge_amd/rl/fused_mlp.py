@@ -20,6 +20,8 @@ from typing import List, Tuple
 
 import torch
 
+from ..native import ACT_RELU, ACT_TANH
+
 
 def _layers(seq) -> List[torch.nn.Linear]:
     return [m for m in seq if isinstance(m, torch.nn.Linear)]
@@ -28,6 +30,27 @@ def _layers(seq) -> List[torch.nn.Linear]:
 def _nets(policy):
     return {"pi": _layers(policy.mlp_extractor.policy_net) + [policy.action_net],
             "vf": _layers(policy.mlp_extractor.value_net) + [policy.value_net]}
+
+
+def activation_code(policy):
+    """The library's code (MYO_ACT_* of include/myobatch.h) of the policy's hidden activation: native.ACT_RELU, native.ACT_TANH, or
+    None for a class the kernels do not compute — then no fused path may run the policy (PPO trains it through autograd).  A policy
+    without hidden MLP layers has no activation to apply and counts as ReLU.  The only place that looks at the class."""
+    if not policy.pi_arch and not policy.vf_arch:
+        return ACT_RELU
+    return {torch.nn.ReLU: ACT_RELU, torch.nn.Tanh: ACT_TANH}.get(policy.activation_fn)
+
+
+def _act_fwd_(h, code):
+    """The hidden activation in place (torch statement of the kernels' epilogue)."""
+    return torch.tanh_(h) if code == ACT_TANH else torch.relu_(h)
+
+
+def _act_bwd(dy, out, code):
+    """dy * activation'(.) from the layer's OUTPUT `out`, in dy's dtype: ReLU dy * (out > 0), tanh dy * (1 - out * out)."""
+    if code == ACT_TANH:
+        return torch.ops.aten.tanh_backward(dy, out)
+    return torch.ops.aten.threshold_backward(dy, out, 0)
 
 
 def _splitk_wgrad(dy: torch.Tensor, x: torch.Tensor, split: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -49,6 +72,9 @@ def ppo_mlp_step_grads(policy, obs, actions, old_logp, adv, returns, clip_range,
     B = obs.shape[0]
     x0 = obs.to(cd)
     nets = _nets(policy)
+    code = activation_code(policy)
+    if code is None:
+        raise ValueError(f"ppo_mlp_step_grads: no hand-derived step for activation_fn={policy.activation_fn!r} (ReLU or Tanh)")
     acts, outs = {}, {}
     for name, layers in nets.items():
         h = x0
@@ -56,7 +82,7 @@ def ppo_mlp_step_grads(policy, obs, actions, old_logp, adv, returns, clip_range,
         for li, lin in enumerate(layers):
             h = torch.addmm(lin.bias.to(cd), h, lin.weight.to(cd).t())
             if li < len(layers) - 1:
-                h = torch.relu_(h)
+                h = _act_fwd_(h, code)
                 saved.append(h)
         acts[name], outs[name] = saved, h.float()
     mean, values = outs["pi"], outs["vf"].squeeze(-1)
@@ -92,7 +118,7 @@ def ppo_mlp_step_grads(policy, obs, actions, old_logp, adv, returns, clip_range,
             put(lin.weight, gw)
             put(lin.bias, gb)
             if li > 0:
-                dy = (dy @ lin.weight.to(cd)) * (saved[li] > 0).to(cd)
+                dy = _act_bwd(dy @ lin.weight.to(cd), saved[li], code)      # (saved[li]: the output of hidden layer li - 1)
     return pl, vl
 
 
@@ -211,6 +237,9 @@ class FusedPPOStep:
 
     def __init__(self, policy, lib, clip_range, ent_coef, vf_coef, split_k=64):
         self.policy, self.lib = policy, lib
+        self.act = activation_code(policy)   # MYO_ACT_*: every kernel below is called with it
+        if self.act is None:
+            raise ValueError(f"no fused PPO step for activation_fn={policy.activation_fn!r} (ReLU or Tanh): train it through autograd")
         self.clip, self.ent, self.vf, self.split = float(clip_range), float(ent_coef), float(vf_coef), split_k
         self.adam_syncs_shadow = False
         self.nets = _nets(policy)
@@ -376,7 +405,7 @@ class FusedPPOStep:
 
     def rollout_policy(self, d):
         stream = torch.cuda.current_stream(self.acc.device).cuda_stream
-        self.lib.check(self.lib.L.myo_ppo_mlp_rollout(C.byref(d), C.c_void_p(stream)))
+        self.lib.check(self.lib.L.myo_ppo_mlp_rollout_act(C.byref(d), self.act, C.c_void_p(stream)))
 
     def _mfma_step(self, d):
         stream = torch.cuda.current_stream(self.acc.device).cuda_stream
@@ -386,11 +415,11 @@ class FusedPPOStep:
                 self.lib.check(self.lib.L.myo_ppo_adv_moments_epoch(C.c_void_p(d.adv), C.c_void_p(d.idx), d.B, 1, C.c_void_p(slot.data_ptr()),
                                                                     C.c_void_p(self.moments_buffers(1)[1].data_ptr()), C.c_void_p(stream)))
             d.compute_adv_stats, d.adv_stats = 0, slot.data_ptr()
-            self.lib.check(self.lib.L.myo_ppo_mlp_step_resident(C.byref(d), C.c_void_p(stream)))
+            self.lib.check(self.lib.L.myo_ppo_mlp_step_act(C.byref(d), 1, self.act, C.c_void_p(stream)))
             self.resident_adam.images = d
         else:
             d.compute_adv_stats, d.adv_stats = (0 if self.external_adv_stats else 1), self.stats.data_ptr()
-            self.lib.check(self.lib.L.myo_ppo_mlp_step(C.byref(d), C.c_void_p(stream)))
+            self.lib.check(self.lib.L.myo_ppo_mlp_step_act(C.byref(d), 0, self.act, C.c_void_p(stream)))
             if self.adam is not None:
                 self.adam.images = None
         if self.adam is not None:           # the Adam call that follows takes the partial sums this step left (or does its own)
@@ -438,29 +467,26 @@ class FusedPPOStep:
             out_a.numel() // groups_a, C.c_void_p(part_b.data_ptr()), int(part_b.dtype == torch.bfloat16),
             C.c_void_p(out_b.data_ptr()), groups_b, splits_b, out_b.numel() // groups_b, C.c_void_p(stream)))
 
-    def _relu_bwd_partial(self, dh, act):
-        """dh *= (act > 0) in place and the per-32-row column sums of the result (fp32 [G*B/32, H]); None if the
-        shape has no fast path (the caller then uses _relu_bwd_bias)."""
+    def _act_bwd_partial(self, dh, act):
+        """dh <- dh * activation'(.) in place from the layer's output `act` and the per-32-row column sums of the result (fp32
+        [G*B/32, H]); None if the shape has no fast path (the caller then uses _act_bwd_bias)."""
         G, B, H = dh.shape
         if not (B % 32 == 0 and H % 16 == 0 and 256 % (H // 2) == 0):
             return None
         partial = torch.empty((G * B // 32, H), device=dh.device)
         stream = torch.cuda.current_stream(dh.device).cuda_stream
-        self.lib.check(self.lib.L.myo_relu_bwd_colsum_bf16(C.c_void_p(dh.data_ptr()), C.c_void_p(act.data_ptr()), G * B, H,
-                                                           C.c_void_p(partial.data_ptr()), C.c_void_p(stream)))
+        self.lib.check(self.lib.L.myo_act_bwd_colsum_bf16(C.c_void_p(dh.data_ptr()), C.c_void_p(act.data_ptr()), G * B, H,
+                                                          C.c_void_p(partial.data_ptr()), self.act, C.c_void_p(stream)))
         return partial
 
-    def _relu_bwd_bias(self, dh, act, bias_grad):
-        """dh *= (act > 0) in place; bias_grad[g] = column sums of dh[g]  (dh, act: bf16 [G, B, H])."""
+    def _act_bwd_bias(self, dh, act, bias_grad):
+        """dh <- dh * activation'(.) from the layer's output `act`; bias_grad[g] = column sums of dh[g]  (dh, act: bf16 [G, B, H])."""
         G, B, H = dh.shape
-        if B % 32 == 0 and H % 16 == 0 and 256 % (H // 2) == 0:
-            partial = torch.empty((G * B // 32, H), device=dh.device)
-            stream = torch.cuda.current_stream(dh.device).cuda_stream
-            self.lib.check(self.lib.L.myo_relu_bwd_colsum_bf16(C.c_void_p(dh.data_ptr()), C.c_void_p(act.data_ptr()), G * B, H,
-                                                               C.c_void_p(partial.data_ptr()), C.c_void_p(stream)))
+        partial = self._act_bwd_partial(dh, act)
+        if partial is not None:
             self._reduce(partial, bias_grad, G, B // 32)
             return dh
-        dh = torch.ops.aten.threshold_backward(dh, act, 0)
+        dh = _act_bwd(dh, act, self.act)
         bias_grad.copy_(_colsum(dh))
         return dh
 
@@ -581,8 +607,8 @@ class FusedPPOStep:
         h, saved = x2, [x2]
         for lay in self.merged:
             h = torch.bmm(h, lay["wh"].transpose(1, 2))
-            self.lib.check(self.lib.L.myo_bias_relu_bf16(C.c_void_p(h.data_ptr()), C.c_void_p(lay["bh"].data_ptr()), 2, B,
-                                                         h.shape[2], C.c_void_p(stream)))
+            self.lib.check(self.lib.L.myo_bias_act_bf16(C.c_void_p(h.data_ptr()), C.c_void_p(lay["bh"].data_ptr()), 2, B,
+                                                        h.shape[2], self.act, C.c_void_p(stream)))
             saved.append(h)
         pi_head, vf_head = self.nets["pi"][-1], self.nets["vf"][-1]
         mean_h = torch.addmm(self.wb[id(pi_head.bias)], h[0], self.wb[id(pi_head.weight)].t())
@@ -625,9 +651,9 @@ class FusedPPOStep:
         torch.mm(dvalue_h, wvf, out=dh[1])
         for li in reversed(range(len(L))):
             lay, x = L[li], saved[li]
-            bias_part = self._relu_bwd_partial(dh, saved[li + 1])
+            bias_part = self._act_bwd_partial(dh, saved[li + 1])
             if bias_part is None:
-                dh = self._relu_bwd_bias(dh, saved[li + 1], lay["bg"])
+                dh = self._act_bwd_bias(dh, saved[li + 1], lay["bg"])
             H, I = lay["wh"].shape[1], lay["wh"].shape[2]
             part = torch.bmm(dh.view(2 * s, B // s, H).transpose(1, 2), x.reshape(2 * s, B // s, I))
             if bias_part is not None and (H * I) % 2 == 0:      # weight partials and bias partials: one launch
@@ -659,7 +685,7 @@ class FusedPPOStep:
             for li, lin in enumerate(layers):
                 h = torch.addmm(self.wb[id(lin.bias)], h, self.wb[id(lin.weight)].t())
                 if li < len(layers) - 1:
-                    h = torch.relu_(h)
+                    h = _act_fwd_(h, self.act)
                     saved.append(h)
             acts[name], outs[name] = saved, h.float()
         mean, values = outs["pi"].contiguous(), outs["vf"].reshape(B).contiguous()
@@ -679,5 +705,5 @@ class FusedPPOStep:
                 torch.sum(part, 0, dtype=torch.float32, out=lin.weight.grad)
                 lin.bias.grad.copy_(_colsum(dy))
                 if li > 0:
-                    dy = torch.ops.aten.threshold_backward(dy @ self.wb[id(lin.weight)], saved[li], 0)
+                    dy = _act_bwd(dy @ self.wb[id(lin.weight)], saved[li], self.act)
         return self.acc[A], self.acc[A + 1]

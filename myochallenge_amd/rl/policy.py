@@ -234,6 +234,7 @@ class ActorCriticPolicy(nn.Module):
         self.exploration_mat = None          # [n_envs, latent_pi, act], set by reset_noise
         self.obs_dim, self.act_dim = obs_dim, act_dim
         self.pi_arch, self.vf_arch = list(pi), list(vf)
+        self.activation_fn = activation_fn       # the class, as given (rl/fused_mlp.py:activation_code maps it to the kernels' code)
         self.lstm_hidden_size, self.enable_critic_lstm = lstm_hidden_size, enable_critic_lstm
         self.recurrent = lstm_hidden_size is not None
         if self.recurrent and not enable_critic_lstm:

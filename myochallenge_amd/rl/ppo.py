@@ -27,7 +27,7 @@ from .. import native
 from ..native import (HP_APPLIED, HP_CLIP, HP_COUNT, HP_LAST_KL, HP_LAST_PL, HP_LAST_VL, HP_STOP, HP_SUM_ENTLOSS, HP_SUM_KL,
                       HP_WORDS)
 from .fused_lstm import FusedRecurrentPPOStep
-from .fused_mlp import FlatAdam, FusedPPOStep, flatten_parameters, hp_record_torch
+from .fused_mlp import FlatAdam, FusedPPOStep, activation_code, flatten_parameters, hp_record_torch
 from .policy import ActorCriticPolicy
 
 
@@ -137,7 +137,9 @@ class PPO:
         self._fused_rec = None       # FusedRecurrentPPOStep: the hand-derived recurrent minibatch step
         self._flat_adam = None       # FlatAdam over the flat parameter vector: every captured update path has one
         fused = None
-        if cfg.use_graphs and on_gpu:
+        # (a hidden activation the kernels do not compute — anything but ReLU / Tanh: no fused object and no flat vectors, the update
+        # is eager autograd and the rollout goes through the torch module, as for gSDE without stacked views below)
+        if cfg.use_graphs and on_gpu and activation_code(self.policy) is not None:
             # flat parameter / gradient vectors (before any graph captures addresses) and the one-kernel optimiser, so that a whole
             # minibatch step (forward, backward, clip + Adam) is ONE hipGraph.  The forward / backward of it is hand-derived
             # (rl/fused_mlp.py, rl/fused_lstm.py) or, for a recurrent policy without such a step, autograd on the flat vectors.

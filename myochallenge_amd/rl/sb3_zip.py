@@ -13,6 +13,7 @@ import base64
 import io
 import json
 import pickle
+import re
 import zipfile
 from typing import Any, Dict, Optional, Tuple
 
@@ -46,8 +47,21 @@ def read_zip(path: str) -> Tuple[Dict[str, Any], Dict[str, torch.Tensor], Option
     return out, sd, opt
 
 
-def policy_from_state_dict(sd: Dict[str, torch.Tensor], use_sde: bool = False) -> ActorCriticPolicy:
-    """Infer the architecture from tensor shapes (what policy_kwargs would say)."""
+def activation_from_name(name: Optional[str]):
+    """The activation class of a zip's policy_kwargs from the readable string stable-baselines3 stores beside the pickle
+    ("<class 'torch.nn.modules.activation.Tanh'>"): the class of that name in torch.nn — nothing is unpickled.  No entry: nn.Tanh,
+    what stable-baselines3 builds without one."""
+    if name is None:
+        return torch.nn.Tanh
+    m = re.fullmatch(r"<class '(?:[A-Za-z_]\w*\.)*([A-Za-z_]\w*)'>", str(name).strip())
+    cls = getattr(torch.nn, m.group(1), None) if m else None
+    if not (isinstance(cls, type) and issubclass(cls, torch.nn.Module) and cls.__module__ == "torch.nn.modules.activation"):
+        raise ValueError(f"policy_kwargs['activation_fn'] = {name!r}: not an activation class of torch.nn")
+    return cls
+
+
+def policy_from_state_dict(sd: Dict[str, torch.Tensor], use_sde: bool = False, activation_fn=torch.nn.ReLU) -> ActorCriticPolicy:
+    """Infer the architecture from tensor shapes (what policy_kwargs would say); the activation is not in the tensors."""
     use_sde = bool(use_sde) or sd["log_std"].dim() == 2        # a gSDE checkpoint's log_std is the [latent_pi, act] matrix
     act_dim = sd["action_net.weight"].shape[0]
     hidden = None
@@ -65,14 +79,16 @@ def policy_from_state_dict(sd: Dict[str, torch.Tensor], use_sde: bool = False) -
     if hidden is None:
         obs_dim = sd["mlp_extractor.policy_net.0.weight"].shape[1] if pi else sd["action_net.weight"].shape[1]
     pol = ActorCriticPolicy(obs_dim, act_dim, pi, vf, lstm_hidden_size=hidden,
-                            enable_critic_lstm="lstm_critic.weight_hh_l0" in sd or hidden is None, use_sde=use_sde)
+                            enable_critic_lstm="lstm_critic.weight_hh_l0" in sd or hidden is None, use_sde=use_sde,
+                            activation_fn=activation_fn)
     pol.load_state_dict(sd, strict=True)
     return pol
 
 
 def load_policy(path: str) -> Tuple[ActorCriticPolicy, Dict[str, Any]]:
     data, sd, _ = read_zip(path)
-    return policy_from_state_dict(sd, bool(data.get("use_sde", False))), data
+    act = activation_from_name((data.get("policy_kwargs") or {}).get("activation_fn"))
+    return policy_from_state_dict(sd, bool(data.get("use_sde", False)), activation_fn=act), data
 
 
 def _ser(obj, type_name: Optional[str] = None, **plain) -> dict:
@@ -110,13 +126,13 @@ def save_sb3_zip(path: str, policy: ActorCriticPolicy, hyper: Dict[str, Any], *,
         box = lambda n, lo, hi: instance(Box, {"dtype": np.dtype("float32"), "shape": (n,), "low": np.full(n, lo, np.float32),
                                               "high": np.full(n, hi, np.float32), "np_random": None})
         if recurrent:
-            pk = {"ortho_init": False, "activation_fn": torch.nn.ReLU, "net_arch": [{"pi": list(policy.pi_arch), "vf": list(policy.vf_arch)}],
+            pk = {"ortho_init": False, "activation_fn": policy.activation_fn, "net_arch": [{"pi": list(policy.pi_arch), "vf": list(policy.vf_arch)}],
                   "enable_critic_lstm": bool(policy.enable_critic_lstm), "lstm_hidden_size": int(policy.lstm_hidden_size)}
             H = int(policy.lstm_hidden_size)
             z = lambda: (torch.zeros(1, n_envs, H), torch.zeros(1, n_envs, H))
             lstm_states = RNNStates(z(), z())
         else:
-            pk = {"ortho_init": False, "activation_fn": torch.nn.ReLU, "net_arch": [{"pi": list(policy.pi_arch), "vf": list(policy.vf_arch)}]}
+            pk = {"ortho_init": False, "activation_fn": policy.activation_fn, "net_arch": [{"pi": list(policy.pi_arch), "vf": list(policy.vf_arch)}]}
             lstm_states = None
         zeros_obs = np.zeros((n_envs, O), np.float32)
         data: Dict[str, Any] = {
@@ -168,9 +184,14 @@ def save_sb3_zip(path: str, policy: ActorCriticPolicy, hyper: Dict[str, Any], *,
 
 def save_policy(path: str, policy: ActorCriticPolicy, data: Optional[dict] = None) -> None:
     """Write policy weights + plain hyper-parameters in the same member layout (``data`` carries
-    only JSON-plain values; SB3's pickled class objects are not reproduced)."""
+    only JSON-plain values; SB3's pickled class objects are not reproduced), plus ``policy_kwargs["activation_fn"]`` as the readable
+    string ``load_policy`` takes the class from.  A zip this function wrote before it recorded the activation has no such entry and
+    loads as ``nn.Tanh`` (the rule for an absent entry) whatever built it: re-save such a policy, or build it with
+    ``policy_from_state_dict(sd, activation_fn=...)``."""
     with zipfile.ZipFile(path, "w") as z:
-        z.writestr("data", json.dumps({k: v for k, v in (data or {}).items() if isinstance(v, (int, float, bool, str, type(None)))}))
+        plain = {k: v for k, v in (data or {}).items() if isinstance(v, (int, float, bool, str, type(None)))}
+        plain["policy_kwargs"] = {"activation_fn": str(policy.activation_fn)}      # (the readable string load_policy takes the class from)
+        z.writestr("data", json.dumps(plain))
         buf = io.BytesIO()
         torch.save({k: v.detach().cpu() for k, v in policy.state_dict().items()}, buf)
         z.writestr("policy.pth", buf.getvalue())
