@@ -796,6 +796,38 @@ typedef struct myo_adam_desc {
 } myo_adam_desc;
 int myo_adam_step(const myo_adam_desc* a, void* stream);
 
+/* One deterministic acting step of an ensemble of M = M0 + M1 actor-only LSTM policies (RecurrentActorCriticPolicy with
+ * net_arch=[dict(pi=[], vf=[])]: LSTM -> action head) on one observation batch, in one launch: what SuperModel.predict does member by
+ * member (/root/reference/src/eval_mixture_of_ensembles.py:250-285).  Member m belongs to group 0 (m < M0, "base") or 1 ("hold").
+ * Per member: x = clamp((obs - mean[m]) / sqrt(var[m] + eps), +-clip) in float64 -> float32 -> bf16; gates = [x | keep h] . w_gates[m]^T
+ * + b_gates[m] as ONE fp32 accumulation of bf16 operands, keep = 1 - start_g[row]; the cell of myo_lstm_step_fwd; c (float32) and
+ * h (bf16) advance in place; a_m = bf16(h_new) . w_a[m]^T + b_a[m] in fp32.  act[row] = the mean of group 1's a_m where
+ * use_group1[row] != 0, of group 0's elsewhere: the members summed in member order in fp32, divided by the group size, not clipped.
+ * Both groups' states advance on every row.
+ *   w_gates  bf16 [M, 4H, OP + H], OP = O rounded up to 32: row k of member m is [W_ih[k, :O] | zeros | W_hh[k, :]]
+ *   w_a      bf16 [M, 48, H]: rows of the action head, zero rows beyond A
+ *   b_gates  f32 [M, 4H] holding bf16(b_ih + b_hh);  b_a f32 [M, A]
+ *   start0 / start1  f32 [N]; start1 and use_group1 (uint8 [N]) may be NULL when M1 = 0
+ *   member_act  NULL, or f32 [M, N, A] <- every a_m
+ * H in {128, 256}, 1 <= O <= 128, 1 <= A <= 48, any N >= 1, M0 >= 1, M1 >= 0; MYO_E_UNSUPPORTED for other H / O / A, MYO_E_ARG for
+ * a NULL or non-positive argument, before any device call. */
+typedef struct myo_ensemble_desc {
+  int32_t N, O, A, H, M0, M1;
+  const float* obs;
+  const double *mean, *var;
+  double eps, clip;
+  const uint16_t *w_gates, *w_a;
+  const float *b_gates, *b_a;
+  uint16_t* h;
+  float* c;
+  const float *start0, *start1;
+  const uint8_t* use_group1;
+  float* act;
+  float* member_act;
+} myo_ensemble_desc;
+int myo_ensemble_supported(int H, int O, int A);
+int myo_ensemble_act(const myo_ensemble_desc* d, void* stream);
+
 const char* myo_last_error(void);
 const char* myo_version(void);
 

@@ -2004,6 +2004,31 @@ extern "C" int myo_lstm_step_bwd(const void* dout, long long dout_sg, const void
   return MYO_OK;
 }
 
+// ------------------------------------------------------------------------------------------ ensemble acting step
+#include "myo_ensemble.h"
+extern "C" int myo_ensemble_supported(int H, int O, int A) {
+  return ((H == 128 || H == 256) && O >= 1 && O <= ENS_OPMAX && A >= 1 && A <= ENS_APM) ? 1 : 0;
+}
+extern "C" int myo_ensemble_act(const myo_ensemble_desc* d, void* stream) {
+  if (!d) return fail(MYO_E_ARG, "myo_ensemble_act: null descriptor");
+  if (d->N <= 0 || d->O <= 0 || d->A <= 0 || d->H <= 0 || d->M0 <= 0 || d->M1 < 0)
+    return fail(MYO_E_ARG, "myo_ensemble_act: non-positive size (N %d, O %d, A %d, H %d, M0 %d, M1 %d)", d->N, d->O, d->A, d->H, d->M0, d->M1);
+  if (!d->obs || !d->mean || !d->var || !d->w_gates || !d->w_a || !d->b_gates || !d->b_a || !d->h || !d->c || !d->start0 || !d->act ||
+      (d->M1 > 0 && (!d->start1 || !d->use_group1)))
+    return fail(MYO_E_ARG, "myo_ensemble_act: null argument");
+  if (!myo_ensemble_supported(d->H, d->O, d->A))
+    return fail(MYO_E_UNSUPPORTED, "myo_ensemble_act: needs hidden 128 or 256, obs <= %d, act <= %d (got %d, %d, %d)", ENS_OPMAX, ENS_APM, d->H, d->O, d->A);
+  EnsArgs a;
+  a.obs = d->obs; a.mean = d->mean; a.var = d->var; a.eps = d->eps; a.clip = d->clip;
+  a.w_gates = d->w_gates; a.w_a = d->w_a; a.b_gates = d->b_gates; a.b_a = d->b_a; a.h = d->h; a.c = d->c;
+  a.start0 = d->start0; a.start1 = d->start1; a.use_group1 = d->use_group1; a.act = d->act; a.member_act = d->member_act;
+  a.N = d->N; a.O = d->O; a.OP = (d->O + 31) / 32 * 32; a.A = d->A; a.M0 = d->M0; a.M1 = d->M1;
+  if (d->H == 128) ensemble_launch<128>(a, (hipStream_t)stream);
+  else ensemble_launch<256>(a, (hipStream_t)stream);
+  LAUNCH_CHECK(0)
+  return MYO_OK;
+}
+
 // whole sequences in one launch per direction (csrc/myo_lstm_seq.h)
 #include "myo_lstm_seq.h"
 extern "C" int myo_lstm_seq_supported(int H) { return (H == 128 || H == 256) ? 1 : 0; }

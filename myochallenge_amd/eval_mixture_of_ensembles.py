@@ -22,9 +22,12 @@ from .models.classifier import N_OBS_PER_TRIAL, OBS_SLICE, TaskClassifier, load_
 
 class SuperModel:
     def __init__(self, models_base: Sequence, envs_base: Sequence, models_hold: Sequence, envs_hold: Sequence,
-                 classifier: TaskClassifier, scaler, num_envs: int, device):
+                 classifier: TaskClassifier, scaler, num_envs: int, device, fused: bool = False):
         """models_*: policies (ActorCriticPolicy); envs_*: one normaliser per member (anything with
-        ``normalize_obs``, e.g. VecNormalize.load(...)); scaler: (mean, scale) from load_scaler."""
+        ``normalize_obs``, e.g. VecNormalize.load(...)); scaler: (mean, scale) from load_scaler.
+        fused: the state machine runs without host synchronisation (``where`` / index arithmetic over all rows, the classifier on
+        every row and masked: ``predict`` can be captured in a graph) and the members act through rl/ensemble.py ``FusedEnsemble``,
+        one launch per step; where that does not apply (``create`` returns None) the member loop acts, after one warning."""
         assert len(models_base) == len(envs_base) and len(models_hold) == len(envs_hold)
         self.models_base, self.envs_base = list(models_base), list(envs_base)
         self.models_hold, self.envs_hold = list(models_hold), list(envs_hold)
@@ -46,9 +49,18 @@ class SuperModel:
         self.current_task = torch.ones(N, dtype=torch.long, device=self.device)
         self.states_base = [m.initial_state(N, self.device) for m in self.models_base]
         self.states_hold = [m.initial_state(N, self.device) for m in self.models_hold]
+        self.fused_mode, self.fused = bool(fused), None
+        if self.fused_mode:
+            from .rl.ensemble import FusedEnsemble
+            self._rows = torch.arange(N, device=self.device)
+            self.fused = FusedEnsemble.create(self.models_base, self.envs_base, self.models_hold, self.envs_hold, N, self.device)
+            if self.fused is None:
+                import warnings
+                warnings.warn("SuperModel(fused=True): the fused ensemble step does not apply to these members on this device; "
+                              "the members act one by one")
 
     @classmethod
-    def load(cls, base_zips, base_pkls, hold_zips, hold_pkls, classifier_pt, scaler_pkl, env):
+    def load(cls, base_zips, base_pkls, hold_zips, hold_pkls, classifier_pt, scaler_pkl, env, fused: bool = False):
         """load_model_and_env / load_classifier / load_data_scaler (:88-165) for a batched ``env``."""
         from .rl.sb3_zip import load_policy
         from .rl.vec_normalize import VecNormalize
@@ -56,10 +68,12 @@ class SuperModel:
         clf.load_state_dict(torch.load(classifier_pt, map_location="cpu"))
         return cls([load_policy(p)[0] for p in base_zips], [VecNormalize.load(p, env) for p in base_pkls],
                    [load_policy(p)[0] for p in hold_zips], [VecNormalize.load(p, env) for p in hold_pkls],
-                   clf, load_scaler(scaler_pkl), env.num_envs, env.device)
+                   clf, load_scaler(scaler_pkl), env.num_envs, env.device, fused=fused)
 
     @torch.no_grad()
     def process_before_action(self, obs: torch.Tensor, episode_start: torch.Tensor) -> None:
+        if self.fused_mode:
+            return self._process_before_action_masked(obs, episode_start)
         es = episode_start.bool()
         self.use_hold_net &= ~es                      # :191-195
         self.just_switched &= ~es
@@ -81,12 +95,37 @@ class SuperModel:
         self.timestep += 1
 
     @torch.no_grad()
+    def _process_before_action_masked(self, obs: torch.Tensor, episode_start: torch.Tensor) -> None:
+        """process_before_action over ALL rows, masked: the same integers and booleans, no value read on the host."""
+        es = episode_start.bool()
+        self.use_hold_net &= ~es
+        self.just_switched &= ~es
+        self.timestep.masked_fill_(es, 0)
+        collect = self.timestep < N_OBS_PER_TRIAL
+        slot = torch.clamp(self.timestep, max=N_OBS_PER_TRIAL - 1)      # (rows past the window rewrite their last slot with itself)
+        new = obs[:, OBS_SLICE[0]:OBS_SLICE[1]].to(torch.float64)
+        self.obs_for_classifier[self._rows, slot] = torch.where(collect.unsqueeze(-1), new, self.obs_for_classifier[self._rows, slot])
+        classify = self.timestep == N_OBS_PER_TRIAL - 1
+        x = self.obs_for_classifier.reshape(self.N, -1)
+        x = ((x - self.scaler_mean) / self.scaler_scale).to(torch.float32)
+        task = self.classifier.predict_task(x)
+        self.current_task.copy_(torch.where(classify, task, self.current_task))
+        hold = classify & (task == 0)
+        self.use_hold_net |= hold
+        self.just_switched |= hold
+        self.timestep += 1
+
+    @torch.no_grad()
     def predict(self, obs: torch.Tensor, episode_start: torch.Tensor, deterministic: bool = True) -> torch.Tensor:
         """Mean action of the active ensemble per env (eval_perf :250-285)."""
         self.process_before_action(obs, episode_start)
         es = episode_start.to(torch.float32)
         hold_start = torch.maximum(es, self.just_switched.to(torch.float32))     # fresh LSTM states on the switch step
         self.just_switched.zero_()
+        if self.fused is not None:
+            if not deterministic:
+                raise NotImplementedError("the fused ensemble step acts deterministically (the reference's evaluation does)")
+            return self.fused.act(obs, es, hold_start, self.use_hold_net)
 
         def ensemble(models, envs, states, starts):
             acts = []

@@ -118,6 +118,17 @@ class AdamDesc(C.Structure):
     ]
 
 
+class EnsembleDesc(C.Structure):
+    """myo_ensemble_desc of include/myobatch.h (one acting step of an ensemble of actor-only LSTM policies)."""
+    _fields_ = [
+        ("N", C.c_int32), ("O", C.c_int32), ("A", C.c_int32), ("H", C.c_int32), ("M0", C.c_int32), ("M1", C.c_int32),
+        ("obs", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p), ("eps", C.c_double), ("clip", C.c_double),
+        ("w_gates", C.c_void_p), ("w_a", C.c_void_p), ("b_gates", C.c_void_p), ("b_a", C.c_void_p),
+        ("h", C.c_void_p), ("c", C.c_void_p), ("start0", C.c_void_p), ("start1", C.c_void_p), ("use_group1", C.c_void_p),
+        ("act", C.c_void_p), ("member_act", C.c_void_p),
+    ]
+
+
 class RenderCamera(C.Structure):
     """myo_render_camera of include/myobatch.h: MuJoCo's free camera, angles in degrees."""
     _fields_ = [("lookat", C.c_double * 3), ("distance", C.c_double), ("azimuth", C.c_double), ("elevation", C.c_double),
@@ -261,6 +272,8 @@ class NativeLib:
         L.myo_ppo_mlp_rollout_refresh.argtypes = [C.POINTER(PpoMlpRolloutDesc), vp]
         L.myo_ppo_mlp_rollout.argtypes = [C.POINTER(PpoMlpRolloutDesc), vp]
         L.myo_ppo_mlp_rollout_act.argtypes = [C.POINTER(PpoMlpRolloutDesc), i32, vp]
+        L.myo_ensemble_supported.argtypes = [i32, i32, i32]
+        L.myo_ensemble_act.argtypes = [C.POINTER(EnsembleDesc), vp]
 
     def check(self, rc: int):
         if rc != 0:
@@ -308,6 +321,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_fatigue",
     "myo_ppo_mlp_step_resident", "myo_ppo_mlp_images", "myo_ppo_adv_moments_epoch",
     "myo_ppo_mlp_step_act", "myo_ppo_mlp_rollout_act", "myo_bias_act_bf16", "myo_act_bwd_colsum_bf16",
+    "myo_ensemble_supported", "myo_ensemble_act",
 ]
 
 # ... of which the lane-serial emulation build (tests/emu/libmyobatch_emu.so: csrc/myobatch_emu.cpp + csrc/emu_host.h, test tooling) has the env
