@@ -481,6 +481,27 @@ int myo_ppo_loss_grad(const float* mean, const float* values, const float* actio
                       uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* work, int in_bf16, float ent_coef,
                       float* g_log_std, float* g_bias_pi, float* g_bias_vf, float* hp, void* stream);
 
+/* The same stage for generalised state-dependent exploration (SB3 StateDependentNoiseDistribution, learn_features = False), in
+ * two launches (csrc/myo_sde_loss.h), fp32 arithmetic on the bf16 trunk outputs:
+ *   var[i,a] = sum_l latent[i,l]^2 exp(2 log_std[l,a]) + sde_eps     (the latent is detached: log_std sees the loss through var only)
+ *   logp[i]  = sum_a (-0.5 (action - mean)^2 / var - 0.5 log var) - 0.5 A log 2 pi;  entropy[i] = sum_a 0.5 log var + 0.5 A (1 + log 2 pi)
+ * and the clipped surrogate, value loss and diagnostics of the Gaussian stage above.  mean_bf16 [B,A], value_bf16 [B], latent_bf16
+ * [B,L] (contiguous) are bfloat16; actions [B,A], old_logp, adv (raw), returns [B], log_std [L,A], adv_stats {mean, std} float32.
+ * Outputs: dmean_bf16 [B,A], dvalue_bf16 [B] (bfloat16, round-to-nearest-even), g_log_std [L,A] (entropy term included),
+ * g_bias_pi [A] and g_bias_vf [1] (column sums of the unrounded dmean / dvalue), acc[A] = policy loss, acc[A+1] = value loss (no other
+ * word of acc is written).  hp: NULL or the hyper-parameter block, as above (clip_range, diagnostics, KL stop).  work: dev float32 of
+ * the size the second function gives; no initialisation needed.  Sums over the batch are formed from per-block partials in block
+ * order by the second launch (deterministic, no float atomics); a block owns up to ceil(B / 8192) tiles of 64 rows, so the [L,A]
+ * partials never exceed 128 per call.  Any B from 1 to 2^24.  A NULL pointer other than hp, or B / L / A < 1, returns MYO_E_ARG
+ * before any device call; L > 256 or A > 64 returns MYO_E_UNSUPPORTED (the first function: 1 where the shape is supported). */
+int myo_ppo_sde_loss_supported(int L, int A);
+long long myo_ppo_sde_loss_work_floats(int B, int L, int A);
+int myo_ppo_sde_loss_grad(const uint16_t* mean_bf16, const uint16_t* value_bf16, const uint16_t* latent_bf16, const float* actions,
+                          const float* old_logp, const float* adv, const float* returns, const float* log_std, const float* adv_stats,
+                          int B, int L, int A, float clip, float vf_coef, float ent_coef, float sde_eps, uint16_t* dmean_bf16,
+                          uint16_t* dvalue_bf16, float* g_log_std, float* g_bias_pi, float* g_bias_vf, float* acc, float* work, float* hp,
+                          void* stream);
+
 /* Minibatch gather of one optimiser step (SB3 RolloutBuffer.get + the per-minibatch advantage
  * normalisation statistics of PPO.train): rows idx[0..bs) (dev int64) of obs[N,obs_dim] act[N,act_dim]
  * oldlp[N] adv[N] ret[N] (dev float32) -> obs_bf16 [copies, bs, obs_dim] (bfloat16), act_mb, oldlp_mb,

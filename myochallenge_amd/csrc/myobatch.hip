@@ -797,6 +797,45 @@ extern "C" int myo_ppo_loss_grad(const float* mean, const float* values, const f
   return MYO_OK;
 }
 
+// the same stage for state-dependent exploration (csrc/myo_sde_loss.h)
+#include "myo_sde_loss.h"
+extern "C" int myo_ppo_sde_loss_supported(int L, int A) { return (L >= 1 && L <= SDE_LMAX && A >= 1 && A <= SDE_AMAX) ? 1 : 0; }
+extern "C" long long myo_ppo_sde_loss_work_floats(int B, int L, int A) {
+  if (B < 1 || L < 1 || A < 1) return 0;
+  return (long long)sde_blocks(B) * ((long long)L * A + SDE_COLS(A));
+}
+extern "C" int myo_ppo_sde_loss_grad(const uint16_t* mean_bf16, const uint16_t* value_bf16, const uint16_t* latent_bf16,
+                                     const float* actions, const float* old_logp, const float* adv, const float* returns,
+                                     const float* log_std, const float* adv_stats, int B, int L, int A, float clip, float vf_coef,
+                                     float ent_coef, float sde_eps, uint16_t* dmean_bf16, uint16_t* dvalue_bf16, float* g_log_std,
+                                     float* g_bias_pi, float* g_bias_vf, float* acc, float* work, float* hp, void* stream) {
+  if (!mean_bf16 || !value_bf16 || !latent_bf16 || !actions || !old_logp || !adv || !returns || !log_std || !adv_stats || !dmean_bf16 ||
+      !dvalue_bf16 || !g_log_std || !g_bias_pi || !g_bias_vf || !acc || !work)
+    return fail(MYO_E_ARG, "myo_ppo_sde_loss_grad: null argument");
+  if (B < 1 || B > (1 << 24) || L < 1 || A < 1)
+    return fail(MYO_E_ARG, "myo_ppo_sde_loss_grad: size out of range (B %d, L %d, A %d)", B, L, A);
+  if (!myo_ppo_sde_loss_supported(L, A))
+    return fail(MYO_E_UNSUPPORTED, "myo_ppo_sde_loss_grad: needs latent <= %d, act <= %d (got %d, %d)", SDE_LMAX, SDE_AMAX, L, A);
+  const int NB = sde_blocks(B);
+  SdeArgs a;
+  a.mean = mean_bf16; a.value = value_bf16; a.lat = latent_bf16; a.actions = actions; a.old_logp = old_logp; a.adv = adv;
+  a.returns = returns; a.log_std = log_std; a.adv_stats = adv_stats; a.hp = hp; a.dmean = dmean_bf16; a.dvalue = dvalue_bf16;
+  a.gpart = work; a.part = work + (size_t)NB * L * A;
+  a.B = B; a.L = L; a.A = A; a.LS = sde_lat_stride(L); a.tpb = sde_tiles_per_block(B);
+  a.clip = clip; a.vf_coef = vf_coef; a.ent_coef = ent_coef; a.eps = sde_eps;
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (A <= 16) rc = sde_launch<4>(a, NB, st);
+  else if (A <= 32) rc = sde_launch<8>(a, NB, st);
+  else if (A <= 48) rc = sde_launch<12>(a, NB, st);
+  else rc = sde_launch<16>(a, NB, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_sde_finish, dim3((L * A + 255) / 256 + 1), dim3(256), 0, st, (const float*)a.gpart, (const float*)a.part, log_std, NB, B, L,
+                     A, g_log_std, g_bias_pi, g_bias_vf, acc, hp);
+  LAUNCH_CHECK(0)
+  return MYO_OK;
+}
+
 // ------------------------------------------------------------------------------------------ split-K
 // out[g, j] = sum_k part[g, k, j]: the reduction that finishes a split-K weight-gradient bmm
 // (bf16 partial products, fp32 sum).  torch's generic reduce over a middle dimension takes 37 us on

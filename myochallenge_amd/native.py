@@ -233,6 +233,10 @@ class NativeLib:
         if b"MYO_EMU" in L.myo_version():
             return      # the emulation build (test tooling, csrc/emu_host.h) implements the env path only: ENV_PATH_SYMBOLS
         L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp, vp]
+        L.myo_ppo_sde_loss_supported.argtypes = [i32, i32]
+        L.myo_ppo_sde_loss_work_floats.argtypes = [i32, i32, i32]
+        L.myo_ppo_sde_loss_work_floats.restype = C.c_longlong
+        L.myo_ppo_sde_loss_grad.argtypes = [vp] * 9 + [i32, i32, i32] + [C.c_float] * 4 + [vp] * 9
         L.myo_ppo_gather.argtypes = [vp] * 6 + [i32, i32, i32, vp, i32] + [vp] * 7
         L.myo_ppo_gather_seq.argtypes = [vp] * 9 + [i32] * 8 + [vp, i32] + [vp] * 11
         L.myo_rollout_state_snapshot.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
@@ -322,6 +326,7 @@ EXPORTED_SYMBOLS = [
     "myo_ppo_mlp_step_resident", "myo_ppo_mlp_images", "myo_ppo_adv_moments_epoch",
     "myo_ppo_mlp_step_act", "myo_ppo_mlp_rollout_act", "myo_bias_act_bf16", "myo_act_bwd_colsum_bf16",
     "myo_ensemble_supported", "myo_ensemble_act",
+    "myo_ppo_sde_loss_supported", "myo_ppo_sde_loss_work_floats", "myo_ppo_sde_loss_grad",
 ]
 
 # ... of which the lane-serial emulation build (tests/emu/libmyobatch_emu.so: csrc/myobatch_emu.cpp + csrc/emu_host.h, test tooling) has the env

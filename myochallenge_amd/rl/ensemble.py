@@ -18,7 +18,8 @@ APM = 48          # ENS_APM of csrc/myo_ensemble.h
 
 
 def _member_ok(p) -> bool:
-    return (getattr(p, "recurrent", False) and not getattr(p, "use_sde", False) and len(p.mlp_extractor.policy_net) == 0
+    """(gSDE members included: deterministic acting is action_net(latent), log_std is not read and repack packs action_net only)"""
+    return (getattr(p, "recurrent", False) and len(p.mlp_extractor.policy_net) == 0
             and p.lstm_actor.num_layers == 1 and not p.lstm_actor.bidirectional)
 
 

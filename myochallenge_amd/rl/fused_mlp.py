@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from typing import List, Tuple
 
 import torch
@@ -284,6 +285,9 @@ class FusedPPOStep:
         self.resident_adam = None
         self.adv_slot = None                 # resident step: where its advantage moments are (a row of epoch_moments' output); None: self.stats
         self._moments = {}                   # per n_mb: (stats [n_mb, 2], scratch) of epoch_moments
+        # gSDE loss stage: the two HIP launches of csrc/myo_sde_loss.h where the shape has them; MYO_SDE_LOSS=torch is the A/B switch
+        # back to the ATen statement (_sde_loss), read once here
+        self.sde_kernel = os.environ.get("MYO_SDE_LOSS") != "torch"
 
     def _fused_layout(self, obs):
         """Where the fused MLP kernels (myo_ppo_mlp_step, myo_ppo_mlp_rollout) find the policy's tensors in the flat vector
@@ -550,6 +554,24 @@ class FusedPPOStep:
             hp_record_torch(self.hp, self.acc[A], self.acc[A + 1], d3[0], d3[1], d3[2])
         return dmean.to(torch.bfloat16), dvalue.to(torch.bfloat16).unsqueeze(-1)
 
+    def _sde_loss_kernel(self, mean_h, value_h, lat_h, actions, old_logp, adv, returns):
+        """_sde_loss as two HIP launches (myo_ppo_sde_loss_grad): the same outputs in the same places.  The workspace is cached per
+        shape: no allocation beyond the two outputs and no host synchronisation, so it is capturable."""
+        pol, A = self.policy, self.A
+        B, L = lat_h.shape
+        dev = mean_h.device
+        pi_head, vf_head = self.nets["pi"][-1], self.nets["vf"][-1]
+        dmean_h = torch.empty((B, A), device=dev, dtype=torch.bfloat16)
+        dvalue_h = torch.empty((B, 1), device=dev, dtype=torch.bfloat16)
+        work = self._workbuf("sde_loss", int(self.lib.L.myo_ppo_sde_loss_work_floats(B, L, A)))
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        c = lambda t: t.contiguous()
+        self.lib.check(self.lib.L.myo_ppo_sde_loss_grad(
+            p(c(mean_h)), p(c(value_h)), p(c(lat_h)), p(c(actions)), p(c(old_logp)), p(c(adv)), p(c(returns)), p(pol.log_std.data),
+            p(self.stats), B, L, A, self.clip, self.vf, self.ent, float(pol.SDE_EPS), p(dmean_h), p(dvalue_h), p(pol.log_std.grad),
+            p(pi_head.bias.grad), p(vf_head.bias.grad), p(self.acc), p(work), p(self.hp), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return dmean_h, dvalue_h
+
     @torch.no_grad()
     def run_indexed(self, obs_all, act_all, oldlp_all, adv_all, ret_all, idx):
         """One minibatch step on rows `idx` of the rollout arrays (merged path: HIP gather kernel)."""
@@ -632,7 +654,10 @@ class FusedPPOStep:
         wpi, wvf = self.wb[id(pi_head.weight)], self.wb[id(vf_head.weight)]
         acc = self.acc
         if getattr(pol, "use_sde", False):
-            dmean_h, dvalue_h = self._sde_loss(mean_h, value_h, h[0], actions, old_logp, adv, returns)
+            sde = self._sde_loss
+            if self.sde_kernel and self.lib.L.myo_ppo_sde_loss_supported(h.shape[2], A) and actions.dtype == torch.float32:
+                sde = self._sde_loss_kernel
+            dmean_h, dvalue_h = sde(mean_h, value_h, h[0], actions, old_logp, adv, returns)
         else:
             dmean_h = torch.empty((B, A), device=dev, dtype=torch.bfloat16)
             dvalue_h = torch.empty((B, 1), device=dev, dtype=torch.bfloat16)

@@ -6,7 +6,10 @@ O = 86, A = 39, with seeded random weights, statistics and observations, at N = 
 process and are timed alternately, block by block, after a warm-up of each; every block of `--steps` predict calls is timed
 between two device synchronisations (host clock), and the per-call time is the median over the blocks.  Needs a GPU.
 
-    python tools/bench_ensemble.py [--steps 50] [--blocks 9] [--out profiles/ensemble_act.json]
+    python tools/bench_ensemble.py [--steps 50] [--blocks 9] [--sde] [--out profiles/ensemble_act.json]
+
+--sde builds the members as the reference trains them (use_sde=True, log_std_init=-2: deterministic acting does not read log_std,
+so the launch is the same); the default run and profiles/ensemble_act.json are the Gaussian members.
 """
 import argparse
 import json
@@ -26,6 +29,7 @@ def main() -> int:
     ap.add_argument("--blocks", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--envs", type=int, nargs="+", default=[256, 4096])
+    ap.add_argument("--sde", action="store_true", help="gSDE members (use_sde=True, log_std_init=-2), as the reference's")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ensemble_act.json"))
     args = ap.parse_args()
     import torch
@@ -43,7 +47,8 @@ def main() -> int:
     results = []
     for N in args.envs:
         torch.manual_seed(1)
-        pols = [ActorCriticPolicy(O, A, (), (), lstm_hidden_size=H) for _ in range(M0 + M1)]
+        kind = dict(use_sde=True, log_std_init=-2.0) if args.sde else {}
+        pols = [ActorCriticPolicy(O, A, (), (), lstm_hidden_size=H, **kind) for _ in range(M0 + M1)]
         clf = TaskClassifier()
         venv = types.SimpleNamespace(num_envs=N, device=dev, obs_dim=O, act_dim=A, observation_space=None, action_space=None)
 
@@ -85,7 +90,7 @@ def main() -> int:
             for name, call in calls.items():
                 times[name].append(block(call, args.steps))
         med = {k: statistics.median(v) for k, v in times.items()}
-        rec = {"num_envs": N, "members": [M0, M1], "obs_dim": O, "act_dim": A, "hidden": H, "steps_per_block": args.steps, "blocks": args.blocks,
+        rec = {"num_envs": N, "members": [M0, M1], **({"use_sde": True} if args.sde else {}), "obs_dim": O, "act_dim": A, "hidden": H, "steps_per_block": args.steps, "blocks": args.blocks,
                "loop_us": med["loop"] * 1e6, "fused_us": med["fused"] * 1e6, "loop_over_fused": med["loop"] / med["fused"],
                "fused_launch_alone_us": med["kernel"] * 1e6,
                "loop_us_min_max": [min(times["loop"]) * 1e6, max(times["loop"]) * 1e6],
