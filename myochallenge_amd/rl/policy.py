@@ -260,8 +260,8 @@ class ActorCriticPolicy(nn.Module):
     @torch.no_grad()
     def reset_noise(self, n_envs: int, generator: Optional[torch.Generator] = None, out: Optional[torch.Tensor] = None) -> None:
         """One exploration matrix per env, W ~ N(0, exp(log_std)) (SB3 ``sample_weights``; called at the start of every
-        rollout for sde_sample_freq = -1).  out: a caller-owned [n_envs, latent, act] buffer to draw into — PPO's captured rollout
-        graph reads ITS buffer by address, so the training matrix must never move (an evaluation on another batch size
+        rollout for sde_sample_freq = -1).  out: a caller-owned [n_envs, latent, act] buffer to draw into — the captured graph of
+        rl/rollout.py's KernelRollout reads ITS buffer (sde_W) by address, so the training matrix must never move (an evaluation on another batch size
         between two rollouts used to replace the tensor and leave the graph reading freed memory)."""
         if not self.use_sde:
             return

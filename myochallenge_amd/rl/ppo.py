@@ -16,7 +16,6 @@ from __future__ import annotations
 import os
 import time
 import warnings
-from collections import deque
 from dataclasses import dataclass, field
 from typing import Callable, Dict, Optional
 
@@ -29,6 +28,7 @@ from ..native import (HP_APPLIED, HP_CLIP, HP_COUNT, HP_LAST_KL, HP_LAST_PL, HP_
 from .fused_lstm import FusedRecurrentPPOStep
 from .fused_mlp import FlatAdam, FusedPPOStep, activation_code, flatten_parameters, hp_record_torch
 from .policy import ActorCriticPolicy
+from .rollout import EpisodeLog, make_rollout
 
 
 @dataclass
@@ -190,30 +190,17 @@ class PPO:
         self._last_starts = torch.ones(N, device=d)
         self._state = policy.initial_state(N, d)
         self._rollout_state0 = None
-        # seq_len: the state entering step s * seq_len of the rollout, slot s.  Eager and torch-graph rollouts: four float32
-        # [S, 1, N, H] views (h_pi, c_pi, h_vf, c_vf); HIP-kernel rollout: stacked (actor, critic) bf16 h / float32 c [S, 2, N, H]
-        self._snap_state, self._snap_full, self._snap_spare, self._snap_h, self._snap_c = None, None, None, None, None
+        self._last_values = None
+        self._rollout = None             # the collector (rl/rollout.py), made at the first rollout step: the ONE rollout attribute here
+        self._episodes = EpisodeLog(T, N, d)
         self.num_timesteps = 0
         self.n_updates = 0
-        self.ep_returns: list = []
-        self.ep_lengths: list = []
         self.gen = torch.Generator(device=self.device if on_gpu else "cpu")   # minibatch permutations on the device
         self.gen.manual_seed(seed + 1000 * self.rank)
         nparam = sum(p.numel() for p in self.policy.parameters())
         self._flat_grad = self.policy._flat["g"] if self._flat_adam is not None else torch.zeros(nparam, device=d)
-        self.timers: Dict[str, float] = {"rollout": 0.0, "gae": 0.0, "update": 0.0}
-        # state that later calls fill in: the rollout graphs (rollout_step) ...
-        self._rollout_ready = False      # the rollout graphs are captured
-        self._native = False             # ... and they are the HIP-kernel rollout (_init_native_rollout)
-        self._gB2 = None                 # second half of graph B with a rank-synchronised normaliser
-        self._sde_W = None               # gSDE exploration matrices of the HIP-kernel rollout
-        self._t_host = 0
-        self._last_values = None
-        self.vn_allreduce_seconds, self.vn_allreduce_calls = 0.0, 0
-        # ... the episode log (_log_episodes, episode_stats) ...
-        self._ep_log, self._ep_t, self._ep_nan_t, self.ep_info_buffer = None, 0, None, None
-        # ... and the update: the captured MLP step (_build_graphs) and the captured recurrent step (_build_recurrent_graphs), each
-        # with the shape it was captured for, its static tensors and its graphs
+        # state that the update fills in later: the captured MLP step (_build_graphs) and the captured recurrent step
+        # (_build_recurrent_graphs), each with the shape it was captured for, its static tensors and its graphs
         self._graph, self._gs, self._graph_fb, self._graph_ap, self._graph_epoch, self._epoch_chunk = None, None, None, None, None, 0
         self._rgraph, self._rg, self._rgraph_fb, self._rgraph_ap, self._rgraph_L = None, None, None, None, None
         self._allreduce_in_graph = False
@@ -223,463 +210,51 @@ class PPO:
         on = self.cfg.bf16 and self.device.type == "cuda"
         return torch.autocast(device_type=self.device.type, dtype=torch.bfloat16, enabled=on)
 
-    # ---------------------------------------------------------------- rollout (hipGraph path)
-    def _graphed_rollout(self) -> bool:
-        return self.cfg.use_graphs and self.device.type == "cuda" and hasattr(self.env, "step_tensor")
+    # ---------------------------------------------------------------- rollout (rl/rollout.py)
+    def _collector(self):
+        """The rollout collector, made at the first rollout step: the path is chosen, the env reset and the graphs captured there."""
+        if self._rollout is None:
+            bufs = (self.obs_buf, self.act_buf, self.rew_buf, self.val_buf, self.logp_buf, self.start_buf)
+            fused = self._fused if self._fused is not None else self._fused_rec
+            self._rollout = make_rollout(self.env, self.policy, self.cfg, bufs, fused, self.gen, self.world, self._episodes,
+                                         (self._last_obs, self._last_starts, self._state))
+        return self._rollout
 
-    @torch.no_grad()
-    def _rollout_policy_part(self):
-        if self.cfg.seq_len is not None and self.policy.recurrent:     # the state entering a chunk's first step goes to its slot, any other step's to the spare one
-            L = self.cfg.seq_len
-            slot = torch.where(self._t_idx % L == 0, torch.div(self._t_idx, L, rounding_mode="floor"), self._snap_spare)
-            for dst, src in zip(self._snap_full, self._state_s):
-                dst.index_copy_(0, slot, src.unsqueeze(0))
-        with self._autocast():
-            if self.policy.recurrent:
-                actions, values, logp, new_state = self.policy.act(self._obs_s, self._state_s, self._starts_s)
-                for dst, src in zip(self._state_new, new_state):
-                    dst.copy_(src)
-            else:
-                actions, values, logp, _ = self.policy.act(self._obs_s, None, None)
-        self._act_s.copy_(actions); self._val_s.copy_(values); self._logp_s.copy_(logp)
-        self._clip_s.copy_(torch.clamp(actions, -1.0, 1.0))
+    def rollout_step(self) -> None:
+        """One environment step for the whole batch."""
+        r = self._collector()
+        r.step()
+        self._rollout_state0 = r.state0
 
-    @torch.no_grad()
-    def _rollout_post_part(self, raw):
-        cfg = self.cfg
-        outs = self._vec.process_step(*raw) if self._vec is not None else raw
-        nobs, rew, done, trunc, term, comps, ep = outs
-        with self._autocast():   # timeout bootstrap r += gamma V(terminal_obs) where truncated (mask, no host sync)
-            if self.policy.recurrent:    # sb3-contrib: critic state after this step, episode_start False [3P-RECALL]
-                tv = self.policy.predict_values(term, self._state_new, None)
-            else:
-                tv = self.policy.predict_values(term)
-        rew = rew + cfg.gamma * tv * trunc.to(rew.dtype)
-        idx = self._t_idx
-        self.obs_buf.index_copy_(0, idx, self._obs_s.unsqueeze(0))
-        self.act_buf.index_copy_(0, idx, self._act_s.unsqueeze(0))
-        self.rew_buf.index_copy_(0, idx, rew.unsqueeze(0))
-        self.val_buf.index_copy_(0, idx, self._val_s.unsqueeze(0))
-        self.logp_buf.index_copy_(0, idx, self._logp_s.unsqueeze(0))
-        self.start_buf.index_copy_(0, idx, self._starts_s.unsqueeze(0))
-        self._obs_s.copy_(nobs)
-        self._starts_s.copy_(done.to(torch.float32))
-        if self.policy.recurrent:
-            for dst, src in zip(self._state_s, self._state_new):
-                dst.copy_(src)
-        self._t_idx.add_(1).remainder_(cfg.n_steps)
+    def finish_rollout(self) -> None:
+        r = self._rollout
+        self._last_values = r.finish()
+        self._last_obs, self._last_starts, self._state = r.obs, r.starts, r.state
 
-    # -- native rollout step: HIP kernels for policy input, sampling, VecNormalize and buffer writes
-    def _native_rollout(self) -> bool:
-        fused = self._fused if self._fused is not None else self._fused_rec
-        return (self._graphed_rollout() and fused is not None and fused.merged is not None
-                and hasattr(self.env, "process_step") and hasattr(self.env, "obs_rms"))
-
-    def _init_native_rollout(self):
-        """Per step: graph A (policy input cast, [LSTM step,] stacked trunks, heads, myo_rollout_sample) -> eager
-        myo_batch_step -> graph B (myo_vecnorm_step, myo_rollout_advance).  The timeout bootstrap
-        r += gamma V(terminal_obs) is applied once per rollout in finish_rollout() from term_buf/trunc_buf (recurrent
-        policy: with the critic's LSTM state after each step, kept in crit_h_buf / crit_c_buf)."""
-        import ctypes as C
-        vec, raw, d, cfg = self.env, self.env.venv, self.device, self.cfg
-        N, A, O, T = vec.num_envs, vec.act_dim, vec.obs_dim, cfg.n_steps
-        recurrent = self.policy.recurrent
-        fused = self._fused_rec if recurrent else self._fused
-        lib = fused.lib
-        first = vec.reset_tensor() if self._last_obs is None else self._last_obs
-        self._obs_s = first.clone().contiguous()
-        self._starts_s = self._last_starts.clone()
-        self._clip_s = torch.zeros((N, A), device=d)
-        self._t_idx = torch.zeros(1, dtype=torch.int32, device=d)
-        self._draw = torch.zeros(2, dtype=torch.int64, device=d)
-        self._x2 = torch.empty((2, N, O), device=d, dtype=torch.bfloat16)
-        self.term_buf = torch.zeros((T, N, O), device=d)
-        self.trunc_buf = torch.zeros((T, N), device=d)
-        self._vn_work = torch.zeros(((N + 127) // 128) * 2 * (O + 1), dtype=torch.float64, device=d)
-        seed = int(self.gen.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        p = lambda t: C.c_void_p(t.data_ptr())
-
-        # policy call of a step: ONE launch on the matrix cores (myo_ppo_mlp_rollout) where the architecture fits, else policy-input
-        # cast + hipBLASLt trunk / head GEMMs + bias/ReLU kernels + myo_rollout_sample
-        rdesc = fused.rollout_desc(self._obs_s, seed, self._draw, self._t_idx, self.obs_buf, self.act_buf, self.val_buf,
-                                   self.logp_buf, self._clip_s) if os.environ.get("MYO_ROLLOUT_GEMM") != "1" else None
-        if recurrent:
-            # LSTM state after the previous step, (actor, critic) stacked; the masked copies that enter the step; the step's
-            # pre-activations / gates are scratch.  h is bf16 (the matrix cores' operand, as the update computes it); the CELL state is
-            # carried in float32 (_cs32 / _cm32) — what stock nn.LSTM carries (/root/reference/src/main_reorient.py:53-71), what
-            # policy.predict carries in an evaluation, and what a bf16 round trip per step would erode over a 300-step episode.  The
-            # bf16 copy _cs is what the step leaves for the bootstrap buffers (and what the cell-kernel fallback computes in).
-            H, bf = self.policy.hidden, torch.bfloat16
-            self._hs, self._cs = torch.zeros((2, N, H), device=d, dtype=bf), torch.zeros((2, N, H), device=d, dtype=bf)
-            self._cs32 = torch.zeros((2, N, H), device=d, dtype=torch.float32)
-            self._hs[0].copy_(self._state[0][0]); self._hs[1].copy_(self._state[2][0])
-            self._cs32[0].copy_(self._state[1][0]); self._cs32[1].copy_(self._state[3][0])
-            self._cs.copy_(self._cs32)
-            self._hm, self._cm = torch.empty_like(self._hs), torch.empty_like(self._cs)
-            self._cm32 = torch.empty_like(self._cs32)
-            self._lat, self._cn = torch.empty_like(self._hs), torch.empty_like(self._hs)
-            self._ws = torch.empty((2, N, 4 * H), device=d, dtype=bf)
-            self._bsum = torch.zeros((2, 1, 4 * H), device=d, dtype=bf)
-            self.crit_h_buf, self.crit_c_buf = torch.zeros((T, N, H), device=d, dtype=bf), torch.zeros((T, N, H), device=d, dtype=bf)
-            Lw = fused.lstm
-            if cfg.seq_len is not None:      # (allocated once: the update's captured graph reads them by address)
-                S = T // cfg.seq_len
-                self._snap_h, self._snap_c = torch.zeros((S, 2, N, H), device=d, dtype=bf), torch.zeros((S, 2, N, H), device=d)
-
-        sde = getattr(self.policy, "use_sde", False)
-        if sde:          # gSDE: myo_rollout_sample_sde leaves actions / log pi in step tensors, the rollout buffers take them by index
-            self._act_s, self._logp_s = torch.zeros((N, A), device=d), torch.zeros(N, device=d)
-            # the exploration matrices live in a buffer of PPO's own: the captured graph reads it by address (see _reset_sde_noise)
-            self._sde_W = torch.zeros((N,) + tuple(self.policy.log_std.shape), device=d)
-            self._reset_sde_noise()
-
-        def sample(saved, mean_h, value_h, st):
-            """Actions, log pi, value of this step into the rollout buffers (row t_idx) and the clipped actions for the env."""
-            if not sde:
-                lib.check(lib.L.myo_rollout_sample(p(mean_h), p(value_h), p(self.policy.log_std.data), N, A, seed, p(self._draw),
-                                                   p(self._t_idx), p(self.act_buf), p(self.val_buf), p(self.logp_buf),
-                                                   p(self._clip_s), 0, st))
-                return
-            mu, lat = mean_h.float(), saved[-1][0].float().contiguous()      # latent_pi: the actor trunk's output (LSTM output without a trunk)
-            lib.check(lib.L.myo_rollout_sample_sde(p(mu), p(lat), p(self._sde_W), p(self.policy.log_std.data), N, lat.shape[1], A,
-                                                   p(self._act_s), p(self._clip_s), p(self._logp_s), 0, st))
-            t64 = self._t_idx.long()
-            self.act_buf.index_copy_(0, t64, self._act_s.unsqueeze(0))
-            self.logp_buf.index_copy_(0, t64, self._logp_s.unsqueeze(0))
-            self.val_buf.index_copy_(0, t64, value_h.float().view(1, N))
-
-        def part_a_recurrent():
-            st = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
-            lib.check(lib.L.myo_rollout_policy_input(p(self._obs_s), N, O, p(self.obs_buf), p(self._x2), 2, p(self._t_idx), st))
-            if self._snap_h is not None:     # seq_len: the state entering a chunk's first step, before the mask (the device decides)
-                lib.check(lib.L.myo_rollout_state_snapshot(p(self._hs), p(self._cs32), 2, N, H, p(self._t_idx), cfg.seq_len,
-                                                           T // cfg.seq_len, p(self._snap_h), p(self._snap_c), st))
-            keep = torch.rsub(self._starts_s, 1.0).view(1, N, 1)            # state zeroed where an episode starts
-            torch.mul(self._hs, keep, out=self._hm)
-            torch.mul(self._cs32, keep, out=self._cm32)
-            if fused.step_kernels:       # recurrent product + cell in one launch; nothing kept for a backward pass
-                # one projection GEMM for both LSTMs with the bias in its epilogue: row n = [actor 4H | critic 4H], read in place
-                gx = torch.addmm(self._bsum.view(8 * H), self._x2[0], Lw["wihh"].view(8 * H, O).t())
-                # (cell state in and out in float32; the bf16 copy beside it for the bootstrap buffers)
-                lib.check(lib.L.myo_lstm_step_fwd(p(gx), 4 * H, 8 * H, p(self._hm), None, p(Lw["whhh"]), None, 2, N, H,
-                                                  p(self._lat), N * H, p(self._hs), p(self._cs), None, None, p(self._cm32), p(self._cs32), st))
-            else:                        # (hidden sizes without a fused time-step kernel: GEMM + cell kernel, cell state through bf16)
-                self._cm.copy_(self._cm32)
-                gx = torch.baddbmm(self._bsum, self._x2, Lw["wihh"].transpose(1, 2))
-                gh = torch.bmm(self._hm, Lw["whhh"].transpose(1, 2))
-                lib.check(lib.L.myo_lstm_cell_fwd(p(gx), p(gh), p(self._cm), None, 2 * N, N, H, 1, p(self._lat), p(self._hs), p(self._cs),
-                                                  p(self._cn), p(self._ws), st))
-                self._cs32.copy_(self._cs)
-            t64 = self._t_idx.long()
-            self.crit_h_buf.index_copy_(0, t64, self._hs[1:2])
-            self.crit_c_buf.index_copy_(0, t64, self._cs[1:2])
-            saved, mean_h, value_h = fused.trunk_heads(self._lat)
-            sample(saved, mean_h, value_h, st)
-
-        def part_a():
-            if recurrent:
-                part_a_recurrent()
-                return
-            if rdesc is not None:
-                fused.rollout_policy(rdesc)
-                return
-            st = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
-            lib.check(lib.L.myo_rollout_policy_input(p(self._obs_s), N, O, p(self.obs_buf), p(self._x2), 2, p(self._t_idx), st))
-            saved, mean_h, value_h = fused.trunk_heads(self._x2)
-            sample(saved, mean_h, value_h, st)
-
-        # N > 1 ranks with a rank-synchronised normaliser: graph B1 (this rank's batch moments) -> eager all-reduce of
-        # 2 O + 3 doubles -> graph B2 (running statistics from the global moments, normalise, buffer writes)
-        self._vn_sync = self.world > 1 and getattr(vec, "sync_ranks", False) and vec.training
-        self._vn_batch = torch.zeros(2 * O + 3, dtype=torch.float64, device=d)
-
-        def part_b1(rawout):
-            obs, rew = rawout[:2]
-            st = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
-            lib.check(lib.L.myo_vecnorm_batch_moments(p(obs), p(rew), N, O, p(vec.returns), float(vec.gamma), int(vec.training),
-                                                      p(self._vn_work), p(self._vn_batch), st))
-
-        def part_b2(rawout):
-            obs, rew, done, trunc, term = rawout[:5]
-            st = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
-            lib.check(lib.L.myo_vecnorm_finish(
-                p(obs), p(rew), p(done), p(trunc), p(term), N, O, p(vec.obs_rms.mean), p(vec.obs_rms.var), p(vec.obs_rms.count),
-                p(vec.ret_rms.buf), p(vec.returns), float(vec.epsilon), float(vec.clip_obs), float(vec.clip_reward),
-                int(vec.training), int(vec.norm_obs), int(vec.norm_reward), p(self._obs_s), p(self._starts_s), p(self._t_idx),
-                p(self.rew_buf), p(self.start_buf), p(self.term_buf), p(self.trunc_buf), p(self._vn_batch), st))
-            lib.check(lib.L.myo_rollout_advance(p(self._t_idx), T, p(self._draw), st))
-
-        def part_b(rawout):
-            if self._vn_sync:
-                part_b1(rawout)
-                dist.all_reduce(self._vn_batch)
-                part_b2(rawout)
-                return
-            obs, rew, done, trunc, term = rawout[:5]
-            st = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
-            lib.check(lib.L.myo_vecnorm_step(
-                p(obs), p(rew), p(done), p(trunc), p(term), N, O, p(vec.obs_rms.mean), p(vec.obs_rms.var), p(vec.obs_rms.count),
-                p(vec.ret_rms.buf), p(vec.returns), float(vec.gamma), float(vec.epsilon), float(vec.clip_obs),
-                float(vec.clip_reward), int(vec.training), int(vec.norm_obs), int(vec.norm_reward), p(self._obs_s),
-                p(self._starts_s), p(self._t_idx), p(self.rew_buf), p(self.start_buf), p(self.term_buf), p(self.trunc_buf),
-                p(self._vn_work), st))
-            lib.check(lib.L.myo_rollout_advance(p(self._t_idx), T, p(self._draw), st))
-
-        self._raw = raw
-        fused.refresh_shadow()
-        # eager warm-up of the two halves (library handles, workspaces) WITHOUT stepping the env: part B runs on
-        # the env's static output buffers as they are, and everything it touches is put back afterwards, so the
-        # recorded rollout starts exactly at the reset
-        rawout = (raw._obs, raw._rew, raw._done, raw._trunc, raw._term, raw._comps, raw._ep)
-        restore = (self._obs_s, self._starts_s, vec.obs_rms.buf, vec.ret_rms.buf, vec.returns) + ((self._hs, self._cs, self._cs32) if recurrent else ())
-        keep = [t.clone() for t in restore]
-        if recurrent:
-            self._refresh_rollout_lstm()
-        side = torch.cuda.Stream(device=d)
-        side.wait_stream(torch.cuda.current_stream(d))
-        with torch.cuda.stream(side):
-            part_a()
-            part_b(rawout)
-        torch.cuda.current_stream(d).wait_stream(side)
-        torch.cuda.synchronize(d)
-        for t, k in zip(restore, keep):
-            t.copy_(k)
-        vec.old_obs, vec.old_reward = rawout[0], rawout[1]      # the env's static output buffers
-        self._t_idx.zero_()
-        self._draw.zero_()
-        self._gA, self._gB, self._gB2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), None
-        with torch.cuda.graph(self._gA, capture_error_mode="thread_local"):
-            part_a()
-        if self._vn_sync:
-            self._gB2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._gB, capture_error_mode="thread_local"):
-                part_b1(rawout)
-            with torch.cuda.graph(self._gB2, capture_error_mode="thread_local"):
-                part_b2(rawout)
-        else:
-            with torch.cuda.graph(self._gB, capture_error_mode="thread_local"):
-                part_b(rawout)
-        self._rollout_ready = True
-        self._native = True
-
-    def _refresh_rollout_lstm(self):
-        """Per rollout: the summed LSTM biases the native recurrent rollout adds to the input projection."""
-        Lw = self._fused_rec.lstm
-        torch.add(Lw["bihh"], Lw["bhhh"], out=self._bsum.view(2, -1))
-
-    def _new_snapshots(self, state):
-        """seq_len on the eager and torch-graph rollouts: four [S, 1, N, H] snapshot buffers shaped after `state`, each the first S
-        slots of a buffer with one spare slot (where the captured rollout sends the steps that open no chunk)."""
-        S = self.cfg.n_steps // self.cfg.seq_len
-        self._snap_spare = torch.full((1,), S, dtype=torch.long, device=self.device)
-        self._snap_full = tuple(torch.zeros((S + 1,) + tuple(x.shape), device=self.device, dtype=x.dtype) for x in state)
-        self._snap_state = tuple(x[:S] for x in self._snap_full)
+    def collect_rollouts(self) -> None:
+        self._collector().begin()
+        for _ in range(self.cfg.n_steps):
+            self.rollout_step()
+        self.finish_rollout()
+        self.num_timesteps += self.cfg.n_steps * self.env.num_envs * self.world
 
     def rollout_snapshots(self):
         """seq_len: (h_pi, c_pi, h_vf, c_vf) float32 [S, 1, N, H], the LSTM state that entered step s * seq_len of the last rollout
         (before the episode-start mask), whichever rollout path stored it.  Slot 0 is _rollout_state0."""
-        if self._snap_h is not None:
-            h, c = self._snap_h, self._snap_c
-            return (h[:, 0:1].float(), c[:, 0:1], h[:, 1:2].float(), c[:, 1:2])
-        return self._snap_state
-
-    def _native_state(self):
-        """(h_pi, c_pi, h_vf, c_vf) float32 [1,N,H] from the native recurrent rollout's stacked state."""
-        f = lambda z, k: z[k:k + 1].float()
-        return (f(self._hs, 0), f(self._cs32, 0).clone(), f(self._hs, 1), f(self._cs32, 1).clone())
-
-    def _init_rollout_graphs(self):
-        """Per step: graph A (policy inference + sampling) -> eager myo_batch_step (so its HIP events can
-        still bracket the kernel) -> graph B (normaliser, timeout bootstrap, buffer writes)."""
-        env, d = self.env, self.device
-        self._vec = env if hasattr(env, "process_step") else None
-        self._raw = env.venv if self._vec is not None else env
-        N, A = env.num_envs, env.act_dim
-        first = env.reset_tensor() if self._last_obs is None else self._last_obs
-        self._obs_s = first.clone()
-        self._starts_s = self._last_starts.clone()
-        self._act_s, self._clip_s = torch.zeros((N, A), device=d), torch.zeros((N, A), device=d)
-        self._val_s, self._logp_s = torch.zeros(N, device=d), torch.zeros(N, device=d)
-        self._t_idx = torch.zeros(1, dtype=torch.long, device=d)
-        if self.policy.recurrent:               # static LSTM state (before / after the current step)
-            self._state_s = tuple(x.clone() for x in self._state)
-            self._state_new = tuple(torch.zeros_like(x) for x in self._state)
-            if self.cfg.seq_len is not None:
-                self._new_snapshots(self._state)
-        side = torch.cuda.Stream(device=d)
-        side.wait_stream(torch.cuda.current_stream(d))
-        with torch.cuda.stream(side):           # eager warm-up (also binds the env's constants)
-            for _ in range(2):
-                self._rollout_policy_part()
-                raw = self._raw.step_tensor(self._clip_s)
-                self._rollout_post_part(raw)
-        torch.cuda.current_stream(d).wait_stream(side)
-        torch.cuda.synchronize(d)
-        self._t_idx.zero_()
-        self._raw_static = raw                  # the env returns views of its own (static) buffers
-        self._gA, self._gB = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._gA, capture_error_mode="thread_local"):
-            self._rollout_policy_part()
-        with torch.cuda.graph(self._gB, capture_error_mode="thread_local"):          # own pool: graph B keeps tensors alive across replays
-            self._rollout_post_part(self._raw_static)
-        self._rollout_ready = True
-
-    def rollout_step(self) -> None:
-        """One environment step for the whole batch (graphed path only)."""
-        if not self._rollout_ready:
-            if self._native_rollout():
-                self._init_native_rollout()
-            else:
-                self._init_rollout_graphs()
-        if hasattr(self.env, "begin_rollout"):
-            self.env.begin_rollout()         # (per-rollout normaliser synchronisation: snapshot at the first step; a no-op otherwise)
-        if self.policy.recurrent:
-            if self._t_host == 0:      # LSTM state at the start of the rollout: initial state of the update's sequences
-                self._rollout_state0 = self._native_state() if self._native else tuple(s.clone() for s in self._state_s)
-            self._t_host = (self._t_host + 1) % self.cfg.n_steps
-        self._gA.replay()
-        raw = self._raw.step_tensor(self._clip_s)
-        self._log_episodes(raw[2], raw[6])
-        self._gB.replay()
-        if self._gB2 is not None:      # rank-synchronised normaliser (see _init_native_rollout)
-            # (host time of the eager collective between the two graph replays — enqueue + whatever the call blocks on — accumulated for
-            #  the bench line of an N > 1 run: `normalizer_allreduce_ms_per_step`, VERDICT r05 item 8)
-            t0 = time.perf_counter()
-            dist.all_reduce(self._vn_batch)
-            self.vn_allreduce_seconds += time.perf_counter() - t0
-            self.vn_allreduce_calls += 1
-            self._gB2.replay()
-
-    def _log_episodes(self, done, ep) -> None:
-        """Monitor statistics (SB3's ep_info_buffer): the (raw return, length) the kernel reports for every env that finished an
-        episode in this step go into row t of a [T, N, 2] log, NaN elsewhere — one small launch per step; episode_stats() reads it."""
-        T, N = self.cfg.n_steps, self.env.num_envs
-        if self._ep_log is None or self._ep_log.shape[:2] != (T, N):
-            self._ep_log = torch.full((T, N, 2), float("nan"), device=self.device)
-            self._ep_t = 0
-            self.ep_info_buffer = deque(maxlen=100)
-        if ep is None:
-            return
-        torch.where(done.view(torch.bool).unsqueeze(1), ep, self._ep_nan, out=self._ep_log[self._ep_t % T])
-        self._ep_t += 1
-
-    @property
-    def _ep_nan(self):
-        if self._ep_nan_t is None:
-            self._ep_nan_t = torch.full((1, 1), float("nan"), device=self.device)
-        return self._ep_nan_t
+        return self._rollout.snapshots() if self._rollout is not None else None
 
     def episode_stats(self) -> Dict[str, float]:
         """rollout/ep_rew_mean and rollout/ep_len_mean as SB3 logs them: means over the last 100 finished episodes (Monitor's raw,
-        un-normalised returns; /root/reference/src/main_baoding.py runs under SB3's logger).  Reads the rollout's episode log once
-        (one host synchronisation per call)."""
-        log = self._ep_log
-        if log is not None and self._ep_t > 0:
-            T = log.shape[0]
-            rows = min(self._ep_t, T)
-            order = [(self._ep_t - rows + k) % T for k in range(rows)]               # oldest step first
-            x = log[order].reshape(-1, 2)
-            fin = x[~torch.isnan(x[:, 0])]
-            if fin.shape[0] > 100:
-                fin = fin[-100:]
-            for r, l in fin.cpu().tolist():
-                self.ep_info_buffer.append((r, l))
-            log.fill_(float("nan"))
-            self._ep_t = 0
-        buf = self.ep_info_buffer
-        if not buf:
-            return {}
-        return {"rollout/ep_rew_mean": float(sum(r for r, _ in buf) / len(buf)), "rollout/ep_len_mean": float(sum(l for _, l in buf) / len(buf))}
+        un-normalised returns; /root/reference/src/main_baoding.py runs under SB3's logger)."""
+        return self._episodes.stats()
 
-    def finish_rollout(self) -> None:
-        if hasattr(self.env, "end_rollout"):
-            self.env.end_rollout()
-        with torch.no_grad(), self._autocast():
-            if self._native and not self.policy.recurrent:
-                # timeout bootstrap for the whole rollout at once: r += gamma V(terminal_obs) where truncated
-                T, N = self.trunc_buf.shape
-                tv = self.policy.predict_values(self.term_buf.view(T * N, -1)).view(T, N)
-                self.rew_buf.add_(self.cfg.gamma * tv * self.trunc_buf)
-            elif self._native:
-                # same with the critic's LSTM state after each step, episode_start False (sb3-contrib [3P-RECALL]); time limits are
-                # rare events (one step in max_episode_steps), so the pass is skipped when the rollout has none (one host sync)
-                self._state_s = self._native_state()
-                if bool(self.trunc_buf.any()):
-                    T, N = self.trunc_buf.shape
-                    H = self.policy.hidden
-                    st = (None, None, self.crit_h_buf.view(1, T * N, H).float(), self.crit_c_buf.view(1, T * N, H).float())
-                    tv = self.policy.predict_values(self.term_buf.view(T * N, -1), st, None).view(T, N)
-                    self.rew_buf.add_(self.cfg.gamma * tv * self.trunc_buf)
-            if self.policy.recurrent:
-                self._last_values = self.policy.predict_values(self._obs_s, self._state_s, self._starts_s)
-                self._state = self._state_s
-            else:
-                self._last_values = self.policy.predict_values(self._obs_s)
-        self._last_obs, self._last_starts = self._obs_s, self._starts_s
-
-    def _reset_sde_noise(self) -> None:
-        """gSDE: new exploration matrices for the rollout.  On the HIP-kernel rollout they are drawn INTO self._sde_W, the buffer whose
-        address the captured graph holds; whatever policy.act did to policy.exploration_mat in between (an evaluation on another batch
-        size) cannot move it."""
-        pol = self.policy
-        gen = self.gen if self.gen.device == pol.log_std.device else None
-        W = self._sde_W
-        if W is not None and W.shape[1:] == tuple(pol.log_std.shape):
-            pol.reset_noise(W.shape[0], gen, out=W)
-        else:
-            pol.reset_noise(self.env.num_envs, gen)
-
-    # ---------------------------------------------------------------- rollout
-    @torch.no_grad()
-    def collect_rollouts(self) -> None:
-        cfg, env, pol = self.cfg, self.env, self.policy
-        if getattr(pol, "use_sde", False):          # SB3: policy.reset_noise(env.num_envs) at the start of a rollout
-            self._reset_sde_noise()
-        if self._graphed_rollout():
-            if self._fused is not None:
-                self._fused.refresh_shadow()        # rollout inference runs on the bf16 shadow weights
-            if self._fused_rec is not None:
-                self._fused_rec.refresh_shadow()
-                if self._native:
-                    self._refresh_rollout_lstm()
-            for _ in range(cfg.n_steps):
-                self.rollout_step()
-            self.finish_rollout()
-            self.num_timesteps += cfg.n_steps * env.num_envs * self.world
-            return
-        if self._last_obs is None:
-            self._last_obs = env.reset_tensor().clone()
-        if pol.recurrent:
-            self._rollout_state0 = tuple(s.clone() for s in self._state)
-            if cfg.seq_len is not None and self._snap_state is None:
-                self._new_snapshots(self._state)
-        if hasattr(env, "begin_rollout"):
-            env.begin_rollout()
-        for t in range(cfg.n_steps):
-            obs, starts = self._last_obs, self._last_starts
-            if cfg.seq_len is not None and t % cfg.seq_len == 0:      # the state entering a chunk's first step
-                for dst, src in zip(self._snap_state, self._state):
-                    dst[t // cfg.seq_len].copy_(src)
-            with self._autocast():
-                actions, values, logp, new_state = pol.act(obs, self._state, starts)
-            clipped = torch.clamp(actions, -1.0, 1.0)
-            nobs, rew, done, trunc, term, comps, ep = env.step_tensor(clipped)
-            self._log_episodes(done, ep)
-            rew = rew.clone()
-            if bool(trunc.any()):   # timeout bootstrap: terminal observation, critic state after this step, no episode start
-                with self._autocast():
-                    tv = pol.predict_values(term, new_state, None)
-                rew = rew + cfg.gamma * tv * trunc.to(rew.dtype)
-            self.obs_buf[t], self.act_buf[t], self.rew_buf[t] = obs, actions, rew
-            self.val_buf[t], self.logp_buf[t], self.start_buf[t] = values, logp, starts
-            self._state = new_state
-            self._last_obs = nobs.clone()
-            self._last_starts = done.to(torch.float32)
-        self.num_timesteps += cfg.n_steps * env.num_envs * self.world
-        if hasattr(env, "end_rollout"):
-            env.end_rollout()
-        with self._autocast():
-            self._last_values = pol.predict_values(self._last_obs, self._state, self._last_starts)
+    # (read-only views of the collector for the benchmark: policy input / episode starts of the next step, and the host time of the
+    # rank-synchronised normaliser's all-reduce)
+    ep_info_buffer = property(lambda self: self._episodes.buffer)
+    _obs_s = property(lambda self: self._rollout.obs)
+    _starts_s = property(lambda self: self._rollout.starts)
+    vn_allreduce_seconds = property(lambda self: self._rollout.vn_allreduce_seconds if self._rollout is not None else 0.0)
+    vn_allreduce_calls = property(lambda self: self._rollout.vn_allreduce_calls if self._rollout is not None else 0)
 
     # ---------------------------------------------------------------- update
     def _allreduce_grads(self) -> None:
@@ -1151,15 +726,18 @@ class PPO:
         if self._fused_rec is not None and L is None:           # stacked (actor, critic) LSTM state of the rollout start
             self._rg["h0"], self._rg["c0"] = torch.zeros((2, N, H), device=d), torch.zeros((2, N, H), device=d)
         elif self._fused_rec is not None:
-            # stacked snapshots, bf16 h / float32 c [S, 2, N, H]: the HIP-kernel rollout's own buffers (written in place, read by address),
-            # else static copies that _rec_stage fills
-            self._rg["h_snap"], self._rg["c_snap"] = (self._snap_h, self._snap_c) if self._snap_h is not None else \
+            # stacked snapshots, bf16 h / float32 c [S, 2, N, H]: the collector's own storage where it keeps them so (written in
+            # place, read by address), else static copies that _rec_stage fills
+            self._rg["h_snap"], self._rg["c_snap"] = self._stacked_snapshots() or \
                 (torch.zeros((T // L, 2, N, H), device=d, dtype=torch.bfloat16), torch.zeros((T // L, 2, N, H), device=d))
         self._rgraph_L = L
         # (BPTT over n_steps is one graph per minibatch already: no all-reduce inside the graph and no epoch-chunk graph here)
         self._rgraph_fb, self._rgraph_ap, _, _ = self._capture_step(self._rec_forward_backward, self._rg, graph_allreduce=False,
                                                                     epoch_steps=0)
         self._rgraph = (T, N, m, L)
+
+    def _stacked_snapshots(self):
+        return self._rollout.stacked_snapshots() if self._rollout is not None else None
 
     def _rec_stage(self, adv, ret, T, N, m, L=None):
         """Graphs for this shape (built on first use) and the update's inputs copied into their static tensors.  L: m chunks of L steps
@@ -1185,7 +763,7 @@ class PPO:
             hp, cp, hv, cv = state
             if L is None:
                 g["h0"][0].copy_(hp[0]); g["h0"][1].copy_(hv[0]); g["c0"][0].copy_(cp[0]); g["c0"][1].copy_(cv[0])
-            elif g["h_snap"] is not self._snap_h:
+            elif self._stacked_snapshots() is None:
                 g["h_snap"][:, 0:1].copy_(hp); g["h_snap"][:, 1:2].copy_(hv); g["c_snap"][:, 0:1].copy_(cp); g["c_snap"][:, 1:2].copy_(cv)
             if not cfg.normalize_advantage:
                 fr.stats.copy_(torch.tensor([0.0, 1.0], device=self.device))

@@ -633,7 +633,7 @@ def _graph_dp_worker(rank, world, port, out):
     out[rank] = torch.cat([p.detach().reshape(-1) for p in pol.parameters()]).cpu().numpy()
     out[10 + rank] = float(algo.rew_buf.sum())
     out[20 + rank] = (venv.obs_rms.mean.cpu().numpy(), venv.obs_rms.var.cpu().numpy(), float(venv.obs_rms.count), float(venv.ret_rms.var))
-    out[30 + rank] = (bool(algo._vn_sync), bool(algo._fused.external_adv_stats))
+    out[30 + rank] = (bool(algo._rollout.vn_sync), bool(algo._fused.external_adv_stats))
     dist.destroy_process_group()
 
 
@@ -753,7 +753,7 @@ def _graph_dp_worker_recurrent(rank, world, port, out):
     torch.cuda.synchronize()
     out[rank] = torch.cat([p.detach().reshape(-1) for p in pol.parameters()]).cpu().numpy()
     out[10 + rank] = float(algo.rew_buf.sum())
-    out[30 + rank] = (bool(getattr(algo, "_native", False)), bool(algo._vn_sync), bool(algo._fused_rec.external_adv_stats), int(algo.n_updates))
+    out[30 + rank] = (type(algo._rollout).__name__ == "KernelRollout", bool(algo._rollout.vn_sync), bool(algo._fused_rec.external_adv_stats), int(algo.n_updates))
     dist.destroy_process_group()
 
 
@@ -1239,7 +1239,7 @@ def test_native_rollout_bookkeeping(hip_lib):
         env = EnvironmentFactory.create("CustomMyoBaodingBallsP1", num_envs=256, seed=11, max_episode_steps=5)
         pol = ActorCriticPolicy(86, 39, (256, 256), (256, 256), lstm_hidden_size=None)
         algo = PPO(VecNormalize(env), pol, PPOConfig(n_steps=12, batch_size=1024, n_epochs=1), seed=0)
-        assert algo._native_rollout()
+        assert type(algo._collector()).__name__ == "KernelRollout"
         for _ in range(12):
             algo.rollout_step()
         torch.cuda.synchronize()
@@ -1248,8 +1248,8 @@ def test_native_rollout_bookkeeping(hip_lib):
         torch.cuda.synchronize()
         return algo, before
     algo, before = run()
-    T, N = algo.trunc_buf.shape
-    tr = algo.trunc_buf
+    T, N = algo._rollout.trunc_buf.shape
+    tr = algo._rollout.trunc_buf
     assert float(tr.sum()) > 0 and set(tr.unique().tolist()) <= {0.0, 1.0}
     # the rollout starts exactly at the reset (the graph-capture warm-up does not step the env): every env starts
     # an episode in row 0, and a 5-step TimeLimit truncates at rows 4 and 9 for every env that never dropped a ball
@@ -1262,7 +1262,7 @@ def test_native_rollout_bookkeeping(hip_lib):
     assert torch.equal(tr[:, clean], want_tr[:, None].expand(T, int(clean.sum())))
     assert float(algo.env.obs_rms.count) == pytest.approx(1e-4 + 13 * N)        # reset + 12 steps, no warm-up residue
     with torch.no_grad(), algo._autocast():
-        tv = algo.policy.predict_values(algo.term_buf.view(T * N, -1)).view(T, N)
+        tv = algo.policy.predict_values(algo._rollout.term_buf.view(T * N, -1)).view(T, N)
     want = before + algo.cfg.gamma * tv * tr
     assert float((algo.rew_buf - want).abs().max()) < 1e-5
     assert torch.equal((algo.rew_buf != before), (tr * tv != 0))
@@ -1297,7 +1297,7 @@ def test_fused_rollout_policy_matches_gemm_path(hip_lib, monkeypatch):
         env = EnvironmentFactory.create("CustomMyoBaodingBallsP1", num_envs=512, seed=11)
         pol = ActorCriticPolicy(86, 39, (256, 256), (256, 256), lstm_hidden_size=None)
         algo = PPO(VecNormalize(env), pol, PPOConfig(n_steps=4, batch_size=1024, n_epochs=1), seed=0)
-        assert algo._native_rollout()
+        assert type(algo._collector()).__name__ == "KernelRollout"
         algo.rollout_step()
         torch.cuda.synchronize()
         return algo
@@ -1767,7 +1767,7 @@ def test_gsde_ppo_round_on_gpu(hip_lib):
     env = VecNormalize(EnvironmentFactory.create("CustomMyoBaodingBallsP1", num_envs=64, seed=3))
     pol = ActorCriticPolicy(86, 39, (64, 64), (64, 64), lstm_hidden_size=None, use_sde=True)
     algo = PPO(env, pol, PPOConfig(n_steps=8, batch_size=128, n_epochs=2))
-    assert algo._fused is not None and algo._fused.merged is not None and algo._native_rollout()     # fused update, HIP-kernel rollout
+    assert algo._fused is not None and algo._fused.merged is not None and type(algo._collector()).__name__ == "KernelRollout"     # fused update, HIP-kernel rollout
     before = torch.cat([p.detach().reshape(-1) for p in pol.parameters()]).clone()
     for _ in range(2):
         algo.collect_rollouts()
@@ -1797,21 +1797,21 @@ def test_gsde_ppo_round_on_gpu(hip_lib):
     assert float((lp - lp2).abs().max()) <= 2e-3 * float(lp2.abs().max())
     assert float((a - mean.float() - noise).abs().max()) <= 1e-4
     # an evaluation on ANOTHER batch size between two rollouts (tools/train_demo.py does that) must not move the
-    # exploration matrices the captured rollout graph reads by address — they live in PPO's own buffer, policy.act uses a temporary
-    ptr = algo._sde_W.data_ptr()
+    # exploration matrices the captured rollout graph reads by address — they live in the collector's own buffer, policy.act uses a temporary
+    ptr = algo._rollout.sde_W.data_ptr()
     assert pol.exploration_mat.data_ptr() == ptr
     obs2 = torch.randn(16, 86, device=pol.log_std.device)
     a_det, _, _, _ = pol.act(obs2, deterministic=True)
     a_sto, _, _, _ = pol.act(obs2)
     assert torch.isfinite(a_det).all() and torch.isfinite(a_sto).all() and not torch.equal(a_det, a_sto)
     assert pol.exploration_mat.data_ptr() == ptr and pol.exploration_mat.shape[0] == 64
-    w_before = algo._sde_W.clone()
+    w_before = algo._rollout.sde_W.clone()
     algo.collect_rollouts()
-    assert algo._sde_W.data_ptr() == ptr and pol.exploration_mat.data_ptr() == ptr and not torch.equal(w_before, algo._sde_W)      # redrawn in place
+    assert algo._rollout.sde_W.data_ptr() == ptr and pol.exploration_mat.data_ptr() == ptr and not torch.equal(w_before, algo._rollout.sde_W)      # redrawn in place
     with torch.no_grad():
         lat = pol._latents(algo.obs_buf[5], None, None)[0]
         mean = pol._dist(lat)[0]
-        noise = torch.bmm(lat.float().unsqueeze(1), algo._sde_W).squeeze(1)
+        noise = torch.bmm(lat.float().unsqueeze(1), algo._rollout.sde_W).squeeze(1)
     assert float((algo.act_buf[5] - mean.float() - noise).abs().max()) <= 2e-2 * (1 + float(algo.act_buf[5].abs().max()))
 
 

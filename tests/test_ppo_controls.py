@@ -190,14 +190,32 @@ def test_init_sets_every_attribute(emu_lib, hidden):
     start (None / False / 0), and a rollout, an update and episode_stats() add no attribute."""
     env, algo = _cpu_algo(emu_lib, hidden)
     at_init = set(vars(algo))
-    late = {"_native", "_rollout_ready", "_gB2", "_sde_W", "vn_allreduce_seconds", "vn_allreduce_calls", "_ep_log", "_ep_nan_t",
-            "ep_info_buffer", "_graph", "_gs", "_graph_fb", "_graph_ap", "_graph_epoch", "_rgraph", "_rg", "_rgraph_fb", "_rgraph_ap",
+    late = {"_rollout", "_episodes", "_graph", "_gs", "_graph_fb", "_graph_ap", "_graph_epoch", "_rgraph", "_rg", "_rgraph_fb", "_rgraph_ap",
             "_allreduce_in_graph", "_last_values", "_early_stopped", "_last_diag", "_fused", "_fused_rec", "_flat_adam", "_hp"}
     assert late <= at_init, sorted(late - at_init)
-    assert algo._native is False and algo._rollout_ready is False and algo._graph_epoch is None and algo._rgraph is None
+    assert algo._rollout is None and algo._graph_epoch is None and algo._rgraph is None
     assert algo.vn_allreduce_seconds == 0.0 and algo.vn_allreduce_calls == 0
     algo.collect_rollouts(); algo.train(); algo.episode_stats()
     assert set(vars(algo)) == at_init, sorted(set(vars(algo)) - at_init)
+    env.close()
+
+
+def test_collector_is_freed_by_reference_counting(emu_lib):
+    """A rollout collector sits in no reference cycle: it dies with its PPO, at once.  torch.cuda.graph no longer runs the cycle
+    collector before a capture, so a dead collector that waited for it would have its graphs and static tensors destroyed wherever
+    the cycle collector next runs — inside another collector's capture, for one, which aborts the process."""
+    import gc
+    import weakref
+    env, algo = _cpu_algo(emu_lib, 8)
+    gc.collect()
+    gc.disable()
+    try:
+        algo.collect_rollouts(); algo.train(); algo.collect_rollouts()
+        refs = [weakref.ref(algo._rollout), weakref.ref(algo.rew_buf)]
+        del algo
+        assert all(r() is None for r in refs)
+    finally:
+        gc.enable()
     env.close()
 
 

@@ -4,6 +4,7 @@ env and the eager path; GPU tests of the two HIP entry points (myo_ppo_gather_se
 step against autograd and of the captured update."""
 import copy
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -240,18 +241,18 @@ def test_native_rollout_stores_the_chunk_states(hip_lib):
     mkpol = lambda: ActorCriticPolicy(env.obs_dim, env.act_dim, (64, 64), (64, 64), lstm_hidden_size=32)
     plain = PPO(VecNormalize(env), mkpol(), PPOConfig(n_steps=T, batch_size=T * N, n_epochs=1))
     plain.rollout_step()
-    assert plain._native and plain._snap_h is None and plain._snap_c is None and plain.rollout_snapshots() is None
+    assert type(plain._rollout).__name__ == "KernelRollout" and plain._rollout.snap_h is None and plain._rollout.snap_c is None and plain.rollout_snapshots() is None
     algo = PPO(VecNormalize(env), mkpol(), PPOConfig(n_steps=T, batch_size=T * N, n_epochs=1, seq_len=L))
     algo.collect_rollouts()
-    assert algo._native and tuple(algo._snap_h.shape) == (3, 2, N, 32) and algo._snap_h.dtype == torch.bfloat16
-    assert tuple(algo._snap_c.shape) == (3, 2, N, 32) and algo._snap_c.dtype == torch.float32
-    algo._fused_rec.refresh_shadow(); algo._refresh_rollout_lstm()
+    assert type(algo._rollout).__name__ == "KernelRollout" and tuple(algo._rollout.snap_h.shape) == (3, 2, N, 32) and algo._rollout.snap_h.dtype == torch.bfloat16
+    assert tuple(algo._rollout.snap_c.shape) == (3, 2, N, 32) and algo._rollout.snap_c.dtype == torch.float32
+    algo._rollout.begin()
     hs, cs = [], []
     for t in range(T):
         if t % L == 0:
-            hs.append(algo._hs.clone()); cs.append(algo._cs32.clone())
+            hs.append(algo._rollout.hs.clone()); cs.append(algo._rollout.cs32.clone())
         algo.rollout_step()
-    snap_h, snap_c = algo._snap_h.clone(), algo._snap_c.clone()
+    snap_h, snap_c = algo._rollout.snap_h.clone(), algo._rollout.snap_c.clone()
     state0 = algo._rollout_state0
     algo.finish_rollout()
     torch.cuda.synchronize()
@@ -284,8 +285,9 @@ def _twin_chunk_algos(monkeypatch, arch, hidden, **cfg):
     for name in BUFFERS:
         getattr(b, name).copy_(getattr(a, name))
     b._rollout_state0 = tuple(x.clone() for x in a._rollout_state0)
-    b._snap_state = tuple(x.clone() for x in a.rollout_snapshots())
-    assert a._native and all(float(x.abs().max()) > 0 for x in b._snap_state)
+    snaps = tuple(x.clone() for x in a.rollout_snapshots())
+    b._rollout = SimpleNamespace(snapshots=lambda: snaps, stacked_snapshots=lambda: None)     # b never rolls out: a stand-in collector that hands out the planted snapshots
+    assert type(a._rollout).__name__ == "KernelRollout" and all(float(x.abs().max()) > 0 for x in b.rollout_snapshots())
     return env, a, b, (N, T, L, m)
 
 

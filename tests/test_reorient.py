@@ -332,7 +332,7 @@ def test_reorient_ppo_mlp_graph_path_on_gpu(hip_lib):
     env = EnvironmentFactory.create("CustomMyoReorientP1", num_envs=512, seed=3)
     pol = ActorCriticPolicy(env.obs_dim, env.act_dim, (256, 256), (256, 256), lstm_hidden_size=None)
     algo = PPO(VecNormalize(env), pol, PPOConfig(n_steps=16, batch_size=2048, n_epochs=2))
-    assert algo._native_rollout()
+    assert type(algo._collector()).__name__ == "KernelRollout"
     algo.learn(2 * 16 * 512)
     assert algo.num_timesteps == 16384 and all(torch.isfinite(p).all() for p in pol.parameters())
     assert float(algo.env.obs_rms.count) > 16000 and torch.isfinite(algo.rew_buf).all()
@@ -435,7 +435,7 @@ def test_fused_recurrent_step_matches_autograd(hip_lib, monkeypatch, arch, hidde
 @pytest.mark.gpu
 @pytest.mark.parametrize("sde", [False, True], ids=["gaussian", "gsde"])
 def test_native_recurrent_rollout_matches_policy(hip_lib, sde):
-    """The HIP-kernel rollout step of a recurrent policy (PPO._init_native_rollout: LSTM cell kernel, stacked trunks, sampling
+    """The HIP-kernel rollout step of a recurrent policy (rl/rollout.py KernelRollout: LSTM cell kernel, stacked trunks, sampling
     kernel, state carried in bf16) records what the policy itself computes: re-evaluating the stored sequences with
     ``evaluate_actions`` from the stored start state reproduces the stored values and log-probabilities, across episode starts,
     and the carried state equals the state evaluate_actions ends in."""
@@ -451,8 +451,8 @@ def test_native_recurrent_rollout_matches_policy(hip_lib, sde):
     assert algo._fused_rec is not None
     for r in range(2):
         algo.collect_rollouts()
-        assert getattr(algo, "_native", False)
-        assert float(algo.start_buf.sum()) > 0 and float(algo.trunc_buf.sum()) > 0
+        assert type(algo._rollout).__name__ == "KernelRollout"
+        assert float(algo.start_buf.sum()) > 0 and float(algo._rollout.trunc_buf.sum()) > 0
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
             lp_, lv_, st = pol._latents(algo.obs_buf, algo._rollout_state0, algo.start_buf)
             v, lp, _ = pol.evaluate_actions(algo.obs_buf, algo.act_buf, algo._rollout_state0, algo.start_buf)
@@ -464,21 +464,21 @@ def test_native_recurrent_rollout_matches_policy(hip_lib, sde):
         assert torch.isfinite(algo.rew_buf).all()
     # timeout bootstrap (sb3-contrib collect_rollouts [3P-RECALL]): r += gamma V(terminal_obs; critic LSTM state AFTER the step,
     # episode_start False) where the time limit ended the episode — step the same rollout by hand and take finish_rollout apart
-    algo._fused_rec.refresh_shadow(); algo._refresh_rollout_lstm()
+    algo._rollout.begin()
     hv, cv = [], []
     for t in range(T):
         algo.rollout_step()
-        hv.append(algo._hs[1].float().clone()); cv.append(algo._cs[1].float().clone())
+        hv.append(algo._rollout.hs[1].float().clone()); cv.append(algo._rollout.cs[1].float().clone())
     before = algo.rew_buf.clone()
     algo.finish_rollout()
-    trunc = algo.trunc_buf
+    trunc = algo._rollout.trunc_buf
     assert float(trunc.sum()) > 0
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
-        tv = torch.stack([pol.predict_values(algo.term_buf[t], (None, None, hv[t].unsqueeze(0), cv[t].unsqueeze(0)), None) for t in range(T)])
+        tv = torch.stack([pol.predict_values(algo._rollout.term_buf[t], (None, None, hv[t].unsqueeze(0), cv[t].unsqueeze(0)), None) for t in range(T)])
     want = before + algo.cfg.gamma * tv * trunc
     assert float((algo.rew_buf - want).abs().max()) < 2e-2 * (1 + float(want.abs().max()))
     assert float((algo.rew_buf - before).abs().max()) > 0 and torch.equal((algo.rew_buf != before) & (trunc == 0), torch.zeros_like(trunc, dtype=torch.bool))
-    assert torch.equal(algo.crit_h_buf.float(), torch.stack(hv)) and torch.equal(algo.crit_c_buf.float(), torch.stack(cv))
+    assert torch.equal(algo._rollout.crit_h_buf.float(), torch.stack(hv)) and torch.equal(algo._rollout.crit_c_buf.float(), torch.stack(cv))
 
 
 @pytest.mark.gpu
@@ -590,7 +590,7 @@ def test_scratch_sizes_keep_their_workgroups_per_cu(hip_lib):
 def test_rollout_carries_the_cell_state_in_float32_over_300_step_episodes(hip_lib):
     """VERDICT r05 item 3.  The reference trains and evaluates a stock float32 `MlpLstmPolicy` (/root/reference/src/main_reorient.py:53-71,
     src/metrics/custom_callbacks.py:19-47: the evaluation carries the state the rollout trained on).  Here the HIP-kernel rollout keeps h in
-    bf16 (the matrix cores' operand) and carries the CELL state in float32 (rl/ppo.py: _cs32): playing config E's policy shape through
+    bf16 (the matrix cores' operand) and carries the CELL state in float32 (rl/rollout.py: cs32): playing config E's policy shape through
     300-step episodes, the actions the rollout recorded must be the actions `policy.predict` gives on the same observations when IT carries
     a float32 state from the rollout's start state — at every step, and without growing along the episode (a cell state through bf16
     puts 2^-9 of itself back in at every step)."""
@@ -605,7 +605,7 @@ def test_rollout_carries_the_cell_state_in_float32_over_300_step_episodes(hip_li
     algo = PPO(VecNormalize(env), pol, PPOConfig(n_steps=T, batch_size=T * N // 4, n_epochs=1))
     assert algo._fused_rec is not None and algo._fused_rec.step_kernels
     algo.collect_rollouts()
-    assert getattr(algo, "_native", False) and algo._cs32.dtype == torch.float32
+    assert type(algo._rollout).__name__ == "KernelRollout" and algo._rollout.cs32.dtype == torch.float32
     starts = algo.start_buf
     longest = int((starts[1:].sum(0) == 0).sum())            # envs whose first episode fills the whole rollout
     assert longest >= N // 2, longest
@@ -619,5 +619,5 @@ def test_rollout_carries_the_cell_state_in_float32_over_300_step_episodes(hip_li
     assert float(err.max()) <= 1e-3, (float(err.max()), first, last)
     assert last <= 2.0 * first + 1e-4, (first, last)          # no drift along the episode
     # the state the rollout ends in is the state predict ends in (c in float32 on both sides; h through bf16 in the rollout)
-    for mine, theirs in zip(algo._native_state(), state):
+    for mine, theirs in zip(algo._state, state):
         assert float((mine - theirs).abs().max()) <= 2e-2 * (1 + float(theirs.abs().max()))

@@ -677,7 +677,7 @@ def test_ppo_rolls_out_trains_and_saves_a_tanh_policy(hip_lib, tmp_path):
     algo, pol = _ppo(torch.nn.Tanh)
     assert algo._fused is not None and algo._fused.act == ACT_TANH
     algo.collect_rollouts()
-    assert getattr(algo, "_native", False) and getattr(algo._fused, "_rollout", None) is not None, "the rollout did not take the fused kernel"
+    assert type(algo._rollout).__name__ == "KernelRollout" and getattr(algo._fused, "_rollout", None) is not None, "the rollout did not take the fused kernel"
     params = R.policy_params(pol)
     T, N, O = algo.obs_buf.shape
     A = algo.act_buf.shape[2]
