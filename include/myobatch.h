@@ -340,6 +340,50 @@ typedef struct myo_data_out {
 } myo_data_out;
 int myo_batch_data(myo_batch* b, const double* ctrl, const myo_data_out* out, void* stream);
 
+/* ---- per-env Jacobians (MuJoCo's mj_jacBody / mj_jacBodyCom / mj_jacSite / mj_jacGeom / mj_jacSubtreeCom / mj_jac) at the envs' PRESENT
+ * states: what task-space rewards, operational-space analysis and the mapping of contact forces to joints are made of.  One wave per
+ * env runs the position stage alone and writes, for each of the k objects obj_ids[0 .. k) (dev int32, any order, repeats allowed), the
+ * dense 3 x nv blocks
+ *   jacp [N, k, 3, nv]   jacp[e, o] . qvel = world-frame linear velocity of the object's point
+ *   jacr [N, k, 3, nv]   jacr[e, o] . qvel = world-frame angular velocity of the object's body
+ * in MuJoCo's conventions: a free joint's three rotational dofs are in the body's local frame, as in qvel; columns of dofs that do not
+ * move the object's body are written as 0.0.  EVERY element of a non-NULL output is written: the caller does not pre-zero.  The point
+ * is the one myo_batch_data reports for the object, with the env's own geometry:
+ *   MYO_JAC_BODY        xpos          (points != NULL: the world point points[e, o], rigidly attached to body obj_ids[o] — mj_jac)
+ *   MYO_JAC_BODYCOM     xipos
+ *   MYO_JAC_SITE        site_xpos     (the Baoding target sites where the task puts them)
+ *   MYO_JAC_GEOM        geom_xpos     (the die's size delta moves its geoms)
+ *   MYO_JAC_SUBTREECOM  subtree_com   (jacp only: the mass-weighted sum over the body's subtree, with the env's own ball masses)
+ * An object on a body with no dof above it — the world body, the die's `target` goal body — has all-zero blocks.  points: dev
+ * double[N, k, 3] or NULL.  The ids live on the device, so the host checks what it can — an unknown objtype, k < 0, a NULL obj_ids
+ * with k > 0, points with another type than MYO_JAC_BODY, a jacr with MYO_JAC_SUBTREECOM: MYO_E_ARG — and an id outside the model
+ * gets all-zero blocks (as an env index outside the batch does in myo_batch_tendon_paths).  A NULL batch / struct or another `size`
+ * returns MYO_E_BADARG (= MYO_E_ARG); all before any device call.  Both outputs NULL, or k = 0, launches nothing.  Read-only exactly
+ * as myo_batch_sense is. */
+enum { MYO_JAC_BODY = 0, MYO_JAC_BODYCOM, MYO_JAC_SITE, MYO_JAC_GEOM, MYO_JAC_SUBTREECOM };
+typedef struct myo_jac_out {
+  size_t size;
+  double *jacp, *jacr;
+} myo_jac_out;
+int myo_batch_jac(myo_batch* b, int objtype, const int32_t* obj_ids, int k, const double* points, const myo_jac_out* out, void* stream);
+
+/* ---- per-env inverse dynamics (MuJoCo's mj_inverse) at the envs' PRESENT states (qpos, qvel, act, the env's own ball and die
+ * parameters): the generalised force that produces the acceleration qacc (dev double[N, nv], required), constraints included —
+ * torque and muscle-load estimation, and the forward / inverse consistency check.  One wave per env runs the position, inertia and
+ * velocity stages, builds the constraint set of a substep (limits, friction-loss rows, the collision passes) and its reference
+ * accelerations, then jar = J qacc - aref and ONE constraint update:
+ *   qfrc_constraint [N, nv]   J' efc_force at that jar
+ *   qfrc_inverse    [N, nv]   M qacc + qfrc_bias - qfrc_passive - qfrc_constraint
+ * No Newton solve, no actuation stage, no ctrl: with qacc = myo_batch_data's qacc, qfrc_inverse is its qfrc_actuator up to the
+ * forward solver's residual.  Read-only exactly as myo_batch_sense is; a pass that has to drop contacts beyond the capacity counts it
+ * in myo_batch_health like a substep.  A NULL batch / struct / qacc or another `size` returns MYO_E_BADARG (= MYO_E_ARG) before any
+ * device call; a struct whose pointers are both NULL launches nothing. */
+typedef struct myo_inverse_out {
+  size_t size;
+  double *qfrc_inverse, *qfrc_constraint;
+} myo_inverse_out;
+int myo_batch_inverse(myo_batch* b, const double* qacc, const myo_inverse_out* out, void* stream);
+
 /* ---- rendering of env states (MuJoCo's mjr_render / mjr_readPixels seam: CustomPenEnv.render -> self.sim.render,
  * /root/reference/src/main_eval.py:96-97).  Draws what the stepper holds: every geom at the pose of the env's present state
  * and with the env's own geometry (Baoding P2 ball radius, die size delta), the Baoding target sites where the task puts

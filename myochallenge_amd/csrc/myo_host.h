@@ -29,6 +29,7 @@
 #include "myo_task.h"
 #include "myo_sense.h"
 #include "myo_data.h"
+#include "myo_jac.h"
 #include "myo_render.h"
 
 
@@ -1761,6 +1762,29 @@ extern "C" int myo_batch_data(myo_batch* b, const double* ctrl, const myo_data_o
   if (d.qacc) d.stage = MYO_DATA_CONSTRAINED;
   if (d.stage < 0) return MYO_OK;
   return be_run(b, DataJob{d}, b->n, stream);
+}
+// myo_batch_jac / myo_batch_inverse (csrc/myo_jac.h): JacJob / InverseJob are rows of the variant table like SenseJob / DataJob, keyed
+// without the integrator.  The per-body ancestor-dof masks env_jac selects columns by are the model's body_dofmask (built with the
+// other derived tables above, uploaded with the model).  The object ids live on the device: an id outside the model gets zero blocks.
+static_assert((int)MYO_JAC_BODY == (int)MYO_JAC_K_BODY && (int)MYO_JAC_BODYCOM == (int)MYO_JAC_K_BODYCOM && (int)MYO_JAC_SITE == (int)MYO_JAC_K_SITE &&
+              (int)MYO_JAC_GEOM == (int)MYO_JAC_K_GEOM && (int)MYO_JAC_SUBTREECOM == (int)MYO_JAC_K_SUBTREECOM, "object types of include/myobatch.h and csrc/myo_jac.h");
+extern "C" int myo_batch_jac(myo_batch* b, int objtype, const int32_t* obj_ids, int k, const double* points, const myo_jac_out* out, void* stream) {
+  if (!b || !out) return fail(MYO_E_BADARG, "myo_batch_jac: null batch or output struct");
+  if (out->size != sizeof(myo_jac_out)) return fail(MYO_E_BADARG, "myo_batch_jac: myo_jac_out.size is %zu, this library's struct has %zu bytes", out->size, sizeof(myo_jac_out));
+  if (objtype < MYO_JAC_BODY || objtype > MYO_JAC_SUBTREECOM) return fail(MYO_E_ARG, "myo_batch_jac: unknown object type %d", objtype);
+  if (k < 0 || (k > 0 && !obj_ids)) return fail(MYO_E_ARG, "myo_batch_jac: k must be >= 0 and obj_ids non-null");
+  if (points && objtype != MYO_JAC_BODY) return fail(MYO_E_ARG, "myo_batch_jac: points go with MYO_JAC_BODY only");
+  if (objtype == MYO_JAC_SUBTREECOM && out->jacr) return fail(MYO_E_ARG, "myo_batch_jac: MYO_JAC_SUBTREECOM has no jacr");
+  if ((long long)k * 3 * b->nv > (1ll << 31) - 1) return fail(MYO_E_ARG, "myo_batch_jac: k * 3 * nv exceeds 2^31");
+  if ((!out->jacp && !out->jacr) || k == 0) return MYO_OK;
+  return be_run(b, JacJob{{objtype, k, obj_ids, points, out->jacp, out->jacr}}, b->n, stream);
+}
+extern "C" int myo_batch_inverse(myo_batch* b, const double* qacc, const myo_inverse_out* out, void* stream) {
+  if (!b || !out) return fail(MYO_E_BADARG, "myo_batch_inverse: null batch or output struct");
+  if (out->size != sizeof(myo_inverse_out)) return fail(MYO_E_BADARG, "myo_batch_inverse: myo_inverse_out.size is %zu, this library's struct has %zu bytes", out->size, sizeof(myo_inverse_out));
+  if (!qacc) return fail(MYO_E_BADARG, "myo_batch_inverse: qacc is required");
+  if (!out->qfrc_inverse && !out->qfrc_constraint) return MYO_OK;
+  return be_run(b, InverseJob{{qacc, out->qfrc_inverse, out->qfrc_constraint}}, b->n, stream);
 }
 extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
   if (int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses")) return rc;

@@ -398,6 +398,77 @@ class BaodingVecEnv:
             out = {k: v[idx] for k, v in out.items()}
         return out
 
+    # ---------------------------------------------------------------- Jacobians and inverse dynamics (include/myobatch.h myo_batch_jac, myo_batch_inverse)
+    def _jac_ids(self, kind, objects):
+        """int ids of `objects` (names or ids; None: every object of the kind) among the kind's objects"""
+        names = {"site": self.site_names(), "geom": self.geom_names}.get(kind, self.body_names)
+        count = self._model.size({"site": "nsite", "geom": "ngeom"}.get(kind, "nbody"))
+        if objects is None:
+            return list(range(count))
+        ids = []
+        for o in ([objects] if isinstance(objects, (str, int, np.integer)) else objects):
+            if isinstance(o, str):
+                if not o or o not in names:
+                    raise KeyError(f"unknown {kind} name {o!r}")
+                o = names.index(o)
+            if not 0 <= int(o) < count:
+                raise KeyError(f"{kind} id {int(o)} outside [0, {count})")
+            ids.append(int(o))
+        return ids
+
+    def jac(self, kind, objects=None, points=None, indices=None, jacr=True) -> dict:
+        """MuJoCo's ``mj_jacBody`` / ``mj_jacBodyCom`` / ``mj_jacSite`` / ``mj_jacGeom`` / ``mj_jacSubtreeCom`` / ``mj_jac`` for the
+        envs' PRESENT states: one position pass on the GPU, nothing about the envs changes.  Device tensors (float64), no host copy.
+
+        kind: ``"body"`` (point: ``xpos``), ``"bodycom"`` (``xipos``), ``"site"`` (``site_xpos``), ``"geom"`` (``geom_xpos``) or
+        ``"subtreecom"`` (``subtree_com``; ``jacp`` only).  objects: names or ids (``body_names`` / ``site_names()`` /
+        ``geom_names``; default: every object of the kind, in id order); they may repeat.  points: [N, k, 3] world points taken as
+        rigidly attached to the bodies (``"body"`` only).  Returns ``jacp`` [k_env, k, 3, nv] with ``jacp @ qvel`` the point's
+        world-frame linear velocity and — ``jacr=True``, not for ``"subtreecom"`` — ``jacr`` with ``jacr @ qvel`` the body's angular
+        velocity; columns of dofs that do not move the object are 0.  indices: the envs' rows to return (default: all; the pass
+        itself always runs the whole batch)."""
+        t = self.torch
+        if kind not in native.JAC_KINDS:
+            raise KeyError(f"unknown Jacobian kind {kind!r}; known: {sorted(native.JAC_KINDS)}")
+        ids = self._jac_ids(kind, objects)
+        n, k, nv = self.num_envs, len(ids), self._model.size("nv")
+        if points is not None:
+            if kind != "body":
+                raise ValueError("points go with kind 'body' only")
+            points = t.as_tensor(points, dtype=t.float64, device=self.device).contiguous()
+            if tuple(points.shape) != (n, k, 3):
+                raise ValueError(f"points must have shape {(n, k, 3)}")
+        ids_t = t.as_tensor(ids, dtype=t.int32, device=self.device)
+        out = {"jacp": t.empty((n, k, 3, nv), dtype=t.float64, device=self.device)}
+        if jacr and kind != "subtreecom":
+            out["jacr"] = t.empty((n, k, 3, nv), dtype=t.float64, device=self.device)
+        self.batch.jac(kind, ids_t, out["jacp"], out.get("jacr"), points, self._stream())
+        if self.device.type == "cuda":
+            t.cuda.synchronize(self.device)       # (ids and points may be temporaries: the pass must have read them)
+        if indices is not None:
+            idx = t.as_tensor([int(i) for i in indices], dtype=t.long, device=self.device)
+            out = {key: v[idx] for key, v in out.items()}
+        return out
+
+    def inverse(self, qacc, indices=None) -> dict:
+        """MuJoCo's ``mj_inverse`` for the envs' PRESENT states: ``qfrc_inverse`` [k_env, nv], the generalised force that produces
+        the acceleration ``qacc`` ([N, nv] tensor or array) with the state's constraints (limits, friction loss, contacts), and the
+        ``qfrc_constraint`` [k_env, nv] it was computed with.  One pass on the GPU without a constraint solve, nothing about the
+        envs changes; device tensors (float64), no host copy.  indices: the envs' rows to return (default: all)."""
+        t = self.torch
+        n, nv = self.num_envs, self._model.size("nv")
+        qacc = t.as_tensor(qacc, dtype=t.float64, device=self.device).contiguous()
+        if tuple(qacc.shape) != (n, nv):
+            raise ValueError(f"qacc must have shape {(n, nv)}")
+        out = {k: t.empty((n, nv), dtype=t.float64, device=self.device) for k in ("qfrc_inverse", "qfrc_constraint")}
+        self.batch.inverse(qacc, out["qfrc_inverse"], out["qfrc_constraint"], self._stream())
+        if self.device.type == "cuda":
+            t.cuda.synchronize(self.device)       # (qacc may be a temporary: the pass must have read it)
+        if indices is not None:
+            idx = t.as_tensor([int(i) for i in indices], dtype=t.long, device=self.device)
+            out = {k: v[idx] for k, v in out.items()}
+        return out
+
     def site_names(self) -> List[str]:
         """names of the model's sites: rows of ``data()``'s ``site_xpos``"""
         return list(self.compiled.names.get("site", []))

@@ -169,6 +169,20 @@ class DataOut(C.Structure):
 DATA_KEYS = tuple(f[0] for f in DataOut._fields_[1:])
 
 
+class JacOut(C.Structure):
+    """myo_jac_out of include/myobatch.h: caller-owned device arrays (doubles, [N, k, 3, nv]) of myo_batch_jac, either may be NULL."""
+    _fields_ = [("size", C.c_size_t), ("jacp", C.c_void_p), ("jacr", C.c_void_p)]
+
+
+class InverseOut(C.Structure):
+    """myo_inverse_out of include/myobatch.h: caller-owned device arrays (doubles, [N, nv]) of myo_batch_inverse, either may be NULL."""
+    _fields_ = [("size", C.c_size_t), ("qfrc_inverse", C.c_void_p), ("qfrc_constraint", C.c_void_p)]
+
+
+JAC_BODY, JAC_BODYCOM, JAC_SITE, JAC_GEOM, JAC_SUBTREECOM = range(5)      # MYO_JAC_* of include/myobatch.h
+JAC_KINDS = {"body": JAC_BODY, "bodycom": JAC_BODYCOM, "site": JAC_SITE, "geom": JAC_GEOM, "subtreecom": JAC_SUBTREECOM}
+
+
 class MyoError(RuntimeError):
     pass
 
@@ -230,6 +244,8 @@ class NativeLib:
         L.myo_batch_contact_capacity.argtypes = [vp]
         L.myo_batch_sense.argtypes = [vp, C.POINTER(SenseOut), vp]
         L.myo_batch_data.argtypes = [vp, vp, C.POINTER(DataOut), vp]
+        L.myo_batch_jac.argtypes = [vp, i32, vp, i32, vp, C.POINTER(JacOut), vp]
+        L.myo_batch_inverse.argtypes = [vp, vp, C.POINTER(InverseOut), vp]
         if b"MYO_EMU" in L.myo_version():
             return      # the emulation build (test tooling, csrc/emu_host.h) implements the env path only: ENV_PATH_SYMBOLS
         L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp, vp]
@@ -320,7 +336,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_ppo_gather_seq", "myo_rollout_state_snapshot", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
     "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_last_error", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
-    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data",
+    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
     "myo_ppo_mlp_step_resident", "myo_ppo_mlp_images", "myo_ppo_adv_moments_epoch",
@@ -339,7 +355,7 @@ ENV_PATH_SYMBOLS = [
     "myo_batch_step", "myo_batch_step_inner", "myo_batch_step_inner_idx", "myo_batch_tune_wrap_order", "myo_batch_warmstart", "myo_debug_wave_slots",
     "myo_last_error", "myo_model_destroy", "myo_model_from_blob", "myo_model_load_mjb", "myo_model_size", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
-    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data",
+    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
 ]
@@ -575,6 +591,25 @@ class Batch:
                 raise KeyError(k)
             setattr(out, k, _ptr(v))
         self.lib.check(self.lib.L.myo_batch_data(self.h, _ptr(ctrl), C.byref(out), stream))
+
+    def jac(self, kind, obj_ids, jacp=None, jacr=None, points=None, stream=None):
+        """Jacobians of the envs' present states (myo_batch_jac): kind = a key of JAC_KINDS (or its MYO_JAC_* code), obj_ids int32[k]
+        device array, jacp / jacr float64 [N, k, 3, nv] device arrays or None, points float64 [N, k, 3] world points or None ("body"
+        only: mj_jac).  Every element of a given output is written; "subtreecom" has no jacr."""
+        if isinstance(kind, str):
+            if kind not in JAC_KINDS:
+                raise KeyError(f"unknown Jacobian kind {kind!r}; known: {sorted(JAC_KINDS)}")
+            kind = JAC_KINDS[kind]
+        out = JacOut()
+        out.size, out.jacp, out.jacr = C.sizeof(JacOut), _ptr(jacp), _ptr(jacr)
+        self.lib.check(self.lib.L.myo_batch_jac(self.h, int(kind), _ptr(obj_ids), int(obj_ids.shape[0]), _ptr(points), C.byref(out), stream))
+
+    def inverse(self, qacc, qfrc_inverse=None, qfrc_constraint=None, stream=None):
+        """inverse dynamics of the envs' present states (myo_batch_inverse): qacc float64 [N, nv] -> qfrc_inverse / qfrc_constraint
+        float64 [N, nv] device arrays (either may be None)"""
+        out = InverseOut()
+        out.size, out.qfrc_inverse, out.qfrc_constraint = C.sizeof(InverseOut), _ptr(qfrc_inverse), _ptr(qfrc_constraint)
+        self.lib.check(self.lib.L.myo_batch_inverse(self.h, _ptr(qacc), C.byref(out), stream))
 
     @property
     def dump_size(self) -> int:

@@ -261,6 +261,13 @@ class VecNormalize:
     def site_names(self):
         return self.venv.site_names()
 
+    # Jacobians and inverse dynamics: forwarded likewise
+    def jac(self, *args, **kwargs):
+        return self.venv.jac(*args, **kwargs)
+
+    def inverse(self, *args, **kwargs):
+        return self.venv.inverse(*args, **kwargs)
+
     # muscle fatigue state (muscle_condition="fatigue"): forwarded likewise
     def fatigue_state(self):
         return self.venv.fatigue_state()
