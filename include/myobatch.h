@@ -384,6 +384,43 @@ typedef struct myo_inverse_out {
 } myo_inverse_out;
 int myo_batch_inverse(myo_batch* b, const double* qacc, const myo_inverse_out* out, void* stream);
 
+/* ---- per-env static optimisation at the envs' PRESENT states: the actuator inputs that deliver a generalised force — the step after
+ * inverse dynamics in a biomechanics tool chain (activations that hold a posture, a reset in muscular equilibrium, supervised
+ * activation targets).  The actuation stage is affine in its input: force_i = gain_i u_i + bias_i, u_i = a muscle's activation, or
+ * the ctrl of an actuator without an activation state.  With R = actuator_moment [nu, nv], one wave per env solves
+ *   minimise  1/2 sum_d w_d (sum_i R[i,d] (gain_i u_i + bias_i) - qfrc_d)^2 + 1/2 reg sum_i (u_i - u_ref_i)^2,   lower_i <= u_i <= upper_i
+ * in doubles whatever the batch's dtype, by projected Newton (the scheme of MuJoCo's mju_boxQP), deterministically.  Inputs (dev):
+ *   qfrc    [N, nv]            the target, typically myo_batch_inverse's qfrc_inverse; required by any output but gain / bias
+ *   weight  [nv] or [N, nv]    (weight_per_env = 0 / 1) w >= 0, negative entries count as 0; NULL: 1 on every dof that some actuator's
+ *                              moment row can reach, 0 on the others (a free object's dofs must not pull the fit)
+ *   u_ref   [N, nu]            NULL: 0, the classic sum of squared activations; the previous solution gives temporal smoothing
+ *   lower, upper [N, nu]       NULL: [0, 1] for muscles, ctrlrange for other actuators with ctrllimited, else unbounded
+ *   reg > 0                    (1e-6: activation 1 costs as much as a 1e-3 N m error); max_iter >= 1 (100); else MYO_E_ARG
+ * Where an actuator is forcelimited and its gain is not 0, the box is tightened to the interval on which the clamp is inactive; a
+ * variable whose interval is empty is pinned at the nearer end of its box, one with lower > upper at lower (both set
+ * MYO_STATIC_OPT_PINNED), one with gain 0 at clip(u_ref).  Outputs (dev, any may be NULL):
+ *   u, force, gain, bias [N, nu]   the solution, its (clamped) actuator force, and the two curves' values at the present state
+ *   qfrc, residual [N, nv]         R' force, and R' force - target (unweighted)
+ *   kkt [N]                        max-norm of the projected gradient at u
+ *   iters, status [N] int32        Newton steps taken; 0 = converged, bit 0 (MYO_STATIC_OPT_CAP) = stopped at max_iter or without a
+ *                                  descent step, bit 2 (MYO_STATIC_OPT_PINNED) = some variable was pinned by an empty interval
+ * All outputs NULL launches nothing; a call for gain / bias alone runs no solve and needs no qfrc.  A NULL batch / struct, another
+ * `size` or a missing qfrc returns MYO_E_BADARG (= MYO_E_ARG) before any device call.  Read-only exactly as myo_batch_sense is. */
+enum { MYO_STATIC_OPT_CAP = 1, MYO_STATIC_OPT_PINNED = 4 };
+typedef struct myo_static_opt_in {
+  size_t size;
+  const double *qfrc, *weight, *u_ref, *lower, *upper;
+  int weight_per_env;
+  double reg;
+  int max_iter;
+} myo_static_opt_in;
+typedef struct myo_static_opt_out {
+  size_t size;
+  double *u, *force, *qfrc, *residual, *gain, *bias, *kkt;
+  int32_t *iters, *status;
+} myo_static_opt_out;
+int myo_batch_static_opt(myo_batch* b, const myo_static_opt_in* in, const myo_static_opt_out* out, void* stream);
+
 /* ---- rendering of env states (MuJoCo's mjr_render / mjr_readPixels seam: CustomPenEnv.render -> self.sim.render,
  * /root/reference/src/main_eval.py:96-97).  Draws what the stepper holds: every geom at the pose of the env's present state
  * and with the env's own geometry (Baoding P2 ball radius, die size delta), the Baoding target sites where the task puts

@@ -30,6 +30,7 @@
 #include "myo_sense.h"
 #include "myo_data.h"
 #include "myo_jac.h"
+#include "myo_static_opt.h"
 #include "myo_render.h"
 
 
@@ -1047,6 +1048,8 @@ struct myo_batch {
   double cam_lookat[3] = {0, 0, 0}, cam_distance = 1;      // the model's default camera (myo_model_default_camera)
   double* render_ws = nullptr; // dev: item poses and cameras of myo_batch_render, grown on demand (not in allocs)
   size_t render_ws_bytes = 0;
+  double* so_ws = nullptr;     // dev [n, MYO_SO_WS_N]: the system matrices of myo_batch_static_opt, allocated by its first solve (not in allocs)
+  unsigned long long act_reach = 0;      // dofs some actuator's moment row can reach: myo_batch_static_opt's default weight
   std::vector<double> cam_host;      // the cameras of the last myo_batch_render (source of its asynchronous upload)
   // how contact items are drawn (myo_batch_set_render_style; the defaults of include/myobatch.h)
   myo_render_style style = {sizeof(myo_render_style), 0.003, 0.0005, 0.001, 0.02, {0.9f, 0.6f, 0.2f, 1.f}, {0.7f, 0.9f, 0.9f, 1.f}, 1.0};
@@ -1255,6 +1258,7 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
   b->ncap = (m->npair > m->npair_std || m->any_rot || (cfg && cfg->kind == MYO_TASK_REORIENT)) ? MYO_NCON_BIG : MYO_NCON_MAX;
   b->geom_friction = m->geom_friction;
   b->nq = m->nq; b->nv = m->nv; b->nu = m->nu; b->na = m->na; b->nbody = m->nbody; b->nsite = m->nsite; b->ntendon = m->ntendon; b->ngeom = m->ngeom;
+  for (int i = 0; i < m->nu; ++i) b->act_reach |= m->act_dofmask[i];
   if (cfg) b->cfg = *cfg; else memset(&b->cfg, 0, sizeof b->cfg);
   make_taskdev(cfg && cfg->kind != MYO_TASK_NONE ? cfg : nullptr, seed, b->K);
   b->nobs = b->K.kind ? task_nobs_host(cfg, m->na) : 0;
@@ -1429,6 +1433,7 @@ extern "C" void myo_batch_destroy(myo_batch* b) {
   be_batch_release(b, b->device, 1);
   for (void* q : b->allocs) be_free(q);
   if (b->render_ws) be_free(b->render_ws);
+  if (b->so_ws) be_free(b->so_ws);
   delete b;
 }
 // ---- rendering (include/myobatch.h; csrc/myo_render.h): checks, cameras, style and workspace; the entry points are further down
@@ -1785,6 +1790,35 @@ extern "C" int myo_batch_inverse(myo_batch* b, const double* qacc, const myo_inv
   if (!qacc) return fail(MYO_E_BADARG, "myo_batch_inverse: qacc is required");
   if (!out->qfrc_inverse && !out->qfrc_constraint) return MYO_OK;
   return be_run(b, InverseJob{{qacc, out->qfrc_inverse, out->qfrc_constraint}}, b->n, stream);
+}
+// myo_batch_static_opt (csrc/myo_static_opt.h): StaticOptJob is a row of the variant table like InverseJob.  The default weight is a
+// structural property of the model (act_reach, built with the batch); the system matrices live in a workspace of the batch's own,
+// allocated by the first call that solves.  Every array lives on the device: the host refuses what it can see.
+static_assert((int)MYO_STATIC_OPT_CAP == (int)MYO_SO_ST_CAP && (int)MYO_STATIC_OPT_PINNED == (int)MYO_SO_ST_PINNED, "status bits of include/myobatch.h and csrc/myo_static_opt.h");
+extern "C" int myo_batch_static_opt(myo_batch* b, const myo_static_opt_in* in, const myo_static_opt_out* out, void* stream) {
+  if (!b || !in || !out) return fail(MYO_E_BADARG, "myo_batch_static_opt: null batch, input or output struct");
+  if (in->size != sizeof(myo_static_opt_in)) return fail(MYO_E_BADARG, "myo_batch_static_opt: myo_static_opt_in.size is %zu, this library's struct has %zu bytes", in->size, sizeof(myo_static_opt_in));
+  if (out->size != sizeof(myo_static_opt_out)) return fail(MYO_E_BADARG, "myo_batch_static_opt: myo_static_opt_out.size is %zu, this library's struct has %zu bytes", out->size, sizeof(myo_static_opt_out));
+  const bool solve = out->u || out->force || out->qfrc || out->residual || out->kkt || out->iters || out->status;
+  if (!solve && !out->gain && !out->bias) return MYO_OK;
+  StaticOptDev d{};
+  d.gain = out->gain; d.bias = out->bias; d.lower = in->lower; d.upper = in->upper; d.u_ref = in->u_ref;
+  d.reg = 1; d.max_iter = 1;
+  if (solve) {
+    if (!in->qfrc) return fail(MYO_E_BADARG, "myo_batch_static_opt: qfrc is required");
+    if (!(in->reg > 0) || !std::isfinite(in->reg)) return fail(MYO_E_ARG, "myo_batch_static_opt: reg must be finite and > 0");
+    if (in->max_iter < 1) return fail(MYO_E_ARG, "myo_batch_static_opt: max_iter must be >= 1");
+    if (!b->so_ws) {
+      void* p = nullptr;
+      const int e = be_malloc(&p, (size_t)b->n * MYO_SO_WS_N * sizeof(double));
+      if (e || !p) return fail(MYO_E_DEVICE, "myo_batch_static_opt: workspace allocation failed: %s", be_errstr(e));
+      b->so_ws = (double*)p;
+    }
+    d.qfrc = in->qfrc; d.weight = in->weight; d.weight_per_env = in->weight && in->weight_per_env ? 1 : 0;
+    d.u = out->u; d.force = out->force; d.qfrc_out = out->qfrc; d.residual = out->residual; d.kkt = out->kkt; d.iters = out->iters; d.status = out->status;
+    d.ws = b->so_ws; d.reach = b->act_reach; d.reg = in->reg; d.max_iter = in->max_iter; d.solve = 1;
+  }
+  return be_run(b, StaticOptJob{d}, b->n, stream);
 }
 extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
   if (int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses")) return rc;

@@ -204,6 +204,10 @@ class BaodingVecEnv:
         if attr_name in native.DATA_KEYS:              # MuJoCo's sim.data.<name> (names sensors() serves keep that route, above)
             v = self.data([attr_name])[attr_name].cpu().numpy()
             return [v[i].copy() for i in idx]
+        if attr_name in ("actuator_gain", "actuator_bias"):      # the actuation stage's two curves at the present state (static_optimization)
+            key = attr_name[len("actuator_"):]
+            v = self.static_optimization(keys=[key])[key].cpu().numpy()
+            return [v[i].copy() for i in idx]
         if attr_name in self.params:
             return [self.params[attr_name] for _ in idx]
         raise AttributeError(attr_name)
@@ -464,6 +468,62 @@ class BaodingVecEnv:
         self.batch.inverse(qacc, out["qfrc_inverse"], out["qfrc_constraint"], self._stream())
         if self.device.type == "cuda":
             t.cuda.synchronize(self.device)       # (qacc may be a temporary: the pass must have read it)
+        if indices is not None:
+            idx = t.as_tensor([int(i) for i in indices], dtype=t.long, device=self.device)
+            out = {k: v[idx] for k, v in out.items()}
+        return out
+
+    # ---------------------------------------------------------------- static optimisation (include/myobatch.h myo_batch_static_opt)
+    def static_optimization(self, qfrc=None, qacc=None, weight=None, reg=1e-6, u_ref=None, lower=None, upper=None, max_iter=100,
+                            indices=None, keys=None) -> dict:
+        """The muscle activations that deliver a generalised force at the envs' PRESENT states — the step after inverse dynamics:
+        per env, minimise ``1/2 sum_d w_d (R' (gain u + bias) - qfrc)_d^2 + 1/2 reg |u - u_ref|^2`` over ``lower <= u <= upper``
+        (``R`` = ``data()``'s ``actuator_moment``; the actuation stage is affine in ``u``, a muscle's activation or another
+        actuator's ctrl).  One pass on the GPU (projected Newton, float64 whatever the batch's dtype, deterministic), nothing about
+        the envs changes; device tensors, no host copy.
+
+        qfrc: [N, nv] target; ``None``: ``inverse(qacc)["qfrc_inverse"]`` with ``qacc`` [N, nv] (``None``: zeros — the activations
+        that hold the present state still).  weight: [nv] or [N, nv], >= 0 (default: 1 on the dofs some actuator reaches, 0 on the
+        others, e.g. a free object's).  u_ref: [N, nu] (default 0; the previous solution gives temporal smoothing).  lower / upper:
+        [N, nu] (default: [0, 1] for muscles, ctrlrange for other limited actuators, else unbounded; a force limit tightens the box
+        to where its clamp is inactive).  Returns (``keys``, default all) ``u`` / ``force`` / ``gain`` / ``bias`` [k_env, nu],
+        ``qfrc`` (achieved) / ``residual`` (achieved - target) [k_env, nv], ``kkt`` [k_env], ``iters`` / ``status`` [k_env] int32
+        (0: converged; bit 0: iteration cap; bit 2: a variable pinned by an empty interval).  indices: the envs' rows to return
+        (default: all; the pass itself always runs the whole batch)."""
+        t = self.torch
+        n, nv, nu = self.num_envs, self._model.size("nv"), self.act_dim
+        shapes = self.batch.static_opt_shapes()
+        keys = list(shapes) if keys is None else list(keys)
+        for k in keys:
+            if k not in shapes:
+                raise KeyError(f"unknown static-optimisation key {k!r}; known: {sorted(shapes)}")
+
+        def arr(x, name, shape_ok):
+            if x is None:
+                return None
+            x = t.as_tensor(x, dtype=t.float64, device=self.device).contiguous()
+            if tuple(x.shape) not in shape_ok:
+                raise ValueError(f"{name} must have shape {' or '.join(str(s) for s in shape_ok)}")
+            return x
+        if qfrc is not None and qacc is not None:
+            raise ValueError("give qfrc or qacc, not both")
+        solve = any(k not in ("gain", "bias") for k in keys)
+        if qfrc is None and solve:
+            qacc = t.zeros((n, nv), dtype=t.float64, device=self.device) if qacc is None else arr(qacc, "qacc", [(n, nv)])
+            qfrc = self.inverse(qacc)["qfrc_inverse"]
+        qfrc = arr(qfrc, "qfrc", [(n, nv)])
+        weight = arr(weight, "weight", [(nv,), (n, nv)])
+        on_host = lambda x: not (isinstance(x, t.Tensor) and x.device.type != "cpu")
+        check_box = lower is not None and upper is not None and on_host(lower) and on_host(upper)
+        u_ref, lower, upper = arr(u_ref, "u_ref", [(n, nu)]), arr(lower, "lower", [(n, nu)]), arr(upper, "upper", [(n, nu)])
+        if check_box and bool((lower > upper).any()):      # (host-visible arrays only: no device read-back; the kernel pins such a variable at lower and says so)
+            raise ValueError("lower > upper")
+        tdt = {np.int32: t.int32, np.float64: t.float64}
+        out = {k: t.empty((n,) + shapes[k][0], dtype=tdt[shapes[k][1]], device=self.device) for k in keys}
+        self.batch.static_opt(qfrc, weight, weight is not None and weight.dim() == 2, float(reg), u_ref, lower, upper, int(max_iter),
+                              self._stream(), **out)
+        if self.device.type == "cuda":
+            t.cuda.synchronize(self.device)       # (the inputs may be temporaries: the pass must have read them)
         if indices is not None:
             idx = t.as_tensor([int(i) for i in indices], dtype=t.long, device=self.device)
             out = {k: v[idx] for k, v in out.items()}

@@ -30,8 +30,11 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
              num_episodes: int = 100, num_envs: int = 256, seed: int = 0, deterministic: bool = True, verbose: bool = True,
              render_dir: str = None, render_envs: int = 1, render_size=(480, 480), render_tendons: bool = False,
              record_dir: str = None, env=None, render_contacts: bool = False, render_geom_alpha: float = None,
-             muscle_condition: str = None, fatigue_params: dict = None, record_data=None):
-    """record_data: keys of ``env.data`` (MuJoCo's sim.data names: ``site_xpos``, ``qacc``, ...) that record_dir's file also gets,
+             muscle_condition: str = None, fatigue_params: dict = None, record_data=None, record_static_opt: bool = False):
+    """record_static_opt: record_dir's file also gets ``so_u`` [T, N, nu], ``so_residual`` [T, N, nv] and ``so_status`` [T, N]: what a
+    static optimiser would have chosen (``env.static_optimization`` for the step's own ``data()["qacc"]``) beside what the policy
+    chose; needs record_dir.
+    record_data: keys of ``env.data`` (MuJoCo's sim.data names: ``site_xpos``, ``qacc``, ...) that record_dir's file also gets,
     [T, N, ...] each; needs record_dir.
     muscle_condition / fatigue_params: evaluate under MyoSuite's ``muscle_condition`` ("sarcopenia", "fatigue", "reafferentation";
     fatigue_params: a dict with any of F, R, r) — they override the config's; with fatigue, record_dir also gets ``fatigue_MA`` /
@@ -78,6 +81,8 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
     record_data = list(record_data or [])
     if record_data and not record_dir:
         raise ValueError("record_data needs record_dir")
+    if record_static_opt and not record_dir:
+        raise ValueError("record_static_opt needs record_dir")
     if record_dir:
         os.makedirs(record_dir, exist_ok=True)
         rec = {k: [] for k in ("qpos", "qvel", "act", "actuator_length", "actuator_velocity", "actuator_force", "ncon", "object_wrench")}
@@ -90,6 +95,8 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
             if k not in DATA_KEYS:
                 raise KeyError(f"unknown data key {k!r}; known: {sorted(DATA_KEYS)}")
             rec[k] = []
+        if record_static_opt:
+            rec.update(so_u=[], so_residual=[], so_status=[])
 
         def on_step(t):
             if draw is not None:
@@ -105,6 +112,10 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
             if record_data:
                 for k, v in env.data(record_data).items():
                     rec[k].append(v.cpu().numpy())
+            if record_static_opt:
+                so = env.static_optimization(qacc=env.data(["qacc"])["qacc"], keys=["u", "residual", "status"])
+                for k, v in so.items():
+                    rec["so_" + k].append(v.cpu().numpy())
     res = evaluate_policy(policy, env, venv, n_eval_episodes=num_episodes, deterministic=deterministic, on_step=on_step)
     if rec is not None:
         np.savez(os.path.join(record_dir, "batch00000.npz"), object_body_ids=np.asarray(obj, np.int64), **{k: np.stack(v) for k, v in rec.items()})
@@ -137,6 +148,9 @@ def main(argv=None):
                                                        "objects' contact wrenches of the evaluated batch to batch00000.npz here")
     ap.add_argument("--record-data", default=None, metavar="KEY[,KEY...]",
                     help="with --record-dir: also write these arrays of env.data (MuJoCo's sim.data names, e.g. site_xpos,qacc), [T, N, ...] each")
+    ap.add_argument("--record-static-opt", action="store_true",
+                    help="with --record-dir: also write so_u / so_residual / so_status per step: the activations a static optimiser "
+                         "(env.static_optimization) would have chosen for the step's own acceleration")
     ap.add_argument("--muscle-condition", default=None, choices=("sarcopenia", "fatigue", "reafferentation"),
                     help="evaluate under MyoSuite's muscle_condition (overrides the config's)")
     ap.add_argument("--fatigue-F", type=float, default=None, help="with --muscle-condition fatigue: fatigue rate F (default 0.00912)")
@@ -151,6 +165,8 @@ def main(argv=None):
         ap.error("--render-geom-alpha needs --render-contacts")
     if a.record_data and not a.record_dir:
         ap.error("--record-data needs --record-dir")
+    if a.record_static_opt and not a.record_dir:
+        ap.error("--record-static-opt needs --record-dir")
     fat = {k: v for k, v in (("F", a.fatigue_F), ("R", a.fatigue_R), ("r", a.fatigue_r)) if v is not None}
     if fat and a.muscle_condition != "fatigue":
         ap.error("--fatigue-F / --fatigue-R / --fatigue-r need --muscle-condition fatigue")
@@ -159,7 +175,8 @@ def main(argv=None):
                       render_dir=a.render_dir, render_envs=a.render_envs, render_size=a.render_size, render_tendons=a.render_tendons,
                       record_dir=a.record_dir, render_contacts=a.render_contacts, render_geom_alpha=a.render_geom_alpha,
                       muscle_condition=a.muscle_condition, fatigue_params=fat or None,
-                      record_data=[k for k in a.record_data.split(",") if k] if a.record_data else None)
+                      record_data=[k for k in a.record_data.split(",") if k] if a.record_data else None,
+                      record_static_opt=a.record_static_opt)
     if a.out:
         np.savez(a.out, **res)
 

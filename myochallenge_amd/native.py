@@ -179,6 +179,20 @@ class InverseOut(C.Structure):
     _fields_ = [("size", C.c_size_t), ("qfrc_inverse", C.c_void_p), ("qfrc_constraint", C.c_void_p)]
 
 
+class StaticOptIn(C.Structure):
+    """myo_static_opt_in of include/myobatch.h: device arrays (doubles) and scalars of myo_batch_static_opt; every pointer but qfrc may be NULL."""
+    _fields_ = [("size", C.c_size_t), ("qfrc", C.c_void_p), ("weight", C.c_void_p), ("u_ref", C.c_void_p), ("lower", C.c_void_p),
+                ("upper", C.c_void_p), ("weight_per_env", C.c_int), ("reg", C.c_double), ("max_iter", C.c_int)]
+
+
+class StaticOptOut(C.Structure):
+    """myo_static_opt_out of include/myobatch.h: caller-owned device arrays of myo_batch_static_opt (doubles; iters / status int32), any of them NULL."""
+    _fields_ = [("size", C.c_size_t)] + [(k, C.c_void_p) for k in ("u", "force", "qfrc", "residual", "gain", "bias", "kkt", "iters", "status")]
+
+
+STATIC_OPT_KEYS = tuple(f[0] for f in StaticOptOut._fields_[1:])
+STATIC_OPT_CAP, STATIC_OPT_PINNED = 1, 4      # MYO_STATIC_OPT_* of include/myobatch.h: bits of `status`
+
 JAC_BODY, JAC_BODYCOM, JAC_SITE, JAC_GEOM, JAC_SUBTREECOM = range(5)      # MYO_JAC_* of include/myobatch.h
 JAC_KINDS = {"body": JAC_BODY, "bodycom": JAC_BODYCOM, "site": JAC_SITE, "geom": JAC_GEOM, "subtreecom": JAC_SUBTREECOM}
 
@@ -246,6 +260,7 @@ class NativeLib:
         L.myo_batch_data.argtypes = [vp, vp, C.POINTER(DataOut), vp]
         L.myo_batch_jac.argtypes = [vp, i32, vp, i32, vp, C.POINTER(JacOut), vp]
         L.myo_batch_inverse.argtypes = [vp, vp, C.POINTER(InverseOut), vp]
+        L.myo_batch_static_opt.argtypes = [vp, C.POINTER(StaticOptIn), C.POINTER(StaticOptOut), vp]
         if b"MYO_EMU" in L.myo_version():
             return      # the emulation build (test tooling, csrc/emu_host.h) implements the env path only: ENV_PATH_SYMBOLS
         L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp, vp]
@@ -336,7 +351,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_ppo_gather_seq", "myo_rollout_state_snapshot", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
     "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_last_error", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
-    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse",
+    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
     "myo_ppo_mlp_step_resident", "myo_ppo_mlp_images", "myo_ppo_adv_moments_epoch",
@@ -355,7 +370,7 @@ ENV_PATH_SYMBOLS = [
     "myo_batch_step", "myo_batch_step_inner", "myo_batch_step_inner_idx", "myo_batch_tune_wrap_order", "myo_batch_warmstart", "myo_debug_wave_slots",
     "myo_last_error", "myo_model_destroy", "myo_model_from_blob", "myo_model_load_mjb", "myo_model_size", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
-    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse",
+    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
 ]
@@ -610,6 +625,27 @@ class Batch:
         out = InverseOut()
         out.size, out.qfrc_inverse, out.qfrc_constraint = C.sizeof(InverseOut), _ptr(qfrc_inverse), _ptr(qfrc_constraint)
         self.lib.check(self.lib.L.myo_batch_inverse(self.h, _ptr(qacc), C.byref(out), stream))
+
+    def static_opt_shapes(self) -> dict:
+        """key -> (per-env shape, dtype) of the arrays of static_opt()"""
+        nv, nu = self.model.size("nv"), self.model.size("nu")
+        return {"u": ((nu,), np.float64), "force": ((nu,), np.float64), "qfrc": ((nv,), np.float64), "residual": ((nv,), np.float64),
+                "gain": ((nu,), np.float64), "bias": ((nu,), np.float64), "kkt": ((), np.float64), "iters": ((), np.int32), "status": ((), np.int32)}
+
+    def static_opt(self, target=None, weight=None, weight_per_env=False, reg=1e-6, u_ref=None, lower=None, upper=None, max_iter=100, stream=None, **arrays):
+        """static optimisation at the envs' present states (myo_batch_static_opt): target = the struct's input qfrc, float64 [N, nv] (not needed by gain / bias
+        alone), weight float64 [nv] or — weight_per_env — [N, nv], u_ref / lower / upper float64 [N, nu], each a device array or
+        None (the library's default); keyword = a key of STATIC_OPT_KEYS, value = the device array that receives it
+        ([N, *static_opt_shapes()[key]]).  Keys not given are not computed; gain / bias alone run no solve."""
+        inp, out = StaticOptIn(), StaticOptOut()
+        inp.size, out.size = C.sizeof(StaticOptIn), C.sizeof(StaticOptOut)
+        inp.qfrc, inp.weight, inp.u_ref, inp.lower, inp.upper = _ptr(target), _ptr(weight), _ptr(u_ref), _ptr(lower), _ptr(upper)
+        inp.weight_per_env, inp.reg, inp.max_iter = int(bool(weight_per_env)), float(reg), int(max_iter)
+        for k, v in arrays.items():
+            if k not in STATIC_OPT_KEYS:
+                raise KeyError(k)
+            setattr(out, k, _ptr(v))
+        self.lib.check(self.lib.L.myo_batch_static_opt(self.h, C.byref(inp), C.byref(out), stream))
 
     @property
     def dump_size(self) -> int:

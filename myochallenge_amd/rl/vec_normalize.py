@@ -268,6 +268,9 @@ class VecNormalize:
     def inverse(self, *args, **kwargs):
         return self.venv.inverse(*args, **kwargs)
 
+    def static_optimization(self, *args, **kwargs):
+        return self.venv.static_optimization(*args, **kwargs)
+
     # muscle fatigue state (muscle_condition="fatigue"): forwarded likewise
     def fatigue_state(self):
         return self.venv.fatigue_state()
