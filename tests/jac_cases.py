@@ -8,7 +8,8 @@ Bounds.
   identities           1e-12 max(1, |value|): both sides are fp64 sums of <= 35 terms of the same numbers.
   forward / inverse    |qfrc_inverse - qfrc_actuator|_inf <= 4 |r|_inf + 1e-10 max|qfrc_*|, r = the forward solver's own stationarity
                        residual from read-outs that exist without this feature (4: summation order — the constraint force is continuous
-                       and piecewise linear in jar; the floor: fp64 rounding of a 35-term sum).
+                       and piecewise linear in jar; the floor: fp64 rounding of a 35-term sum).  The residual itself: |r|_2 <= tolerance
+                       meaninertia nv, what the Newton solver's stop rule (scale |grad| < tolerance, scale = 1 / (meaninertia nv)) promises.
   other dtypes         tests/data_cases.py's TOL[dtype], relative to the array's largest magnitude, against the fp64 stepper."""
 import ctypes as C
 import os
@@ -296,6 +297,9 @@ def forward_inverse(b, mem, label):
     scale = np.max([np.abs(h[k]).max(1) for k in ("qfrc_bias", "qfrc_passive", "qfrc_actuator")] + [np.abs(fc).max(1)], 0)
     for e in range(b.n):
         print(f"    {label} env {e}: |r| {rn[e]:.3e}  |qfrc_inverse - qfrc_actuator| {dn[e]:.3e}  |dqfrc_constraint| {cn[e]:.3e}  scale {scale[e]:.3e}")
+    opt = np.asarray(b.model.compiled.fields["opt_f64"], float)          # timestep, tolerance, ..., meaninertia
+    stop = opt[1] * opt[7] * b.model.size("nv")
+    assert (np.linalg.norm(r, axis=1) <= stop).all(), (label, np.linalg.norm(r, axis=1), stop)
     bound = 4 * rn + 1e-10 * scale
     assert (dn <= bound).all(), (label, dn, bound)
     assert (cn <= bound).all(), (label, cn, bound)
