@@ -118,6 +118,13 @@ int myo_model_from_blob(const void* blob, size_t nbytes, myo_model** out);
 int myo_model_load_mjb(const char* path, int integrator, int unsupported_contacts, myo_model** out);
 void myo_model_destroy(myo_model* m);
 int myo_model_size(const myo_model* m, const char* name); /* nq nv nu na nbody ... ; -1 unknown */
+/* Read access to what the loader derived (tests pin the host tables through it): *data points INTO the model, host memory, valid until
+ * myo_model_destroy; nothing is copied and no device is touched.  `name` is a table of the model (every array of csrc/myo_model_dev.h's
+ * MYO_MODEL_*_ARRAYS lists, vis, tvis, titem_adr) or one of its scalars that is no int (timestep, tolerance, impratio, gravity,
+ * meaninertia, cam_lookat, cam_distance, arrow_pad); the int scalars are myo_model_size's.  *bytes = size of the table, *dtype = one
+ * of MYO_TABLE_* (its element type).  An unknown name: MYO_E_ARG. */
+enum { MYO_TABLE_I32 = 0, MYO_TABLE_U64 = 1, MYO_TABLE_F32 = 2, MYO_TABLE_F64 = 3 };
+int myo_model_table(const myo_model* m, const char* name, const void** data, size_t* bytes, int* dtype);
 
 /* -- batch ------------------------------------------------------------------------------
  * replaces SubprocVecEnv([thunk]*n) + TimeLimit + Monitor (src/main_baoding.py:56-65).

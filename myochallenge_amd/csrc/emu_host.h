@@ -16,16 +16,8 @@ static const char* be_errstr(int) { return "emu"; }
 static int be_batch_workspaces(myo_batch* b, int n_envs, int device) {
   (void)device;
   int rc = 0;
-  void* w = nullptr;             // (emulation: one workspace per env)
-  rc |= be_malloc(&w, sizeof(double) * (size_t)n_envs * MYO_ENVWS_N);
-  b->K.ctrl_ws = (double*)w;
-  if (w) b->allocs.push_back(w);
-  if (b->ncap > MYO_NCON_MAX) {
-    void* g = nullptr;
-    rc |= be_malloc(&g, (size_t)n_envs * MYO_BIGWS_BYTES);
-    b->K.big_ws = (char*)g;
-    if (g) b->allocs.push_back(g);
-  }
+  b->K.ctrl_ws = dev_alloc<double>(b->allocs, rc, (size_t)n_envs * MYO_ENVWS_N);             // (emulation: one workspace per env)
+  if (b->ncap > MYO_NCON_MAX) b->K.big_ws = dev_alloc<char>(b->allocs, rc, (size_t)n_envs * MYO_BIGWS_BYTES);
   return rc;
 }
 static int be_batch_launch_state(myo_batch* b, const myo_model* m, int n_envs, int rc) { (void)b; (void)m; (void)n_envs; return rc; }

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include <cmath>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -85,6 +86,22 @@ extern "C" const char* myo_version(void) {      // "... build <hash of the nativ
 }
 
 // ------------------------------------------------------------------------------------------ host model
+// myo_model_from_blob is a sequence of stages on the model, in an order that is part of the contract: a blob with several defects is
+// reported by the first stage that meets one.
+//   read_fields          required fields (MYO_BLOB_*_FIELDS), optional fields with their defaults, sizes and options
+//   check_untrusted      sizes, array lengths and every id, before anything is indexed with them
+//   order_pairs          npair_std: primitive pairs first
+//   check_capacity       the stepper's capacities and feature gates that need no derived table
+//   build_tree_tables    body_depth .. dof_prevmask, dof_Madr / M_*, mv_*
+//   build_wrap_records, build_path_elements, build_actuator_gather
+//                        tendon_dofmask, wrap_side; wr_*, gw_elem; te_*, the staging-area limits; actuator_tendon, aq_*, act_*
+//   build_muscle_constants   act_pre
+//   build_lane_records   bk_*, jk_i, dk_i, dof_spr, dof_submask
+//   build_pair_records   pc_*, pair_mg, any_rot, any_gen
+//   build_frames         body_imat, geom_mat, nlead
+//   resolve_solver_params    (solref, solimp) -> what sol_param reads, in place
+//   build_ldl_tables, build_arrow_tables, set_feature_flags, render_vis_table, render_tendon_table
+// A capacity check that guards a table sits in that table's builder, before the first write it guards.
 struct myo_model {
   int nq, nv, nu, na, nbody, njnt, ngeom, nsite, ntendon, nwrap, npair, nM, maxdepth;
   int integrator, iterations, disableflags, any_damping, any_tendon_passive, nlead, ngw, nte, npair_std, ld_nfq, ld_nsq, arrow_nf, any_rot, any_gen, any_floss;
@@ -118,20 +135,16 @@ static const myo_blob_field* blob_find(const void* blob, const char* name) {
     if (strncmp(f[i].name, name, MYO_BLOB_NAME_LEN) == 0) return &f[i];
   return nullptr;
 }
-static bool get_i(const void* blob, size_t nbytes, const char* name, std::vector<int>& out) {
+template <typename U>
+static bool blob_get(const void* blob, size_t nbytes, const char* name, uint32_t dtype, std::vector<U>& out) {
   const myo_blob_field* f = blob_find(blob, name);
-  if (!f || f->dtype != MYO_BLOB_I32 || f->offset + 4ull * f->count > nbytes) return false;
-  const int* p = (const int*)((const char*)blob + f->offset);
+  if (!f || f->dtype != dtype || f->offset + (unsigned long long)sizeof(U) * f->count > nbytes) return false;
+  const U* p = (const U*)((const char*)blob + f->offset);
   out.assign(p, p + f->count);
   return true;
 }
-static bool get_d(const void* blob, size_t nbytes, const char* name, std::vector<double>& out) {
-  const myo_blob_field* f = blob_find(blob, name);
-  if (!f || f->dtype != MYO_BLOB_F64 || f->offset + 8ull * f->count > nbytes) return false;
-  const double* p = (const double*)((const char*)blob + f->offset);
-  out.assign(p, p + f->count);
-  return true;
-}
+static bool get_i(const void* blob, size_t nbytes, const char* name, std::vector<int>& out) { return blob_get(blob, nbytes, name, MYO_BLOB_I32, out); }
+static bool get_d(const void* blob, size_t nbytes, const char* name, std::vector<double>& out) { return blob_get(blob, nbytes, name, MYO_BLOB_F64, out); }
 static void quat2mat_h(const double* q, double* R) {
   double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
   double w = q[0] / n, x = q[1] / n, y = q[2] / n, z = q[3] / n;
@@ -421,251 +434,261 @@ static void render_vis_table(myo_model* m, const void* blob, size_t nbytes) {
   m->cam_distance = 1.5 * 2.0 * (r > 0 ? r : 1.0);
 }
 
-static int model_from_blob_impl(const void* blob, size_t nbytes, myo_model** out);
-extern "C" int myo_model_from_blob(const void* blob, size_t nbytes, myo_model** out) {
-  try { return model_from_blob_impl(blob, nbytes, out); }          // no C++ exception crosses the C ABI
-  catch (const std::exception& e) { return fail(MYO_E_ARG, "model blob rejected: %s", e.what()); }
+// ---- the loader's stages (the list at the head of this file)
+// The required blob fields that the model keeps under their own name: X(name, least number of elements), the counts in terms of
+// check_untrusted's nq_ .. nu_.  read_fields and check_untrusted's length check both expand from these two lists.
+#define MYO_BLOB_INT_FIELDS(X)                                                                                                  \
+  X(body_parentid, nb_) X(body_rootid, nb_) X(body_jntnum, nb_) X(body_jntadr, nb_) X(body_dofnum, nb_) X(body_dofadr, nb_)      \
+  X(jnt_type, nj_) X(jnt_qposadr, nj_) X(jnt_dofadr, nj_) X(jnt_bodyid, nj_) X(jnt_limited, nj_)                                 \
+  X(dof_bodyid, nv_) X(dof_jntid, nv_) X(dof_parentid, nv_) X(geom_type, ng_) X(geom_bodyid, ng_) X(geom_priority, ng_)          \
+  X(site_bodyid, ns_) X(tendon_adr, nt_) X(tendon_num, nt_) X(tendon_limited, nt_) X(wrap_type, nw_) X(wrap_objid, nw_)          \
+  X(actuator_dyntype, nu_) X(actuator_gaintype, nu_) X(actuator_biastype, nu_) X(actuator_ctrllimited, nu_) X(actuator_forcelimited, nu_)
+#define MYO_BLOB_REAL_FIELDS(X)                                                                                                 \
+  X(qpos0, nq_) X(qpos_spring, nq_) X(body_pos, 3 * nb_) X(body_quat, 4 * nb_) X(body_ipos, 3 * nb_) X(body_mass, nb_)           \
+  X(body_inertia, 3 * nb_) X(body_invweight0, 2 * nb_) X(jnt_solref, 2 * nj_) X(jnt_solimp, 5 * nj_) X(jnt_pos, 3 * nj_)         \
+  X(jnt_axis, 3 * nj_) X(jnt_stiffness, nj_) X(jnt_range, 2 * nj_) X(jnt_margin, nj_) X(dof_armature, nv_) X(dof_damping, nv_)   \
+  X(dof_invweight0, nv_) X(geom_solmix, ng_) X(geom_solref, 2 * ng_) X(geom_solimp, 5 * ng_) X(geom_size, 3 * ng_)               \
+  X(geom_rbound, ng_) X(geom_pos, 3 * ng_) X(geom_friction, 3 * ng_) X(geom_margin, ng_) X(geom_gap, ng_) X(site_pos, 3 * ns_)   \
+  X(tendon_solref_lim, 2 * nt_) X(tendon_solimp_lim, 5 * nt_) X(tendon_range, 2 * nt_) X(tendon_margin, nt_) X(tendon_stiffness, nt_) \
+  X(tendon_damping, nt_) X(tendon_lengthspring, nt_) X(tendon_invweight0, nt_) X(wrap_prm, nw_) X(actuator_dynprm, 10 * nu_)     \
+  X(actuator_gainprm, 10 * nu_) X(actuator_biasprm, 10 * nu_) X(actuator_ctrlrange, 2 * nu_) X(actuator_forcerange, 2 * nu_)     \
+  X(actuator_gear, 6 * nu_) X(actuator_acc0, nu_) X(actuator_lengthrange, 2 * nu_)
+
+// blob arrays that the table builders read and the model does not keep
+struct BlobOnly {
+  std::vector<int> trntype, trnid, geom_condim, pair_sub, pair_xp, xp_dim;
+  std::vector<double> body_iquat, geom_quat, xp_margin, xp_gap, xp_solref, xp_solimp, xp_friction;
+};
+
+static int corrupt(const char* fmt, ...) {
+  char why[160] = "";
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(why, sizeof why, fmt, ap);
+  va_end(ap);
+  return fail(MYO_E_ARG, "corrupt model: %s", why);
 }
-static int model_from_blob_impl(const void* blob, size_t nbytes, myo_model** out) {
-  if (!blob || !out || nbytes < sizeof(myo_blob_header)) return fail(MYO_E_ARG, "null or short blob");
-  const myo_blob_header* h = (const myo_blob_header*)blob;
-  if (h->magic != MYO_BLOB_MAGIC || h->version != MYO_BLOB_VERSION || h->total_bytes != nbytes ||
-      sizeof(myo_blob_header) + (size_t)h->n_fields * sizeof(myo_blob_field) > nbytes)
-    return fail(MYO_E_ARG, "bad model blob header");
-  myo_model* m = new myo_model();
-  std::vector<int> sizes, opt_i, trntype, trnid, body_weldid, geom_condim, pair_sub, pair_xp, xp_dim;
-  std::vector<double> opt_d, body_iquat, geom_quat, xp_margin, xp_gap, xp_solref, xp_solimp, xp_friction;
+static int over_capacity(const char* what) { return fail(MYO_E_UNSUPPORTED, "model exceeds stepper capacity: %s", what); }
+static int popcount64(unsigned long long x) { return __builtin_popcountll(x); }
+// entry k of a row of 16-bit entries, two per word (the even entry in the low half); the row starts out zeroed
+static void pack16(int* row, int k, unsigned ent) {
+  unsigned& w = reinterpret_cast<unsigned&>(row[k / 2]);
+  w |= (k & 1) ? (ent << 16) : ent;
+}
+
+static int read_fields(const void* blob, size_t nbytes, myo_model& m, BlobOnly& x) {
+  std::vector<int> sizes, opt_i;
+  std::vector<double> opt_d;
   bool ok = get_i(blob, nbytes, "sizes", sizes) && sizes.size() >= 10 && get_i(blob, nbytes, "opt_int", opt_i) &&
             opt_i.size() >= 4 && get_d(blob, nbytes, "opt_f64", opt_d) && opt_d.size() >= 8;
   const char* missing = nullptr;
-#define GI(n) if (ok && !get_i(blob, nbytes, #n, m->n)) { ok = false; missing = #n; }
-#define GD(n) if (ok && !get_d(blob, nbytes, #n, m->n)) { ok = false; missing = #n; }
-  GI(body_parentid) GI(body_rootid) GI(body_jntnum) GI(body_jntadr) GI(body_dofnum) GI(body_dofadr)
-  GI(jnt_type) GI(jnt_qposadr) GI(jnt_dofadr) GI(jnt_bodyid) GI(jnt_limited) GI(dof_bodyid) GI(dof_jntid)
-  GI(dof_parentid) GI(geom_type) GI(geom_bodyid) GI(geom_priority) GI(site_bodyid) GI(tendon_adr)
-  GI(tendon_num) GI(tendon_limited) GI(wrap_type) GI(wrap_objid) GI(actuator_dyntype) GI(actuator_gaintype)
-  GI(actuator_biastype) GI(actuator_ctrllimited) GI(actuator_forcelimited)
-  GD(qpos0) GD(qpos_spring) GD(body_pos) GD(body_quat) GD(body_ipos) GD(body_mass) GD(body_inertia)
-  GD(body_invweight0) GD(jnt_solref) GD(jnt_solimp) GD(jnt_pos) GD(jnt_axis) GD(jnt_stiffness) GD(jnt_range)
-  GD(jnt_margin) GD(dof_armature) GD(dof_damping) GD(dof_invweight0) GD(geom_solmix) GD(geom_solref)
-  GD(geom_solimp) GD(geom_size) GD(geom_rbound) GD(geom_pos) GD(geom_friction) GD(geom_margin) GD(geom_gap)
-  GD(site_pos) GD(tendon_solref_lim) GD(tendon_solimp_lim) GD(tendon_range) GD(tendon_margin)
-  GD(tendon_stiffness) GD(tendon_damping) GD(tendon_lengthspring) GD(tendon_invweight0) GD(wrap_prm)
-  GD(actuator_dynprm) GD(actuator_gainprm) GD(actuator_biasprm) GD(actuator_ctrlrange) GD(actuator_forcerange)
-  GD(actuator_gear) GD(actuator_acc0) GD(actuator_lengthrange)
-#undef GI
-#undef GD
-  if (ok) ok = get_i(blob, nbytes, "actuator_trntype", trntype) && get_i(blob, nbytes, "actuator_trnid", trnid) &&
-               get_d(blob, nbytes, "body_iquat", body_iquat) && get_d(blob, nbytes, "geom_quat", geom_quat) &&
-               get_i(blob, nbytes, "x_pair_geom1", m->pair_geom1) && get_i(blob, nbytes, "x_pair_geom2", m->pair_geom2);
-  if (ok && !get_i(blob, nbytes, "x_pair_sub", pair_sub)) pair_sub.assign(m->pair_geom1.size(), 0);      // (older blobs: no box-box candidates)
-  if (ok && !get_i(blob, nbytes, "geom_condim", geom_condim)) geom_condim.clear();                        // (older blobs: condim 3 everywhere)
-  if (ok) {                                   // explicit <contact><pair> parameters (older blobs: none)
-    if (!get_i(blob, nbytes, "x_pair_explicit", pair_xp) || pair_xp.size() != m->pair_geom1.size()) pair_xp.assign(m->pair_geom1.size(), -1);
-    const bool have = get_i(blob, nbytes, "x_xp_dim", xp_dim) && get_d(blob, nbytes, "x_xp_margin", xp_margin) && get_d(blob, nbytes, "x_xp_gap", xp_gap) &&
-                      get_d(blob, nbytes, "x_xp_solref", xp_solref) && get_d(blob, nbytes, "x_xp_solimp", xp_solimp) && get_d(blob, nbytes, "x_xp_friction", xp_friction);
-    const size_t nx = have ? xp_dim.size() : 0;
-    if (have && (xp_margin.size() != nx || xp_gap.size() != nx || xp_solref.size() != 2 * nx || xp_solimp.size() != 5 * nx || xp_friction.size() != 3 * nx)) {
-      int rc = fail(MYO_E_ARG, "corrupt model: explicit contact pair arrays differ in length"); delete m; return rc;
-    }
-    for (int& v : pair_xp) if (v < -1 || v >= (int)nx) { int rc = fail(MYO_E_ARG, "corrupt model: explicit contact pair index %d", v); delete m; return rc; }
+#define X(n, cnt) if (ok && !get_i(blob, nbytes, #n, m.n)) { ok = false; missing = #n; }
+  MYO_BLOB_INT_FIELDS(X)
+#undef X
+#define X(n, cnt) if (ok && !get_d(blob, nbytes, #n, m.n)) { ok = false; missing = #n; }
+  MYO_BLOB_REAL_FIELDS(X)
+#undef X
+  if (ok) ok = get_i(blob, nbytes, "actuator_trntype", x.trntype) && get_i(blob, nbytes, "actuator_trnid", x.trnid) &&
+               get_d(blob, nbytes, "body_iquat", x.body_iquat) && get_d(blob, nbytes, "geom_quat", x.geom_quat) &&
+               get_i(blob, nbytes, "x_pair_geom1", m.pair_geom1) && get_i(blob, nbytes, "x_pair_geom2", m.pair_geom2);
+  if (!ok) return fail(MYO_E_ARG, "model blob lacks field %s", missing ? missing : "(sizes/opt/derived)");
+  if (!get_i(blob, nbytes, "x_pair_sub", x.pair_sub)) x.pair_sub.assign(m.pair_geom1.size(), 0);      // (older blobs: no box-box candidates)
+  if (!get_i(blob, nbytes, "geom_condim", x.geom_condim)) x.geom_condim.clear();                        // (older blobs: condim 3 everywhere)
+  // explicit <contact><pair> parameters (older blobs: none)
+  if (!get_i(blob, nbytes, "x_pair_explicit", x.pair_xp) || x.pair_xp.size() != m.pair_geom1.size()) x.pair_xp.assign(m.pair_geom1.size(), -1);
+  const bool have = get_i(blob, nbytes, "x_xp_dim", x.xp_dim) && get_d(blob, nbytes, "x_xp_margin", x.xp_margin) && get_d(blob, nbytes, "x_xp_gap", x.xp_gap) &&
+                    get_d(blob, nbytes, "x_xp_solref", x.xp_solref) && get_d(blob, nbytes, "x_xp_solimp", x.xp_solimp) && get_d(blob, nbytes, "x_xp_friction", x.xp_friction);
+  const size_t nx = have ? x.xp_dim.size() : 0;
+  if (have && (x.xp_margin.size() != nx || x.xp_gap.size() != nx || x.xp_solref.size() != 2 * nx || x.xp_solimp.size() != 5 * nx || x.xp_friction.size() != 3 * nx))
+    return fail(MYO_E_ARG, "corrupt model: explicit contact pair arrays differ in length");
+  for (int v : x.pair_xp) if (v < -1 || v >= (int)nx) return fail(MYO_E_ARG, "corrupt model: explicit contact pair index %d", v);
+  // friction loss: optional fields (older blobs: none), MuJoCo's default solver parameters
+  const size_t nv0 = sizes[1] > 0 && sizes[1] <= 4096 ? sizes[1] : 0, nt0 = sizes[8] > 0 && sizes[8] <= 4096 ? sizes[8] : 0;     // (untrusted sizes: capacity checks follow)
+  auto opt = [&](const char* name, std::vector<double>& v, size_t cnt, std::initializer_list<double> def) {
+    if (!get_d(blob, nbytes, name, v) || v.size() < cnt * def.size()) { v.clear(); for (size_t i = 0; i < cnt; ++i) v.insert(v.end(), def); }
+  };
+  opt("dof_frictionloss", m.dof_frictionloss, nv0, {0.0}); opt("dof_solref", m.dof_solref, nv0, {0.02, 1.0});
+  opt("dof_solimp", m.dof_solimp, nv0, {0.9, 0.95, 0.001, 0.5, 2.0});
+  opt("tendon_frictionloss", m.tendon_frictionloss, nt0, {0.0}); opt("tendon_solref_fri", m.tendon_solref_fri, nt0, {0.02, 1.0});
+  opt("tendon_solimp_fri", m.tendon_solimp_fri, nt0, {0.9, 0.95, 0.001, 0.5, 2.0});
+  m.nq = sizes[0]; m.nv = sizes[1]; m.nu = sizes[2]; m.na = sizes[3]; m.nbody = sizes[4]; m.njnt = sizes[5];
+  m.ngeom = sizes[6]; m.nsite = sizes[7]; m.ntendon = sizes[8]; m.nwrap = sizes[9];
+  m.npair = (int)m.pair_geom1.size();
+  m.npair_std = 0;
+  m.integrator = opt_i[0]; m.iterations = opt_i[2]; m.disableflags = opt_i[3];
+  m.timestep = opt_d[0]; m.tolerance = opt_d[1]; m.impratio = opt_d[2];
+  m.gravity[0] = opt_d[3]; m.gravity[1] = opt_d[4]; m.gravity[2] = opt_d[5]; m.meaninertia = opt_d[7];
+  for (int k = 0; k < 10; ++k) if (sizes[k] < 0) return corrupt("negative size %d", k);
+  return MYO_OK;
+}
+
+// ---- the blob is untrusted input: sizes, array lengths and every id are checked before anything is indexed with them
+static int check_untrusted(const myo_model& m, BlobOnly& x) {
+  if (m.nbody < 1 || m.na > m.nu) return corrupt("nbody < 1 or na > nu");
+  if (m.pair_geom1.size() != m.pair_geom2.size() || x.pair_sub.size() != m.pair_geom1.size()) return corrupt("pair arrays differ in length");
+  for (int v : x.pair_sub) if (v < 0 || v > 17) return corrupt("collision pair sub-index %d", v);
+  const size_t nq_ = m.nq, nb_ = m.nbody, nj_ = m.njnt, nv_ = m.nv, ng_ = m.ngeom, ns_ = m.nsite, nt_ = m.ntendon, nw_ = m.nwrap, nu_ = m.nu;
+  const char* short_arr = nullptr;
+  size_t has = 0, needs = 0;
+#define X(n, cnt) if (!short_arr && m.n.size() < (size_t)(cnt)) { short_arr = #n; has = m.n.size(); needs = (size_t)(cnt); }
+  MYO_BLOB_INT_FIELDS(X) MYO_BLOB_REAL_FIELDS(X)
+#undef X
+  if (short_arr) return corrupt("array %s has %zu entries, needs %zu", short_arr, has, needs);
+  if (x.geom_condim.empty()) x.geom_condim.assign(ng_, 3);
+  if (x.geom_condim.size() < ng_) return corrupt("geom_condim too short");
+  if (x.trntype.size() < nu_ || x.trnid.size() < 2 * nu_ || x.body_iquat.size() < 4 * nb_ || x.geom_quat.size() < 4 * ng_) return corrupt("actuator_trn* / body_iquat / geom_quat too short");
+  if (m.body_parentid[0] != 0) return corrupt("body_parentid[0] != 0");
+  for (int b = 0; b < m.nbody; ++b) {
+    if (b > 0 && (m.body_parentid[b] < 0 || m.body_parentid[b] >= b)) return corrupt("body_parentid[%d] = %d", b, m.body_parentid[b]);
+    if (m.body_rootid[b] < 0 || m.body_rootid[b] >= m.nbody) return corrupt("body_rootid[%d] = %d", b, m.body_rootid[b]);
+    const int jn = m.body_jntnum[b], ja = m.body_jntadr[b], dn = m.body_dofnum[b], da = m.body_dofadr[b];
+    if (jn < 0 || (jn > 0 && (ja < 0 || ja > m.njnt || jn > m.njnt - ja))) return corrupt("body_jntadr/num[%d] = %d/%d", b, ja, jn);
+    if (dn < 0 || (dn > 0 && (da < 0 || da > m.nv || dn > m.nv - da))) return corrupt("body_dofadr/num[%d] = %d/%d", b, da, dn);
   }
-  if (ok) {                                   // friction loss: optional fields (older blobs: none), MuJoCo's default solver parameters
-    const size_t nv0 = sizes[1] > 0 && sizes[1] <= 4096 ? sizes[1] : 0, nt0 = sizes[8] > 0 && sizes[8] <= 4096 ? sizes[8] : 0;     // (untrusted sizes: capacity checks follow)
-    auto opt = [&](const char* name, std::vector<double>& v, size_t cnt, std::initializer_list<double> def) {
-      if (!get_d(blob, nbytes, name, v) || v.size() < cnt * def.size()) { v.clear(); for (size_t i = 0; i < cnt; ++i) v.insert(v.end(), def); }
-    };
-    opt("dof_frictionloss", m->dof_frictionloss, nv0, {0.0}); opt("dof_solref", m->dof_solref, nv0, {0.02, 1.0});
-    opt("dof_solimp", m->dof_solimp, nv0, {0.9, 0.95, 0.001, 0.5, 2.0});
-    opt("tendon_frictionloss", m->tendon_frictionloss, nt0, {0.0}); opt("tendon_solref_fri", m->tendon_solref_fri, nt0, {0.02, 1.0});
-    opt("tendon_solimp_fri", m->tendon_solimp_fri, nt0, {0.9, 0.95, 0.001, 0.5, 2.0});
+  for (int j = 0; j < m.njnt; ++j) {
+    const int ty = m.jnt_type[j], nqj = ty == MYO_JNT_FREE ? 7 : (ty == MYO_JNT_BALL ? 4 : 1), nvj = ty == MYO_JNT_FREE ? 6 : (ty == MYO_JNT_BALL ? 3 : 1);
+    if (ty < 0 || ty > 3) return corrupt("jnt_type[%d] = %d", j, ty);
+    if (m.jnt_qposadr[j] < 0 || m.jnt_qposadr[j] > m.nq - nqj) return corrupt("jnt_qposadr[%d] = %d", j, m.jnt_qposadr[j]);
+    if (m.jnt_dofadr[j] < 0 || m.jnt_dofadr[j] > m.nv - nvj) return corrupt("jnt_dofadr[%d] = %d", j, m.jnt_dofadr[j]);
+    if (m.jnt_bodyid[j] < 0 || m.jnt_bodyid[j] >= m.nbody) return corrupt("jnt_bodyid[%d] = %d", j, m.jnt_bodyid[j]);
   }
-  if (!ok) {
-    int rc = fail(MYO_E_ARG, "model blob lacks field %s", missing ? missing : "(sizes/opt/derived)");
-    delete m;
-    return rc;
+  for (int d = 0; d < m.nv; ++d) {
+    if (m.dof_bodyid[d] < 0 || m.dof_bodyid[d] >= m.nbody) return corrupt("dof_bodyid[%d] = %d", d, m.dof_bodyid[d]);
+    if (m.dof_jntid[d] < 0 || m.dof_jntid[d] >= m.njnt) return corrupt("dof_jntid[%d] = %d", d, m.dof_jntid[d]);
+    if (m.dof_parentid[d] < -1 || m.dof_parentid[d] >= d) return corrupt("dof_parentid[%d] = %d", d, m.dof_parentid[d]);
   }
-  m->nq = sizes[0]; m->nv = sizes[1]; m->nu = sizes[2]; m->na = sizes[3]; m->nbody = sizes[4]; m->njnt = sizes[5];
-  m->ngeom = sizes[6]; m->nsite = sizes[7]; m->ntendon = sizes[8]; m->nwrap = sizes[9];
-  m->npair = (int)m->pair_geom1.size();
-  m->npair_std = 0;
-  m->integrator = opt_i[0]; m->iterations = opt_i[2]; m->disableflags = opt_i[3];
-  m->timestep = opt_d[0]; m->tolerance = opt_d[1]; m->impratio = opt_d[2];
-  m->gravity[0] = opt_d[3]; m->gravity[1] = opt_d[4]; m->gravity[2] = opt_d[5]; m->meaninertia = opt_d[7];
-  // ---- the blob is untrusted input: sizes, array lengths and every id are checked before anything is indexed with them
-  {
-    char why[160] = "";
-#define BAD(...) { snprintf(why, sizeof why, __VA_ARGS__); int rc = fail(MYO_E_ARG, "corrupt model: %s", why); delete m; return rc; }
-    for (int k = 0; k < 10; ++k) if (sizes[k] < 0) BAD("negative size %d", k)
-    if (m->nbody < 1 || m->na > m->nu) BAD("nbody < 1 or na > nu")
-    if (m->pair_geom1.size() != m->pair_geom2.size() || pair_sub.size() != m->pair_geom1.size()) BAD("pair arrays differ in length")
-    for (int v : pair_sub) if (v < 0 || v > 17) BAD("collision pair sub-index %d", v)
-#define NEED(arr, cnt) if (m->arr.size() < (size_t)(cnt)) BAD("array %s has %zu entries, needs %zu", #arr, m->arr.size(), (size_t)(cnt))
-    const size_t nb_ = m->nbody, nj_ = m->njnt, nv_ = m->nv, ng_ = m->ngeom, ns_ = m->nsite, nt_ = m->ntendon, nw_ = m->nwrap, nu_ = m->nu;
-    NEED(body_parentid, nb_) NEED(body_rootid, nb_) NEED(body_jntnum, nb_) NEED(body_jntadr, nb_) NEED(body_dofnum, nb_) NEED(body_dofadr, nb_)
-    NEED(jnt_type, nj_) NEED(jnt_qposadr, nj_) NEED(jnt_dofadr, nj_) NEED(jnt_bodyid, nj_) NEED(jnt_limited, nj_)
-    NEED(dof_bodyid, nv_) NEED(dof_jntid, nv_) NEED(dof_parentid, nv_) NEED(geom_type, ng_) NEED(geom_bodyid, ng_) NEED(geom_priority, ng_)
-    NEED(site_bodyid, ns_) NEED(tendon_adr, nt_) NEED(tendon_num, nt_) NEED(tendon_limited, nt_) NEED(wrap_type, nw_) NEED(wrap_objid, nw_)
-    NEED(actuator_dyntype, nu_) NEED(actuator_gaintype, nu_) NEED(actuator_biastype, nu_) NEED(actuator_ctrllimited, nu_) NEED(actuator_forcelimited, nu_)
-    NEED(qpos0, m->nq) NEED(qpos_spring, m->nq) NEED(body_pos, 3 * nb_) NEED(body_quat, 4 * nb_) NEED(body_ipos, 3 * nb_) NEED(body_mass, nb_)
-    NEED(body_inertia, 3 * nb_) NEED(body_invweight0, 2 * nb_) NEED(jnt_solref, 2 * nj_) NEED(jnt_solimp, 5 * nj_) NEED(jnt_pos, 3 * nj_)
-    NEED(jnt_axis, 3 * nj_) NEED(jnt_stiffness, nj_) NEED(jnt_range, 2 * nj_) NEED(jnt_margin, nj_) NEED(dof_armature, nv_) NEED(dof_damping, nv_)
-    NEED(dof_invweight0, nv_) NEED(geom_solmix, ng_) NEED(geom_solref, 2 * ng_) NEED(geom_solimp, 5 * ng_) NEED(geom_size, 3 * ng_)
-    NEED(geom_rbound, ng_) NEED(geom_pos, 3 * ng_) NEED(geom_friction, 3 * ng_) NEED(geom_margin, ng_) NEED(geom_gap, ng_) NEED(site_pos, 3 * ns_)
-    NEED(tendon_solref_lim, 2 * nt_) NEED(tendon_solimp_lim, 5 * nt_) NEED(tendon_range, 2 * nt_) NEED(tendon_margin, nt_) NEED(tendon_stiffness, nt_)
-    NEED(tendon_damping, nt_) NEED(tendon_lengthspring, nt_) NEED(tendon_invweight0, nt_) NEED(wrap_prm, nw_) NEED(actuator_dynprm, 10 * nu_)
-    NEED(actuator_gainprm, 10 * nu_) NEED(actuator_biasprm, 10 * nu_) NEED(actuator_ctrlrange, 2 * nu_) NEED(actuator_forcerange, 2 * nu_)
-    NEED(actuator_gear, 6 * nu_) NEED(actuator_acc0, nu_) NEED(actuator_lengthrange, 2 * nu_)
-#undef NEED
-    if (geom_condim.empty()) geom_condim.assign(ng_, 3);
-    if (geom_condim.size() < ng_) BAD("geom_condim too short")
-    if (trntype.size() < nu_ || trnid.size() < 2 * nu_ || body_iquat.size() < 4 * nb_ || geom_quat.size() < 4 * ng_) BAD("actuator_trn* / body_iquat / geom_quat too short")
-    if (m->body_parentid[0] != 0) BAD("body_parentid[0] != 0")
-    for (int b = 0; b < m->nbody; ++b) {
-      if (b > 0 && (m->body_parentid[b] < 0 || m->body_parentid[b] >= b)) BAD("body_parentid[%d] = %d", b, m->body_parentid[b])
-      if (m->body_rootid[b] < 0 || m->body_rootid[b] >= m->nbody) BAD("body_rootid[%d] = %d", b, m->body_rootid[b])
-      const int jn = m->body_jntnum[b], ja = m->body_jntadr[b], dn = m->body_dofnum[b], da = m->body_dofadr[b];
-      if (jn < 0 || (jn > 0 && (ja < 0 || ja > m->njnt || jn > m->njnt - ja))) BAD("body_jntadr/num[%d] = %d/%d", b, ja, jn)
-      if (dn < 0 || (dn > 0 && (da < 0 || da > m->nv || dn > m->nv - da))) BAD("body_dofadr/num[%d] = %d/%d", b, da, dn)
-    }
-    for (int j = 0; j < m->njnt; ++j) {
-      const int ty = m->jnt_type[j], nqj = ty == MYO_JNT_FREE ? 7 : (ty == MYO_JNT_BALL ? 4 : 1), nvj = ty == MYO_JNT_FREE ? 6 : (ty == MYO_JNT_BALL ? 3 : 1);
-      if (ty < 0 || ty > 3) BAD("jnt_type[%d] = %d", j, ty)
-      if (m->jnt_qposadr[j] < 0 || m->jnt_qposadr[j] > m->nq - nqj) BAD("jnt_qposadr[%d] = %d", j, m->jnt_qposadr[j])
-      if (m->jnt_dofadr[j] < 0 || m->jnt_dofadr[j] > m->nv - nvj) BAD("jnt_dofadr[%d] = %d", j, m->jnt_dofadr[j])
-      if (m->jnt_bodyid[j] < 0 || m->jnt_bodyid[j] >= m->nbody) BAD("jnt_bodyid[%d] = %d", j, m->jnt_bodyid[j])
-    }
-    for (int d = 0; d < m->nv; ++d) {
-      if (m->dof_bodyid[d] < 0 || m->dof_bodyid[d] >= m->nbody) BAD("dof_bodyid[%d] = %d", d, m->dof_bodyid[d])
-      if (m->dof_jntid[d] < 0 || m->dof_jntid[d] >= m->njnt) BAD("dof_jntid[%d] = %d", d, m->dof_jntid[d])
-      if (m->dof_parentid[d] < -1 || m->dof_parentid[d] >= d) BAD("dof_parentid[%d] = %d", d, m->dof_parentid[d])
-    }
-    for (int g = 0; g < m->ngeom; ++g) {
-      if (m->geom_bodyid[g] < 0 || m->geom_bodyid[g] >= m->nbody) BAD("geom_bodyid[%d] = %d", g, m->geom_bodyid[g])
-      if (m->geom_type[g] < 0 || m->geom_type[g] > MYO_GEOM_MESH) BAD("geom_type[%d] = %d", g, m->geom_type[g])
-    }
-    for (int k = 0; k < m->nsite; ++k) if (m->site_bodyid[k] < 0 || m->site_bodyid[k] >= m->nbody) BAD("site_bodyid[%d] = %d", k, m->site_bodyid[k])
-    for (int t = 0; t < m->ntendon; ++t) {
-      const int a = m->tendon_adr[t], c = m->tendon_num[t];
-      if (a < 0 || c < 0 || a > m->nwrap || c > m->nwrap - a) BAD("tendon_adr/num[%d] = %d/%d", t, a, c)
-    }
-    for (int w = 0; w < m->nwrap; ++w) {
-      const int ty = m->wrap_type[w], id = m->wrap_objid[w];
-      if (ty == MYO_WRAP_SITE && (id < 0 || id >= m->nsite)) BAD("wrap_objid[%d] = %d (site)", w, id)
-      if (ty == MYO_WRAP_SPHERE || ty == MYO_WRAP_CYLINDER) {
-        if (id < 0 || id >= m->ngeom) BAD("wrap_objid[%d] = %d (geom)", w, id)
-        if (m->wrap_prm[w] >= 0 && !(m->wrap_prm[w] < (double)m->nsite)) BAD("wrap_prm[%d]: side site out of range", w)
-      }
-    }
-    for (int i = 0; i < m->nu; ++i) if (trntype[i] == MYO_TRN_TENDON && (trnid[2 * i] < 0 || trnid[2 * i] >= m->ntendon)) BAD("actuator_trnid[%d] = %d", i, trnid[2 * i])
-    for (size_t p = 0; p < m->pair_geom1.size(); ++p)
-      if (m->pair_geom1[p] < 0 || m->pair_geom1[p] >= m->ngeom || m->pair_geom2[p] < 0 || m->pair_geom2[p] >= m->ngeom) BAD("collision pair %zu names a geom out of range", p)
-    if (!(m->timestep > 0) || !std::isfinite(m->timestep) || m->iterations < 0) BAD("opt.timestep / opt.iterations")
-#undef BAD
+  for (int g = 0; g < m.ngeom; ++g) {
+    if (m.geom_bodyid[g] < 0 || m.geom_bodyid[g] >= m.nbody) return corrupt("geom_bodyid[%d] = %d", g, m.geom_bodyid[g]);
+    if (m.geom_type[g] < 0 || m.geom_type[g] > MYO_GEOM_MESH) return corrupt("geom_type[%d] = %d", g, m.geom_type[g]);
   }
-  {   // pairs of the primitive narrow phases first, the extended ones (csrc/myo_physics.h:collide_pair_ext) after them
-    auto is_std = [&](int p) {
-      const int t1 = m->geom_type[m->pair_geom1[p]], t2 = m->geom_type[m->pair_geom2[p]];
-      return (t1 == MYO_GEOM_PLANE && (t2 == MYO_GEOM_SPHERE || t2 == MYO_GEOM_CAPSULE)) || (t1 == MYO_GEOM_SPHERE && (t2 == MYO_GEOM_SPHERE || t2 == MYO_GEOM_CAPSULE || t2 == MYO_GEOM_BOX)) ||
-             (t1 == MYO_GEOM_CAPSULE && t2 == MYO_GEOM_CAPSULE);
-    };
-    int k = 0;
-    while (k < m->npair && is_std(k)) k++;
-    m->npair_std = k;
-    for (; k < m->npair; ++k)
-      if (is_std(k)) { int rc = fail(MYO_E_ARG, "corrupt model: collision pairs are not ordered (primitive pairs first)"); delete m; return rc; }
+  for (int k = 0; k < m.nsite; ++k) if (m.site_bodyid[k] < 0 || m.site_bodyid[k] >= m.nbody) return corrupt("site_bodyid[%d] = %d", k, m.site_bodyid[k]);
+  for (int t = 0; t < m.ntendon; ++t) {
+    const int a = m.tendon_adr[t], c = m.tendon_num[t];
+    if (a < 0 || c < 0 || a > m.nwrap || c > m.nwrap - a) return corrupt("tendon_adr/num[%d] = %d/%d", t, a, c);
   }
-  // ---- capacity / feature checks
-#define LIM(cond, what) if (cond) { int rc = fail(MYO_E_UNSUPPORTED, "model exceeds stepper capacity: %s", what); delete m; return rc; }
-  LIM(m->nbody > MYO_NB_MAX, "nbody") LIM(m->njnt > MYO_NJ_MAX, "njnt") LIM(m->nv > MYO_NV_MAX, "nv")
-  LIM(m->nq > MYO_NQ_MAX, "nq") LIM(m->ntendon > MYO_NT_MAX, "ntendon") LIM(m->nu > MYO_NU_MAX, "nu")
-  LIM(m->nbody > 64 || m->njnt > 64 || m->ntendon > 64 || m->nu > 64, "more than 64 bodies/joints/tendons/actuators")
-  for (int i = 0; i < m->nu; ++i) LIM(trntype[i] != MYO_TRN_TENDON, "only tendon transmissions are supported")
-  for (int j = 0; j < m->njnt; ++j) LIM(m->jnt_type[j] == MYO_JNT_BALL, "ball joints")
-  // ---- derived tables
-  const int nb = m->nbody, nv = m->nv;
-  m->body_depth.assign(nb, 0);
-  m->maxdepth = 0;
-  for (int b = 1; b < nb; ++b) { m->body_depth[b] = m->body_depth[m->body_parentid[b]] + 1; if (m->body_depth[b] > m->maxdepth) m->maxdepth = m->body_depth[b]; }
-  m->dof_rootbody.resize(nv);
-  for (int d = 0; d < nv; ++d) m->dof_rootbody[d] = m->body_rootid[m->dof_bodyid[d]];
-  m->body_dofmask.assign(nb, 0ull);
+  for (int w = 0; w < m.nwrap; ++w) {
+    const int ty = m.wrap_type[w], id = m.wrap_objid[w];
+    if (ty == MYO_WRAP_SITE && (id < 0 || id >= m.nsite)) return corrupt("wrap_objid[%d] = %d (site)", w, id);
+    if (ty == MYO_WRAP_SPHERE || ty == MYO_WRAP_CYLINDER) {
+      if (id < 0 || id >= m.ngeom) return corrupt("wrap_objid[%d] = %d (geom)", w, id);
+      if (m.wrap_prm[w] >= 0 && !(m.wrap_prm[w] < (double)m.nsite)) return corrupt("wrap_prm[%d]: side site out of range", w);
+    }
+  }
+  for (int i = 0; i < m.nu; ++i) if (x.trntype[i] == MYO_TRN_TENDON && (x.trnid[2 * i] < 0 || x.trnid[2 * i] >= m.ntendon)) return corrupt("actuator_trnid[%d] = %d", i, x.trnid[2 * i]);
+  for (size_t p = 0; p < m.pair_geom1.size(); ++p)
+    if (m.pair_geom1[p] < 0 || m.pair_geom1[p] >= m.ngeom || m.pair_geom2[p] < 0 || m.pair_geom2[p] >= m.ngeom) return corrupt("collision pair %zu names a geom out of range", p);
+  if (!(m.timestep > 0) || !std::isfinite(m.timestep) || m.iterations < 0) return corrupt("opt.timestep / opt.iterations");
+  return MYO_OK;
+}
+
+// pairs of the primitive narrow phases first, the extended ones (csrc/myo_physics.h:collide_pair_ext) after them
+static int order_pairs(myo_model& m) {
+  auto is_std = [&](int p) {
+    const int t1 = m.geom_type[m.pair_geom1[p]], t2 = m.geom_type[m.pair_geom2[p]];
+    return (t1 == MYO_GEOM_PLANE && (t2 == MYO_GEOM_SPHERE || t2 == MYO_GEOM_CAPSULE)) || (t1 == MYO_GEOM_SPHERE && (t2 == MYO_GEOM_SPHERE || t2 == MYO_GEOM_CAPSULE || t2 == MYO_GEOM_BOX)) ||
+           (t1 == MYO_GEOM_CAPSULE && t2 == MYO_GEOM_CAPSULE);
+  };
+  int k = 0;
+  while (k < m.npair && is_std(k)) k++;
+  m.npair_std = k;
+  for (; k < m.npair; ++k)
+    if (is_std(k)) return fail(MYO_E_ARG, "corrupt model: collision pairs are not ordered (primitive pairs first)");
+  return MYO_OK;
+}
+
+// ---- capacity / feature checks that need no derived table
+static int check_capacity(const myo_model& m, const BlobOnly& x) {
+  const struct { int n, cap; const char* what; } sizes[] = {{m.nbody, MYO_NB_MAX, "nbody"}, {m.njnt, MYO_NJ_MAX, "njnt"}, {m.nv, MYO_NV_MAX, "nv"},
+                                                           {m.nq, MYO_NQ_MAX, "nq"}, {m.ntendon, MYO_NT_MAX, "ntendon"}, {m.nu, MYO_NU_MAX, "nu"}};
+  for (const auto& s : sizes) if (s.n > s.cap) return over_capacity(s.what);
+  if (m.nbody > 64 || m.njnt > 64 || m.ntendon > 64 || m.nu > 64) return over_capacity("more than 64 bodies/joints/tendons/actuators");
+  for (int i = 0; i < m.nu; ++i) if (x.trntype[i] != MYO_TRN_TENDON) return over_capacity("only tendon transmissions are supported");
+  for (int j = 0; j < m.njnt; ++j) if (m.jnt_type[j] == MYO_JNT_BALL) return over_capacity("ball joints");
+  return MYO_OK;
+}
+
+// ---- derived tables
+static int build_tree_tables(myo_model& m) {
+  const int nb = m.nbody, nv = m.nv;
+  m.body_depth.assign(nb, 0);
+  m.maxdepth = 0;
+  for (int b = 1; b < nb; ++b) { m.body_depth[b] = m.body_depth[m.body_parentid[b]] + 1; if (m.body_depth[b] > m.maxdepth) m.maxdepth = m.body_depth[b]; }
+  m.dof_rootbody.resize(nv);
+  for (int d = 0; d < nv; ++d) m.dof_rootbody[d] = m.body_rootid[m.dof_bodyid[d]];
+  m.body_dofmask.assign(nb, 0ull);
   for (int b = 1; b < nb; ++b) {
-    unsigned long long mk = m->body_dofmask[m->body_parentid[b]];
-    for (int k = 0; k < m->body_dofnum[b]; ++k) mk |= 1ull << (m->body_dofadr[b] + k);
-    m->body_dofmask[b] = mk;
+    unsigned long long mk = m.body_dofmask[m.body_parentid[b]];
+    for (int k = 0; k < m.body_dofnum[b]; ++k) mk |= 1ull << (m.body_dofadr[b] + k);
+    m.body_dofmask[b] = mk;
   }
-  m->body_submask.assign(nb, 0ull);
+  m.body_submask.assign(nb, 0ull);
   for (int b = nb - 1; b >= 1; --b) {
-    m->body_submask[b] |= 1ull << b;
-    if (m->body_parentid[b] > 0) m->body_submask[m->body_parentid[b]] |= m->body_submask[b];
+    m.body_submask[b] |= 1ull << b;
+    if (m.body_parentid[b] > 0) m.body_submask[m.body_parentid[b]] |= m.body_submask[b];
   }
-  m->dof_prevmask.assign(nv, 0ull);
+  m.dof_prevmask.assign(nv, 0ull);
   for (int d = 0; d < nv; ++d) {
-    const int j = m->dof_jntid[d], b = m->dof_bodyid[d];
+    const int j = m.dof_jntid[d], b = m.dof_bodyid[d];
     unsigned long long below = (d == 0) ? 0ull : ((1ull << d) - 1ull);
-    if (m->jnt_type[j] == MYO_JNT_FREE) {
-      const int da = m->jnt_dofadr[j];
-      if (d < da + 3) m->dof_prevmask[d] = 1ull << 63;  // translational: cdof_dot = 0
-      else m->dof_prevmask[d] = (m->body_dofmask[b] & ((da == 0) ? 0ull : ((1ull << da) - 1ull))) | (7ull << da);
-    } else m->dof_prevmask[d] = m->body_dofmask[b] & below;
+    if (m.jnt_type[j] == MYO_JNT_FREE) {
+      const int da = m.jnt_dofadr[j];
+      if (d < da + 3) m.dof_prevmask[d] = 1ull << 63;  // translational: cdof_dot = 0
+      else m.dof_prevmask[d] = (m.body_dofmask[b] & ((da == 0) ? 0ull : ((1ull << da) - 1ull))) | (7ull << da);
+    } else m.dof_prevmask[d] = m.body_dofmask[b] & below;
   }
   // tree-sparse M (MuJoCo's dof_Madr order: row i holds (i,i),(i,parent),(i,grandparent),...)
-  m->dof_Madr.resize(nv);
-  m->M_i.clear(); m->M_j.clear();
+  m.dof_Madr.resize(nv);
+  m.M_i.clear(); m.M_j.clear();
   for (int i = 0; i < nv; ++i) {
-    m->dof_Madr[i] = (int)m->M_i.size();
-    for (int j = i; j >= 0; j = m->dof_parentid[j]) { m->M_i.push_back(i); m->M_j.push_back(j); }
+    m.dof_Madr[i] = (int)m.M_i.size();
+    for (int j = i; j >= 0; j = m.dof_parentid[j]) { m.M_i.push_back(i); m.M_j.push_back(j); }
   }
-  m->nM = (int)m->M_i.size();
+  m.nM = (int)m.M_i.size();
+  if (m.nM > MYO_NM_MAX) return over_capacity("nM");
   // packed entry table: row | column << 8 | body of the row dof << 16 (one load per entry of the sparse M)
-  m->M_pk.assign(MYO_NM_MAX, 0);
-  for (int e = 0; e < m->nM && e < MYO_NM_MAX; ++e)
-    m->M_pk[e] = m->M_i[e] | (m->M_j[e] << 8) | (m->dof_bodyid[m->M_i[e]] << 16);
-  LIM(m->nM > MYO_NM_MAX, "nM")
-  {
-    std::vector<std::vector<std::pair<int, int>>> rows(nv);
-    for (int e = 0; e < m->nM; ++e) {
-      rows[m->M_i[e]].push_back({m->M_j[e], e});
-      if (m->M_i[e] != m->M_j[e]) rows[m->M_j[e]].push_back({m->M_i[e], e});
-    }
-    m->mv_adr.assign(nv + 1, 0);
-    for (int i = 0; i < nv; ++i) {
-      m->mv_adr[i] = (int)m->mv_col.size();
-      for (auto& pr : rows[i]) { m->mv_col.push_back(pr.first); m->mv_e.push_back(pr.second); }
-    }
-    m->mv_adr[nv] = (int)m->mv_col.size();
-    // the same rows packed for one wide load per dof: 16-bit entries (qM index << 6 | column), two per word
-    m->mv_pack.assign((size_t)nv * (MYO_MV_ROW / 2), 0);
-    m->mv_len.assign(nv, 0);
-    for (int i = 0; i < nv; ++i) {
-      const int len = m->mv_adr[i + 1] - m->mv_adr[i];
-      LIM(len > MYO_MV_ROW, "a row of the inertia matrix has more than MYO_MV_ROW non-zeros")
-      m->mv_len[i] = len;
-      for (int k = 0; k < len; ++k) {
-        const unsigned ent = ((unsigned)m->mv_e[m->mv_adr[i] + k] << 6) | (unsigned)m->mv_col[m->mv_adr[i] + k];
-        unsigned& w = reinterpret_cast<unsigned&>(m->mv_pack[(size_t)i * (MYO_MV_ROW / 2) + k / 2]);
-        w |= (k & 1) ? (ent << 16) : ent;
-      }
-    }
+  m.M_pk.assign(MYO_NM_MAX, 0);
+  for (int e = 0; e < m.nM; ++e)
+    m.M_pk[e] = m.M_i[e] | (m.M_j[e] << 8) | (m.dof_bodyid[m.M_i[e]] << 16);
+  std::vector<std::vector<std::pair<int, int>>> rows(nv);
+  for (int e = 0; e < m.nM; ++e) {
+    rows[m.M_i[e]].push_back({m.M_j[e], e});
+    if (m.M_i[e] != m.M_j[e]) rows[m.M_j[e]].push_back({m.M_i[e], e});
   }
-  // tendons: dofs each one can move; side sites
-  m->tendon_dofmask.assign(m->ntendon, 0ull);
-  m->wrap_side.assign(m->nwrap, -1);
-  for (int t = 0; t < m->ntendon; ++t) {
+  m.mv_adr.assign(nv + 1, 0);
+  for (int i = 0; i < nv; ++i) {
+    m.mv_adr[i] = (int)m.mv_col.size();
+    for (auto& pr : rows[i]) { m.mv_col.push_back(pr.first); m.mv_e.push_back(pr.second); }
+  }
+  m.mv_adr[nv] = (int)m.mv_col.size();
+  // the same rows packed for one wide load per dof: 16-bit entries (qM index << 6 | column), two per word
+  m.mv_pack.assign((size_t)nv * (MYO_MV_ROW / 2), 0);
+  m.mv_len.assign(nv, 0);
+  for (int i = 0; i < nv; ++i) {
+    const int len = m.mv_adr[i + 1] - m.mv_adr[i];
+    if (len > MYO_MV_ROW) return over_capacity("a row of the inertia matrix has more than MYO_MV_ROW non-zeros");
+    m.mv_len[i] = len;
+    for (int k = 0; k < len; ++k)
+      pack16(&m.mv_pack[(size_t)i * (MYO_MV_ROW / 2)], k, ((unsigned)m.mv_e[m.mv_adr[i] + k] << 6) | (unsigned)m.mv_col[m.mv_adr[i] + k]);
+  }
+  return MYO_OK;
+}
+
+// tendons: dofs each one can move; side sites
+static int build_wrap_records(myo_model& m, const BlobOnly& x) {
+  m.tendon_dofmask.assign(m.ntendon, 0ull);
+  m.wrap_side.assign(m.nwrap, -1);
+  for (int t = 0; t < m.ntendon; ++t) {
     unsigned long long mk = 0;
-    for (int w = m->tendon_adr[t]; w < m->tendon_adr[t] + m->tendon_num[t]; ++w) {
-      const int ty = m->wrap_type[w];
-      if (ty == MYO_WRAP_SITE) mk |= m->body_dofmask[m->site_bodyid[m->wrap_objid[w]]];
+    for (int w = m.tendon_adr[t]; w < m.tendon_adr[t] + m.tendon_num[t]; ++w) {
+      const int ty = m.wrap_type[w];
+      if (ty == MYO_WRAP_SITE) mk |= m.body_dofmask[m.site_bodyid[m.wrap_objid[w]]];
       else if (ty == MYO_WRAP_SPHERE || ty == MYO_WRAP_CYLINDER) {
-        mk |= m->body_dofmask[m->geom_bodyid[m->wrap_objid[w]]];
-        m->wrap_side[w] = m->wrap_prm[w] >= 0 ? (int)lround(m->wrap_prm[w]) : -1;
-      } else if (ty != MYO_WRAP_PULLEY) LIM(true, "fixed (joint) tendons")
+        mk |= m.body_dofmask[m.geom_bodyid[m.wrap_objid[w]]];
+        m.wrap_side[w] = m.wrap_prm[w] >= 0 ? (int)lround(m.wrap_prm[w]) : -1;
+      } else if (ty != MYO_WRAP_PULLEY) return over_capacity("fixed (joint) tendons");
     }
-    m->tendon_dofmask[t] = mk;
-    int cnt = 0;
-    for (unsigned long long x = mk; x; x &= x - 1) cnt++;
-    LIM(cnt > MYO_TJ_MAX, "a tendon moves more than MYO_TJ_MAX dofs")
+    m.tendon_dofmask[t] = mk;
+    if (popcount64(mk) > MYO_TJ_MAX) return over_capacity("a tendon moves more than MYO_TJ_MAX dofs");
   }
   // resolved wrap records: everything the tendon stage needs about wrap object w behind ONE level of
   // indexing (the stage is bound by dependent table loads otherwise: type -> objid -> bodyid -> pos):
@@ -674,124 +697,134 @@ static int model_from_blob_impl(const void* blob, size_t nbytes, myo_model** out
   //   wr_p[4w..]  = local position (site_pos / geom_pos), pulley divisor
   //   wr_m[12w..] = geom_mat (9), side-site local position (3)
   //   wr_mask[w]  = body_dofmask[body]
-  m->wr_i.assign(8 * (size_t)m->nwrap, 0);
-  m->wr_p.assign(4 * (size_t)m->nwrap, 0.0);
-  m->wr_m.assign(12 * (size_t)m->nwrap, 0.0);
-  m->wr_mask.assign(m->nwrap, 0ull);
-  for (int w = 0; w < m->nwrap; ++w) {
-    const int ty = m->wrap_type[w], id = m->wrap_objid[w];
-    int* I = &m->wr_i[8 * (size_t)w];
+  m.wr_i.assign(8 * (size_t)m.nwrap, 0);
+  m.wr_p.assign(4 * (size_t)m.nwrap, 0.0);
+  m.wr_m.assign(12 * (size_t)m.nwrap, 0.0);
+  m.wr_mask.assign(m.nwrap, 0ull);
+  for (int w = 0; w < m.nwrap; ++w) {
+    const int ty = m.wrap_type[w], id = m.wrap_objid[w];
+    int* I = &m.wr_i[8 * (size_t)w];
     I[0] = ty; I[1] = -1; I[2] = -1; I[3] = -1; I[4] = 0; I[5] = 0;
     if (ty == MYO_WRAP_SITE) {
-      I[1] = m->site_bodyid[id];
-      for (int k = 0; k < 3; ++k) m->wr_p[4 * (size_t)w + k] = m->site_pos[3 * id + k];
+      I[1] = m.site_bodyid[id];
+      for (int k = 0; k < 3; ++k) m.wr_p[4 * (size_t)w + k] = m.site_pos[3 * id + k];
     } else if (ty == MYO_WRAP_SPHERE || ty == MYO_WRAP_CYLINDER) {
-      I[1] = m->geom_bodyid[id]; I[2] = id;
-      for (int k = 0; k < 3; ++k) m->wr_p[4 * (size_t)w + k] = m->geom_pos[3 * id + k];
+      I[1] = m.geom_bodyid[id]; I[2] = id;
+      for (int k = 0; k < 3; ++k) m.wr_p[4 * (size_t)w + k] = m.geom_pos[3 * id + k];
       double gm[9];
-      quat2mat_h(&geom_quat[4 * id], gm);
-      for (int k = 0; k < 9; ++k) m->wr_m[12 * (size_t)w + k] = gm[k];
-      const int sid = m->wrap_side[w];
+      quat2mat_h(&x.geom_quat[4 * id], gm);
+      for (int k = 0; k < 9; ++k) m.wr_m[12 * (size_t)w + k] = gm[k];
+      const int sid = m.wrap_side[w];
       if (sid >= 0) {
-        I[3] = m->site_bodyid[sid]; I[5] = m->body_rootid[I[3]];
-        for (int k = 0; k < 3; ++k) m->wr_m[12 * (size_t)w + 9 + k] = m->site_pos[3 * sid + k];
+        I[3] = m.site_bodyid[sid]; I[5] = m.body_rootid[I[3]];
+        for (int k = 0; k < 3; ++k) m.wr_m[12 * (size_t)w + 9 + k] = m.site_pos[3 * sid + k];
       }
-    } else if (ty == MYO_WRAP_PULLEY) m->wr_p[4 * (size_t)w + 3] = m->wrap_prm[w];
-    if (I[1] >= 0) { I[4] = m->body_rootid[I[1]]; m->wr_mask[w] = m->body_dofmask[I[1]]; }
+    } else if (ty == MYO_WRAP_PULLEY) m.wr_p[4 * (size_t)w + 3] = m.wrap_prm[w];
+    if (I[1] >= 0) { I[4] = m.body_rootid[I[1]]; m.wr_mask[w] = m.body_dofmask[I[1]]; }
   }
   // geom wraps, enumerated: gw_elem[k] = path element of the k-th sphere/cylinder wrap; wr_i[8w+6] = k
-  m->gw_elem.clear();
-  for (int w = 0; w < m->nwrap; ++w) {
-    m->wr_i[8 * (size_t)w + 6] = -1;
-    if (m->wrap_type[w] == MYO_WRAP_SPHERE || m->wrap_type[w] == MYO_WRAP_CYLINDER) {
-      m->wr_i[8 * (size_t)w + 6] = (int)m->gw_elem.size();
-      m->gw_elem.push_back(w);
+  m.gw_elem.clear();
+  for (int w = 0; w < m.nwrap; ++w) {
+    m.wr_i[8 * (size_t)w + 6] = -1;
+    if (m.wrap_type[w] == MYO_WRAP_SPHERE || m.wrap_type[w] == MYO_WRAP_CYLINDER) {
+      m.wr_i[8 * (size_t)w + 6] = (int)m.gw_elem.size();
+      m.gw_elem.push_back(w);
     }
   }
-  m->ngw = (int)m->gw_elem.size();
-  if (m->gw_elem.empty()) m->gw_elem.push_back(0);
-  // path elements, enumerated (the walk mj_tendon makes along each tendon, resolved once): element e runs from the site
-  // te_i[4e] to the site te_i[4e+1], around the wrap geom te_i[4e+2] (-1: straight), belongs to tendon te_i[4e+3] and
-  // counts with 1 / te_div[e] (the last pulley before it).  The tendon stage gives each element its own lane.
-  m->te_i.clear(); m->te_div.clear();
-  m->tendon_eadr.assign(m->ntendon, 0); m->tendon_enum.assign(m->ntendon, 0);
-  for (int t = 0; t < m->ntendon; ++t) {
-    const int adr = m->tendon_adr[t], num = m->tendon_num[t];
+  m.ngw = (int)m.gw_elem.size();
+  if (m.gw_elem.empty()) m.gw_elem.push_back(0);
+  return MYO_OK;
+}
+
+// path elements, enumerated (the walk mj_tendon makes along each tendon, resolved once): element e runs from the site
+// te_i[4e] to the site te_i[4e+1], around the wrap geom te_i[4e+2] (-1: straight), belongs to tendon te_i[4e+3] and
+// counts with 1 / te_div[e] (the last pulley before it).  The tendon stage gives each element its own lane.
+static int build_path_elements(myo_model& m) {
+  m.te_i.clear(); m.te_div.clear();
+  m.tendon_eadr.assign(m.ntendon, 0); m.tendon_enum.assign(m.ntendon, 0);
+  for (int t = 0; t < m.ntendon; ++t) {
+    const int adr = m.tendon_adr[t], num = m.tendon_num[t];
     double divisor = 1.0;
-    m->tendon_eadr[t] = (int)m->te_div.size();
+    m.tendon_eadr[t] = (int)m.te_div.size();
     for (int j = 0; j < num - 1;) {
-      const int ty0 = m->wrap_type[adr + j], ty1 = m->wrap_type[adr + j + 1];
+      const int ty0 = m.wrap_type[adr + j], ty1 = m.wrap_type[adr + j + 1];
       if (ty0 == MYO_WRAP_PULLEY || ty1 == MYO_WRAP_PULLEY) {
-        if (ty0 == MYO_WRAP_PULLEY) divisor = m->wrap_prm[adr + j];
+        if (ty0 == MYO_WRAP_PULLEY) divisor = m.wrap_prm[adr + j];
         j++;
         continue;
       }
       const int is_geom = (ty1 == MYO_WRAP_SPHERE || ty1 == MYO_WRAP_CYLINDER);
-      LIM(is_geom && j + 2 >= num, "a tendon path ends on a wrap geom")
+      if (is_geom && j + 2 >= num) return over_capacity("a tendon path ends on a wrap geom");
       const int end = j + (is_geom ? 2 : 1);
-      m->te_i.push_back(adr + j); m->te_i.push_back(adr + end); m->te_i.push_back(is_geom ? adr + j + 1 : -1); m->te_i.push_back(t);
-      m->te_div.push_back(divisor);
+      m.te_i.push_back(adr + j); m.te_i.push_back(adr + end); m.te_i.push_back(is_geom ? adr + j + 1 : -1); m.te_i.push_back(t);
+      m.te_div.push_back(divisor);
       j = end;
     }
-    m->tendon_enum[t] = (int)m->te_div.size() - m->tendon_eadr[t];
+    m.tendon_enum[t] = (int)m.te_div.size() - m.tendon_eadr[t];
   }
-  m->nte = (int)m->te_div.size();
+  m.nte = (int)m.te_div.size();
   // element lengths are staged (HP) in the part of H that is free during the tendon stage (behind cinert)
-  LIM((size_t)m->nte * sizeof(double) > (size_t)(MYO_H_SIZE - MYO_NB_MAX * 10) * sizeof(float), "tendon path elements (length staging)")
-  if (m->te_div.empty()) { m->te_i.assign(4, 0); m->te_div.push_back(1.0); }
+  if ((size_t)m.nte * sizeof(double) > (size_t)(MYO_H_SIZE - MYO_NB_MAX * 10) * sizeof(float)) return over_capacity("tendon path elements (length staging)");
+  if (m.te_div.empty()) { m.te_i.assign(4, 0); m.te_div.push_back(1.0); }
   // staging area of the tendon stage.  Mixed stepper: T path points in con[], then (8-byte aligned) 7 HP wrap results per geom wrap,
   // running on through the limit-row, efc_* and solver vectors up to rk.  fp64 stepper: the wrap results only, up to the solver
   // vectors (where its body poses live during the position stage)
   typedef Scratch<double, MYO_NCON_F64> ScratchD;
-  typedef Scratch<double, MYO_NCON_BIG> ScratchDB;
   // (... and not beyond efc_jv, where that stepper accumulates the tendon moment arms meanwhile)
-  LIM(7 * (size_t)m->ngw * sizeof(double) > offsetof(ScratchD, efc_jv) - offsetof(ScratchD, con) ||
-      m->ngw > MYO_BIGWS_GW ||                     /* (the 48-slot fp64 scratch: in the big workspace, TaskDev::big_ws) */
-      ((3 * (size_t)m->nwrap * sizeof(float) + 7) & ~(size_t)7) + 7 * (size_t)m->ngw * sizeof(double) >
-          offsetof(Scratch<float>, rk) - offsetof(Scratch<float>, con), "tendon path elements / wrap geoms (staging area of the tendon stage)")
-  m->actuator_tendon.resize(m->nu);
-  for (int i = 0; i < m->nu; ++i) m->actuator_tendon[i] = trnid[2 * i];
+  if (7 * (size_t)m.ngw * sizeof(double) > offsetof(ScratchD, efc_jv) - offsetof(ScratchD, con) ||
+      m.ngw > MYO_BIGWS_GW ||                     /* (the 48-slot fp64 scratch: in the big workspace, TaskDev::big_ws) */
+      ((3 * (size_t)m.nwrap * sizeof(float) + 7) & ~(size_t)7) + 7 * (size_t)m.ngw * sizeof(double) >
+          offsetof(Scratch<float>, rk) - offsetof(Scratch<float>, con))
+    return over_capacity("tendon path elements / wrap geoms (staging area of the tendon stage)");
+  return MYO_OK;
+}
+
+static int build_actuator_gather(myo_model& m, const BlobOnly& x) {
+  const int nv = m.nv;
+  m.actuator_tendon.resize(m.nu);
+  for (int i = 0; i < m.nu; ++i) m.actuator_tendon[i] = x.trnid[2 * i];
   // qfrc_actuator gather, dof-major: for dof d the (ten_J offset << 6 | actuator) pairs of every
   // actuator whose tendon moves d, in actuator order; 16-bit entries, two per word (one wide load per dof)
-  m->aq_pack.assign((size_t)nv * (MYO_AQ_ROW / 2), 0);
-  m->aq_len.assign(nv, 0);
+  m.aq_pack.assign((size_t)nv * (MYO_AQ_ROW / 2), 0);
+  m.aq_len.assign(nv, 0);
   for (int d = 0; d < nv; ++d) {
     int len = 0;
-    for (int i = 0; i < m->nu; ++i) {
-      const int t = m->actuator_tendon[i];
-      const unsigned long long mk = m->tendon_dofmask[t];
+    for (int i = 0; i < m.nu; ++i) {
+      const int t = m.actuator_tendon[i];
+      const unsigned long long mk = m.tendon_dofmask[t];
       if (!((mk >> d) & 1ull)) continue;
-      LIM(len >= MYO_AQ_ROW, "more than MYO_AQ_ROW actuators act on one dof")
-      int slot = 0;
-      for (int b = 0; b < d; ++b) slot += (int)((mk >> b) & 1ull);
-      const unsigned ent = ((unsigned)(t * MYO_TJ_MAX + slot) << 6) | (unsigned)i;
-      unsigned& w = reinterpret_cast<unsigned&>(m->aq_pack[(size_t)d * (MYO_AQ_ROW / 2) + len / 2]);
-      w |= (len & 1) ? (ent << 16) : ent;
+      if (len >= MYO_AQ_ROW) return over_capacity("more than MYO_AQ_ROW actuators act on one dof");
+      const int slot = popcount64(mk & ((1ull << d) - 1ull));      // the tendon's moving dofs below d
+      pack16(&m.aq_pack[(size_t)d * (MYO_AQ_ROW / 2)], len, ((unsigned)(t * MYO_TJ_MAX + slot) << 6) | (unsigned)i);
       len++;
     }
-    m->aq_len[d] = len;
+    m.aq_len[d] = len;
   }
   // actuator-major copies for the moment-transpose gather, zero-padded to MYO_NU_MAX so the loop
   // runs in unconditional groups of 8 (scalar loads merge into s_load_dwordx8/x16)
-  m->act_dofmask.assign(MYO_NU_MAX, 0ull);
-  m->act_tj.assign(MYO_NU_MAX, 0);
-  m->act_gear0.assign(MYO_NU_MAX, 0.0);
-  m->act_sd.assign((size_t)MYO_NU_MAX * MYO_TJ_MAX, -1);      // dof of slot k of actuator i's tendon (-1: the tendon moves fewer dofs)
-  for (int i = 0; i < m->nu; ++i) {
-    m->act_dofmask[i] = m->tendon_dofmask[m->actuator_tendon[i]];
-    m->act_tj[i] = m->actuator_tendon[i] * MYO_TJ_MAX;
-    m->act_gear0[i] = m->actuator_gear[6 * i];
-    { int k = 0; for (int d = 0; d < nv && k < MYO_TJ_MAX; ++d) if ((m->act_dofmask[i] >> d) & 1ull) m->act_sd[(size_t)i * MYO_TJ_MAX + k++] = d; }
+  m.act_dofmask.assign(MYO_NU_MAX, 0ull);
+  m.act_tj.assign(MYO_NU_MAX, 0);
+  m.act_gear0.assign(MYO_NU_MAX, 0.0);
+  m.act_sd.assign((size_t)MYO_NU_MAX * MYO_TJ_MAX, -1);      // dof of slot k of actuator i's tendon (-1: the tendon moves fewer dofs)
+  for (int i = 0; i < m.nu; ++i) {
+    m.act_dofmask[i] = m.tendon_dofmask[m.actuator_tendon[i]];
+    m.act_tj[i] = m.actuator_tendon[i] * MYO_TJ_MAX;
+    m.act_gear0[i] = m.actuator_gear[6 * i];
+    { int k = 0; for (int d = 0; d < nv && k < MYO_TJ_MAX; ++d) if ((m.act_dofmask[i] >> d) & 1ull) m.act_sd[(size_t)i * MYO_TJ_MAX + k++] = d; }
   }
-  // muscle constants of every actuator (fwd_actuation: what mju_muscleGain / mju_muscleBias / mju_muscleDynamics derive from the
-  // parameters alone, with every constant denominator turned into a reciprocal): MYO_ACT_PRE doubles per actuator, see myo_physics.h
-  m->act_pre.assign((size_t)MYO_NU_MAX * MYO_ACT_PRE, 0.0);
-  for (int i = 0; i < m->nu; ++i) {
-    double* P = &m->act_pre[(size_t)i * MYO_ACT_PRE];
-    const double* gp = &m->actuator_gainprm[10 * (size_t)i];
-    const double* bp = &m->actuator_biasprm[10 * (size_t)i];
-    const double* dp = &m->actuator_dynprm[10 * (size_t)i];
-    const double lr0 = m->actuator_lengthrange[2 * (size_t)i], lr1 = m->actuator_lengthrange[2 * (size_t)i + 1], acc0 = m->actuator_acc0[i];
+  return MYO_OK;
+}
+
+// muscle constants of every actuator (fwd_actuation: what mju_muscleGain / mju_muscleBias / mju_muscleDynamics derive from the
+// parameters alone, with every constant denominator turned into a reciprocal): MYO_ACT_PRE doubles per actuator, see myo_physics.h
+static void build_muscle_constants(myo_model& m) {
+  m.act_pre.assign((size_t)MYO_NU_MAX * MYO_ACT_PRE, 0.0);
+  for (int i = 0; i < m.nu; ++i) {
+    double* P = &m.act_pre[(size_t)i * MYO_ACT_PRE];
+    const double* gp = &m.actuator_gainprm[10 * (size_t)i];
+    const double* bp = &m.actuator_biasprm[10 * (size_t)i];
+    const double* dp = &m.actuator_dynprm[10 * (size_t)i];
+    const double lr0 = m.actuator_lengthrange[2 * (size_t)i], lr1 = m.actuator_lengthrange[2 * (size_t)i + 1], acc0 = m.actuator_acc0[i];
     const double tiny = 1e-15;
     {   // gain
       const double force = gp[2] < 0 ? gp[3] / std::max(tiny, acc0) : gp[2];
@@ -811,161 +844,200 @@ static int model_from_blob_impl(const void* blob, size_t nbytes, myo_model** out
     // activation dynamics: 1 / tau_deact when tau = tau_deact / (0.5 + 1.5 act) can never reach the floor (act in [0, 1]); else 0: the formula as written
     P[22] = dp[1] / 2.0 >= tiny ? 1.0 / dp[1] : 0.0;
   }
-  // per-lane records (myo_model_dev.h: bk_i / bk_f / jk_i / dk_i / dof_spr / dof_submask): what a body / joint / dof lane reads in a
-  // stage, behind ONE index instead of body -> joint -> qpos chains of dependent vector loads
-  {
-    const int njnt = m->njnt;
-    m->bk_i.assign((size_t)MYO_BK_I * (nb > 0 ? nb : 1), 0);
-    m->bk_f.assign((size_t)MYO_BK_F * (nb > 0 ? nb : 1), 0.0);
-    for (int b = 0; b < nb; ++b) {
-      int* I = &m->bk_i[(size_t)MYO_BK_I * b];
-      double* F = &m->bk_f[(size_t)MYO_BK_F * b];
-      const int jn = m->body_jntnum[b], ja = m->body_jntadr[b];
-      const bool is_free = jn == 1 && m->jnt_type[ja] == MYO_JNT_FREE;
-      LIM(jn > MYO_BK_NJ, "more than three joints on one body")
-      I[0] = m->body_depth[b]; I[1] = m->body_parentid[b]; I[2] = jn; I[3] = ja; I[4] = is_free ? 1 : 0;
-      for (int k = 0; k < 3; ++k) F[k] = m->body_pos[3 * (size_t)b + k];
-      for (int k = 0; k < 4; ++k) F[3 + k] = m->body_quat[4 * (size_t)b + k];
-      for (int k = 0; k < jn && k < MYO_BK_NJ; ++k) {
-        const int j = ja + k, qa = m->jnt_qposadr[j];
-        I[5 + k] = qa; I[8 + k] = m->jnt_type[j];
-        for (int e = 0; e < 3; ++e) { F[7 + 7 * k + e] = m->jnt_pos[3 * (size_t)j + e]; F[10 + 7 * k + e] = m->jnt_axis[3 * (size_t)j + e]; }
-        F[13 + 7 * k] = m->qpos0[qa];
-      }
-    }
-    m->jk_i.assign((size_t)4 * (njnt > 0 ? njnt : 1), 0);
-    for (int j = 0; j < njnt; ++j) {
-      int* I = &m->jk_i[(size_t)4 * j];
-      I[0] = m->jnt_bodyid[j]; I[1] = m->jnt_dofadr[j]; I[2] = m->jnt_type[j]; I[3] = m->body_rootid[m->jnt_bodyid[j]];
-    }
-    m->dk_i.assign((size_t)2 * (nv > 0 ? nv : 1), 0);
-    m->dof_spr.assign((size_t)2 * (nv > 0 ? nv : 1), 0.0);
-    m->dof_submask.assign(nv > 0 ? nv : 1, 0ull);
-    for (int d = 0; d < nv; ++d) {
-      const int j = m->dof_jntid[d], qa = m->jnt_qposadr[j];
-      m->dk_i[(size_t)2 * d] = qa;
-      const bool spring = m->jnt_type[j] != MYO_JNT_FREE && m->jnt_stiffness[j] != 0;
-      m->dof_spr[(size_t)2 * d] = spring ? m->jnt_stiffness[j] : 0.0;
-      m->dof_spr[(size_t)2 * d + 1] = m->qpos_spring[qa];
-      m->dof_submask[d] = m->body_submask[m->dof_bodyid[d]];
-    }
-  }
+}
+
+// per-lane records (myo_model_dev.h: bk_i / bk_f / jk_i / dk_i / dof_spr / dof_submask): what a body / joint / dof lane reads in a
+// stage, behind ONE index instead of body -> joint -> qpos chains of dependent vector loads
+static int build_lane_records(myo_model& m) {
+  const int nb = m.nbody, nv = m.nv, njnt = m.njnt;
+  m.bk_i.assign((size_t)MYO_BK_I * (nb > 0 ? nb : 1), 0);
+  m.bk_f.assign((size_t)MYO_BK_F * (nb > 0 ? nb : 1), 0.0);
   for (int b = 0; b < nb; ++b) {
-    int cnt = 0;
-    for (unsigned long long x = m->body_dofmask[b]; x; x &= x - 1) cnt++;
-    LIM(2 * cnt > MYO_CS_MAX + 4 && false, "contact support")
+    int* I = &m.bk_i[(size_t)MYO_BK_I * b];
+    double* F = &m.bk_f[(size_t)MYO_BK_F * b];
+    const int jn = m.body_jntnum[b], ja = m.body_jntadr[b];
+    const bool is_free = jn == 1 && m.jnt_type[ja] == MYO_JNT_FREE;
+    if (jn > MYO_BK_NJ) return over_capacity("more than three joints on one body");
+    I[0] = m.body_depth[b]; I[1] = m.body_parentid[b]; I[2] = jn; I[3] = ja; I[4] = is_free ? 1 : 0;
+    for (int k = 0; k < 3; ++k) F[k] = m.body_pos[3 * (size_t)b + k];
+    for (int k = 0; k < 4; ++k) F[3 + k] = m.body_quat[4 * (size_t)b + k];
+    for (int k = 0; k < jn && k < MYO_BK_NJ; ++k) {
+      const int j = ja + k, qa = m.jnt_qposadr[j];
+      I[5 + k] = qa; I[8 + k] = m.jnt_type[j];
+      for (int e = 0; e < 3; ++e) { F[7 + 7 * k + e] = m.jnt_pos[3 * (size_t)j + e]; F[10 + 7 * k + e] = m.jnt_axis[3 * (size_t)j + e]; }
+      F[13 + 7 * k] = m.qpos0[qa];
+    }
   }
-  // per-pair contact records: everything mj_contactParam / the constraint build derive from the two geoms
-  // alone is resolved here (the device stage was a chain of dependent table loads per contact):
-  //   pc_i[8p..]  = body1, body2, root body 1, root body 2, nsup, box-box candidate (0 none; 1 + v: vertex v of geom 1 against
-  //                 geom 2, 9 + v: vertex v of geom 2 against geom 1, 17: the edge-edge candidate), 0, friction selector (0 max, 1 geom1, 2 geom2)
-  //   pc_sup[4p..] = the dofs either body can move (<= 16 bytes, ascending)
-  //   pc_f[16p..] = margin, margin - gap, (K, B) and (d0, d1, 1 / width, mid, power) of the mixed solref[2] / solimp[5] (sol_precompute), friction1[3], friction2[3], invweight sum
-  //   pc_mask[2p..] = ancestor-dof masks of the two bodies
-  {
-    const int np = m->npair > 0 ? m->npair : 1;
-    m->pc_i.assign(8 * (size_t)np, 0); m->pc_sup.assign(4 * (size_t)np, 0);
-    m->pc_f.assign(16 * (size_t)np, 0.0); m->pc_mask.assign(2 * (size_t)np, 0ull);
-    m->pair_mg.assign(2 * (size_t)np, 0.0);     // margin, margin - gap per pair row (HP copy on the device: the general narrow-phase path reads them)
+  m.jk_i.assign((size_t)4 * (njnt > 0 ? njnt : 1), 0);
+  for (int j = 0; j < njnt; ++j) {
+    int* I = &m.jk_i[(size_t)4 * j];
+    I[0] = m.jnt_bodyid[j]; I[1] = m.jnt_dofadr[j]; I[2] = m.jnt_type[j]; I[3] = m.body_rootid[m.jnt_bodyid[j]];
   }
-  m->any_rot = 0; m->any_gen = 0;
-  for (int p = 0; p < m->npair; ++p) {
-    const int g1 = m->pair_geom1[p], g2 = m->pair_geom2[p];
-    const int b1 = m->geom_bodyid[g1], b2 = m->geom_bodyid[g2];
-    const unsigned long long m1 = m->body_dofmask[b1], m2 = m->body_dofmask[b2];
+  m.dk_i.assign((size_t)2 * (nv > 0 ? nv : 1), 0);
+  m.dof_spr.assign((size_t)2 * (nv > 0 ? nv : 1), 0.0);
+  m.dof_submask.assign(nv > 0 ? nv : 1, 0ull);
+  for (int d = 0; d < nv; ++d) {
+    const int j = m.dof_jntid[d], qa = m.jnt_qposadr[j];
+    m.dk_i[(size_t)2 * d] = qa;
+    const bool spring = m.jnt_type[j] != MYO_JNT_FREE && m.jnt_stiffness[j] != 0;
+    m.dof_spr[(size_t)2 * d] = spring ? m.jnt_stiffness[j] : 0.0;
+    m.dof_spr[(size_t)2 * d + 1] = m.qpos_spring[qa];
+    m.dof_submask[d] = m.body_submask[m.dof_bodyid[d]];
+  }
+  return MYO_OK;
+}
+
+// MuJoCo's mix of two geoms' solver parameters (mj_contactParam): all of the higher-priority geom's, else by solmix
+static double pair_solmix(const myo_model& m, int g1, int g2) {
+  const int pr1 = m.geom_priority[g1], pr2 = m.geom_priority[g2];
+  if (pr1 != pr2) return pr1 > pr2 ? 1.0 : 0.0;
+  const double x1 = m.geom_solmix[g1], x2 = m.geom_solmix[g2];
+  const double tiny = 1e-15;      // MYO_MINVAL
+  if (x1 >= tiny && x2 >= tiny) return x1 / (x1 + x2);
+  if (x1 < tiny && x2 < tiny) return 0.5;
+  return x1 < tiny ? 0.0 : 1.0;
+}
+// per-pair contact records: everything mj_contactParam / the constraint build derive from the two geoms
+// alone is resolved here (the device stage was a chain of dependent table loads per contact):
+//   pc_i[8p..]  = body1, body2, root body 1, root body 2, nsup, box-box candidate (0 none; 1 + v: vertex v of geom 1 against
+//                 geom 2, 9 + v: vertex v of geom 2 against geom 1, 17: the edge-edge candidate), 0, friction selector (0 max, 1 geom1, 2 geom2)
+//   pc_sup[4p..] = the dofs either body can move (<= 16 bytes, ascending)
+//   pc_f[16p..] = margin, margin - gap, (K, B) and (d0, d1, 1 / width, mid, power) of the mixed solref[2] / solimp[5] (sol_precompute), friction1[3], friction2[3], invweight sum
+//   pc_mask[2p..] = ancestor-dof masks of the two bodies
+static int build_pair_records(myo_model& m, const BlobOnly& x) {
+  const int np = m.npair > 0 ? m.npair : 1;
+  m.pc_i.assign(8 * (size_t)np, 0); m.pc_sup.assign(4 * (size_t)np, 0);
+  m.pc_f.assign(16 * (size_t)np, 0.0); m.pc_mask.assign(2 * (size_t)np, 0ull);
+  m.pair_mg.assign(2 * (size_t)np, 0.0);     // margin, margin - gap per pair row (HP copy on the device: the general narrow-phase path reads them)
+  m.any_rot = 0; m.any_gen = 0;
+  for (int p = 0; p < m.npair; ++p) {
+    const int g1 = m.pair_geom1[p], g2 = m.pair_geom2[p];
+    const int b1 = m.geom_bodyid[g1], b2 = m.geom_bodyid[g2];
+    const unsigned long long m1 = m.body_dofmask[b1], m2 = m.body_dofmask[b2];
     unsigned long long mk = m1 | m2;
-    int cnt = 0;
-    for (unsigned long long x = mk; x; x &= x - 1) cnt++;
-    LIM(cnt > MYO_CS_MAX, "a contact pair moves more than MYO_CS_MAX dofs")
-    int* I = &m->pc_i[8 * (size_t)p];
-    I[0] = b1; I[1] = b2; I[2] = m->body_rootid[b1]; I[3] = m->body_rootid[b2]; I[4] = cnt; I[5] = pair_sub[p];
-    unsigned char* sup = reinterpret_cast<unsigned char*>(&m->pc_sup[4 * (size_t)p]);
+    const int cnt = popcount64(mk);
+    if (cnt > MYO_CS_MAX) return over_capacity("a contact pair moves more than MYO_CS_MAX dofs");
+    int* I = &m.pc_i[8 * (size_t)p];
+    I[0] = b1; I[1] = b2; I[2] = m.body_rootid[b1]; I[3] = m.body_rootid[b2]; I[4] = cnt; I[5] = x.pair_sub[p];
+    unsigned char* sup = reinterpret_cast<unsigned char*>(&m.pc_sup[4 * (size_t)p]);
     // (bit 6 / bit 7 of an entry: ancestor dof of body 1 / body 2 — ContactRec::sup)
     { int ns = 0; for (int d = 0; d < 64 && ns < MYO_CS_MAX; ++d) if ((mk >> d) & 1ull) sup[ns++] = (unsigned char)(d | (int)((m1 >> d) & 1ull) << 6 | (int)((m2 >> d) & 1ull) << 7); }
-    m->pc_mask[2 * (size_t)p] = m1; m->pc_mask[2 * (size_t)p + 1] = m2;
-    const int pr1 = m->geom_priority[g1], pr2 = m->geom_priority[g2];
-    double mix;
-    if (pr1 != pr2) mix = pr1 > pr2 ? 1.0 : 0.0;
-    else {
-      const double x1 = m->geom_solmix[g1], x2 = m->geom_solmix[g2];
-      const double tiny = 1e-15;      // MYO_MINVAL
-      if (x1 >= tiny && x2 >= tiny) mix = x1 / (x1 + x2);
-      else if (x1 < tiny && x2 < tiny) mix = 0.5;
-      else mix = x1 < tiny ? 0.0 : 1.0;
-    }
-    double* F = &m->pc_f[16 * (size_t)p];
-    const double margin = std::max(m->geom_margin[g1], m->geom_margin[g2]);
-    F[0] = margin; F[1] = margin - std::max(m->geom_gap[g1], m->geom_gap[g2]);
-    const double *r1 = &m->geom_solref[2 * g1], *r2 = &m->geom_solref[2 * g2];
+    m.pc_mask[2 * (size_t)p] = m1; m.pc_mask[2 * (size_t)p + 1] = m2;
+    const int pr1 = m.geom_priority[g1], pr2 = m.geom_priority[g2];
+    const double mix = pair_solmix(m, g1, g2);
+    double* F = &m.pc_f[16 * (size_t)p];
+    const double margin = std::max(m.geom_margin[g1], m.geom_margin[g2]);
+    F[0] = margin; F[1] = margin - std::max(m.geom_gap[g1], m.geom_gap[g2]);
+    const double *r1 = &m.geom_solref[2 * g1], *r2 = &m.geom_solref[2 * g2];
     for (int e = 0; e < 2; ++e) F[2 + e] = (r1[0] > 0 && r2[0] > 0) ? mix * r1[e] + (1 - mix) * r2[e] : std::min(r1[e], r2[e]);
-    for (int e = 0; e < 5; ++e) F[4 + e] = mix * m->geom_solimp[5 * g1 + e] + (1 - mix) * m->geom_solimp[5 * g2 + e];
-    for (int e = 0; e < 3; ++e) { F[9 + e] = m->geom_friction[3 * g1 + e]; F[12 + e] = m->geom_friction[3 * g2 + e]; }
-    F[15] = m->body_invweight0[2 * b1] + m->body_invweight0[2 * b2];
+    for (int e = 0; e < 5; ++e) F[4 + e] = mix * m.geom_solimp[5 * g1 + e] + (1 - mix) * m.geom_solimp[5 * g2 + e];
+    for (int e = 0; e < 3; ++e) { F[9 + e] = m.geom_friction[3 * g1 + e]; F[12 + e] = m.geom_friction[3 * g2 + e]; }
+    F[15] = m.body_invweight0[2 * b1] + m.body_invweight0[2 * b2];
     I[7] = (pr1 == pr2) ? 0 : (pr1 > pr2 ? 1 : 2);
     // condim of the contact (mj_contactParam): the higher-priority geom's, the larger of the two at equal priority
-    const int d1 = geom_condim[g1], d2 = geom_condim[g2];
+    const int d1 = x.geom_condim[g1], d2 = x.geom_condim[g2];
     I[6] = (pr1 == pr2) ? std::max(d1, d2) : (pr1 > pr2 ? d1 : d2);
     double mg0 = margin, mg1 = F[1];
-    if (pair_xp[p] >= 0) {                    // an explicit <pair>: its own margin / gap / solref / solimp / friction / condim, nothing mixed, no per-env friction
-      const int x = pair_xp[p];
-      mg0 = xp_margin[x]; mg1 = xp_margin[x] - xp_gap[x];
+    if (x.pair_xp[p] >= 0) {                  // an explicit <pair>: its own margin / gap / solref / solimp / friction / condim, nothing mixed, no per-env friction
+      const int xi = x.pair_xp[p];
+      mg0 = x.xp_margin[xi]; mg1 = x.xp_margin[xi] - x.xp_gap[xi];
       F[0] = mg0; F[1] = mg1;
-      for (int e = 0; e < 2; ++e) F[2 + e] = xp_solref[2 * x + e];
-      for (int e = 0; e < 5; ++e) F[4 + e] = xp_solimp[5 * x + e];
-      for (int e = 0; e < 3; ++e) { F[9 + e] = xp_friction[3 * x + e]; F[12 + e] = xp_friction[3 * x + e]; }
-      I[6] = xp_dim[x] | 0x100;
+      for (int e = 0; e < 2; ++e) F[2 + e] = x.xp_solref[2 * xi + e];
+      for (int e = 0; e < 5; ++e) F[4 + e] = x.xp_solimp[5 * xi + e];
+      for (int e = 0; e < 3; ++e) { F[9 + e] = x.xp_friction[3 * xi + e]; F[12 + e] = x.xp_friction[3 * xi + e]; }
+      I[6] = x.xp_dim[xi] | 0x100;
       I[7] = 0;
-      m->any_gen = 1;                         // (the general path reads the pair's own margin and skips the per-env friction patch)
+      m.any_gen = 1;                          // (the general path reads the pair's own margin and skips the per-env friction patch)
     }
-    m->pair_mg[2 * (size_t)p] = mg0; m->pair_mg[2 * (size_t)p + 1] = mg1;
-    sol_precompute(F + 2, F + 4, m->timestep, m->disableflags);      // pc_f[2..8]: (K, B), (d0, d1, 1 / width, mid, power) — what sol_param reads
-    LIM((I[6] & 255) != 1 && (I[6] & 255) != 3 && (I[6] & 255) != 4 && (I[6] & 255) != 6, "contact dimension (condim) other than 1, 3, 4, 6")
-    if ((I[6] & 255) > 3) m->any_rot = 1;
-    if ((I[6] & 255) != 3) m->any_gen = 1;
+    m.pair_mg[2 * (size_t)p] = mg0; m.pair_mg[2 * (size_t)p + 1] = mg1;
+    sol_precompute(F + 2, F + 4, m.timestep, m.disableflags);      // pc_f[2..8]: (K, B), (d0, d1, 1 / width, mid, power) — what sol_param reads
+    const int dim = I[6] & 255;
+    if (dim != 1 && dim != 3 && dim != 4 && dim != 6) return over_capacity("contact dimension (condim) other than 1, 3, 4, 6");
+    if (dim > 3) m.any_rot = 1;
+    if (dim != 3) m.any_gen = 1;
   }
-  m->body_imat.resize(9 * nb);
-  for (int b = 0; b < nb; ++b) quat2mat_h(&body_iquat[4 * b], &m->body_imat[9 * b]);
-  m->geom_mat.resize(9 * (size_t)m->ngeom);
-  for (int g = 0; g < m->ngeom; ++g) quat2mat_h(&geom_quat[4 * g], &m->geom_mat[9 * g]);
+  return MYO_OK;
+}
+
+static void build_frames(myo_model& m, const BlobOnly& x) {
+  const int nb = m.nbody;
+  m.body_imat.resize(9 * nb);
+  for (int b = 0; b < nb; ++b) quat2mat_h(&x.body_iquat[4 * b], &m.body_imat[9 * b]);
+  m.geom_mat.resize(9 * (size_t)m.ngeom);
+  for (int g = 0; g < m.ngeom; ++g) quat2mat_h(&x.geom_quat[4 * g], &m.geom_mat[9 * g]);
   // trailing dofs whose row of M is diagonal by construction: a free joint on a leaf body whose
   // inertial frame coincides with the body frame (M = diag(m,m,m,Ixx,Iyy,Izz)); nlead = first of them
-  m->nlead = nv;
-  for (int j = m->njnt - 1; j >= 0; --j) {
-    const int b = m->jnt_bodyid[j];
+  m.nlead = m.nv;
+  for (int j = m.njnt - 1; j >= 0; --j) {
+    const int b = m.jnt_bodyid[j];
     bool leaf = true;
-    for (int o = 1; o < nb; ++o) if (m->body_parentid[o] == b) leaf = false;
-    const double* iq = &body_iquat[4 * b]; const double* ip = &m->body_ipos[3 * b];
+    for (int o = 1; o < nb; ++o) if (m.body_parentid[o] == b) leaf = false;
+    const double* iq = &x.body_iquat[4 * b]; const double* ip = &m.body_ipos[3 * b];
     const bool aligned = fabs(fabs(iq[0]) - 1.0) < 1e-12 && fabs(ip[0]) + fabs(ip[1]) + fabs(ip[2]) < 1e-14;
-    if (m->jnt_type[j] == MYO_JNT_FREE && leaf && aligned && m->body_jntnum[b] == 1 && m->jnt_dofadr[j] + 6 == m->nlead)
-      m->nlead = m->jnt_dofadr[j];
+    if (m.jnt_type[j] == MYO_JNT_FREE && leaf && aligned && m.body_jntnum[b] == 1 && m.jnt_dofadr[j] + 6 == m.nlead)
+      m.nlead = m.jnt_dofadr[j];
     else break;
   }
-  // the rows' solver parameters in the form sol_param reads them (in place: same names, same sizes)
-  for (int j = 0; j < m->njnt; ++j) sol_precompute(&m->jnt_solref[2 * (size_t)j], &m->jnt_solimp[5 * (size_t)j], m->timestep, m->disableflags);
-  for (int t2 = 0; t2 < m->ntendon; ++t2) {
-    sol_precompute(&m->tendon_solref_lim[2 * (size_t)t2], &m->tendon_solimp_lim[5 * (size_t)t2], m->timestep, m->disableflags);
-    sol_precompute(&m->tendon_solref_fri[2 * (size_t)t2], &m->tendon_solimp_fri[5 * (size_t)t2], m->timestep, m->disableflags);
+}
+
+// the rows' solver parameters in the form sol_param reads them (in place: same names, same sizes)
+static void resolve_solver_params(myo_model& m) {
+  for (int j = 0; j < m.njnt; ++j) sol_precompute(&m.jnt_solref[2 * (size_t)j], &m.jnt_solimp[5 * (size_t)j], m.timestep, m.disableflags);
+  for (int t = 0; t < m.ntendon; ++t) {
+    sol_precompute(&m.tendon_solref_lim[2 * (size_t)t], &m.tendon_solimp_lim[5 * (size_t)t], m.timestep, m.disableflags);
+    sol_precompute(&m.tendon_solref_fri[2 * (size_t)t], &m.tendon_solimp_fri[5 * (size_t)t], m.timestep, m.disableflags);
   }
-  for (int d = 0; d < nv; ++d) sol_precompute(&m->dof_solref[2 * (size_t)d], &m->dof_solimp[5 * (size_t)d], m->timestep, m->disableflags);
-  build_ldl_tables(m);
-  build_arrow_tables(m);
-  m->any_floss = 0;
-  {
-    int nfr = 0;
-    for (int d = 0; d < nv; ++d) if (m->dof_frictionloss[d] > 0) { m->any_floss = 1; nfr++; }
-    for (int t = 0; t < m->ntendon; ++t) if (m->tendon_frictionloss[t] > 0) { m->any_floss = 1; nfr++; }
-    LIM(nfr > MYO_NLIM_MAX / 2, "friction-loss rows (more than half of the limit-row capacity)")
-    for (int d = 0; d < nv; ++d) LIM(m->dof_frictionloss[d] > 0 && m->jnt_type[m->dof_jntid[d]] == MYO_JNT_FREE, "friction loss on the dofs of a free joint")
-  }
-  m->any_damping = 0;
-  for (int d = 0; d < nv; ++d) if (m->dof_damping[d] > 0) m->any_damping = 1;
-  m->any_tendon_passive = 0;
-  for (int t = 0; t < m->ntendon; ++t) if (m->tendon_stiffness[t] != 0 || m->tendon_damping[t] != 0) m->any_tendon_passive = 1;
-#undef LIM
-  render_vis_table(m, blob, nbytes);
-  render_tendon_table(m, blob, nbytes, trntype);
-  *out = m;
+  for (int d = 0; d < m.nv; ++d) sol_precompute(&m.dof_solref[2 * (size_t)d], &m.dof_solimp[5 * (size_t)d], m.timestep, m.disableflags);
+}
+
+static int set_feature_flags(myo_model& m) {
+  m.any_floss = 0;
+  int nfr = 0;
+  for (int d = 0; d < m.nv; ++d) if (m.dof_frictionloss[d] > 0) { m.any_floss = 1; nfr++; }
+  for (int t = 0; t < m.ntendon; ++t) if (m.tendon_frictionloss[t] > 0) { m.any_floss = 1; nfr++; }
+  if (nfr > MYO_NLIM_MAX / 2) return over_capacity("friction-loss rows (more than half of the limit-row capacity)");
+  for (int d = 0; d < m.nv; ++d)
+    if (m.dof_frictionloss[d] > 0 && m.jnt_type[m.dof_jntid[d]] == MYO_JNT_FREE) return over_capacity("friction loss on the dofs of a free joint");
+  m.any_damping = 0;
+  for (int d = 0; d < m.nv; ++d) if (m.dof_damping[d] > 0) m.any_damping = 1;
+  m.any_tendon_passive = 0;
+  for (int t = 0; t < m.ntendon; ++t) if (m.tendon_stiffness[t] != 0 || m.tendon_damping[t] != 0) m.any_tendon_passive = 1;
   return MYO_OK;
+}
+
+static int model_from_blob_impl(const void* blob, size_t nbytes, myo_model** out) {
+  if (!blob || !out || nbytes < sizeof(myo_blob_header)) return fail(MYO_E_ARG, "null or short blob");
+  const myo_blob_header* h = (const myo_blob_header*)blob;
+  if (h->magic != MYO_BLOB_MAGIC || h->version != MYO_BLOB_VERSION || h->total_bytes != nbytes ||
+      sizeof(myo_blob_header) + (size_t)h->n_fields * sizeof(myo_blob_field) > nbytes)
+    return fail(MYO_E_ARG, "bad model blob header");
+  std::unique_ptr<myo_model> owner(new myo_model());
+  myo_model& m = *owner;
+  BlobOnly x;
+  if (int rc = read_fields(blob, nbytes, m, x)) return rc;
+  if (int rc = check_untrusted(m, x)) return rc;
+  if (int rc = order_pairs(m)) return rc;
+  if (int rc = check_capacity(m, x)) return rc;
+  if (int rc = build_tree_tables(m)) return rc;
+  if (int rc = build_wrap_records(m, x)) return rc;
+  if (int rc = build_path_elements(m)) return rc;
+  if (int rc = build_actuator_gather(m, x)) return rc;
+  build_muscle_constants(m);
+  if (int rc = build_lane_records(m)) return rc;
+  if (int rc = build_pair_records(m, x)) return rc;
+  build_frames(m, x);
+  resolve_solver_params(m);
+  build_ldl_tables(&m);
+  build_arrow_tables(&m);
+  if (int rc = set_feature_flags(m)) return rc;
+  render_vis_table(&m, blob, nbytes);
+  render_tendon_table(&m, blob, nbytes, x.trntype);
+  *out = owner.release();
+  return MYO_OK;
+}
+extern "C" int myo_model_from_blob(const void* blob, size_t nbytes, myo_model** out) {
+  try { return model_from_blob_impl(blob, nbytes, out); }          // no C++ exception crosses the C ABI
+  catch (const std::exception& e) { return fail(MYO_E_ARG, "model blob rejected: %s", e.what()); }
 }
 
 extern "C" int myo_model_load_mjb(const char* path, int integrator, int unsupported_contacts, myo_model** out) {
@@ -999,9 +1071,33 @@ extern "C" void myo_model_destroy(myo_model* m) { delete m; }
 extern "C" int myo_model_size(const myo_model* m, const char* n) {
   if (!m || !n) return -1;
 #define S(x) if (!strcmp(n, #x)) return m->x;
-  S(nq) S(nv) S(nu) S(na) S(nbody) S(njnt) S(ngeom) S(nsite) S(ntendon) S(nwrap) S(npair) S(nM) S(integrator) S(nlead) S(arrow_nf) S(ld_nfq) S(ld_nsq) S(ntendon_item)
+  S(nq) S(nv) S(nu) S(na) S(nbody) S(njnt) S(ngeom) S(nsite) S(ntendon) S(nwrap) S(npair) S(nM) S(maxdepth)
+  S(integrator) S(iterations) S(disableflags) S(any_damping) S(any_tendon_passive) S(nlead) S(ngw) S(nte) S(npair_std) S(ld_nfq) S(ld_nsq) S(arrow_nf)
+  S(any_rot) S(any_gen) S(any_floss) S(has_visual) S(ntendon_item)
 #undef S
   return -1;
+}
+// read access to the tables (include/myobatch.h): pointers into the model, nothing copied, no device touched
+static int table_dtype(const int*) { return MYO_TABLE_I32; }
+static int table_dtype(const unsigned long long*) { return MYO_TABLE_U64; }
+static int table_dtype(const float*) { return MYO_TABLE_F32; }
+static int table_dtype(const double*) { return MYO_TABLE_F64; }
+extern "C" int myo_model_table(const myo_model* m, const char* name, const void** data, size_t* bytes, int* dtype) {
+  if (!m || !name || !data || !bytes || !dtype) return fail(MYO_E_ARG, "myo_model_table: null argument");
+  bool found = false;
+  auto hit = [&](auto* p, size_t count) { *data = p; *bytes = count * sizeof *p; *dtype = table_dtype(p); found = true; };
+#define X(n) if (!found && !strcmp(name, #n)) hit(m->n.data(), m->n.size());
+  MYO_MODEL_INT_ARRAYS(X) MYO_MODEL_U64_ARRAYS(X) MYO_MODEL_REAL_ARRAYS(X) X(vis) X(tvis) X(titem_adr)
+#undef X
+  if (!found && !strcmp(name, "timestep")) hit(&m->timestep, 1);
+  if (!found && !strcmp(name, "tolerance")) hit(&m->tolerance, 1);
+  if (!found && !strcmp(name, "impratio")) hit(&m->impratio, 1);
+  if (!found && !strcmp(name, "gravity")) hit(m->gravity, 3);
+  if (!found && !strcmp(name, "meaninertia")) hit(&m->meaninertia, 1);
+  if (!found && !strcmp(name, "cam_lookat")) hit(m->cam_lookat, 3);
+  if (!found && !strcmp(name, "cam_distance")) hit(&m->cam_distance, 1);
+  if (!found && !strcmp(name, "arrow_pad")) hit(&m->arrow_pad, 1);
+  return found ? MYO_OK : fail(MYO_E_ARG, "myo_model_table: no table named %s", name);
 }
 
 // ------------------------------------------------------------------------------------------ batch
@@ -1083,6 +1179,29 @@ constexpr size_t variant_lds_bytes() {
   return RK && MYO_RK_IN_LDS(T, NC) ? MYO_LDS_ALIGN(sizeof(Scratch<T, NC>)) + sizeof(RkScratch<T>) : sizeof(Scratch<T, NC>);
 }
 
+// ---- device memory of a batch.  Every allocation goes through these two: `count` elements of U (never zero bytes), recorded in
+// `allocs` (what release_allocs frees), the pointer returned (null: the allocation failed).  `rc` accumulates the backend's error
+// bits over a whole create; dev_upload copies only while rc is clean, so one failure leaves the rest allocated, unfilled and reported.
+template <typename U>
+static U* dev_alloc(std::vector<void*>& allocs, int& rc, size_t count) {
+  void* p = nullptr;
+  rc |= be_malloc(&p, count * sizeof(U));
+  if (p) allocs.push_back(p);
+  return (U*)p;
+}
+template <typename U>
+static U* dev_upload(std::vector<void*>& allocs, int& rc, const U* host, size_t count) {
+  U* p = dev_alloc<U>(allocs, rc, count);
+  if (!rc && count) rc |= be_h2d(p, host, count * sizeof(U));
+  return p;
+}
+template <typename U>
+static U* dev_upload(std::vector<void*>& allocs, int& rc, const std::vector<U>& host) { return dev_upload(allocs, rc, host.data(), host.size()); }
+static void release_allocs(std::vector<void*>& allocs) {
+  for (void* q : allocs) be_free(q);
+  allocs.clear();
+}
+
 template <typename T>
 static int upload_model(const myo_model* m, DevModel<T>& D, std::vector<void*>& allocs) {
   D.nq = m->nq; D.nv = m->nv; D.nu = m->nu; D.na = m->na; D.nbody = m->nbody; D.njnt = m->njnt; D.ngeom = m->ngeom;
@@ -1096,47 +1215,15 @@ static int upload_model(const myo_model* m, DevModel<T>& D, std::vector<void*>& 
   for (int k = 0; k < 3; ++k) D.gravity[k] = (T)m->gravity[k];
   D.meaninertia = (T)m->meaninertia;
   int rc = 0;
-#define X(n)                                                                            \
-  {                                                                                     \
-    void* p = nullptr;                                                                  \
-    rc |= be_malloc(&p, m->n.size() * sizeof(int));                                     \
-    if (!rc && !m->n.empty()) rc |= be_h2d(p, m->n.data(), m->n.size() * sizeof(int));  \
-    allocs.push_back(p);                                                                \
-    D.n.p = (const int*)p;                                                              \
-  }
+#define X(n) D.n.p = dev_upload(allocs, rc, m->n);
   MYO_MODEL_INT_ARRAYS(X)
-#undef X
-#define X(n)                                                                                               \
-  {                                                                                                        \
-    void* p = nullptr;                                                                                     \
-    rc |= be_malloc(&p, m->n.size() * sizeof(unsigned long long));                                         \
-    if (!rc && !m->n.empty()) rc |= be_h2d(p, m->n.data(), m->n.size() * sizeof(unsigned long long));      \
-    allocs.push_back(p);                                                                                   \
-    D.n.p = (const unsigned long long*)p;                                                                  \
-  }
   MYO_MODEL_U64_ARRAYS(X)
 #undef X
-#define X(n)                                                                  \
-  {                                                                           \
-    std::vector<T> tmp(m->n.begin(), m->n.end());                             \
-    void* p = nullptr;                                                        \
-    rc |= be_malloc(&p, tmp.size() * sizeof(T));                              \
-    if (!rc && !tmp.empty()) rc |= be_h2d(p, tmp.data(), tmp.size() * sizeof(T)); \
-    allocs.push_back(p);                                                      \
-    D.n.p = (const T*)p;                                                      \
-  }
+#define X(n) D.n.p = dev_upload(allocs, rc, std::vector<T>(m->n.begin(), m->n.end()));
   MYO_MODEL_REAL_ARRAYS(X)
 #undef X
   // HP tables: the fp64 stepper's ordinary tables; separate fp64 copies for the mixed stepper
-#define X(n)                                                                                   \
-  if (sizeof(T) == sizeof(double)) D.h_##n.p = (const double*)(const void*)D.n.p;              \
-  else {                                                                                       \
-    void* p = nullptr;                                                                         \
-    rc |= be_malloc(&p, m->n.size() * sizeof(double));                                         \
-    if (!rc && !m->n.empty()) rc |= be_h2d(p, m->n.data(), m->n.size() * sizeof(double));      \
-    allocs.push_back(p);                                                                       \
-    D.h_##n.p = (const double*)p;                                                              \
-  }
+#define X(n) D.h_##n.p = sizeof(T) == sizeof(double) ? (const double*)(const void*)D.n.p : dev_upload(allocs, rc, m->n);
   MYO_MODEL_HP_ARRAYS(X)
 #undef X
   return rc;
@@ -1213,10 +1300,9 @@ static int task_nobs_host(const myo_task_cfg* c, int na) {
   return c->kind == MYO_TASK_REORIENT ? 2 * c->n_hand + 18 + na : c->n_hand + 24 + na;
 }
 
-extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int n_envs, int device, uint64_t seed,
-                                int dtype, myo_batch** out) {
-  if (!m || !out || n_envs <= 0) return fail(MYO_E_ARG, "bad arguments to myo_batch_create");
-  if (dtype != MYO_F64 && dtype != MYO_F32) return fail(MYO_E_ARG, "dtype must be MYO_F64 or MYO_F32");
+// ---- myo_batch_create, step by step
+// a task cfg against the model, per kind, and its muscle_condition fields
+static int task_cfg_check(const myo_model* m, const myo_task_cfg* cfg) {
   if (cfg && cfg->kind != MYO_TASK_NONE) {
     if (cfg->kind != MYO_TASK_BAODING_P1 && cfg->kind != MYO_TASK_BAODING_P2 && cfg->kind != MYO_TASK_REORIENT && cfg->kind != MYO_TASK_POSE)
       return fail(MYO_E_ARG, "unknown task kind");
@@ -1235,17 +1321,152 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
       for (int k = 0; k < 3; ++k)
         if (cfg->ro_n_rot_choice[k] < 0 || cfg->ro_n_rot_choice[k] > MYO_ROT_CHOICE_MAX) return fail(MYO_E_ARG, "goal_rot_x/y/z: at most %d ranges", MYO_ROT_CHOICE_MAX);
     } else {
-    if (cfg->obj1_sid < 0 || cfg->obj1_sid >= m->nsite || cfg->obj2_sid < 0 || cfg->obj2_sid >= m->nsite ||
-        cfg->target1_sid < 0 || cfg->target1_sid >= m->nsite || cfg->target2_sid < 0 || cfg->target2_sid >= m->nsite ||
-        cfg->obj1_bid <= 0 || cfg->obj1_bid >= m->nbody || cfg->obj2_bid <= 0 || cfg->obj2_bid >= m->nbody ||
-        cfg->obj1_gid < 0 || cfg->obj1_gid >= m->ngeom || cfg->obj2_gid < 0 || cfg->obj2_gid >= m->ngeom)
-      return fail(MYO_E_ARG, "task ids out of range");
-    if (cfg->n_hand + 14 != m->nq || m->nv < 12 || cfg->n_hand + 24 + m->na > MYO_OBS_MAX)
-      return fail(MYO_E_UNSUPPORTED, "Baoding task needs nq = n_hand + 14 (two free balls last)");
+      if (cfg->obj1_sid < 0 || cfg->obj1_sid >= m->nsite || cfg->obj2_sid < 0 || cfg->obj2_sid >= m->nsite ||
+          cfg->target1_sid < 0 || cfg->target1_sid >= m->nsite || cfg->target2_sid < 0 || cfg->target2_sid >= m->nsite ||
+          cfg->obj1_bid <= 0 || cfg->obj1_bid >= m->nbody || cfg->obj2_bid <= 0 || cfg->obj2_bid >= m->nbody ||
+          cfg->obj1_gid < 0 || cfg->obj1_gid >= m->ngeom || cfg->obj2_gid < 0 || cfg->obj2_gid >= m->ngeom)
+        return fail(MYO_E_ARG, "task ids out of range");
+      if (cfg->n_hand + 14 != m->nq || m->nv < 12 || cfg->n_hand + 24 + m->na > MYO_OBS_MAX)
+        return fail(MYO_E_UNSUPPORTED, "Baoding task needs nq = n_hand + 14 (two free balls last)");
     }
     if (cfg->frame_skip <= 0 || cfg->max_episode_steps <= 0) return fail(MYO_E_ARG, "frame_skip / max_episode_steps");
   }
-  if (int mrc = muscle_condition_check(m, cfg)) return mrc;
+  return muscle_condition_check(m, cfg);
+}
+
+// the env record of this batch (b->L; b->K.fat_off): a pose batch has its pose block, a batch with fatigue its muscle states
+static int record_layout(myo_batch* b, const myo_model* m) {
+  EnvRecordLayout& L = b->L;
+  L.nq = m->nq; L.nv = m->nv; L.na = m->na;
+  int o = 0;
+  L.off_qpos = o; o += m->nq; L.off_qvel = o; o += m->nv; L.off_act = o; o += m->na; L.off_warm = o; o += m->nv;
+  L.off_time = o; o += 1; L.off_taskd = o; o += MYO_TASKD_N; L.off_balld = o; o += MYO_BALLD_N; L.off_misc = o; o += MYO_MISC_N;
+  L.off_objfric = o; o += 3 * MYO_OBJG_MAX;
+  L.off_pose = o; if (b->K.kind == MYO_TASK_POSE) o += 2 * m->nq;     // (the other kinds' records keep their size)
+  b->K.fat_off = o; if (b->K.muscle_condition == MYO_MUSCLE_FATIGUE) o += 3 * m->nu;      // (a batch without fatigue keeps its record's size)
+  // (store_env writes qpos | qvel | act | warm | time as one run: the order above is part of the kernels' contract)
+  if (L.off_qvel != L.off_qpos + m->nq || L.off_act != L.off_qvel + m->nv || L.off_warm != L.off_act + m->na || L.off_time != L.off_warm + m->nv) return fail(MYO_E_STATE, "record layout");
+  L.stride = (o + 15) / 16 * 16;      // whole 128-byte lines per env: no line is shared by two workgroups
+  b->K.objf_off = L.off_objfric - L.off_warm;      // (Scratch::SPILL reads the object group's friction in the record)
+  return MYO_OK;
+}
+static void dump_layout(DumpLayout& D, const myo_model* m) {
+  int o = 0;
+  D.ten_length = o; o += m->ntendon; D.ten_J = o; o += m->ntendon * m->nv; D.M = o; o += m->nv * m->nv;
+  D.qfrc_bias = o; o += m->nv; D.qfrc_passive = o; o += m->nv; D.qfrc_actuator = o; o += m->nv;
+  D.qacc_smooth = o; o += m->nv; D.qacc = o; o += m->nv; D.actuator_force = o; o += m->nu; D.act_dot = o; o += m->na;
+  D.counts = o; o += 4; D.efc_aref = o; o += MYO_NLIM_MAX + 4 * MYO_NCON_BIG; D.efc_D = o; o += MYO_NLIM_MAX + 4 * MYO_NCON_BIG;
+  D.site_xpos = o; o += 3 * m->nsite; D.subtree_com = o; o += 3 * m->nbody; D.xpos = o; o += 3 * m->nbody; D.total = o;
+}
+
+// initial record of an env (r: L.stride zeros): qpos0, zero velocity; model ball parameters; target sites at their model xy;
+// start angles per _setup (baoding.py:246-247 P1; :349-354 P2 decided per env at reset time here)
+static void initial_record(const myo_model* m, const TaskDev& K, const EnvRecordLayout& L, double* r) {
+  for (int i = 0; i < m->nq; ++i) r[L.off_qpos + i] = m->qpos0[i];
+  double* td = r + L.off_taskd; double* bd = r + L.off_balld; double* mi = r + L.off_misc;
+  if (K.muscle_condition == MYO_MUSCLE_FATIGUE) for (int i = 0; i < m->nu; ++i) r[K.fat_off + m->nu + i] = 1.0;      // rested muscles: (MA, MR, MF) = (0, 1, 0)
+  td[0] = 3.0 * MYO_PI / 4.0; td[1] = -MYO_PI / 4.0; td[2] = 0.025; td[3] = 0.028; td[4] = 5.0;
+  mi[0] = MYO_WHICH_CCW;
+  if (K.kind == MYO_TASK_REORIENT) {
+    // goal at its setup pose, identity orientation, nominal die; reset() draws the episode's values
+    memset(td, 0, sizeof(double) * MYO_TASKD_N); mi[0] = 0;
+    for (int k = 0; k < 3; ++k) td[k] = K.ro_goal_init_pos[k];
+    td[3] = 1.0;
+    for (int j = 0; j < 3 * (K.objg_gidn - K.objg_gid0); ++j) r[L.off_objfric + j] = m->geom_friction[3 * K.objg_gid0 + j];
+  } else if (K.kind == MYO_TASK_POSE) {
+    // the init pose and the pseudo target of CustomPoseEnv._setup (pose.py:38-43: the mean of each target range); reset() draws the episode's
+    memset(td, 0, sizeof(double) * MYO_TASKD_N); mi[0] = 0;
+    for (int i = 0; i < m->nq; ++i) {
+      const double tv = K.pose_target_type == MYO_POSE_TARGET_FIXED ? K.pose_target_value[i]
+                                                                     : 0.5 * (K.pose_target_range[i][0] + K.pose_target_range[i][1]);
+      r[L.off_qpos + i] = K.pose_init_qpos[i];
+      r[L.off_pose + i] = tv; r[L.off_pose + m->nq + i] = K.pose_init_qpos[i];
+    }
+  } else if (K.kind) {
+    td[2] = 0.5 * (K.goal_xrange[0] + K.goal_xrange[1]); td[3] = 0.5 * (K.goal_yrange[0] + K.goal_yrange[1]);
+    td[4] = 0.5 * (K.goal_time_period[0] + K.goal_time_period[1]);
+    if (K.kind == MYO_TASK_BAODING_P2 && !(K.overlap_probability >= 1.0)) { td[0] = MYO_PI / 4.0; td[1] = MYO_PI / 4.0 - MYO_PI; }
+    td[5] = m->site_pos[3 * K.target1_sid]; td[6] = m->site_pos[3 * K.target1_sid + 1];
+    td[7] = m->site_pos[3 * K.target2_sid]; td[8] = m->site_pos[3 * K.target2_sid + 1];
+    bd[0] = m->body_mass[K.obj1_bid]; bd[1] = m->body_mass[K.obj2_bid];
+    for (int k = 0; k < 3; ++k) { bd[2 + k] = m->geom_friction[3 * K.obj1_gid + k]; bd[5 + k] = m->geom_friction[3 * K.obj2_gid + k]; }
+    bd[8] = m->geom_size[3 * K.obj1_gid]; bd[9] = m->geom_size[3 * K.obj2_gid];
+    if (K.task_choice == MYO_CHOICE_CW) mi[0] = MYO_WHICH_CW;
+  }
+}
+
+// the parts of an env step (k_step): MYO_STEP_SPLIT = "7,3" (substeps per part; "0" or one number = whole steps; A/B switch
+// of the tools and of the bit-identity tests).  The emulation build runs the parts one after the other through the record.
+// `parts`: the batch has a task layer (a physics-only batch steps whole)
+static StepPlan step_plan(int frame_skip, bool parts) {
+  StepPlan whole = {}, pl = {};
+  whole.nparts = 1; whole.k[1] = frame_skip;
+  { const char* pm = getenv("MYO_PUBLISH"); pl.wt = pm && !strcmp(pm, "fence") ? 0 : 1; }     // A/B switch: "wt" (default) | "fence"
+  if (!parts || frame_skip < 2) return whole;
+  const char* sp = getenv("MYO_STEP_SPLIT");
+  if (sp) {
+    int acc = 0;
+    for (const char* q = sp; *q && pl.nparts < MYO_PARTS_MAX;) {
+      const int v = atoi(q);
+      if (v <= 0) break;
+      acc += v; pl.k[++pl.nparts] = acc;
+      while (*q && *q != ',') ++q;
+      if (*q == ',') ++q;
+    }
+    if (acc != frame_skip) pl.nparts = 0;
+  } else {
+    // parts of decreasing length, 4 : 3 : 2 : 1 of the frame_skip (measured at 4096 envs, frame_skip 10, k_step ms:
+    // whole 2.73, 7+3 2.33, 6+3+1 2.27, 5+3+2 2.27, 4+3+2+1 2.24, 5+3+1+1 2.25, 3+3+2+1+1 2.26)
+    const int f = frame_skip, np = f < 4 ? f : 4;
+    static const int w[4] = {4, 3, 2, 1};
+    int wsum = 0, acc = 0;
+    for (int i = 0; i < np; ++i) wsum += w[i];
+    for (int i = 0; i < np; ++i) {
+      int len = i == np - 1 ? f - acc : (f * w[i] + wsum / 2) / wsum;
+      const int room = f - acc - (np - 1 - i);        // every later part keeps at least one substep
+      len = len < 1 ? 1 : (len > room ? room : len);
+      acc += len; pl.k[i + 1] = acc;
+    }
+    pl.nparts = np;
+  }
+  return pl.nparts >= 2 ? pl : whole;
+}
+
+// render items: the task's target sites are always drawn (the Baoding targets; the die's target is a body); the tendon tables; the default camera
+static int upload_render_tables(myo_batch* b, const myo_model* m, int rc) {
+  std::vector<float> vis = m->vis;
+  const int ts[2] = {b->K.target1_sid, b->K.target2_sid};
+  if (b->K.kind == MYO_TASK_BAODING_P1 || b->K.kind == MYO_TASK_BAODING_P2)
+    for (int j : ts)
+      if (j >= 0 && j < m->nsite) {
+        float* v = &vis[8 * (size_t)(m->ngeom + j)];
+        v[5] = 0.f;
+        if (!m->has_visual) { v[0] = 0.2f; v[1] = 0.85f; v[2] = 0.3f; v[3] = 1.f; v[4] = 0.01f; }
+      }
+  b->vis = dev_upload(b->allocs, rc, vis);
+  b->nitem = m->ngeom + m->nsite;
+  b->tvis = dev_upload(b->allocs, rc, m->tvis);
+  b->titem_adr = dev_upload(b->allocs, rc, m->titem_adr);
+  b->ntitem = m->ntendon_item;
+  for (int k = 0; k < 3; ++k) b->cam_lookat[k] = m->cam_lookat[k];
+  b->cam_distance = m->cam_distance;
+  return rc;
+}
+
+// the one release of a batch: a finished one (myo_batch_destroy), or what a failed myo_batch_create has built so far (destroying = 0)
+static void batch_release(myo_batch* b, int destroying) {
+  be_batch_release(b, b->device, destroying);
+  release_allocs(b->allocs);
+  if (b->render_ws) be_free(b->render_ws);
+  if (b->so_ws) be_free(b->so_ws);
+  delete b;
+}
+
+extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int n_envs, int device, uint64_t seed,
+                                int dtype, myo_batch** out) {
+  if (!m || !out || n_envs <= 0) return fail(MYO_E_ARG, "bad arguments to myo_batch_create");
+  if (dtype != MYO_F64 && dtype != MYO_F32) return fail(MYO_E_ARG, "dtype must be MYO_F64 or MYO_F32");
+  if (int crc = task_cfg_check(m, cfg)) return crc;
   int rc = be_set_device(device);
   if (rc) return fail(MYO_E_DEVICE, "hipSetDevice(%d): %s", device, be_errstr(rc));
   myo_batch* b = new myo_batch();
@@ -1262,166 +1483,32 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
   if (cfg) b->cfg = *cfg; else memset(&b->cfg, 0, sizeof b->cfg);
   make_taskdev(cfg && cfg->kind != MYO_TASK_NONE ? cfg : nullptr, seed, b->K);
   b->nobs = b->K.kind ? task_nobs_host(cfg, m->na) : 0;
+  b->order = nullptr; b->cost = nullptr; b->ticks = nullptr; b->part_state = nullptr; b->step_gen = nullptr;
   memset(&b->Md, 0, sizeof b->Md); memset(&b->Mf, 0, sizeof b->Mf);
   rc = (dtype == MYO_F64) ? upload_model<double>(m, b->Md, b->allocs) : upload_model<float>(m, b->Mf, b->allocs);
-  EnvRecordLayout& L = b->L;
-  L.nq = m->nq; L.nv = m->nv; L.na = m->na;
-  int o = 0;
-  L.off_qpos = o; o += m->nq; L.off_qvel = o; o += m->nv; L.off_act = o; o += m->na; L.off_warm = o; o += m->nv;
-  L.off_time = o; o += 1; L.off_taskd = o; o += MYO_TASKD_N; L.off_balld = o; o += MYO_BALLD_N; L.off_misc = o; o += MYO_MISC_N;
-  L.off_objfric = o; o += 3 * MYO_OBJG_MAX;
-  L.off_pose = o; if (b->K.kind == MYO_TASK_POSE) o += 2 * m->nq;     // (the other kinds' records keep their size)
-  const bool fatigue = b->K.muscle_condition == MYO_MUSCLE_FATIGUE;
-  b->K.fat_off = o; if (fatigue) o += 3 * m->nu;                      // (a batch without fatigue keeps its record's size)
-  // (store_env writes qpos | qvel | act | warm | time as one run: the order above is part of the kernels' contract)
-  if (L.off_qvel != L.off_qpos + m->nq || L.off_act != L.off_qvel + m->nv || L.off_warm != L.off_act + m->na || L.off_time != L.off_warm + m->nv) { delete b; return fail(MYO_E_STATE, "record layout"); }
-  L.stride = (o + 15) / 16 * 16;      // whole 128-byte lines per env: no line is shared by two workgroups
-  DumpLayout& D = b->D;
-  o = 0;
-  D.ten_length = o; o += m->ntendon; D.ten_J = o; o += m->ntendon * m->nv; D.M = o; o += m->nv * m->nv;
-  D.qfrc_bias = o; o += m->nv; D.qfrc_passive = o; o += m->nv; D.qfrc_actuator = o; o += m->nv;
-  D.qacc_smooth = o; o += m->nv; D.qacc = o; o += m->nv; D.actuator_force = o; o += m->nu; D.act_dot = o; o += m->na;
-  D.counts = o; o += 4; D.efc_aref = o; o += MYO_NLIM_MAX + 4 * MYO_NCON_BIG; D.efc_D = o; o += MYO_NLIM_MAX + 4 * MYO_NCON_BIG;
-  D.site_xpos = o; o += 3 * m->nsite; D.subtree_com = o; o += 3 * m->nbody; D.xpos = o; o += 3 * m->nbody; D.total = o;
-  // initial records: qpos0, zero velocity; model ball parameters; target sites at their model xy;
-  // start angles per _setup (baoding.py:246-247 P1; :349-354 P2 decided per env at reset time here)
-  std::vector<double> host((size_t)n_envs * L.stride, 0.0);
-  for (int e = 0; e < n_envs; ++e) {
-    double* r = &host[(size_t)e * L.stride];
-    for (int i = 0; i < m->nq; ++i) r[L.off_qpos + i] = m->qpos0[i];
-    double* td = r + L.off_taskd; double* bd = r + L.off_balld; double* mi = r + L.off_misc;
-    if (fatigue) for (int i = 0; i < m->nu; ++i) r[b->K.fat_off + m->nu + i] = 1.0;      // rested muscles: (MA, MR, MF) = (0, 1, 0)
-    td[0] = 3.0 * MYO_PI / 4.0; td[1] = -MYO_PI / 4.0; td[2] = 0.025; td[3] = 0.028; td[4] = 5.0;
-    mi[0] = MYO_WHICH_CCW;
-    if (b->K.kind == MYO_TASK_REORIENT) {
-      // goal at its setup pose, identity orientation, nominal die; reset() draws the episode's values
-      memset(td, 0, sizeof(double) * MYO_TASKD_N); mi[0] = 0;
-      for (int k = 0; k < 3; ++k) td[k] = b->K.ro_goal_init_pos[k];
-      td[3] = 1.0;
-      for (int j = 0; j < 3 * (b->K.objg_gidn - b->K.objg_gid0); ++j) r[L.off_objfric + j] = m->geom_friction[3 * b->K.objg_gid0 + j];
-    } else if (b->K.kind == MYO_TASK_POSE) {
-      // the init pose and the pseudo target of CustomPoseEnv._setup (pose.py:38-43: the mean of each target range); reset() draws the episode's
-      memset(td, 0, sizeof(double) * MYO_TASKD_N); mi[0] = 0;
-      for (int i = 0; i < m->nq; ++i) {
-        const double tv = b->K.pose_target_type == MYO_POSE_TARGET_FIXED ? b->K.pose_target_value[i]
-                                                                          : 0.5 * (b->K.pose_target_range[i][0] + b->K.pose_target_range[i][1]);
-        r[L.off_qpos + i] = b->K.pose_init_qpos[i];
-        r[L.off_pose + i] = tv; r[L.off_pose + m->nq + i] = b->K.pose_init_qpos[i];
-      }
-    } else if (b->K.kind) {
-      td[2] = 0.5 * (b->K.goal_xrange[0] + b->K.goal_xrange[1]); td[3] = 0.5 * (b->K.goal_yrange[0] + b->K.goal_yrange[1]);
-      td[4] = 0.5 * (b->K.goal_time_period[0] + b->K.goal_time_period[1]);
-      if (b->K.kind == MYO_TASK_BAODING_P2 && !(b->K.overlap_probability >= 1.0)) { td[0] = MYO_PI / 4.0; td[1] = MYO_PI / 4.0 - MYO_PI; }
-      td[5] = m->site_pos[3 * b->K.target1_sid]; td[6] = m->site_pos[3 * b->K.target1_sid + 1];
-      td[7] = m->site_pos[3 * b->K.target2_sid]; td[8] = m->site_pos[3 * b->K.target2_sid + 1];
-      bd[0] = m->body_mass[b->K.obj1_bid]; bd[1] = m->body_mass[b->K.obj2_bid];
-      for (int k = 0; k < 3; ++k) { bd[2 + k] = m->geom_friction[3 * b->K.obj1_gid + k]; bd[5 + k] = m->geom_friction[3 * b->K.obj2_gid + k]; }
-      bd[8] = m->geom_size[3 * b->K.obj1_gid]; bd[9] = m->geom_size[3 * b->K.obj2_gid];
-      if (b->K.task_choice == MYO_CHOICE_CW) mi[0] = MYO_WHICH_CW;
-    }
-  }
-  void* p = nullptr;
-  rc |= be_malloc(&p, host.size() * sizeof(double));
-  if (!rc) rc |= be_h2d(p, host.data(), host.size() * sizeof(double));
-  b->rec = (double*)p;
-  b->allocs.push_back(p);
-  if (fatigue) {                   // the muscles' time constants in fp64, whatever the stepper's arithmetic (fatigue_ctrl, csrc/myo_task.h)
+  if (int lrc = record_layout(b, m)) { batch_release(b, 0); return lrc; }
+  dump_layout(b->D, m);
+  std::vector<double> host((size_t)n_envs * b->L.stride, 0.0);
+  for (int e = 0; e < n_envs; ++e) initial_record(m, b->K, b->L, &host[(size_t)e * b->L.stride]);
+  b->rec = dev_upload(b->allocs, rc, host);
+  if (b->K.muscle_condition == MYO_MUSCLE_FATIGUE) {      // the muscles' time constants in fp64, whatever the stepper's arithmetic (fatigue_ctrl, csrc/myo_task.h)
     std::vector<double> tau(2 * (size_t)m->nu);
     for (int i = 0; i < m->nu; ++i) { tau[2 * i] = m->actuator_dynprm[10 * (size_t)i]; tau[2 * i + 1] = m->actuator_dynprm[10 * (size_t)i + 1]; }
-    void* tp = nullptr;
-    rc |= be_malloc(&tp, tau.size() * sizeof(double));
-    if (!rc) rc |= be_h2d(tp, tau.data(), tau.size() * sizeof(double));
-    b->K.fatigue_tau = (const double*)tp;
-    if (tp) b->allocs.push_back(tp);
+    b->K.fatigue_tau = dev_upload(b->allocs, rc, tau);
   }
-  {                                // health counters (myo_batch_health), zeroed
-    void* hc = nullptr;
-    const int zero4[4] = {0, 0, 0, 0};
-    rc |= be_malloc(&hc, sizeof zero4);
-    if (!rc) rc |= be_h2d(hc, zero4, sizeof zero4);
-    b->K.health = (int*)hc;
-    if (hc) b->allocs.push_back(hc);
-  }
-  if (dtype == MYO_F64) {          // the fp64 stepper keeps controls, moment arms and the warm start in global memory (ScratchPoses<double>::ctrl_g)
-    rc |= be_batch_workspaces(b, n_envs, device);
-  }
-  b->K.objf_off = b->L.off_objfric - b->L.off_warm;      // (Scratch::SPILL reads the object group's friction in the record)
+  const int zero4[4] = {0, 0, 0, 0};           // health counters (myo_batch_health), zeroed
+  b->K.health = dev_upload(b->allocs, rc, zero4, 4);
+  if (dtype == MYO_F64) rc |= be_batch_workspaces(b, n_envs, device);      // the fp64 stepper keeps controls, moment arms and the warm start in global memory (ScratchPoses<double>::ctrl_g)
   if (m->integrator == 1) {        // RK4 stage storage, one RkScratch per env (global memory)
-    void* w = nullptr;
     const size_t each = dtype == MYO_F64 ? sizeof(RkScratch<double>) : sizeof(RkScratch<float>);
-    rc |= be_malloc(&w, each * (size_t)n_envs * MYO_PARTS_MAX);      // indexed by workgroup: a step in P parts launches P n of them
-    b->K.rk_ws = w;
-    if (w) b->allocs.push_back(w);
+    b->K.rk_ws = dev_alloc<char>(b->allocs, rc, each * (size_t)n_envs * MYO_PARTS_MAX);      // indexed by workgroup: a step in P parts launches P n of them
   }
-  b->order = nullptr; b->cost = nullptr; b->ticks = nullptr; b->part_state = nullptr; b->step_gen = nullptr; b->plan.nparts = 1; b->plan.k[0] = 0; b->plan.k[1] = cfg ? cfg->frame_skip : 0; b->plan.wt = 0;
-  {
-    // the parts of an env step (k_step): MYO_STEP_SPLIT = "7,3" (substeps per part; "0" or one number = whole steps; A/B switch
-    // of the tools and of the bit-identity tests).  The emulation build runs the parts one after the other through the record.
-    StepPlan pl; pl.nparts = 0; pl.k[0] = 0;
-    { const char* pm = getenv("MYO_PUBLISH"); pl.wt = pm && !strcmp(pm, "fence") ? 0 : 1; }     // A/B switch: "wt" (default) | "fence"
-    if (b->K.kind && cfg->frame_skip >= 2) {
-      const char* sp = getenv("MYO_STEP_SPLIT");
-      if (sp) {
-        int acc = 0;
-        for (const char* q = sp; *q && pl.nparts < MYO_PARTS_MAX;) {
-          const int v = atoi(q);
-          if (v <= 0) break;
-          acc += v; pl.k[++pl.nparts] = acc;
-          while (*q && *q != ',') ++q;
-          if (*q == ',') ++q;
-        }
-        if (acc != cfg->frame_skip) pl.nparts = 0;
-      } else {
-        // parts of decreasing length, 4 : 3 : 2 : 1 of the frame_skip (measured at 4096 envs, frame_skip 10, k_step ms:
-        // whole 2.73, 7+3 2.33, 6+3+1 2.27, 5+3+2 2.27, 4+3+2+1 2.24, 5+3+1+1 2.25, 3+3+2+1+1 2.26)
-        const int f = cfg->frame_skip, np = f < 4 ? f : 4;
-        static const int w[4] = {4, 3, 2, 1};
-        int wsum = 0, acc = 0;
-        for (int i = 0; i < np; ++i) wsum += w[i];
-        for (int i = 0; i < np; ++i) {
-          int len = i == np - 1 ? f - acc : (f * w[i] + wsum / 2) / wsum;
-          const int room = f - acc - (np - 1 - i);        // every later part keeps at least one substep
-          len = len < 1 ? 1 : (len > room ? room : len);
-          acc += len; pl.k[i + 1] = acc;
-        }
-        pl.nparts = np;
-      }
-    }
-    if (pl.nparts >= 2) b->plan = pl;
-  }
-  if (!rc) {      // render items: the task's target sites are always drawn (the Baoding targets; the die's target is a body)
-    std::vector<float> vis = m->vis;
-    const int ts[2] = {b->K.target1_sid, b->K.target2_sid};
-    if (b->K.kind == MYO_TASK_BAODING_P1 || b->K.kind == MYO_TASK_BAODING_P2)
-      for (int j : ts)
-        if (j >= 0 && j < m->nsite) {
-          float* v = &vis[8 * (size_t)(m->ngeom + j)];
-          v[5] = 0.f;
-          if (!m->has_visual) { v[0] = 0.2f; v[1] = 0.85f; v[2] = 0.3f; v[3] = 1.f; v[4] = 0.01f; }
-        }
-    void* p = nullptr;
-    rc |= be_malloc(&p, vis.size() * sizeof(float));
-    if (p) b->allocs.push_back(p);
-    if (!rc) rc |= be_h2d(p, vis.data(), vis.size() * sizeof(float));
-    b->vis = (float*)p;
-    b->nitem = m->ngeom + m->nsite;
-    void *pt = nullptr, *pa = nullptr;
-    rc |= be_malloc(&pt, m->tvis.size() * sizeof(float));
-    if (pt) b->allocs.push_back(pt);
-    rc |= be_malloc(&pa, m->titem_adr.size() * sizeof(int));
-    if (pa) b->allocs.push_back(pa);
-    if (!rc) rc |= be_h2d(pt, m->tvis.data(), m->tvis.size() * sizeof(float));
-    if (!rc) rc |= be_h2d(pa, m->titem_adr.data(), m->titem_adr.size() * sizeof(int));
-    b->tvis = (float*)pt; b->titem_adr = (int*)pa; b->ntitem = m->ntendon_item;
-    for (int k = 0; k < 3; ++k) b->cam_lookat[k] = m->cam_lookat[k];
-    b->cam_distance = m->cam_distance;
-  }
+  b->plan = step_plan(cfg ? cfg->frame_skip : 0, b->K.kind != MYO_TASK_NONE);
+  if (!rc) rc = upload_render_tables(b, m, rc);
   rc = be_batch_launch_state(b, m, n_envs, rc);      // (the HIP backend: timing events, launch order, the step plan's state, the wrap census)
   if (rc) {
-    int r2 = fail(MYO_E_DEVICE, "device allocation/upload failed: %s", be_errstr(rc));
-    for (void* q : b->allocs) be_free(q);
-    be_batch_release(b, device, 0);
-    delete b;
+    const int r2 = fail(MYO_E_DEVICE, "device allocation/upload failed: %s", be_errstr(rc));
+    batch_release(b, 0);
     return r2;
   }
   *out = b;
@@ -1429,12 +1516,7 @@ extern "C" int myo_batch_create(const myo_model* m, const myo_task_cfg* cfg, int
 }
 
 extern "C" void myo_batch_destroy(myo_batch* b) {
-  if (!b) return;
-  be_batch_release(b, b->device, 1);
-  for (void* q : b->allocs) be_free(q);
-  if (b->render_ws) be_free(b->render_ws);
-  if (b->so_ws) be_free(b->so_ws);
-  delete b;
+  if (b) batch_release(b, 1);
 }
 // ---- rendering (include/myobatch.h; csrc/myo_render.h): checks, cameras, style and workspace; the entry points are further down
 extern "C" int myo_model_default_camera(const myo_model* m, myo_render_camera* out) {
@@ -1572,18 +1654,18 @@ extern "C" int myo_batch_set_object_group(myo_batch* b, int gid0, int gidn) {
   if (b->K.kind != MYO_TASK_NONE) return fail(MYO_E_STATE, "object groups are for physics-only batches (the reorient task owns its own; the Baoding tasks have the two balls)");
   if (gidn - gid0 > MYO_OBJG_MAX) return fail(MYO_E_UNSUPPORTED, "an object group holds at most %d geoms", MYO_OBJG_MAX);
   b->K.objg_gid0 = gid0; b->K.objg_gidn = gidn;
-  void* tmp = nullptr;
+  std::vector<void*> tmp;      // (the upload lives until the scatter has run: be_task_changed waits for it)
   if (gidn > 0) {   // every env starts from the model's friction of the group's geoms
     const int cnt = 3 * (gidn - gid0);
     std::vector<double> host((size_t)b->n * cnt);
     for (int e = 0; e < b->n; ++e) for (int j = 0; j < cnt; ++j) host[(size_t)e * cnt + j] = b->geom_friction[3 * gid0 + j];
-    int rc = be_malloc(&tmp, host.size() * sizeof(double));
-    if (!rc) rc = be_h2d(tmp, host.data(), host.size() * sizeof(double));
-    if (rc) { if (tmp) be_free(tmp); return fail(MYO_E_DEVICE, "object group upload failed: %s", be_errstr(rc)); }
-    be_xfer(b, b->L.off_objfric, cnt, (double*)tmp, 0, nullptr);
+    int rc = 0;
+    double* dev = dev_upload(tmp, rc, host);
+    if (rc) { release_allocs(tmp); return fail(MYO_E_DEVICE, "object group upload failed: %s", be_errstr(rc)); }
+    be_xfer(b, b->L.off_objfric, cnt, dev, 0, nullptr);
   }
   be_task_changed(b);
-  if (tmp) be_free(tmp);
+  release_allocs(tmp);
   return MYO_OK;
 }
 extern "C" int myo_batch_object_friction(myo_batch* b, const double* set_fric, double* get_fric, void* stream) {

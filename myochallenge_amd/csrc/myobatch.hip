@@ -407,29 +407,23 @@ static int be_batch_launch_state(myo_batch* b, const myo_model* m, int n_envs, i
     if (!rc && b->K.kind && e && e[0] == '1') {
       std::vector<int> ident(n_envs);
       for (int i = 0; i < n_envs; ++i) ident[i] = i;
-      void *po = nullptr, *pc = nullptr, *pt = nullptr;
-      rc |= be_malloc(&po, sizeof(int) * (size_t)n_envs); rc |= be_malloc(&pc, sizeof(float) * (size_t)n_envs); rc |= be_malloc(&pt, sizeof(unsigned) * (size_t)n_envs);
-      if (po) b->allocs.push_back(po);
-      if (pc) b->allocs.push_back(pc);
-      if (pt) b->allocs.push_back(pt);
-      if (!rc) { rc |= be_h2d(po, ident.data(), sizeof(int) * (size_t)n_envs); rc |= (int)hipMemset(pc, 0, sizeof(float) * (size_t)n_envs); rc |= (int)hipMemset(pt, 0, sizeof(unsigned) * (size_t)n_envs); }
-      if (!rc) { b->order = (int*)po; b->cost = (float*)pc; b->ticks = (unsigned*)pt; }
+      int* po = dev_upload(b->allocs, rc, ident);
+      float* pc = dev_alloc<float>(b->allocs, rc, n_envs);
+      unsigned* pt = dev_alloc<unsigned>(b->allocs, rc, n_envs);
+      if (!rc) { rc |= (int)hipMemset(pc, 0, sizeof(float) * (size_t)n_envs); rc |= (int)hipMemset(pt, 0, sizeof(unsigned) * (size_t)n_envs); }
+      if (!rc) { b->order = po; b->cost = pc; b->ticks = pt; }
     }
     if (!rc && b->plan.nparts >= 2) {
-      void *ps = nullptr, *pg = nullptr;
-      rc |= be_malloc(&ps, sizeof(int) * (size_t)n_envs); rc |= be_malloc(&pg, sizeof(int) * 4);
-      if (ps) b->allocs.push_back(ps);
-      if (pg) b->allocs.push_back(pg);
       const int zero[4] = {0, 0, 0, 0};
-      if (!rc) { rc |= (int)hipMemset(ps, 0, sizeof(int) * (size_t)n_envs); rc |= be_h2d(pg, zero, sizeof zero); }
-      if (!rc) { b->part_state = (int*)ps; b->step_gen = (int*)pg; } else b->plan.nparts = 1;
+      int* ps = dev_alloc<int>(b->allocs, rc, n_envs);
+      int* pg = dev_upload(b->allocs, rc, zero, 4);
+      if (!rc) rc |= (int)hipMemset(ps, 0, sizeof(int) * (size_t)n_envs);
+      if (!rc) { b->part_state = ps; b->step_gen = pg; } else b->plan.nparts = 1;
     }
     if (!rc && m->ngw > 64 && !getenv("MYO_NO_WRAP_ORDER")) {        // (more than one pass of the wrap solver: worth ordering, see env_wrap_census)
-      void* pw = nullptr;
-      if (!be_malloc(&pw, sizeof(int) * (size_t)m->ngw)) {
-        b->allocs.push_back(pw);
-        if (hipMemset(pw, 0, sizeof(int) * (size_t)m->ngw) == hipSuccess) b->wrap_cnt = (int*)pw;
-      }
+      int wrc = 0;                                                   // (a batch without the census still steps: not an error of the create)
+      int* pw = dev_alloc<int>(b->allocs, wrc, m->ngw);
+      if (!wrc && hipMemset(pw, 0, sizeof(int) * (size_t)m->ngw) == hipSuccess) b->wrap_cnt = pw;
     }
   }
   return rc;

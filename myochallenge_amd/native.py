@@ -197,6 +197,9 @@ JAC_BODY, JAC_BODYCOM, JAC_SITE, JAC_GEOM, JAC_SUBTREECOM = range(5)      # MYO_
 JAC_KINDS = {"body": JAC_BODY, "bodycom": JAC_BODYCOM, "site": JAC_SITE, "geom": JAC_GEOM, "subtreecom": JAC_SUBTREECOM}
 
 
+TABLE_DTYPES = (np.int32, np.uint64, np.float32, np.float64)      # MYO_TABLE_* of include/myobatch.h
+
+
 class MyoError(RuntimeError):
     pass
 
@@ -217,6 +220,7 @@ class NativeLib:
         L.myo_model_load_mjb.argtypes = [C.c_char_p, i32, i32, C.POINTER(vp)]
         L.myo_model_destroy.argtypes = [vp]
         L.myo_model_size.argtypes = [vp, C.c_char_p]
+        L.myo_model_table.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i32)]
         L.myo_batch_create.argtypes = [vp, C.POINTER(TaskCfg), i32, i32, u64, i32, C.POINTER(vp)]
         L.myo_batch_destroy.argtypes = [vp]
         L.myo_batch_num_envs.argtypes = [vp]
@@ -343,7 +347,7 @@ def load(path: Optional[str] = None) -> NativeLib:
 
 
 EXPORTED_SYMBOLS = [
-    "myo_model_from_blob", "myo_model_load_mjb", "myo_model_destroy", "myo_model_size", "myo_batch_create",
+    "myo_model_from_blob", "myo_model_load_mjb", "myo_model_destroy", "myo_model_size", "myo_model_table", "myo_batch_create",
     "myo_batch_destroy", "myo_batch_set_step_generation", "myo_batch_health", "myo_debug_wave_slots", "myo_batch_num_envs", "myo_batch_obs_dim", "myo_batch_lds_bytes",
     "myo_batch_reset", "myo_batch_step", "myo_batch_step_inner", "myo_batch_step_inner_idx", "myo_batch_copy_envs", "myo_batch_physics_step", "myo_batch_get_state",
     "myo_batch_set_state", "myo_batch_warmstart", "myo_batch_set_bad_state_buffer", "myo_batch_set_task", "myo_batch_get_task", "myo_batch_set_object_group", "myo_batch_object_friction", "myo_batch_bind_constants", "myo_batch_tune_wrap_order", "myo_batch_forward_dump",
@@ -368,7 +372,7 @@ ENV_PATH_SYMBOLS = [
     "myo_batch_lds_bytes", "myo_batch_num_envs", "myo_batch_object_friction", "myo_batch_obs_dim", "myo_batch_physics_step", "myo_batch_reset",
     "myo_batch_set_bad_state_buffer", "myo_batch_set_object_group", "myo_batch_set_state", "myo_batch_set_step_generation", "myo_batch_set_task",
     "myo_batch_step", "myo_batch_step_inner", "myo_batch_step_inner_idx", "myo_batch_tune_wrap_order", "myo_batch_warmstart", "myo_debug_wave_slots",
-    "myo_last_error", "myo_model_destroy", "myo_model_from_blob", "myo_model_load_mjb", "myo_model_size", "myo_version",
+    "myo_last_error", "myo_model_destroy", "myo_model_from_blob", "myo_model_load_mjb", "myo_model_size", "myo_model_table", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
     "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
@@ -402,6 +406,13 @@ class Model:
 
     def size(self, name: str) -> int:
         return self.lib.L.myo_model_size(self.h, name.encode())
+
+    def table(self, name: str) -> np.ndarray:
+        """A copy of one table (or non-int scalar) of the host model, as the loader derived it (myo_model_table)."""
+        p, nbytes, dtype = C.c_void_p(), C.c_size_t(), C.c_int()
+        self.lib.check(self.lib.L.myo_model_table(self.h, name.encode(), C.byref(p), C.byref(nbytes), C.byref(dtype)))
+        raw = C.string_at(p, nbytes.value) if nbytes.value else b""
+        return np.frombuffer(raw, dtype=TABLE_DTYPES[dtype.value]).copy()
 
     def default_camera(self) -> dict:
         """The model's default free camera (myo_model_default_camera): lookat, distance, azimuth, elevation, fovy."""

@@ -376,22 +376,12 @@ def test_explicit_pair_replaces_every_dynamic_pair_of_its_two_bodies(models, emu
     other bodies' pairs with the ball are untouched."""
     from myochallenge_amd import native
     from myochallenge_amd.mjb import dump_mjb
+    from host_table_cases import explicit_pair_model
     hand = models["hand"]
     base = compile_model(hand)
     gb = np.asarray(hand.geom_bodyid)
     pairs = list(zip(base.x_pair_geom1.tolist(), base.x_pair_geom2.tolist()))
-    g_ball = hand.names["geom"].index("ball1")
-    b_ball = int(gb[g_ball])
-    # a hand body with >= 2 geoms colliding with ball1
-    partners = [int(b if a == g_ball else a) for a, b in pairs if g_ball in (a, b)]
-    by_body = {}
-    for g in partners:
-        by_body.setdefault(int(gb[g]), []).append(g)
-    body, geoms = next((b, gs) for b, gs in by_body.items() if len(gs) >= 2 and b != b_ball)
-    xp = _with(hand, pair_dim=np.full(1, 3, np.int32), pair_geom1=np.array([geoms[0]], np.int32), pair_geom2=np.array([g_ball], np.int32),
-               pair_signature=np.array([((min(body, b_ball) + 1) << 16) + max(body, b_ball) + 1], np.int32), pair_solref=np.array([[0.02, 1.0]]),
-               pair_solimp=np.array([[0.9, 0.95, 0.001, 0.5, 2.0]]), pair_margin=np.zeros(1), pair_gap=np.zeros(1),
-               pair_friction=np.array([[1.0, 1.0, 0.005, 1e-4, 1e-4]]), name_pairadr=np.zeros(1, np.int32), npair=1)
+    xp, body, geoms, g_ball, b_ball = explicit_pair_model(hand)      # a hand body with >= 2 geoms colliding with ball1, one explicit pair
     cm = compile_model(xp)
     kept = list(zip(cm.x_pair_geom1.tolist(), cm.x_pair_geom2.tolist(), cm.x_pair_explicit.tolist()))
     between = [(a, b, x) for a, b, x in kept if {int(gb[a]), int(gb[b])} == {body, b_ball}]

@@ -444,7 +444,31 @@ def classifier_goldens(allobs):
     print("classifier goldens:", X.shape, "hold fraction", float((task == 0).mean()))
 
 
+def host_tables(values_path=None):
+    """`make_golden.py host_tables [--values FILE.npz]`: what the host model loader derives (tests/host_table_cases.py) ->
+    host_tables.json, from the emulation library of THIS checkout; needs no reference checkout.  Regenerate it only on purpose: the
+    file pins the loader (tests/test_host_tables.py).  --values also writes every table's values, outside the repository, for that
+    test's first-differing-index report."""
+    sys.path.insert(0, os.path.join(OUT, ".."))
+    import host_table_cases as htc
+    from myochallenge_amd import native
+    from myochallenge_amd.build import build_emu
+    lib = native.load(build_emu())
+    out, values = {}, {}
+    for case in htc.case_names():
+        read = htc.read_model(htc.load_case(case, lib))
+        out[case] = htc.digest(read)
+        values.update({"%s/%s" % (case, n): a for n, a in read["tables"].items()})
+    htc.write_fixture(out)
+    if values_path:
+        np.savez_compressed(values_path, **values)
+    print("host tables:", len(out), "models,", len(htc.table_names()), "tables each,", os.path.getsize(htc.FIXTURE), "bytes")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["host_tables"]:
+        host_tables(sys.argv[3] if sys.argv[2:3] == ["--values"] else None)
+        sys.exit(0)
     ref = import_reference_baoding()
     allobs, cfgs = artifacts()
     mjb_fixtures()
