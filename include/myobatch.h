@@ -428,6 +428,52 @@ typedef struct myo_static_opt_out {
 } myo_static_opt_out;
 int myo_batch_static_opt(myo_batch* b, const myo_static_opt_in* in, const myo_static_opt_out* out, void* stream);
 
+/* ---- per-env inverse kinematics: the joint pose that puts k sites on k world targets — the first link of the tool chain above
+ * (task-space data such as fingertip targets or marker positions -> qpos -> inverse dynamics -> static optimisation).  The ACTIVE
+ * joints are the model's hinge and slide joints, or those of them whose dof is set in `active`; every other qpos entry (the balls'
+ * and the die's free joints) stays at its start value.  One wave per env solves
+ *   minimise  1/2 sum_o w_o |site_xpos_o(q) - t_o|^2 + 1/2 reg sum_a (q_a - q_ref_a)^2,   lower_a <= q_a <= upper_a
+ * in doubles whatever the batch's dtype, by projected Levenberg-Marquardt (each step a box QP solved by projected Newton, accepted on
+ * the cost of a fresh position pass, so the cost never increases), deterministically.  The env's record is only read: the envs'
+ * states do not move.  Inputs (dev):
+ *   site_ids [k] int32         the sites to place, k <= MYO_IK_K_MAX; an id outside the model contributes nothing (its output rows are 0)
+ *   targets  [N, k, 3]         world positions; required
+ *   weight   [k] or [N, k]     (weight_per_env = 0 / 1) w >= 0, negative entries count as 0; NULL: 1
+ *   q_init   [N, nq]           the start point (every entry, frozen ones included); NULL: the env's present qpos.  Projected into the box
+ *   q_ref    [N, nq]           the regularisation centre; NULL: the start point as given
+ *   lower, upper [N, nv]       indexed by dof; NULL: jnt_range where jnt_limited, else unbounded.  lower > upper pins the joint at
+ *                              lower (MYO_IK_PINNED)
+ *   active                     dof mask, bit i = dof i; 0: every hinge / slide dof; bits of other joints' dofs are ignored
+ *   reg > 0 finite (1e-6), tol > 0 (1e-10), max_iter >= 1 (50); else MYO_E_ARG
+ * It stops when the projected gradient's max-norm is <= tol (1 + |J'We|_inf at the start), after max_iter steps (MYO_IK_CAP), or
+ * when the damping passes its cap without an acceptable step (MYO_IK_STALL).  Outputs (dev, any may be NULL):
+ *   qpos [N, nq]                     the solution: an accepted iterate or the projected start; frozen entries bit for bit the start's
+ *   site_xpos, residual [N, k, 3]    the sites there, and position - target (unweighted)
+ *   cost, kkt [N]                    the cost there and the projected gradient's max-norm
+ *   iters, status [N] int32          accepted + rejected steps; 0 = converged, else bits MYO_IK_CAP / MYO_IK_STALL / MYO_IK_PINNED
+ * k = 0 is legal (q goes to clip(q_ref)).  All outputs NULL launches nothing.  A NULL batch / struct, another `size` or missing
+ * targets (k > 0) returns MYO_E_BADARG (= MYO_E_ARG); k < 0, k > MYO_IK_K_MAX, a NULL site_ids with k > 0, a bad reg / tol / max_iter
+ * MYO_E_ARG; all before any device call. */
+#define MYO_IK_K_MAX 16
+enum { MYO_IK_CAP = 1, MYO_IK_STALL = 2, MYO_IK_PINNED = 4 };
+typedef struct myo_ik_in {
+  size_t size;
+  const int32_t* site_ids;
+  int k;
+  const double *targets, *weight;
+  int weight_per_env;
+  const double *q_init, *q_ref, *lower, *upper;
+  uint64_t active;
+  double reg, tol;
+  int max_iter;
+} myo_ik_in;
+typedef struct myo_ik_out {
+  size_t size;
+  double *qpos, *site_xpos, *residual, *cost, *kkt;
+  int32_t *iters, *status;
+} myo_ik_out;
+int myo_batch_ik(myo_batch* b, const myo_ik_in* in, const myo_ik_out* out, void* stream);
+
 /* ---- rendering of env states (MuJoCo's mjr_render / mjr_readPixels seam: CustomPenEnv.render -> self.sim.render,
  * /root/reference/src/main_eval.py:96-97).  Draws what the stepper holds: every geom at the pose of the env's present state
  * and with the env's own geometry (Baoding P2 ball radius, die size delta), the Baoding target sites where the task puts

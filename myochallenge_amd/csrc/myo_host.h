@@ -32,6 +32,7 @@
 #include "myo_data.h"
 #include "myo_jac.h"
 #include "myo_static_opt.h"
+#include "myo_ik.h"
 #include "myo_render.h"
 
 
@@ -1145,6 +1146,7 @@ struct myo_batch {
   double* render_ws = nullptr; // dev: item poses and cameras of myo_batch_render, grown on demand (not in allocs)
   size_t render_ws_bytes = 0;
   double* so_ws = nullptr;     // dev [n, MYO_SO_WS_N]: the system matrices of myo_batch_static_opt, allocated by its first solve (not in allocs)
+  double* ik_ws = nullptr;     // dev [n, MYO_IK_WS_N]: system matrix, Jacobian and site points of myo_batch_ik, allocated by its first call (not in allocs)
   unsigned long long act_reach = 0;      // dofs some actuator's moment row can reach: myo_batch_static_opt's default weight
   std::vector<double> cam_host;      // the cameras of the last myo_batch_render (source of its asynchronous upload)
   // how contact items are drawn (myo_batch_set_render_style; the defaults of include/myobatch.h)
@@ -1459,6 +1461,7 @@ static void batch_release(myo_batch* b, int destroying) {
   release_allocs(b->allocs);
   if (b->render_ws) be_free(b->render_ws);
   if (b->so_ws) be_free(b->so_ws);
+  if (b->ik_ws) be_free(b->ik_ws);
   delete b;
 }
 
@@ -1901,6 +1904,36 @@ extern "C" int myo_batch_static_opt(myo_batch* b, const myo_static_opt_in* in, c
     d.ws = b->so_ws; d.reach = b->act_reach; d.reg = in->reg; d.max_iter = in->max_iter; d.solve = 1;
   }
   return be_run(b, StaticOptJob{d}, b->n, stream);
+}
+// myo_batch_ik (csrc/myo_ik.h): IkJob is a row of the variant table like StaticOptJob; the system matrix, the Jacobian and the site
+// points of the accepted iterate live in a workspace of the batch's own, allocated by the first call.  Every array lives on the
+// device: the host refuses what it can see.
+static_assert((int)MYO_IK_CAP == (int)MYO_IK_ST_CAP && (int)MYO_IK_STALL == (int)MYO_IK_ST_STALL && (int)MYO_IK_PINNED == (int)MYO_IK_ST_PINNED, "status bits of include/myobatch.h and csrc/myo_ik.h");
+extern "C" int myo_batch_ik(myo_batch* b, const myo_ik_in* in, const myo_ik_out* out, void* stream) {
+  if (!b || !in || !out) return fail(MYO_E_BADARG, "myo_batch_ik: null batch, input or output struct");
+  if (in->size != sizeof(myo_ik_in)) return fail(MYO_E_BADARG, "myo_batch_ik: myo_ik_in.size is %zu, this library's struct has %zu bytes", in->size, sizeof(myo_ik_in));
+  if (out->size != sizeof(myo_ik_out)) return fail(MYO_E_BADARG, "myo_batch_ik: myo_ik_out.size is %zu, this library's struct has %zu bytes", out->size, sizeof(myo_ik_out));
+  if (!out->qpos && !out->site_xpos && !out->residual && !out->cost && !out->kkt && !out->iters && !out->status) return MYO_OK;
+  if (in->k < 0 || in->k > MYO_IK_K_MAX) return fail(MYO_E_ARG, "myo_batch_ik: k must be in [0, %d], got %d", MYO_IK_K_MAX, in->k);
+  if (in->k > 0 && !in->site_ids) return fail(MYO_E_ARG, "myo_batch_ik: site_ids is NULL with k = %d", in->k);
+  if (in->k > 0 && !in->targets) return fail(MYO_E_BADARG, "myo_batch_ik: targets is required");
+  if (!(in->reg > 0) || !std::isfinite(in->reg)) return fail(MYO_E_ARG, "myo_batch_ik: reg must be finite and > 0");
+  if (!(in->tol > 0)) return fail(MYO_E_ARG, "myo_batch_ik: tol must be > 0");
+  if (in->max_iter < 1) return fail(MYO_E_ARG, "myo_batch_ik: max_iter must be >= 1");
+  if (!b->ik_ws) {
+    void* p = nullptr;
+    const int e = be_malloc(&p, (size_t)b->n * MYO_IK_WS_N * sizeof(double));
+    if (e || !p) return fail(MYO_E_DEVICE, "myo_batch_ik: workspace allocation failed: %s", be_errstr(e));
+    b->ik_ws = (double*)p;
+  }
+  IkDev d{};
+  d.site_ids = in->site_ids; d.targets = in->targets; d.weight = in->weight; d.q_init = in->q_init; d.q_ref = in->q_ref;
+  d.lower = in->lower; d.upper = in->upper;
+  d.qpos = out->qpos; d.site_xpos = out->site_xpos; d.residual = out->residual; d.cost = out->cost; d.kkt = out->kkt;
+  d.iters = out->iters; d.status = out->status;
+  d.ws = b->ik_ws; d.active = in->active; d.reg = in->reg; d.tol = in->tol;
+  d.k = in->k; d.weight_per_env = in->weight && in->weight_per_env ? 1 : 0; d.max_iter = in->max_iter;
+  return be_run(b, IkJob{d}, b->n, stream);
 }
 extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
   if (int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses")) return rc;

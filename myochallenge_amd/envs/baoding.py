@@ -529,6 +529,85 @@ class BaodingVecEnv:
             out = {k: v[idx] for k, v in out.items()}
         return out
 
+    # ---------------------------------------------------------------- inverse kinematics (include/myobatch.h myo_batch_ik)
+    def _ik_active(self, joints):
+        """dof mask of `joints` (names or ids of hinge / slide joints); None: 0, the library's default (every hinge / slide dof)"""
+        if joints is None:
+            return 0
+        f = self.compiled.fields
+        jtype, dofadr = np.asarray(f["jnt_type"]), np.asarray(f["jnt_dofadr"])
+        names = list(self.compiled.names.get("jnt", []))
+        mask = 0
+        for j in ([joints] if isinstance(joints, (str, int, np.integer)) else joints):
+            if isinstance(j, str):
+                if not j or j not in names:
+                    raise KeyError(f"unknown joint name {j!r}")
+                j = names.index(j)
+            if not 0 <= int(j) < len(jtype):
+                raise KeyError(f"joint id {int(j)} outside [0, {len(jtype)})")
+            if int(jtype[int(j)]) not in (2, 3):
+                raise ValueError(f"joint {int(j)} is neither a hinge nor a slide joint: inverse kinematics does not move it")
+            mask |= 1 << int(dofadr[int(j)])
+        if mask == 0:
+            raise ValueError("joints is empty")
+        return mask
+
+    def inverse_kinematics(self, sites, targets, weight=None, q_init=None, q_ref=None, lower=None, upper=None, joints=None, reg=1e-6,
+                           tol=1e-10, max_iter=50, indices=None, keys=None) -> dict:
+        """The joint pose that puts sites on world targets — the step before inverse dynamics: per env, minimise
+        ``1/2 sum_o w_o |site_xpos_o(q) - t_o|^2 + 1/2 reg |q - q_ref|^2`` over ``lower <= q <= upper`` for the hinge and slide joints
+        (or ``joints``); every other qpos entry keeps its start value.  One pass on the GPU (projected Levenberg-Marquardt, float64
+        whatever the batch's dtype, deterministic), nothing about the envs changes — apply the result with ``set_state`` if wanted;
+        device tensors, no host copy.
+
+        sites: names or ids (``site_names()``), at most ``native.IK_K_MAX``.  targets: [N, k, 3].  weight: [k] or [N, k], >= 0
+        (default 1).  q_init: [N, nq] start point (default: the envs' present qpos).  q_ref: [N, nq] (default: the start point).
+        lower / upper: [N, nv], by dof (default: jnt_range of limited joints, else unbounded).  joints: names or ids of the hinge /
+        slide joints to move (default: all of them).  Returns (``keys``, default all) ``qpos`` [k_env, nq], ``site_xpos`` /
+        ``residual`` (position - target) [k_env, k, 3], ``cost`` / ``kkt`` [k_env], ``iters`` / ``status`` [k_env] int32 (0: converged;
+        ``native.IK_CAP``: max_iter; ``native.IK_STALL``: no acceptable step; ``native.IK_PINNED``: a joint with lower > upper).
+        indices: the envs' rows to return (default: all; the pass itself always runs the whole batch)."""
+        t = self.torch
+        ids = self._jac_ids("site", [] if sites is None else sites)
+        n, k, nv, nq = self.num_envs, len(ids), self._model.size("nv"), self._model.size("nq")
+        if k > native.IK_K_MAX:
+            raise ValueError(f"at most {native.IK_K_MAX} sites per call, got {k}")
+        shapes = self.batch.ik_shapes(k)
+        keys = list(shapes) if keys is None else list(keys)
+        for key in keys:
+            if key not in shapes:
+                raise KeyError(f"unknown inverse-kinematics key {key!r}; known: {sorted(shapes)}")
+
+        def arr(x, name, shape_ok):
+            if x is None:
+                return None
+            x = t.as_tensor(x, dtype=t.float64, device=self.device).contiguous()
+            if tuple(x.shape) not in shape_ok:
+                raise ValueError(f"{name} must have shape {' or '.join(str(s) for s in shape_ok)}")
+            return x
+        active = self._ik_active(joints)
+        targets = arr(targets, "targets", [(n, k, 3)])
+        if targets is None:
+            raise ValueError(f"targets must have shape {(n, k, 3)}")
+        weight = arr(weight, "weight", [(k,), (n, k)])
+        on_host = lambda x: not (isinstance(x, t.Tensor) and x.device.type != "cpu")
+        check_box = lower is not None and upper is not None and on_host(lower) and on_host(upper)
+        q_init, q_ref = arr(q_init, "q_init", [(n, nq)]), arr(q_ref, "q_ref", [(n, nq)])
+        lower, upper = arr(lower, "lower", [(n, nv)]), arr(upper, "upper", [(n, nv)])
+        if check_box and bool((lower > upper).any()):      # (host-visible arrays only, as static_optimization: the kernel pins such a joint at lower and says so)
+            raise ValueError("lower > upper")
+        tdt = {np.int32: t.int32, np.float64: t.float64}
+        out = {key: t.empty((n,) + shapes[key][0], dtype=tdt[shapes[key][1]], device=self.device) for key in keys}
+        ids_t = t.as_tensor(ids, dtype=t.int32, device=self.device)
+        self.batch.ik(ids_t, targets, weight, weight is not None and weight.dim() == 2, q_init, q_ref,
+                      lower, upper, active, float(reg), float(tol), int(max_iter), self._stream(), **out)
+        if self.device.type == "cuda":
+            t.cuda.synchronize(self.device)       # (the inputs may be temporaries: the pass must have read them)
+        if indices is not None:
+            idx = t.as_tensor([int(i) for i in indices], dtype=t.long, device=self.device)
+            out = {key: v[idx] for key, v in out.items()}
+        return out
+
     def site_names(self) -> List[str]:
         """names of the model's sites: rows of ``data()``'s ``site_xpos``"""
         return list(self.compiled.names.get("site", []))

@@ -193,6 +193,26 @@ class StaticOptOut(C.Structure):
 STATIC_OPT_KEYS = tuple(f[0] for f in StaticOptOut._fields_[1:])
 STATIC_OPT_CAP, STATIC_OPT_PINNED = 1, 4      # MYO_STATIC_OPT_* of include/myobatch.h: bits of `status`
 
+
+
+class IkIn(C.Structure):
+    """myo_ik_in of include/myobatch.h: device arrays (site_ids int32, the others doubles) and scalars of myo_batch_ik; every pointer but
+    site_ids / targets (k > 0) may be NULL."""
+    _fields_ = [("size", C.c_size_t), ("site_ids", C.c_void_p), ("k", C.c_int), ("targets", C.c_void_p), ("weight", C.c_void_p),
+                ("weight_per_env", C.c_int), ("q_init", C.c_void_p), ("q_ref", C.c_void_p), ("lower", C.c_void_p), ("upper", C.c_void_p),
+                ("active", C.c_uint64), ("reg", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int)]
+
+
+class IkOut(C.Structure):
+    """myo_ik_out of include/myobatch.h: caller-owned device arrays of myo_batch_ik (doubles; iters / status int32), any of them NULL."""
+    _fields_ = [("size", C.c_size_t)] + [(k, C.c_void_p) for k in ("qpos", "site_xpos", "residual", "cost", "kkt", "iters", "status")]
+
+
+IK_KEYS = tuple(f[0] for f in IkOut._fields_[1:])
+IK_CAP, IK_STALL, IK_PINNED = 1, 2, 4      # MYO_IK_* of include/myobatch.h: bits of `status`
+IK_K_MAX = 16                              # MYO_IK_K_MAX of include/myobatch.h
+IK_WS_DOUBLES = 2448                       # MYO_IK_WS_N of csrc/myo_ik.h: doubles per env of the library's own workspace
+
 JAC_BODY, JAC_BODYCOM, JAC_SITE, JAC_GEOM, JAC_SUBTREECOM = range(5)      # MYO_JAC_* of include/myobatch.h
 JAC_KINDS = {"body": JAC_BODY, "bodycom": JAC_BODYCOM, "site": JAC_SITE, "geom": JAC_GEOM, "subtreecom": JAC_SUBTREECOM}
 
@@ -265,6 +285,7 @@ class NativeLib:
         L.myo_batch_jac.argtypes = [vp, i32, vp, i32, vp, C.POINTER(JacOut), vp]
         L.myo_batch_inverse.argtypes = [vp, vp, C.POINTER(InverseOut), vp]
         L.myo_batch_static_opt.argtypes = [vp, C.POINTER(StaticOptIn), C.POINTER(StaticOptOut), vp]
+        L.myo_batch_ik.argtypes = [vp, C.POINTER(IkIn), C.POINTER(IkOut), vp]
         if b"MYO_EMU" in L.myo_version():
             return      # the emulation build (test tooling, csrc/emu_host.h) implements the env path only: ENV_PATH_SYMBOLS
         L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp, vp]
@@ -355,7 +376,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_ppo_gather_seq", "myo_rollout_state_snapshot", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
     "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_last_error", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
-    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt",
+    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt", "myo_batch_ik",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
     "myo_ppo_mlp_step_resident", "myo_ppo_mlp_images", "myo_ppo_adv_moments_epoch",
@@ -374,7 +395,7 @@ ENV_PATH_SYMBOLS = [
     "myo_batch_step", "myo_batch_step_inner", "myo_batch_step_inner_idx", "myo_batch_tune_wrap_order", "myo_batch_warmstart", "myo_debug_wave_slots",
     "myo_last_error", "myo_model_destroy", "myo_model_from_blob", "myo_model_load_mjb", "myo_model_size", "myo_model_table", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
-    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt",
+    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt", "myo_batch_ik",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
 ]
@@ -657,6 +678,28 @@ class Batch:
                 raise KeyError(k)
             setattr(out, k, _ptr(v))
         self.lib.check(self.lib.L.myo_batch_static_opt(self.h, C.byref(inp), C.byref(out), stream))
+
+    def ik_shapes(self, k: int) -> dict:
+        """key -> (per-env shape, dtype) of the arrays of ik() for k targets"""
+        return {"qpos": ((self.model.size("nq"),), np.float64), "site_xpos": ((k, 3), np.float64), "residual": ((k, 3), np.float64),
+                "cost": ((), np.float64), "kkt": ((), np.float64), "iters": ((), np.int32), "status": ((), np.int32)}
+
+    def ik(self, site_ids, targets, weight=None, weight_per_env=False, q_init=None, q_ref=None, lower=None, upper=None, active=0,
+           reg=1e-6, tol=1e-10, max_iter=50, stream=None, **arrays):
+        """inverse kinematics from the envs' present states or q_init (myo_batch_ik): site_ids int32 [k] device array, targets float64
+        [N, k, 3], weight float64 [k] or — weight_per_env — [N, k], q_init / q_ref float64 [N, nq], lower / upper float64 [N, nv] (by dof),
+        each a device array or None (the library's default); active: dof mask (0: every hinge / slide dof); keyword = a key of IK_KEYS,
+        value = the device array that receives it ([N, *ik_shapes(k)[key]]).  Keys not given are not computed; the envs do not move."""
+        inp, out = IkIn(), IkOut()
+        inp.size, out.size = C.sizeof(IkIn), C.sizeof(IkOut)
+        inp.site_ids, inp.k, inp.targets, inp.weight = _ptr(site_ids), int(site_ids.shape[0]) if site_ids is not None else 0, _ptr(targets), _ptr(weight)
+        inp.weight_per_env, inp.q_init, inp.q_ref, inp.lower, inp.upper = int(bool(weight_per_env)), _ptr(q_init), _ptr(q_ref), _ptr(lower), _ptr(upper)
+        inp.active, inp.reg, inp.tol, inp.max_iter = int(active), float(reg), float(tol), int(max_iter)
+        for k, v in arrays.items():
+            if k not in IK_KEYS:
+                raise KeyError(k)
+            setattr(out, k, _ptr(v))
+        self.lib.check(self.lib.L.myo_batch_ik(self.h, C.byref(inp), C.byref(out), stream))
 
     @property
     def dump_size(self) -> int:

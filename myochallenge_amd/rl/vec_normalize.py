@@ -271,6 +271,9 @@ class VecNormalize:
     def static_optimization(self, *args, **kwargs):
         return self.venv.static_optimization(*args, **kwargs)
 
+    def inverse_kinematics(self, *args, **kwargs):
+        return self.venv.inverse_kinematics(*args, **kwargs)
+
     # muscle fatigue state (muscle_condition="fatigue"): forwarded likewise
     def fatigue_state(self):
         return self.venv.fatigue_state()
