@@ -474,6 +474,51 @@ typedef struct myo_ik_out {
 } myo_ik_out;
 int myo_batch_ik(myo_batch* b, const myo_ik_in* in, const myo_ik_out* out, void* stream);
 
+/* ---- read-only open-loop simulation: what happens from this state under these controls?  S control sequences ("samples") for each
+ * of k listed envs, T control steps of nsub substeps each, in ONE launch of k S workgroups — the primitive of sampling-based control
+ * (MPPI, predictive sampling), of tracking controllers, of finite-difference linearisation, and the check that static optimisation's
+ * activations deliver the motion they were solved for.  Each sample runs on a copy of the env's whole record in a workspace of the
+ * library's own (the env's warm start, time, per-episode ball / object parameters and task block go with it): the env's record is
+ * only read, the envs do not move, and an env may be listed more than once.  The stepper is the batch's own (dtype, integrator,
+ * contact capacity); the controls are muscle controls exactly as myo_batch_physics_step takes them: no action map, no fatigue
+ * advance, no task layer, no reset.  Row (e, j) below is sample j of env env_idx[e].  Inputs (dev):
+ *   env_idx  [k] int32               the envs; NULL: envs 0 .. k - 1 (k = N: all envs in order).  An index outside [0, N): the rows of
+ *                                    its samples are NaN, bad = 1, steps = 0
+ *   k >= 0, S >= 1, T >= 1           k S must fit an int
+ *   nsub >= 0                        substeps per control step; 0: the task's frame_skip (1 without a task layer)
+ *   every >= 1                       the state is recorded after every `every`-th control step: R = T / every rows; T % every must be 0
+ *   ctrl                             [k, S, T, nu] (ctrl_per_sample = 1) or [k, T, nu] shared by an env's samples (0); NULL: zeros
+ *   qpos0, qvel0, act0               [k, S, nq / nv / na]: the samples' start states; NULL: the env's own
+ *   site_ids [ns] int32              sites whose world positions are recorded, ns <= MYO_SIM_NS_MAX; an id outside the model gives NaN
+ * Outputs (dev, doubles, any may be NULL):
+ *   qpos [k, S, R, nq], qvel [k, S, R, nv], act [k, S, R, na], time [k, S, R]     the state after control step (row + 1) * every
+ *   site_xpos [k, S, R, ns, 3]       the listed sites there (one extra position pass per recorded step), as myo_batch_data places them
+ *   bad, steps [k, S] int32          a sample whose state blows up (MuJoCo's mj_checkPos / mj_checkVel / mj_checkAcc) stops: bad = 1,
+ *                                    steps = the control steps it completed, its remaining rows NaN; else bad = 0, steps = T
+ * The same bits on every run, whatever S and whoever a sample's neighbours are.  k = 0 or all outputs NULL launches nothing.  The
+ * workspace (k S rows of one record, plus the RK4 stage block where that lives in global memory) grows on demand and is freed with
+ * the batch; growing it frees the old block, so a call that has to grow it while `stream` is capturing returns MYO_E_STATE: size it
+ * with an eager call of the same k S first.  A NULL batch / struct or another `size` returns MYO_E_BADARG (= MYO_E_ARG); a bad
+ * k / S / T / nsub / every / ns, T % every != 0, k S beyond an int, site outputs without site_ids: MYO_E_ARG; all before any device
+ * call. */
+#define MYO_SIM_NS_MAX 16
+typedef struct myo_sim_in {
+  size_t size;
+  const int32_t* env_idx;
+  int k, S, T, nsub, every;
+  const double* ctrl;
+  int ctrl_per_sample;
+  const double *qpos0, *qvel0, *act0;
+  const int32_t* site_ids;
+  int ns;
+} myo_sim_in;
+typedef struct myo_sim_out {
+  size_t size;
+  double *qpos, *qvel, *act, *time, *site_xpos;
+  int32_t *bad, *steps;
+} myo_sim_out;
+int myo_batch_simulate(myo_batch* b, const myo_sim_in* in, const myo_sim_out* out, void* stream);
+
 /* ---- rendering of env states (MuJoCo's mjr_render / mjr_readPixels seam: CustomPenEnv.render -> self.sim.render,
  * /root/reference/src/main_eval.py:96-97).  Draws what the stepper holds: every geom at the pose of the env's present state
  * and with the env's own geometry (Baoding P2 ball radius, die size delta), the Baoding target sites where the task puts

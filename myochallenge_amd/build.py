@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["myobatch.hip", "myo_host.h", "myo_task.h", "myo_physics.h", "myo_model_dev.h", "wave.h", "myo_mjb.h", "mjb_layout.inc", "myo_render.h", "myo_sense.h", "myo_data.h", "myo_jac.h", "myo_static_opt.h", "myo_ik.h",
+SOURCES = ["myobatch.hip", "myo_host.h", "myo_task.h", "myo_physics.h", "myo_model_dev.h", "wave.h", "myo_mjb.h", "mjb_layout.inc", "myo_render.h", "myo_sense.h", "myo_data.h", "myo_jac.h", "myo_static_opt.h", "myo_ik.h", "myo_simulate.h",
            "myo_ppo_mlp.h", "myo_act.h", "myo_sparse_ldl.h", "myo_arrow_chol.h", "myo_lstm_step.h", "myo_lstm_seq.h", "myo_ensemble.h", "myo_sde_loss.h"]
 HEADERS = [os.path.join(ROOT, "include", "myobatch.h"), os.path.join(ROOT, "include", "myo_model_blob.h")]
 # the emulation build's own translation unit and backend (TEST TOOLING: nothing of it is compiled into libmyobatch.so, and it is not part

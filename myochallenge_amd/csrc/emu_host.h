@@ -39,6 +39,7 @@ static void be_xfer_i(myo_batch* b, int off, int cnt, int* ext, int to_ext, void
       if (to_ext) ext[(size_t)e * cnt + k] = (int)*r; else *r = (double)ext[(size_t)e * cnt + k];
     }
 }
+static int be_capturing(void*) { return 0; }
 static int be_launch_status() { return MYO_OK; }
 static void be_task_changed(myo_batch*) {}
 

@@ -33,6 +33,7 @@
 #include "myo_jac.h"
 #include "myo_static_opt.h"
 #include "myo_ik.h"
+#include "myo_simulate.h"
 #include "myo_render.h"
 
 
@@ -51,6 +52,7 @@ static void be_batch_release(myo_batch* b, int device, int destroying);         
 // `stream` is the ABI's (a hipStream_t, or unused)
 static void be_xfer(myo_batch* b, int off, int cnt, double* ext, int to_ext, void* stream);
 static void be_xfer_i(myo_batch* b, int off, int cnt, int* ext, int to_ext, void* stream);   // ... of a field that holds integers
+static int be_capturing(void* stream);                                                       // 1 while `stream` records a graph (allocations and frees are not to happen then)
 static int be_launch_status();                                                             // MYO_OK, or what became of the launches just issued (MYO_E_DEVICE)
 static void be_task_changed(myo_batch* b);                                                 // the host's task block (b->K) changed: what was issued is waited for, the next launch uploads it again
 // the launches of the env path (`stream` as above).  be_run: job J (csrc/myo_task.h) for blocks 0 .. nblocks - 1 of the batch's kernel
@@ -1147,6 +1149,8 @@ struct myo_batch {
   size_t render_ws_bytes = 0;
   double* so_ws = nullptr;     // dev [n, MYO_SO_WS_N]: the system matrices of myo_batch_static_opt, allocated by its first solve (not in allocs)
   double* ik_ws = nullptr;     // dev [n, MYO_IK_WS_N]: system matrix, Jacobian and site points of myo_batch_ik, allocated by its first call (not in allocs)
+  double* sim_ws = nullptr;    // dev [rows, stride + RK4 stage block]: the shadow records of myo_batch_simulate, grown on demand (not in allocs)
+  size_t sim_ws_bytes = 0;
   unsigned long long act_reach = 0;      // dofs some actuator's moment row can reach: myo_batch_static_opt's default weight
   std::vector<double> cam_host;      // the cameras of the last myo_batch_render (source of its asynchronous upload)
   // how contact items are drawn (myo_batch_set_render_style; the defaults of include/myobatch.h)
@@ -1462,6 +1466,7 @@ static void batch_release(myo_batch* b, int destroying) {
   if (b->render_ws) be_free(b->render_ws);
   if (b->so_ws) be_free(b->so_ws);
   if (b->ik_ws) be_free(b->ik_ws);
+  if (b->sim_ws) be_free(b->sim_ws);
   delete b;
 }
 
@@ -1934,6 +1939,46 @@ extern "C" int myo_batch_ik(myo_batch* b, const myo_ik_in* in, const myo_ik_out*
   d.ws = b->ik_ws; d.active = in->active; d.reg = in->reg; d.tol = in->tol;
   d.k = in->k; d.weight_per_env = in->weight && in->weight_per_env ? 1 : 0; d.max_iter = in->max_iter;
   return be_run(b, IkJob{d}, b->n, stream);
+}
+// myo_batch_simulate (csrc/myo_simulate.h): SimJob is a row of the variant table like PhysicsJob, keyed with the integrator, over
+// k S blocks.  The shadow records (and, where the variant keeps its RK4 stage storage in global memory, one stage block per row: the
+// batch's own is indexed by workgroup and sized for n envs) live in a workspace of the batch's own, grown on demand.  Every array
+// lives on the device: the host refuses what it can see.
+extern "C" int myo_batch_simulate(myo_batch* b, const myo_sim_in* in, const myo_sim_out* out, void* stream) {
+  if (!b || !in || !out) return fail(MYO_E_BADARG, "myo_batch_simulate: null batch, input or output struct");
+  if (in->size != sizeof(myo_sim_in)) return fail(MYO_E_BADARG, "myo_batch_simulate: myo_sim_in.size is %zu, this library's struct has %zu bytes", in->size, sizeof(myo_sim_in));
+  if (out->size != sizeof(myo_sim_out)) return fail(MYO_E_BADARG, "myo_batch_simulate: myo_sim_out.size is %zu, this library's struct has %zu bytes", out->size, sizeof(myo_sim_out));
+  if (in->k < 0 || in->S < 1 || in->T < 1) return fail(MYO_E_ARG, "myo_batch_simulate: k must be >= 0, S and T >= 1, got k = %d, S = %d, T = %d", in->k, in->S, in->T);
+  if (!in->env_idx && in->k > b->n) return fail(MYO_E_ARG, "myo_batch_simulate: env_idx is NULL with k = %d beyond the batch's %d envs", in->k, b->n);
+  if (in->nsub < 0) return fail(MYO_E_ARG, "myo_batch_simulate: nsub must be >= 0, got %d", in->nsub);
+  if (in->every < 1 || in->T % in->every) return fail(MYO_E_ARG, "myo_batch_simulate: every must be >= 1 and divide T, got T = %d, every = %d", in->T, in->every);
+  if (in->ns < 0 || in->ns > MYO_SIM_NS_MAX) return fail(MYO_E_ARG, "myo_batch_simulate: ns must be in [0, %d], got %d", MYO_SIM_NS_MAX, in->ns);
+  if (out->site_xpos && in->ns > 0 && !in->site_ids) return fail(MYO_E_ARG, "myo_batch_simulate: site_ids is NULL with ns = %d", in->ns);
+  if ((long long)in->k * in->S > (1ll << 31) - 1) return fail(MYO_E_ARG, "myo_batch_simulate: k * S = %lld exceeds 2^31 - 1", (long long)in->k * in->S);
+  if (in->k == 0 || (!out->qpos && !out->qvel && !out->act && !out->time && !out->site_xpos && !out->bad && !out->steps)) return MYO_OK;
+  const int rows = in->k * in->S;
+  const int rkd = with_variant(b, [](auto v) {
+    using V = decltype(v);
+    return V::RK && !MYO_RK_IN_LDS(typename V::T, V::NC) ? (int)((sizeof(RkScratch<typename V::T>) + 7) / 8) : 0;
+  });
+  const int rk_off = rkd ? (b->L.stride + 1) / 2 * 2 : 0;      // (16-byte aligned behind the record)
+  const int ws_stride = ((rkd ? rk_off + rkd : b->L.stride) + 1) / 2 * 2;
+  const size_t need = (size_t)rows * ws_stride * sizeof(double);
+  if (b->sim_ws_bytes < need) {
+    if (be_capturing(stream)) return fail(MYO_E_STATE, "myo_batch_simulate: the workspace has to grow to %zu bytes while the stream is capturing; size it with an eager call of the same k * S first", need);
+    if (b->sim_ws) { be_free(b->sim_ws); b->sim_ws = nullptr; b->sim_ws_bytes = 0; }
+    void* p = nullptr;
+    const int e = be_malloc(&p, need);
+    if (e || !p) return fail(MYO_E_DEVICE, "myo_batch_simulate: workspace allocation of %zu bytes failed: %s", need, be_errstr(e));
+    b->sim_ws = (double*)p; b->sim_ws_bytes = need;
+  }
+  SimDev d{};
+  d.env_idx = in->env_idx; d.ctrl = in->ctrl; d.qpos0 = in->qpos0; d.qvel0 = in->qvel0; d.act0 = in->act0; d.site_ids = in->site_ids;
+  d.qpos = out->qpos; d.qvel = out->qvel; d.act = out->act; d.time = out->time; d.site_xpos = in->ns > 0 ? out->site_xpos : nullptr;
+  d.bad = out->bad; d.steps = out->steps; d.ws = b->sim_ws;
+  d.S = in->S; d.T = in->T; d.nsub = in->nsub ? in->nsub : (b->K.frame_skip > 0 ? b->K.frame_skip : 1); d.every = in->every; d.ns = in->ns;
+  d.ctrl_per_sample = in->ctrl && in->ctrl_per_sample ? 1 : 0; d.ws_stride = ws_stride; d.rk_off = rk_off;
+  return be_run(b, SimJob{d}, rows, stream);
 }
 extern "C" int myo_batch_geom_poses(myo_batch* b, const int32_t* env_idx, int k, double* out, void* stream) {
   if (int rc = render_check_items(b, env_idx, k, "myo_batch_geom_poses")) return rc;

@@ -454,6 +454,11 @@ static void be_xfer_i(myo_batch* b, int off, int cnt, int* ext, int to_ext, void
   const long long tot = (long long)b->n * cnt;
   hipLaunchKernelGGL(k_state_i, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, b->rec, b->L.stride, off, cnt, b->n, ext, to_ext);
 }
+static int be_capturing(void* stream) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing((hipStream_t)stream, &cap);
+  return cap != hipStreamCaptureStatusNone;
+}
 static int be_launch_status() {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MYO_OK : fail(MYO_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));

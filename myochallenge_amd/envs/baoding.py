@@ -608,6 +608,124 @@ class BaodingVecEnv:
             out = {key: v[idx] for key, v in out.items()}
         return out
 
+    # ---------------------------------------------------------------- open-loop simulation (include/myobatch.h myo_batch_simulate)
+    def simulate(self, ctrl, samples=None, nsub=None, every=1, qpos=None, qvel=None, act=None, sites=None, indices=None, keys=None) -> dict:
+        """What happens from the envs' PRESENT states (or from given start states) under given muscle controls: ``samples`` control
+        sequences per env, rolled out for T control steps in ONE launch on copies of the envs' records - nothing about the envs
+        changes.  The primitive of sampling-based control (MPPI, predictive sampling), of tracking controllers and of
+        ``linearize``; device tensors (float64), no host copy.
+
+        ctrl: [k, T, nu] shared by an env's samples, or [k, S, T, nu] per sample - the actuators' ``ctrl`` as ``data(ctrl=...)`` takes
+        it: no action map, no fatigue advance, no task layer, no reset.  samples: S (default: ctrl's, else 1).  nsub: substeps per
+        control step (default: the task's frame_skip).  every: record every ``every``-th control step (T % every == 0; R = T / every
+        rows).  qpos / qvel / act: [k, S, nq / nv / na] start states (default: the env's own).  sites: names or ids
+        (``site_names()``, at most ``native.SIM_NS_MAX``) whose world positions are recorded.  indices: the envs to simulate, in this
+        order; they may repeat (default: all, k = N).  Returns (``keys``, default all) ``qpos`` [k, S, R, nq], ``qvel``, ``act``,
+        ``time`` [k, S, R], ``site_xpos`` [k, S, R, ns, 3] (with sites), ``bad`` / ``steps`` [k, S] int32: a sample whose state
+        blows up stops with bad = 1, steps = the control steps it completed, and NaN in the rows it did not reach."""
+        t = self.torch
+        n, m = self.num_envs, self._model
+        nq, nv, na, nu = m.size("nq"), m.size("nv"), m.size("na"), self.act_dim
+        if indices is None:
+            idx, k = None, n
+        else:
+            idx = [int(i) for i in indices]
+            for i in idx:
+                if not 0 <= i < n:
+                    raise IndexError(f"env index {i} outside [0, {n})")
+            k = len(idx)
+        ids = [] if sites is None else self._jac_ids("site", sites)
+        if len(ids) > native.SIM_NS_MAX:
+            raise ValueError(f"at most {native.SIM_NS_MAX} sites per call, got {len(ids)}")
+        ctrl = t.as_tensor(ctrl, dtype=t.float64, device=self.device).contiguous()
+        if ctrl.dim() not in (3, 4) or ctrl.shape[0] != k or ctrl.shape[-1] != nu:
+            raise ValueError(f"ctrl must have shape ({k}, T, {nu}) or ({k}, S, T, {nu})")
+        per_sample = ctrl.dim() == 4
+        S = int(ctrl.shape[1]) if per_sample else (1 if samples is None else int(samples))
+        if samples is not None and int(samples) != S:
+            raise ValueError(f"samples = {int(samples)} but ctrl holds {S} sequences per env")
+        T, every = int(ctrl.shape[-2]), int(every)
+        if S < 1 or T < 1:
+            raise ValueError("samples and the number of control steps must be >= 1")
+        if every < 1 or T % every:
+            raise ValueError(f"every must be >= 1 and divide the number of control steps, got T = {T}, every = {every}")
+        if nsub is not None and int(nsub) < 1:
+            raise ValueError("nsub must be >= 1")
+
+        def start(x, name, w):
+            if x is None:
+                return None
+            x = t.as_tensor(x, dtype=t.float64, device=self.device).contiguous()
+            if tuple(x.shape) != (k, S, w):
+                raise ValueError(f"{name} must have shape {(k, S, w)}")
+            return x
+        qpos, qvel, act = start(qpos, "qpos", nq), start(qvel, "qvel", nv), start(act, "act", na)
+        shapes = self.batch.simulate_shapes(S, T // every, len(ids))
+        if not ids:
+            shapes.pop("site_xpos")
+        keys = list(shapes) if keys is None else list(keys)
+        for key in keys:
+            if key not in shapes:
+                raise KeyError(f"unknown simulation key {key!r}; known: {sorted(shapes)}")
+        tdt = {np.int32: t.int32, np.float64: t.float64}
+        out = {key: t.empty((k,) + shapes[key][0], dtype=tdt[shapes[key][1]], device=self.device) for key in keys}
+        if k == 0:
+            return out
+        idx_t = None if idx is None else t.as_tensor(idx, dtype=t.int32, device=self.device)
+        ids_t = t.as_tensor(ids, dtype=t.int32, device=self.device) if ids else None
+        self.batch.simulate(k, S, T, ctrl, per_sample, idx_t, 0 if nsub is None else int(nsub), every, qpos, qvel, act, ids_t, self._stream(), **out)
+        if self.device.type == "cuda" and not t.cuda.is_current_stream_capturing():
+            t.cuda.synchronize(self.device)       # (the inputs may be temporaries: the launch must have read them)
+        return out
+
+    def _tangent_tables(self):
+        f = self.compiled.fields
+        return tuple(np.asarray(f[key]).astype(int) for key in ("jnt_type", "jnt_qposadr", "jnt_dofadr"))
+
+    def linearize(self, ctrl=None, eps=1e-6, nsub=None, centered=True, indices=None) -> dict:
+        """Finite-difference linearisation of one control step around the envs' PRESENT states - the analogue of MuJoCo's
+        ``mjd_transitionFD``, layered on ``simulate`` (one launch, nothing about the envs changes).  The state is
+        ``x = (qpos in tangent coordinates [nv], qvel [nv], act [na])``, ``nx = 2 nv + na``; the ``nx + nu`` perturbations of size
+        ``eps`` (both signs when ``centered``) and the unperturbed step are the samples of one call.  qpos is perturbed with
+        ``mathutil.integrate_pos`` (a free joint's position adds, its quaternion is rotated by the local-frame rotation vector) and
+        differenced with ``mathutil.differentiate_pos``; controls are not clamped to their range.
+
+        ctrl: [k, nu] (default zeros).  nsub: substeps of the step (default: the task's frame_skip).  Returns ``A`` [k, nx, nx] and
+        ``B`` [k, nx, nu] with ``dx' ~ A dx + B du``, and ``x_next`` [k, nq + nv + na], the unperturbed next state (qpos | qvel | act)."""
+        from ..mathutil import differentiate_pos, integrate_pos
+        t = self.torch
+        n, m = self.num_envs, self._model
+        nq, nv, na, nu = m.size("nq"), m.size("nv"), m.size("na"), self.act_dim
+        eps = float(eps)
+        if not eps > 0:
+            raise ValueError("eps must be > 0")
+        idx = list(range(n)) if indices is None else [int(i) for i in indices]
+        k, nx = len(idx), 2 * nv + na
+        sel = t.as_tensor(idx, dtype=t.long, device=self.device)
+        q0, v0, a0, _ = (x[sel] for x in self.get_state())
+        u0 = t.zeros((k, nu), dtype=t.float64, device=self.device) if ctrl is None else t.as_tensor(ctrl, dtype=t.float64, device=self.device)
+        if tuple(u0.shape) != (k, nu):
+            raise ValueError(f"ctrl must have shape {(k, nu)}")
+        P = nx + nu
+        signs = (1.0, -1.0) if centered else (1.0,)
+        S = 1 + len(signs) * P
+        d = t.zeros((S, P), dtype=t.float64, device=self.device)      # sample 0: the unperturbed step; then +eps e_i (and -eps e_i)
+        for g, sg in enumerate(signs):
+            d[1 + g * P:1 + (g + 1) * P] = sg * eps * t.eye(P, dtype=t.float64, device=self.device)
+        tabs = self._tangent_tables()
+        dq, dv, da, du = (d[None, :, a:b] for a, b in ((0, nv), (nv, 2 * nv), (2 * nv, nx), (nx, P)))
+        qs = integrate_pos(q0[:, None].expand(k, S, nq), dq.expand(k, S, nv), *tabs)
+        out = self.simulate((u0[:, None] + du)[:, :, None], nsub=nsub, qpos=qs, qvel=v0[:, None] + dv, act=a0[:, None] + da if na else None,
+                            indices=idx, keys=("qpos", "qvel", "act", "bad"))
+        qn, vn, an = out["qpos"][:, :, 0], out["qvel"][:, :, 0], out["act"][:, :, 0]
+
+        def diff(hi, lo, h):      # (x'[hi] - x'[lo]) / h in tangent coordinates: [k, P, nx]
+            return t.cat([differentiate_pos(qn[:, hi], qn[:, lo], *tabs), vn[:, hi] - vn[:, lo], an[:, hi] - an[:, lo]], -1) / h
+        plus = slice(1, 1 + P)
+        J = diff(plus, slice(1 + P, 1 + 2 * P), 2 * eps) if centered else diff(plus, t.zeros(P, dtype=t.long, device=self.device), eps)
+        J = J.transpose(1, 2)      # [k, nx, P]: column i = the response to perturbation i
+        return {"A": J[:, :, :nx].contiguous(), "B": J[:, :, nx:].contiguous(), "x_next": t.cat([qn[:, 0], vn[:, 0], an[:, 0]], -1), "bad": out["bad"]}
+
     def site_names(self) -> List[str]:
         """names of the model's sites: rows of ``data()``'s ``site_xpos``"""
         return list(self.compiled.names.get("site", []))

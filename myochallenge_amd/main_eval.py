@@ -30,8 +30,12 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
              num_episodes: int = 100, num_envs: int = 256, seed: int = 0, deterministic: bool = True, verbose: bool = True,
              render_dir: str = None, render_envs: int = 1, render_size=(480, 480), render_tendons: bool = False,
              record_dir: str = None, env=None, render_contacts: bool = False, render_geom_alpha: float = None,
-             muscle_condition: str = None, fatigue_params: dict = None, record_data=None, record_static_opt: bool = False):
-    """record_static_opt: record_dir's file also gets ``so_u`` [T, N, nu], ``so_residual`` [T, N, nv] and ``so_status`` [T, N]: what a
+             muscle_condition: str = None, fatigue_params: dict = None, record_data=None, record_static_opt: bool = False,
+             record_simulate: int = 0):
+    """record_simulate: T > 0: record_dir's file also gets ``sim_qpos`` [T_steps, N, nq], the final qpos of ``env.simulate``'s
+    T-control-step prediction from the step's state under zero muscle controls (``sim_bad`` [T_steps, N]: the prediction blew up);
+    needs record_dir.
+    record_static_opt: record_dir's file also gets ``so_u`` [T, N, nu], ``so_residual`` [T, N, nv] and ``so_status`` [T, N]: what a
     static optimiser would have chosen (``env.static_optimization`` for the step's own ``data()["qacc"]``) beside what the policy
     chose; needs record_dir.
     record_data: keys of ``env.data`` (MuJoCo's sim.data names: ``site_xpos``, ``qacc``, ...) that record_dir's file also gets,
@@ -83,6 +87,11 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
         raise ValueError("record_data needs record_dir")
     if record_static_opt and not record_dir:
         raise ValueError("record_static_opt needs record_dir")
+    record_simulate = int(record_simulate or 0)
+    if record_simulate < 0:
+        raise ValueError("record_simulate must be >= 0")
+    if record_simulate and not record_dir:
+        raise ValueError("record_simulate needs record_dir")
     if record_dir:
         os.makedirs(record_dir, exist_ok=True)
         rec = {k: [] for k in ("qpos", "qvel", "act", "actuator_length", "actuator_velocity", "actuator_force", "ncon", "object_wrench")}
@@ -97,6 +106,9 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
             rec[k] = []
         if record_static_opt:
             rec.update(so_u=[], so_residual=[], so_status=[])
+        if record_simulate:
+            rec.update(sim_qpos=[], sim_bad=[])
+            zero_ctrl = env.torch.zeros((env.num_envs, record_simulate, env.act_dim), dtype=env.torch.float64, device=env.device)
 
         def on_step(t):
             if draw is not None:
@@ -116,6 +128,10 @@ def evaluate(model_path: str, env_path: str, env_name: str = "CustomMyoBaodingBa
                 so = env.static_optimization(qacc=env.data(["qacc"])["qacc"], keys=["u", "residual", "status"])
                 for k, v in so.items():
                     rec["so_" + k].append(v.cpu().numpy())
+            if record_simulate:
+                sm = env.simulate(zero_ctrl, every=record_simulate, keys=["qpos", "bad"])
+                rec["sim_qpos"].append(sm["qpos"][:, 0, 0].cpu().numpy())
+                rec["sim_bad"].append(sm["bad"][:, 0].cpu().numpy())
     res = evaluate_policy(policy, env, venv, n_eval_episodes=num_episodes, deterministic=deterministic, on_step=on_step)
     if rec is not None:
         np.savez(os.path.join(record_dir, "batch00000.npz"), object_body_ids=np.asarray(obj, np.int64), **{k: np.stack(v) for k, v in rec.items()})
@@ -151,6 +167,9 @@ def main(argv=None):
     ap.add_argument("--record-static-opt", action="store_true",
                     help="with --record-dir: also write so_u / so_residual / so_status per step: the activations a static optimiser "
                          "(env.static_optimization) would have chosen for the step's own acceleration")
+    ap.add_argument("--record-simulate", type=int, default=0, metavar="T",
+                    help="with --record-dir: also write sim_qpos / sim_bad per step: the final qpos of the T-step zero-control prediction "
+                         "(env.simulate) from the step's state")
     ap.add_argument("--muscle-condition", default=None, choices=("sarcopenia", "fatigue", "reafferentation"),
                     help="evaluate under MyoSuite's muscle_condition (overrides the config's)")
     ap.add_argument("--fatigue-F", type=float, default=None, help="with --muscle-condition fatigue: fatigue rate F (default 0.00912)")
@@ -167,6 +186,10 @@ def main(argv=None):
         ap.error("--record-data needs --record-dir")
     if a.record_static_opt and not a.record_dir:
         ap.error("--record-static-opt needs --record-dir")
+    if a.record_simulate < 0:
+        ap.error("--record-simulate must be >= 0")
+    if a.record_simulate and not a.record_dir:
+        ap.error("--record-simulate needs --record-dir")
     fat = {k: v for k, v in (("F", a.fatigue_F), ("R", a.fatigue_R), ("r", a.fatigue_r)) if v is not None}
     if fat and a.muscle_condition != "fatigue":
         ap.error("--fatigue-F / --fatigue-R / --fatigue-r need --muscle-condition fatigue")
@@ -176,7 +199,7 @@ def main(argv=None):
                       record_dir=a.record_dir, render_contacts=a.render_contacts, render_geom_alpha=a.render_geom_alpha,
                       muscle_condition=a.muscle_condition, fatigue_params=fat or None,
                       record_data=[k for k in a.record_data.split(",") if k] if a.record_data else None,
-                      record_static_opt=a.record_static_opt)
+                      record_static_opt=a.record_static_opt, record_simulate=a.record_simulate)
     if a.out:
         np.savez(a.out, **res)
 

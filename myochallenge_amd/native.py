@@ -213,6 +213,23 @@ IK_CAP, IK_STALL, IK_PINNED = 1, 2, 4      # MYO_IK_* of include/myobatch.h: bit
 IK_K_MAX = 16                              # MYO_IK_K_MAX of include/myobatch.h
 IK_WS_DOUBLES = 2448                       # MYO_IK_WS_N of csrc/myo_ik.h: doubles per env of the library's own workspace
 
+
+class SimIn(C.Structure):
+    """myo_sim_in of include/myobatch.h: device arrays (env_idx / site_ids int32, the others doubles) and scalars of myo_batch_simulate;
+    every pointer may be NULL."""
+    _fields_ = [("size", C.c_size_t), ("env_idx", C.c_void_p), ("k", C.c_int), ("S", C.c_int), ("T", C.c_int), ("nsub", C.c_int),
+                ("every", C.c_int), ("ctrl", C.c_void_p), ("ctrl_per_sample", C.c_int), ("qpos0", C.c_void_p), ("qvel0", C.c_void_p),
+                ("act0", C.c_void_p), ("site_ids", C.c_void_p), ("ns", C.c_int)]
+
+
+class SimOut(C.Structure):
+    """myo_sim_out of include/myobatch.h: caller-owned device arrays of myo_batch_simulate (doubles; bad / steps int32), any of them NULL."""
+    _fields_ = [("size", C.c_size_t)] + [(k, C.c_void_p) for k in ("qpos", "qvel", "act", "time", "site_xpos", "bad", "steps")]
+
+
+SIM_KEYS = tuple(f[0] for f in SimOut._fields_[1:])
+SIM_NS_MAX = 16                            # MYO_SIM_NS_MAX of include/myobatch.h
+
 JAC_BODY, JAC_BODYCOM, JAC_SITE, JAC_GEOM, JAC_SUBTREECOM = range(5)      # MYO_JAC_* of include/myobatch.h
 JAC_KINDS = {"body": JAC_BODY, "bodycom": JAC_BODYCOM, "site": JAC_SITE, "geom": JAC_GEOM, "subtreecom": JAC_SUBTREECOM}
 
@@ -286,6 +303,7 @@ class NativeLib:
         L.myo_batch_inverse.argtypes = [vp, vp, C.POINTER(InverseOut), vp]
         L.myo_batch_static_opt.argtypes = [vp, C.POINTER(StaticOptIn), C.POINTER(StaticOptOut), vp]
         L.myo_batch_ik.argtypes = [vp, C.POINTER(IkIn), C.POINTER(IkOut), vp]
+        L.myo_batch_simulate.argtypes = [vp, C.POINTER(SimIn), C.POINTER(SimOut), vp]
         if b"MYO_EMU" in L.myo_version():
             return      # the emulation build (test tooling, csrc/emu_host.h) implements the env path only: ENV_PATH_SYMBOLS
         L.myo_ppo_loss_grad.argtypes = [vp] * 8 + [i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp, vp]
@@ -376,7 +394,7 @@ EXPORTED_SYMBOLS = [
     "myo_batch_enable_timing", "myo_ppo_loss_grad", "myo_ppo_gather", "myo_ppo_gather_seq", "myo_rollout_state_snapshot", "myo_bias_relu_bf16", "myo_rollout_policy_input", "myo_rollout_sample",
     "myo_vecnorm_step", "myo_rollout_sample_sde", "myo_vecnorm_batch_moments", "myo_vecnorm_finish", "myo_rollout_advance", "myo_gae", "myo_lstm_cell_fwd", "myo_lstm_cell_bwd", "myo_lstm_step_supported", "myo_lstm_step_fwd", "myo_lstm_step_bwd", "myo_lstm_seq_supported", "myo_lstm_seq_fwd", "myo_lstm_seq_bwd", "myo_splitk_reduce", "myo_splitk_reduce2", "myo_relu_bwd_colsum_bf16", "myo_adam_step", "myo_ppo_mlp_workspace_bytes", "myo_ppo_mlp_step", "myo_ppo_mlp_sqnorm_parts", "myo_ppo_mlp_rollout_workspace_bytes", "myo_ppo_mlp_rollout_refresh", "myo_ppo_mlp_rollout", "myo_last_error", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
-    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt", "myo_batch_ik",
+    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt", "myo_batch_ik", "myo_batch_simulate",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
     "myo_ppo_mlp_step_resident", "myo_ppo_mlp_images", "myo_ppo_adv_moments_epoch",
@@ -395,7 +413,7 @@ ENV_PATH_SYMBOLS = [
     "myo_batch_step", "myo_batch_step_inner", "myo_batch_step_inner_idx", "myo_batch_tune_wrap_order", "myo_batch_warmstart", "myo_debug_wave_slots",
     "myo_last_error", "myo_model_destroy", "myo_model_from_blob", "myo_model_load_mjb", "myo_model_size", "myo_model_table", "myo_version",
     "myo_model_default_camera", "myo_batch_geom_poses", "myo_batch_tendon_paths", "myo_batch_render",
-    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt", "myo_batch_ik",
+    "myo_batch_contact_capacity", "myo_batch_sense", "myo_batch_data", "myo_batch_jac", "myo_batch_inverse", "myo_batch_static_opt", "myo_batch_ik", "myo_batch_simulate",
     "myo_batch_contact_items", "myo_batch_set_render_style", "myo_batch_get_render_style",
     "myo_batch_fatigue",
 ]
@@ -700,6 +718,30 @@ class Batch:
                 raise KeyError(k)
             setattr(out, k, _ptr(v))
         self.lib.check(self.lib.L.myo_batch_ik(self.h, C.byref(inp), C.byref(out), stream))
+
+    def simulate_shapes(self, S: int, R: int, ns: int = 0) -> dict:
+        """key -> (per-listed-env shape, dtype) of the arrays of simulate() for S samples, R recorded steps and ns sites"""
+        m = self.model
+        return {"qpos": ((S, R, m.size("nq")), np.float64), "qvel": ((S, R, m.size("nv")), np.float64), "act": ((S, R, m.size("na")), np.float64),
+                "time": ((S, R), np.float64), "site_xpos": ((S, R, ns, 3), np.float64), "bad": ((S,), np.int32), "steps": ((S,), np.int32)}
+
+    def simulate(self, k, S, T, ctrl=None, ctrl_per_sample=False, env_idx=None, nsub=0, every=1, qpos0=None, qvel0=None, act0=None,
+                 site_ids=None, stream=None, **arrays):
+        """read-only open-loop simulation (myo_batch_simulate): S samples of T control steps (nsub substeps each; 0: the task's
+        frame_skip) for each of the k envs env_idx (int32 [k] device array; None: envs 0 .. k - 1), from the envs' present states or
+        qpos0 / qvel0 / act0 (float64 [k, S, .]); ctrl float64 [k, T, nu] or - ctrl_per_sample - [k, S, T, nu] (None: zeros); site_ids
+        int32 [ns] device array; keyword = a key of SIM_KEYS, value = the device array that receives it
+        ([k, *simulate_shapes(S, T // every, ns)[key]]).  Keys not given are not written; the envs do not move."""
+        inp, out = SimIn(), SimOut()
+        inp.size, out.size = C.sizeof(SimIn), C.sizeof(SimOut)
+        inp.env_idx, inp.k, inp.S, inp.T, inp.nsub, inp.every = _ptr(env_idx), int(k), int(S), int(T), int(nsub), int(every)
+        inp.ctrl, inp.ctrl_per_sample, inp.qpos0, inp.qvel0, inp.act0 = _ptr(ctrl), int(bool(ctrl_per_sample)), _ptr(qpos0), _ptr(qvel0), _ptr(act0)
+        inp.site_ids, inp.ns = _ptr(site_ids), int(site_ids.shape[0]) if site_ids is not None else 0
+        for key, v in arrays.items():
+            if key not in SIM_KEYS:
+                raise KeyError(key)
+            setattr(out, key, _ptr(v))
+        self.lib.check(self.lib.L.myo_batch_simulate(self.h, C.byref(inp), C.byref(out), stream))
 
     @property
     def dump_size(self) -> int:

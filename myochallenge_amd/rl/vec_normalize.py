@@ -274,6 +274,12 @@ class VecNormalize:
     def inverse_kinematics(self, *args, **kwargs):
         return self.venv.inverse_kinematics(*args, **kwargs)
 
+    def simulate(self, *args, **kwargs):
+        return self.venv.simulate(*args, **kwargs)
+
+    def linearize(self, *args, **kwargs):
+        return self.venv.linearize(*args, **kwargs)
+
     # muscle fatigue state (muscle_condition="fatigue"): forwarded likewise
     def fatigue_state(self):
         return self.venv.fatigue_state()
